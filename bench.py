@@ -5,21 +5,29 @@ A "step" = one full `Match` (cost volume -> 4x cross aggregation -> 4 scanline p
 refinement) of one 1920x1080, D=128 stereo pair whose images are already resident in HBM (adc_match_device); the
 disparity map stays in HBM.  The timed region is a FARM over a batch of DISTINCT pairs (BASELINE.json configs[4],
 SURVEY.md 8d config 5), pair i = the seeded synthetic pair 12345 + i:
-  default       weak scaling: batch = steps x ranks pairs, static partition (rank r takes the pairs i = r mod ranks),
-                every GPU does exactly `steps` pairs;
+  default       weak scaling: batch = min(steps, --distinct-pairs) x ranks pairs, static partition (rank r takes the pairs
+                i = r mod ranks), every GPU does exactly `steps` pairs (its share of the batch over and over when steps exceeds
+                --distinct-pairs, 160 by default: generating and uploading a pair costs ~20 ms of host time);
   --batch B     strong scaling = configs[4] literally: a FIXED batch of B pairs (64), every rank holds all B pairs in its
                 HBM and PULLS the next pair index from one shared counter on the job's rendezvous store
                 (adcensus_amd/farm.py PullQueue; a failed Match is re-queued and the rank retires).  steps := B.
 `--inflight` pipelines (ADCensusStereo objects on separate streams) per GPU: default 1 for one GPU (clean per-kernel
-timings for the roofline), 2 for several.  There is no data-path collective: RCCL carries the barriers, the MAX over ranks
-of the elapsed time, the SUM of the done counter and an all-gather of one SHA-256 per pair.  After the timed region every
-output of the batch is recomputed on another GPU (N = 1: a second time) and the digests compared; they are also compared
-with the digests of the REFERENCE CPU program's maps for the same pairs (tests/golden/farm_ref_digests.json) when the size matches.
+timings for the roofline), 2 for several.  There is no data-path collective: RCCL carries the barriers and the MAX over ranks
+of the elapsed time (with --full also the SUM of the done counter and an all-gather of one SHA-256 per pair).
+
+A plain run sets up, spins the device up, warms up, times the steps, writes the outputs of the last timed step if
+--dump-outputs DIR is given (DIR/disparity.npy: the float32 map of that pair, as adc_match_device leaves it in HBM) and prints
+the line: metric, value, unit, ms_per_step, config, async_fallbacks.  Nothing else runs: no event marks in the timed region.
+`--full` adds everything below.  After the timed region every output of the batch is recomputed on another GPU (N = 1: a
+second time) and the digests compared; they are also compared with the digests of the REFERENCE CPU program's maps for the
+same pairs (tests/golden/farm_ref_digests.json) when the size matches (also done for --write-digests).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects (--full only):
+  farm_check     the verification above.
+  stage_ms       stage times from up to ten Matches behind the timed region with the stage marks on.
   roofline       the aggregation kernel (K4): achieved = the bytes a regular launch really moves through HBM (read V +
                  write V + records; a pass-pair launch does that once for two passes of work) / the average launch
                  duration from HIP events on the handle's own stream inside the timed region; frac = achieved / 8 TB/s
@@ -106,6 +114,14 @@ def parse():
                     help="processes of the all-host-cores CPU figure (0 = skip; clamped to the host's cores and free memory)")
     ap.add_argument("--no-cone-leg", action="store_true", help="skip the Cone 450x375 D=64 leg (BASELINE.json configs[0] / [1])")
     ap.add_argument("--write-digests", default="", help="write {pair id: sha256} of the batch outputs to this file (N = 1)")
+    ap.add_argument("--distinct-pairs", type=int, default=160,
+                    help="weak scaling: at most this many distinct pairs per GPU, cycled when --steps is larger (160 = the pairs "
+                         "tests/golden/farm_selfcheck_digests.json covers)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify every output, time the stages and rooflines, run the other legs and the CPU baselines "
+                         "(the plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the disparity map of the last step to DIR/disparity.npy (float32)")
     return ap.parse_args()
 
 
@@ -135,6 +151,7 @@ class Matcher:
             self.handles.append(st)
         self.buf = {}  # pair id -> (d_left, d_right, d_disp)
         self.soft_fail = False  # True: a failed Match raises farm.MatchFailed (pull queue: re-queue + retire) instead of aborting
+        self.slot_pid, self.last_pid = {}, None  # pair in flight per slot; pair of the Match collected last
 
     def _fail(self, what):
         if self.soft_fail:
@@ -151,12 +168,14 @@ class Matcher:
 
     def submit(self, slot, pid):
         dl, dr, dd = self.buf[pid]
+        self.slot_pid[slot] = pid
         if not self.handles[slot].match_device(dl, dr, dd):
             self._fail("Match failed")
 
     def wait(self, slot):
         if not self.handles[slot].wait():
             self._fail("Match failed")
+        self.last_pid = self.slot_pid.get(slot)
 
     def output(self, pid):
         out = np.empty((self.H, self.W), np.float32)
@@ -218,6 +237,20 @@ def make_pair(workload, W, H, D, pid):
     if workload == "noise":
         return workloads.noise_pair(W, H, 12345 + pid)  # seeds 12345 + i
     return workloads.structured_pair(W, H, D, seed=777 + pid)
+
+
+def dump_outputs(path, m, workload):
+    """--dump-outputs DIR: what the timed path computed in its last step, i.e. the disparity map adc_match_device left in HBM
+    for that pair (float32 [H][W], read back right after the timed region), as DIR/disparity.npy.  A map above 64 MB is
+    written as every k-th row (the smallest k that fits; `row_stride` in the line)."""
+    if getattr(m, "last_output", None) is None:
+        raise SystemExit("bench.py: --dump-outputs: no timed step was collected")
+    disp = np.ascontiguousarray(m.last_output, dtype=np.float32)
+    stride = -(-disp.nbytes // (64 << 20))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "disparity.npy"), np.ascontiguousarray(disp[::stride]))
+    return {"files": ["disparity.npy"], "pair": int(m.last_pid), "seed": (12345 if workload == "noise" else 777) + int(m.last_pid),
+            "row_stride": int(stride)}
 
 
 def device_copy_rate(lib, nbytes):
@@ -305,10 +338,12 @@ def stage_roofline(stage, ms_per_step, W, H, D, fused_tail=False):
 
 
 def measure_workload(A, device, W, H, D, workload, steps, warmup, inflight, pair_ids, dist=None, tensor_device="cpu",
-                     queue_factory=None, host_pairs=None, spinup_ms=0.0):
+                     queue_factory=None, host_pairs=None, spinup_ms=0.0, profile=True, capture_last=False):
     """Uploads the pairs, runs warm-up + the timed farm region; returns (matcher, elapsed, total, stage_ms, roofline-prof).
     queue_factory: None = static list `pair_ids` repeated to `steps`; else a callable returning a farm.PullQueue for the
-    timed region (the batch = range(queue.n): every pair must be in `pair_ids`)."""
+    timed region (the batch = range(queue.n): every pair must be in `pair_ids`).
+    profile: aggregation marks in the timed region + stage-timing Matches behind it (False: none, stage_ms / prof empty).
+    capture_last: m.last_output = the map of the last timed step (pair m.last_pid), read back right after the region."""
     from adcensus_amd import farm
     if host_pairs is not None:
         m = HostFedMatcher(A, device, W, H, D, inflight, host_pairs)
@@ -320,12 +355,13 @@ def measure_workload(A, device, W, H, D, workload, steps, warmup, inflight, pair
         # the timed region records only the marks around the aggregation launches (the live duration of the roofline kernel); the
         # stage times come from extra Matches BEHIND the region with the stage marks on (an event record costs the stream ~6 us:
         # ten of them are 1.3 % of a 1080p Match -- instrumentation the product path does not have)
-        m.handles[0].set_profiling(2)
+        if profile:
+            m.handles[0].set_profiling(2)
     prof, stages = [], []
     m.mine, m.retired = list(pair_ids), False
 
     def on_collected(slot):
-        if slot == 0 and host_pairs is None:
+        if slot == 0 and host_pairs is None and profile:
             prof.append(m.handles[0].aggregate_info())
             stages.append(m.handles[0].stage_ms())
 
@@ -357,8 +393,10 @@ def measure_workload(A, device, W, H, D, workload, steps, warmup, inflight, pair
     elapsed, total = farm.timed_region(run_timed, steps, 0, dist=dist, device_sync=sync, tensor_device=tensor_device)
     if queue_factory is not None:  # the units really processed: this rank's share of the batch, SUMmed over the ranks
         total = farm.done_counter(len(m.mine), dist, tensor_device)
+    if capture_last and host_pairs is None and m.last_pid is not None:
+        m.last_output = m.output(m.last_pid)
     keep = max(1, (steps + inflight - 1) // inflight)
-    if host_pairs is None:  # stage times: the same pairs once more (at most 10 Matches), untimed, stage marks on
+    if host_pairs is None and profile:  # stage times: the same pairs once more (at most 10 Matches), untimed, stage marks on
         del stages[:]
         m.handles[0].set_profiling(1)
         run.timed = False
@@ -462,6 +500,8 @@ def main():
         batch, steps = a.batch, a.batch  # a step = one pair of the fixed batch (whole job)
     else:
         batch, steps = a.steps * world, a.steps
+        if mode == "static":  # (steps beyond --distinct-pairs cycle through every GPU's share of the batch)
+            batch = max(1, min(a.steps, a.distinct_pairs)) * world
     if mode == "pull":
         mine = list(range(batch))  # every rank holds every pair: any rank may pull any index
         qname = "timed"
@@ -473,40 +513,46 @@ def main():
     else:
         mine = farm.partition(batch, world, rank)
         queue_factory = None
+    verify = a.full or bool(a.write_digests)
     m, elapsed, total, stages, prof = measure_workload(A, local_rank, W, H, D, a.workload, steps if mode == "static" else batch, a.warmup, F, mine,
-                                                       dist=dist, tensor_device=tensor_device, queue_factory=queue_factory, spinup_ms=a.spinup_ms)
-    computed = list(m.mine) if mode == "pull" else mine
-    # ---- verification (untimed): digests of this rank's outputs, recomputation on another GPU
-    primary = {pid: farm.digest(m.output(pid).tobytes()) for pid in computed}
-    all_primary = farm.gather_digests(primary, dist)
-    todo = farm.recheck_assignment(all_primary, rank) if mode == "pull" else farm.neighbour_pairs(batch, world, rank)
-    recheck = {}
-    for pid in ([] if m.retired else todo):
-        own = pid in m.buf
-        if not own:
-            l, r = make_pair(a.workload, W, H, D, pid)
-            m.upload(pid, l, r)
-        else:
-            m.clear_output(pid)
-        m.submit(0, pid)
-        m.wait(0)
-        recheck[pid] = farm.digest(m.output(pid).tobytes())
-        if not own:
-            m.free(pid)
-    done = farm.done_counter(len(primary), dist, tensor_device)
-    all_recheck = farm.gather_digests(recheck, dist)
-    retired = farm.done_counter(1 if m.retired else 0, dist, tensor_device)
+                                                       dist=dist, tensor_device=tensor_device, queue_factory=queue_factory, spinup_ms=a.spinup_ms,
+                                                       profile=a.full, capture_last=bool(a.dump_outputs) and rank == 0)
+    dumped = dump_outputs(a.dump_outputs, m, a.workload) if a.dump_outputs and rank == 0 else None
+    if verify:
+        computed = list(m.mine) if mode == "pull" else mine
+        # ---- verification (untimed): digests of this rank's outputs, recomputation on another GPU
+        primary = {pid: farm.digest(m.output(pid).tobytes()) for pid in computed}
+        all_primary = farm.gather_digests(primary, dist)
+        todo = farm.recheck_assignment(all_primary, rank) if mode == "pull" else farm.neighbour_pairs(batch, world, rank)
+        recheck = {}
+        for pid in ([] if m.retired else todo):
+            own = pid in m.buf
+            if not own:
+                l, r = make_pair(a.workload, W, H, D, pid)
+                m.upload(pid, l, r)
+            else:
+                m.clear_output(pid)
+            m.submit(0, pid)
+            m.wait(0)
+            recheck[pid] = farm.digest(m.output(pid).tobytes())
+            if not own:
+                m.free(pid)
+        done = farm.done_counter(len(primary), dist, tensor_device)
+        all_recheck = farm.gather_digests(recheck, dist)
+        retired = farm.done_counter(1 if m.retired else 0, dist, tensor_device)
 
     out = None
     if rank == 0:
-        ref_table, self_table = farm.load_digest_tables(ROOT, a.workload, [W, H, D])
-        check = farm.cross_check(all_primary, all_recheck, ref_table, self_table)
-        check["reference"] = "tests/golden/farm_ref_digests.json: SHA-256 of the reference CPU program's maps (oracle/_ref, tools/make_farm_ref_digests.py)"
-        check["done_counter"] = done
-        check["retired_ranks"] = retired
-        check["pairs_per_rank"] = [len(d) for d in all_primary]
-        check["ok"] = (done == batch and check["pairs"] == batch and not check["duplicates"] and not check["mismatches"]
-                       and not check["reference_mismatches"] and not check["selfcheck_1gpu_mismatches"])
+        check = None
+        if verify:
+            ref_table, self_table = farm.load_digest_tables(ROOT, a.workload, [W, H, D])
+            check = farm.cross_check(all_primary, all_recheck, ref_table, self_table)
+            check["reference"] = "tests/golden/farm_ref_digests.json: SHA-256 of the reference CPU program's maps (oracle/_ref, tools/make_farm_ref_digests.py)"
+            check["done_counter"] = done
+            check["retired_ranks"] = retired
+            check["pairs_per_rank"] = [len(d) for d in all_primary]
+            check["ok"] = (done == batch and check["pairs"] == batch and not check["duplicates"] and not check["mismatches"]
+                           and not check["reference_mismatches"] and not check["selfcheck_1gpu_mismatches"])
         if a.write_digests and world == 1:
             with open(a.write_digests, "w") as f:
                 json.dump({"workload": a.workload, "size": [W, H, D], "generator": "python bench.py --steps %d --write-digests ... (1 GPU)" % a.steps,
@@ -523,30 +569,36 @@ def main():
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s %dx%d D=%d%s" % (a.workload, W, H, D, sizes.get((W, H, D), "")),
                        "batch": ("fixed batch of %d distinct pairs (seeds 12345+i) over %d GPU(s) = BASELINE.json configs[4]; a step = one pair of the batch" % (batch, world)) if strong
-                                else "%d distinct pairs (seeds 12345+i), %d per GPU" % (batch, a.steps),
+                                else "%d distinct pairs (seeds 12345+i), %d per GPU%s" % (batch, a.steps, " (cycled)" if batch < a.steps * world else ""),
                        "queue": "pull (shared counter on the rendezvous store, re-queue on failure)" if mode == "pull" else "static round-robin partition",
                        "in_flight_per_gpu": F, "parallelism": "replicas x%d (independent pairs)" % world,
                        "spinup_ms": a.spinup_ms,
-                       "comm_backend": (backend if dist is not None else None), "comm": comm},
-            "farm_check": check,
-            "device_binding": {"rank": rank, "local_rank_env": int(os.environ.get("LOCAL_RANK", "0")), "device_index": local_rank,
-                               "matcher_module": stub_module or "adcensus_amd"},
-            "ms_per_pair_latency": round(float(np.sum(list(stage.values()))), 4) if stage else None,
-            "stage_ms": stage,
-            "stage_ms_source": "Matches behind the timed region with the stage marks on (an event record costs the stream ~6 us; the timed region "
-                               "records only the marks around the aggregation launches, which the roofline figure needs)",
-            "roofline": k4_roofline(prof, W, H, D, lib, a.workload, m.handles[0].aggregate_kernel(), F),
-            # (per-GPU time per Match: weak scaling = ms_per_step, strong = ms_per_step x ranks)
-            "stage_roofline": dict(stage_roofline(stage, ms_per_step * (world if strong else 1), W, H, D,
-                                                  fused_tail=m.fallbacks.get("aggregation_tail_in_scanline", 0) * 2 > m.fallbacks.get("matches", 1) * len(m.handles)),
-                                   **({} if F == 1 else {"note": "%d pipelines in flight: stage times include co-running kernels of other pairs; whole_match is a throughput figure" % F})),
-            "async_fallbacks": m.fallbacks,
+                       "comm_backend": (backend if dist is not None else None), "comm": comm, "full": a.full},
         }
+        if check is not None:
+            out["farm_check"] = check
+        out["device_binding"] = {"rank": rank, "local_rank_env": int(os.environ.get("LOCAL_RANK", "0")), "device_index": local_rank,
+                                 "matcher_module": stub_module or "adcensus_amd"}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if a.full:
+            out.update({
+                "ms_per_pair_latency": round(float(np.sum(list(stage.values()))), 4) if stage else None,
+                "stage_ms": stage,
+                "stage_ms_source": "Matches behind the timed region with the stage marks on (an event record costs the stream ~6 us; the timed region "
+                                   "records only the marks around the aggregation launches, which the roofline figure needs)",
+                "roofline": k4_roofline(prof, W, H, D, lib, a.workload, m.handles[0].aggregate_kernel(), F),
+                # (per-GPU time per Match: weak scaling = ms_per_step, strong = ms_per_step x ranks)
+                "stage_roofline": dict(stage_roofline(stage, ms_per_step * (world if strong else 1), W, H, D,
+                                                      fused_tail=m.fallbacks.get("aggregation_tail_in_scanline", 0) * 2 > m.fallbacks.get("matches", 1) * len(m.handles)),
+                                       **({} if F == 1 else {"note": "%d pipelines in flight: stage times include co-running kernels of other pairs; whole_match is a throughput figure" % F})),
+            })
+        out["async_fallbacks"] = m.fallbacks
     host_pairs_all = None
     m.release()
 
     # ---- N > 1: the same farm fed from pageable host buffers through adc_farm_* (PCIe inclusive; never `value`)
-    if world > 1 and not a.no_host_leg:
+    if world > 1 and a.full and not a.no_host_leg:
         ids = list(range(batch)) if mode == "pull" else mine
         host_pairs_all = {pid: make_pair(a.workload, W, H, D, pid) for pid in ids}
         qf2 = None
@@ -562,7 +614,7 @@ def main():
                                                "(pinned staging + H2D + kernels + D2H + copy-out inside the timed region)"}
         host_pairs_all = None
     # ---- N > 1: rank 0 alone with the same per-GPU load (the others wait at the barrier)
-    if world > 1:
+    if world > 1 and a.full:
         if rank == 0:
             n1 = steps if not strong else max(1, batch // world)
             m1, e1, t1, _, _ = measure_workload(A, local_rank, W, H, D, a.workload, n1, min(a.warmup, 2), F, list(range(min(n1, 16))))
@@ -571,7 +623,7 @@ def main():
             m1.release()
         dist.barrier()
 
-    if rank == 0 and world == 1 and not a.no_extra_legs:
+    if rank == 0 and world == 1 and a.full and not a.no_extra_legs:
         other = "structured" if a.workload == "noise" else "noise"
         # ---- second workload (one pair: generating structured pairs costs seconds each), one pipeline
         n2 = max(5, min(10, a.steps))
@@ -624,13 +676,13 @@ def main():
                              other: {"pageable": brief(out[other]["host_inclusive"])},
                              "note": "`value` of this line is adc_match_device (BASELINE.json: inputs resident in HBM when the timed region starts)"}
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(make_pair(a.workload, W, H, D, 0), D, a.cpu_rows, H)
             if a.cpu_baseline_structured and "structured" in out:
                 out["structured"]["cpu_baseline"] = cpu_baseline(make_pair("structured", W, H, D, 0), D, a.cpu_rows, H)
             if a.cpu_all_cores > 1 and not a.no_extra_legs:
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(a.workload, W, H, D, a.cpu_all_cores)
-        if world == 1 and not a.no_cone_leg and not a.no_extra_legs:
+        if world == 1 and a.full and not a.no_cone_leg and not a.no_extra_legs:
             out["cone"] = cone_leg(A, local_rank, with_cpu=not a.no_cpu_baseline)
         sys.stdout.flush()
         try:

@@ -17,10 +17,12 @@ def cone_pair():
 
 
 def data_pair(name):
-    """cloth3 / piano / wood2: the other pairs of the reference's Data/ directory, committed as BGR arrays
-    (tests/golden/<name>_pair.npz, written by tools/make_golden.py; PNG decode is lossless)."""
-    z = np.load(os.path.join(GOLDEN_DIR, name + "_pair.npz"))
-    return np.ascontiguousarray(z["left"]), np.ascontiguousarray(z["right"])
+    """cloth3 / piano / wood2: the other pairs of the reference's Data/ directory, committed as BGR arrays, one file per
+    view so that each stays below 1 MiB (tests/golden/<name>_{left,right}.npz, written by tools/make_golden.py; PNG decode
+    is lossless)."""
+    left = np.load(os.path.join(GOLDEN_DIR, name + "_left.npz"))["left"]
+    right = np.load(os.path.join(GOLDEN_DIR, name + "_right.npz"))["right"]
+    return np.ascontiguousarray(left), np.ascontiguousarray(right)
 
 
 DATA_RANGES = {"cloth3": 128, "piano": 64, "wood2": 128}  # Data/*/d_range.txt

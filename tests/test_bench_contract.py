@@ -170,7 +170,7 @@ def test_bench_two_ranks_gloo_stub():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "64", "--height", "48",
-                        "--disp", "16", "--spinup-ms", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--disp", "16", "--spinup-ms", "0", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines  # exactly one line on stdout: rank 0's
@@ -193,7 +193,7 @@ def test_bench_pull_queue_two_ranks_gloo_stub():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8", "--warmup", "1", "--width", "64", "--height", "48",
-                        "--disp", "16", "--spinup-ms", "0", "--no-host-leg"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--disp", "16", "--spinup-ms", "0", "--no-host-leg", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -212,9 +212,52 @@ def test_bench_exits_nonzero_when_rccl_was_asked_for_and_gloo_carried_the_job():
     for k in ("WORLD_SIZE", "RANK", "ADC_BENCH_BACKEND"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "64", "--height", "48",
-                        "--disp", "16", "--spinup-ms", "0", "--no-host-leg"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--disp", "16", "--spinup-ms", "0", "--no-host-leg", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]
     d = json.loads(lines[0])
     assert d["config"]["comm_backend"] == "gloo (RCCL failed)" and d["farm_check"]["ok"]
+
+
+def _plain_stub_run(out_dir, *extra):
+    import subprocess
+    import sys
+    env = dict(os.environ, ADC_BENCH_MATCHER_MODULE="tests.bench_stub", PYTHONPATH=ROOT)
+    for k in ("WORLD_SIZE", "RANK", "ADC_BENCH_BACKEND", "ADC_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--width", "64", "--height", "48",
+                        "--disp", "16", "--spinup-ms", "0", "--distinct-pairs", "3", "--dump-outputs", str(out_dir), *extra],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dump_outputs_stub(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the K steps and nothing else: the headline fields, no verification,
+    stage timings, roofline, other legs or CPU baselines (those need --full).  --dump-outputs writes the map of the last timed
+    step; with the same arguments the inputs and therefore the dump are the same from run to run."""
+    import numpy as np
+    from adcensus_amd import workloads
+    from tests import bench_stub
+    d = _plain_stub_run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["config"]["full"] is False and d["unit"] == "pairs/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"]) / d["value"] < 0.02
+    assert d["async_fallbacks"]["matches"] == 9  # warm-up + timed steps
+    for k in ("farm_check", "roofline", "stage_ms", "stage_roofline", "cpu_baseline", "cone", "structured", "host_inclusive", "match_host"):
+        assert k not in d, k
+    assert "3 distinct pairs" in d["config"]["batch"] and "(cycled)" in d["config"]["batch"]
+    assert d["dump_outputs"]["pair"] == (7 - 1) % 3 and d["dump_outputs"]["files"] == ["disparity.npy"] and d["dump_outputs"]["row_stride"] == 1
+    got = np.load(str(tmp_path / "a" / "disparity.npy"))
+    l, r = workloads.noise_pair(64, 48, 12345 + d["dump_outputs"]["pair"])
+    assert got.dtype == np.float32 and got.shape == (48, 64)
+    assert np.array_equal(got, bench_stub._fake_disp(l.tobytes(), r.tobytes(), 64, 48))
+    _plain_stub_run(tmp_path / "b")
+    assert np.array_equal(np.load(str(tmp_path / "b" / "disparity.npy")), got)
+    d = _plain_stub_run(tmp_path / "c", "--full", "--no-cpu-baseline")  # the same headline with the checks and legs behind it
+    assert d["config"]["full"] is True and d["farm_check"]["ok"] and "roofline" in d and "stage_ms" in d
+    assert np.array_equal(np.load(str(tmp_path / "c" / "disparity.npy")), got)

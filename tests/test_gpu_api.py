@@ -560,3 +560,30 @@ def test_voting_sweep_layout_matches_the_device(hip):
     mode = st.debug_counter(14)
     st.Release()
     assert mode == 1
+
+
+def test_bench_plain_run_dumps_the_map_of_the_last_step(hip, oracle, tmp_path):
+    """`bench.py --dump-outputs DIR` on the device: DIR/disparity.npy is the map the timed path computed in its last step,
+    bit for bit the checker's map of that pair, and a plain run reports the headline only."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from adcensus_amd import workloads
+    from oracle import pyoracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H, D = 320, 192, 64
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--width", str(W),
+                        "--height", str(H), "--disp", str(D), "--spinup-ms", "0", "--dump-outputs", str(tmp_path)],
+                       cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and "farm_check" not in d and "roofline" not in d
+    assert d["dump_outputs"]["pair"] == 4
+    got = np.load(str(tmp_path / "disparity.npy"))
+    assert got.dtype == np.float32 and got.shape == (H, W)
+    left, right = workloads.noise_pair(W, H, 12345 + 4)
+    want, _ = oracle.match(left, right, pyoracle.Option(max_disparity=D))
+    assert np.array_equal(got.view(np.uint32), np.asarray(want, np.float32).view(np.uint32))

@@ -26,7 +26,7 @@ def test_stage_parity(hip, oracle, name):
 
 @pytest.mark.parametrize("name", ["cloth3", "piano", "wood2"])
 def test_middlebury_pairs(hip, oracle, name):
-    """The other pairs of the reference's Data/ directory (committed fixtures tests/golden/<name>_pair.npz); the
+    """The other pairs of the reference's Data/ directory (committed fixtures tests/golden/<name>_{left,right}.npz); the
     oracle's dumps are additionally checked against the committed SHA-256 table of the reference build."""
     import hashlib
     import json

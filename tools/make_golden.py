@@ -11,7 +11,7 @@ Writes
   tests/golden/golden.json       SHA-256 of every stage dump of the reference for a list of named,
                                  seeded cases (Cone + small synthetic cases + option variants)
   tests/golden/cone_final.npy.gz not written: the final map is pinned by its SHA-256 only
-  tests/golden/{cloth3,piano,wood2}_pair.npz  the other pairs of the reference's Data/ dir (committed too)
+  tests/golden/{cloth3,piano,wood2}_{left,right}.npz  the other pairs of the reference's Data/ dir (committed too)
 """
 import hashlib
 import json
@@ -43,8 +43,8 @@ def main():
         data = gold  # committed (about 4.7 MB): the GPU parity tests of these pairs must run on a fresh clone
         for name, l, r in (("cloth3", "Cloth3/view1.png", "Cloth3/view5.png"), ("piano", "Piano/im0.png", "Piano/im1.png"),
                            ("wood2", "Wood2/view1.png", "Wood2/view5.png")):
-            np.savez_compressed(os.path.join(data, name + "_pair.npz"), left=bgr(os.path.join(REF_DATA, l)),
-                                right=bgr(os.path.join(REF_DATA, r)))
+            np.savez_compressed(os.path.join(data, name + "_left.npz"), left=bgr(os.path.join(REF_DATA, l)))  # (one file per view:
+            np.savez_compressed(os.path.join(data, name + "_right.npz"), right=bgr(os.path.join(REF_DATA, r)))  # each below 1 MiB)
     ref = pyoracle.load("reference")
     out = {"_generator": "tools/make_golden.py", "_oracle": "oracle/_ref (reference sources, canonical recipe)", "cases": {}}
     for name in cases.GOLDEN_CASES:
