@@ -1046,7 +1046,11 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         // ERROR of the debug call instead of a silently inexact volume
         int fails = 0;
         if (hipMemcpy(&fails, h->armmax + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { set_error("adc_debug_run: seam flag", hipGetLastError()); return 2; }
-        if (fails != 0) { g_last_error = "adc_debug_run(ADC_RUN_SCANLINE): a speculative row segment failed its seam check; rerun with ADC_SO_SEG=1"; return 3; }
+        if (fails != 0) { // (as behind a Match: the handle's next scanline runs take whole rows, so a caller can write the volume again and rerun)
+            h->so_seg_off = 64;
+            g_last_error = "adc_debug_run(ADC_RUN_SCANLINE): a speculative row segment failed its seam check; rerun with ADC_SO_SEG=1";
+            return 3;
+        }
     }
     if (stage == ADC_RUN_MEDIAN && h->pin_flags && h->pin_flags[0] != 0) { // what adc_wait does behind a Match
         e = adc_median_fallback(h);

@@ -269,8 +269,8 @@ ADC_HD IrvBlock irv_decode_block(uint32_t vx, uint32_t vy, uint32_t vz, uint32_t
 // them or not), so an entry that is skipped would vote what it voted.
 // Division-free form (a vote computes it for every level it decides): thresholds moved by 2^-20 relative -- 16 times the rounding of
 // the reference's float division -- so that the REAL inequalities  (m + k) <= tl (c - k)  /  (m - k) >= th (c + k)  imply the
-// float tests; solved for k with a precomputed 1 / (1 + t); the float evaluation of the bound is off by < 0.01 for counts up to
-// 69 x 69, one is subtracted.  K = 0 is always valid, and so is every value below the true bound (the tests are monotone in k).
+// float tests; solved for k with a precomputed 1 / (1 + t); the float evaluation of the bound is off by well below one for counts up
+// to 511 x 511 (arms of 255, the reference's maximum; emul_irv_slack_check), one is subtracted.  K = 0 is always valid, and so is every value below the true bound (the tests are monotone in k).
 struct IrvSlackK { float tl, rl, th, rh; int ok; };
 ADC_HD IrvSlackK irv_slack_consts(float irv_th)
 {
@@ -307,3 +307,12 @@ ADC_HD int irv_level_slack(bool pass, int c, int m, int m2, int ts, const IrvSla
 // Kernel k sets bits in plane k % 3, reads plane (k + 2) % 3 (its predecessor's) and clears plane (k + 1) % 3 for its successor.
 #define IRV_PX_PLANES 3
 ADC_HD int irv_px_pitch(int W) { return ((W + 31) >> 5) + 4; } // (+4: a 16-byte load that starts at a row's last word stays inside the row)
+// The slack count of an entry (k_voting.hip: irv_region_changes) reads ONE 128-bit window of a bitmap row, starting at the word of the
+// rectangle's left end xa: it sees every column of the rectangle only while (xa & 31) + ml + mr + 1 <= 128.  Arms are at most
+// min(cross_L1, 255), so that holds for every entry up to an arm limit of 48 (31 + 2 * 48 + 1 = 128).  Above it a row's columns past
+// the window would go uncounted, the budget would not be used up, and an entry that has to vote again would be skipped: the budgets
+// are off for longer arms (every hit entry votes again, as with ADC_IRV_SLACK=0).
+#ifndef IRV_SLACK_MAX_ARM
+#define IRV_SLACK_MAX_ARM 48 // (A/B builds only: tools/build_variant.sh with -DIRV_SLACK_MAX_ARM=255 brings the undercount back)
+#endif
+ADC_HD int irv_slack_mode(int use_slack, int cross_L1) { return adc_imin(cross_L1, 255) > IRV_SLACK_MAX_ARM ? 0 : use_slack; }

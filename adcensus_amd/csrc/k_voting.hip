@@ -709,7 +709,7 @@ static hipError_t irv_launch(adc_handle* h, int k0, int count)
                            reinterpret_cast<const IrvCold*>(h->irv_cold), h->st16, reinterpret_cast<int4*>(h->vote_list), h->chg_a,
                            reinterpret_cast<const uint32_t*>(h->arms), p.W, p.H, h->st16_pitch, p.dmin, p.D, chg_bytes, tpitch, p.opt.irv_ts, p.opt.irv_th,
                            h->vote_evals_arr, (int)irv_seg_cap(p.W, p.H, h->irv_grid, wpb, h->irv_xcd_mode), h->vote_evals_arr + (size_t)IRV_MAXW * h->irv_grid,
-                           h->irv_px, irv_px_pitch(p.W), irv_use_slack());
+                           h->irv_px, irv_px_pitch(p.W), irv_slack_mode(irv_use_slack(), p.opt.cross_L1)); // (budgets off above arm limit 48: irv_plan.h)
     return hipGetLastError();
 }
 

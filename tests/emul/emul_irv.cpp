@@ -12,10 +12,13 @@
 #include "../../adcensus_amd/csrc/irv_plan.h"
 
 // use_slack (0 = off, else the number of hit entries per wave from which the wave filters; the product's default is 1): the slack budgets of round 6 (irv_plan.h, bottom): per-pixel change planes, a budget per entry (low half of the entry's
-// box word), changed pixels counted over the region -- as in the kernel
-extern "C" long emul_irv_chain2(float* disp, const uint8_t* label, const uint8_t* arms, const uint16_t* sup_h, int W, int H, int dmin,
-                                int D, int irv_ts, float irv_th, int min_region, unsigned seed, int groups, int wpb, int use_slack, long* out_stats)
+// box word), changed pixels counted over the region -- as in the kernel: from one 128-bit window of the bitmap row per region row,
+// and switched off by the host above arm limit 48 (irv_slack_mode with the handle's cross_L1)
+extern "C" long emul_irv_chain3(float* disp, const uint8_t* label, const uint8_t* arms, const uint16_t* sup_h, int W, int H, int dmin,
+                                int D, int irv_ts, float irv_th, int min_region, unsigned seed, int groups, int wpb, int use_slack, int cross_L1,
+                                long* out_stats)
 {
+    use_slack = irv_slack_mode(use_slack, cross_L1);
     const int P = W * H, SP = (W + 7) & ~7, T = IRV_TILE;
     const int tiles_x = (W + T - 1) / T, tiles_y = (H + T - 1) / T;
     const int G = groups > 0 ? groups : 2, WPB = wpb > 0 ? wpb : 4; // the (emulated) grid: decides the list layout
@@ -152,13 +155,15 @@ extern "C" long emul_irv_chain2(float* disp, const uint8_t* label, const uint8_t
                         }
                         if (dirty && use_slack > 0 && round != 0 && nh >= use_slack) { // phase 1 (k_voting.hip): changed pixels of the region's bounding RECTANGLE in the
                             // previous kernel's plane (a superset of the region: an upper bound; no arm lookups), without the entry's own pixel,
-                            // against the entry's budget
+                            // against the entry's budget.  Per row the kernel reads the 128 bits from word xa >> 5 on (irv_region_changes):
+                            // columns past them are not counted (which irv_slack_mode keeps from happening)
                             const uint8_t* pa = arms + (size_t)p * 4;
                             const int ml = (e.box >> 16) & 255, mr = (e.box >> 24) & 255;
+                            const int xa = x - ml, xw = std::min(x + mr, ((xa >> 5) << 5) + 127);
                             int used = 0;
                             for (int yy = y - (int)pa[2]; yy <= y + (int)pa[3]; yy++)
-                                for (int xx = x - ml; xx <= x + mr; xx++)
-                                    if (!(yy == y && xx == x)) used += px_rd[(size_t)yy * W + xx];
+                                for (int xx = xa; xx <= xw; xx++) used += px_rd[(size_t)yy * W + xx];
+                            used -= px_rd[(size_t)y * W + x]; // (the kernel takes the own pixel's bit off, inside the window or not)
                             const int rem = (e.box & 0xFFFF) - used;
                             dirty = rem < 0;
                             if (rem >= 0 && used > 0) e.box = (int)(((uint32_t)e.box & 0xFFFF0000u) | (uint32_t)rem);
@@ -230,6 +235,12 @@ extern "C" long emul_irv_chain2(float* disp, const uint8_t* label, const uint8_t
     return fin[0] == IRV_DONE ? fin[5] : -2;
 }
 
+extern "C" long emul_irv_chain2(float* disp, const uint8_t* label, const uint8_t* arms, const uint16_t* sup_h, int W, int H, int dmin,
+                                int D, int irv_ts, float irv_th, int min_region, unsigned seed, int groups, int wpb, int use_slack, long* out_stats)
+{
+    return emul_irv_chain3(disp, label, arms, sup_h, W, H, dmin, D, irv_ts, irv_th, min_region, seed, groups, wpb, use_slack, 34, out_stats);
+}
+
 extern "C" long emul_irv_chain(float* disp, const uint8_t* label, const uint8_t* arms, const uint16_t* sup_h, int W, int H, int dmin,
                                int D, int irv_ts, float irv_th, int min_region, unsigned seed, int groups, int wpb, long* out_stats)
 {
@@ -244,25 +255,44 @@ static bool slack_holds(bool pass, int c, int m, int m2, int ts, float th, int k
     if (!pass) return (c + k <= ts) || (c - k >= 1 && !((float)(m + k) * 1.0f / (float)(c - k) > th));
     return (c - k > ts) && (m - k >= 1) && ((float)(m - k) * 1.0f / (float)(c + k) > th) && (m - k > m2 + k);
 }
-extern "C" long emul_irv_slack_check(unsigned seed, long trials)
+// *clamped (may be null): trials whose largest valid budget is above 0xFFFF, where the returned K must be the clamp itself.
+extern "C" long emul_irv_slack_check2(unsigned seed, long trials, long* clamped)
 {
     srand(seed);
-    long invalid = 0, loose = 0;
+    long invalid = 0, loose = 0, nclamped = 0;
     for (long t = 0; t < trials; t++) {
-        const int ts = rand() % 60 - 5;
+        // counts up to (2 * 255 + 1)^2 = 261121 (arms of 255, the reference's maximum) and thresholds ts across the count range;
+        // every fourth level a large count, so that budgets beyond the 0xFFFF clamp occur
+        const int cmax = t % 4 == 0 ? 261122 : (t % 4 == 1 ? 9410 : 400);
+        const int c = (int)(((long)rand() * 32768L + rand()) % cmax), m = c ? 1 + (int)(((long)rand() * 32768L + rand()) % c) : 0;
+        const int m2 = std::min(m, c - m > 0 ? (int)(((long)rand() * 32768L + rand()) % (c - m + 1)) : 0);
+        const int ts = t % 3 == 0 ? rand() % 60 - 5 : (int)(((long)rand() * 32768L + rand()) % (c + 2)) - 1;
         const float th = (float)(rand() % 1000) / 1000.0f;
-        const int c = rand() % (t % 4 == 0 ? 5000 : 400), m = c ? 1 + rand() % c : 0, m2 = std::min(m, c - m > 0 ? rand() % (c - m + 1) : 0);
         const bool pass = m > 0 && c > ts && (float)m * 1.0f / (float)c > th;
         const int K = irv_level_slack(pass, c, m, m2, ts, irv_slack_consts(th));
         if (K > 0 && !slack_holds(pass, c, m, m2, ts, th, K)) invalid++;
-        for (int k = 1; k < K; k++) if (!slack_holds(pass, c, m, m2, ts, th, k)) { invalid++; break; } // (monotone: everything below K holds too)
-        int best = 0;
-        while (best < 5000 && slack_holds(pass, c, m, m2, ts, th, best + 1)) best++;
+        // slack_holds is monotone in k by construction (every condition is a bound that only gets harder as k grows: c + k,
+        // c - k, m - k, m2 + k, and float division is monotone), so "every k below K is valid" follows from K, and the largest
+        // valid k is found by bisection (k = 0 always holds).  The monotonicity is not assumed blindly: one k below K, drawn at
+        // random, is checked directly as well (the old per-k loop, which stopped at counts of 5000).
+        if (K > 1 && !slack_holds(pass, c, m, m2, ts, th, (int)(((long)rand() * 32768L + rand()) % K))) invalid++;
+        int lo = 0, hi = 2 * 261121 + 2;
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            (slack_holds(pass, c, m, m2, ts, th, mid) ? lo : hi) = mid;
+        }
+        const int best = lo;
         if (K > best) invalid++;
+        if (best > 0xFFFF + 3) { // the clamp: irv_level_slack returns exactly 0xFFFF where the valid range goes past it
+            nclamped++;
+            if (K != 0xFFFF) invalid++;
+        }
         if (best - K > 3 && K < 0xFFFF) loose++;
     }
+    if (clamped) *clamped = nclamped;
     return invalid * 1000000 + loose;
 }
+extern "C" long emul_irv_slack_check(unsigned seed, long trials) { return emul_irv_slack_check2(seed, trials, nullptr); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The packed-halfword helpers of irv_plan.h against per-pixel loops on random inputs (values drawn so that equal keys,

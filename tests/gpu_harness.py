@@ -7,6 +7,11 @@ import adcensus_amd as A
 from tests import cases
 
 
+# Largest arm limit up to which every stage case's scanline seams held with the production warm-up (measured on MI355X: all cases
+# up to cross_L1 = 49, and 64 with cross_L2 = 64; seams failed at 64 with cross_L2 = 200, at 128 and at 255 on flat-patch images).
+SO_SEAMS_HOLD_UP_TO_L1 = 49
+
+
 def diff(got, want):
     """(number of differing elements, first differing index or None)"""
     g = np.ascontiguousarray(got)
@@ -80,14 +85,26 @@ def stage_report(left, right, opt, o, device=0, paper_modes=0):
         rec("cost_aggr(pass pairs)", st.debug_read(A.BUF_VOLUME_A), o["cost_aggr"])
 
         st.debug_write(A.BUF_VOLUME_A, o["cost_aggr"])
-        st.debug_run(A.RUN_SCANLINE, 4)
+        seam_error = None
+        try:
+            st.debug_run(A.RUN_SCANLINE, 4)
+        except RuntimeError as exc:
+            # a failed seam of the speculative row segments: the handle now runs whole rows (as adc_wait redoes it behind a Match)
+            if "seam check" not in str(exc):
+                raise
+            seam_error = str(exc)
+            st.debug_write(A.BUF_VOLUME_A, o["cost_aggr"])
+            st.debug_run(A.RUN_SCANLINE, 4)
         rec("cost_so", st.debug_read(A.BUF_VOLUME_A), o["cost_so"])
         # the row passes were cut into verified segments when counter 5 > 1: no seam may have failed (counter 6) -- with the
-        # production warm-up; a run with ADC_SO_WARM < 64 (test_scanline_segment_variants) expects failures and checks the redo
+        # production warm-up; a run with ADC_SO_WARM < 64 (test_scanline_segment_variants) expects failures and checks the redo.
+        # Long arms aggregate flat regions into volumes whose path costs need more than the 64-column warm-up to converge: seams
+        # may fail there, and the redo with whole rows must be exact.  No bound on the arm limit follows from the scanline itself
+        # (convergence depends on how flat the volume is); SO_SEAMS_HOLD_UP_TO_L1 is the measured one of the suite's cases.
         import os
         rep["cost_so"]["segments"] = st.debug_counter(5)
-        rep["cost_so"]["seam_fails"] = st.debug_counter(6) if st.debug_counter(5) > 1 else 0
-        if int(os.environ.get("ADC_SO_WARM", "64")) >= 64:
+        rep["cost_so"]["seam_fails"] = 1 if seam_error else (st.debug_counter(6) if st.debug_counter(5) > 1 else 0)
+        if int(os.environ.get("ADC_SO_WARM", "64")) >= 64 and min(opt.cross_L1, 255) <= SO_SEAMS_HOLD_UP_TO_L1:
             assert rep["cost_so"]["seam_fails"] == 0, rep["cost_so"]
 
         # production form of the scanline stage: the last pass also delivers the left-view winner-takes-all

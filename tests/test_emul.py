@@ -29,6 +29,10 @@ LANE_CASES = EMUL_CASES + ["s2_320x180_d128", "s2_200x120_d200", "noise_160x90_d
                            "noise_96x50_d160_neg", "s2_360x60_d300", "noise_80x40_d520"]
 
 
+# long arm limits whose arms reach 128 and 255 on short lines: ring depths of up to 511 entries, halos of 2L past the line ends
+LONG_ARM_CASES = ["flat_640x96_L128", "flat_200x64_L255", "flat_600x1_L255", "flat_1x300_L255"]
+
+
 @pytest.fixture(scope="module")
 def dumps(port_oracle):
     cache = {}
@@ -41,7 +45,7 @@ def dumps(port_oracle):
     return get
 
 
-@pytest.mark.parametrize("name", ["s2_96x64_d32", "q_20x40_d32", "q_9x20_d8", "q_1x40_d8", "q_40x1_d8", "q_3x3_d2"])
+@pytest.mark.parametrize("name", ["s2_96x64_d32", "q_20x40_d32", "q_9x20_d8", "q_1x40_d8", "q_40x1_d8", "q_3x3_d2"] + LONG_ARM_CASES)
 @pytest.mark.parametrize("pf,hseg,vseg", [(8, 1, 1), (8, 4, 2), (5, 3, 1), (2, 1, 7)])
 def test_marching_ring_aggregation(emul, dumps, name, pf, hseg, vseg):
     left, right, opt, o = dumps(name)
@@ -59,7 +63,7 @@ def test_marching_ring_aggregation(emul, dumps, name, pf, hseg, vseg):
     assert same(a, o["cost_aggr"])
 
 
-@pytest.mark.parametrize("name", ["s2_96x64_d32", "q_20x40_d32", "q_9x20_d8", "q_1x40_d8", "q_40x1_d8", "q_3x3_d2"])
+@pytest.mark.parametrize("name", ["s2_96x64_d32", "q_20x40_d32", "q_9x20_d8", "q_1x40_d8", "q_40x1_d8", "q_3x3_d2"] + LONG_ARM_CASES)
 @pytest.mark.parametrize("pf,hseg,vseg", [(8, 1, 1), (8, 3, 2), (3, 2, 5)])
 def test_marching_ring_pass_pairs(emul, dumps, name, pf, hseg, vseg):
     """Production launch sequence on short-arm images: H0 | V0+V1 | H1+H2 | V2+V3 | H3 (8 passes in 5 launches); a pair =
@@ -632,12 +636,15 @@ def test_voting_tiles_partition_the_image(emul):
 
 def test_voting_slack_budget_closed_forms(emul):
     """irv_plan.h: irv_level_slack -- the budget of a vote level (how many region pixels may change before the level's outcome can)
-    -- is VALID (the level's tests hold at K and below) on a million random levels, and within 3 of the largest valid value."""
-    emul.emul_irv_slack_check.restype = C.c_long
+    -- is VALID (the level's tests hold at K and below) on a million random levels with counts up to 511 x 511 (arms of 255) and
+    thresholds across the count range, at most the 0xFFFF clamp, and within 3 of the largest valid value below the clamp."""
+    emul.emul_irv_slack_check2.restype = C.c_long
     for seed in (1, 2, 3):
-        r = emul.emul_irv_slack_check(seed, C.c_long(400000))
+        clamped = C.c_long(0)
+        r = emul.emul_irv_slack_check2(seed, C.c_long(400000), C.byref(clamped))
         assert r // 1000000 == 0, r  # no invalid budget, ever
         assert r % 1000000 <= 4000, r  # (loose ones: float rounding right at the threshold)
+        assert clamped.value > 1000, clamped.value  # levels whose largest valid budget lies above the 0xFFFF clamp were drawn
 
 
 def test_voting_packed_halfword_helpers(emul):
@@ -679,3 +686,61 @@ def test_voting_chain_slack_budgets_random_cases(emul, port_oracle, case):
             evals[(slack, seed)] = stats[1]
     assert sum(v for (s, _), v in evals.items() if s == 1) <= sum(v for (s, _), v in evals.items() if s == 0)
     assert sum(v for (s, _), v in evals.items() if s == 8) <= sum(v for (s, _), v in evals.items() if s == 0)
+
+
+@pytest.mark.parametrize("case", range(8))
+def test_voting_chain_long_arms(emul, port_oracle, case):
+    """The voting chain as the product runs it above arm limit 48 (irv_slack_mode: no slack budgets, every hit entry votes again) on
+    wide flat-patch images whose arms reach the limit (49 / 64 / 128 / 255), under shuffled schedules and two work-list layouts:
+    the reference's region voting.  (The guard itself is pinned by test_voting_slack_window_guard_on_a_constructed_region: these
+    images do not depend on it.)"""
+    from oracle import pyoracle
+    rng = np.random.default_rng(7000 + case)
+    w, h = int(rng.integers(512, 700)), int(rng.integers(48, 110))
+    D = int(rng.choice([16, 32]))
+    L1 = [49, 64, 128, 255][case % 4]
+    left, right = cases.flat_patch_pair(w, h, D, seed=700 + case)
+    opt = pyoracle.Option(max_disparity=D, irv_ts=int(rng.choice([0, 3, 8, 20])), irv_th=float(rng.choice([0.05, 0.2, 0.4, 0.6])),
+                          cross_L1=L1, cross_L2=int(rng.choice([L1 // 2, L1])))
+    o = port_oracle.run(left, right, opt)
+    assert int((o["disp_after_irv"].view(np.uint32) != o["disp_after_lr"].view(np.uint32)).sum()) > 0  # (an active voting chain)
+    emul.emul_irv_chain3.restype = C.c_long
+    for seed, groups, wpb in ((21, 2, 4), (22, 16, 2)):
+        d, stats = o["disp_after_lr"].copy(), (C.c_long * 3)()
+        r = emul.emul_irv_chain3(P(d), P(o["outlier_label"]), P(o["arms"]), P(o["sup_count_h"]), w, h, 0, D, opt.irv_ts,
+                                 C.c_float(opt.irv_th), opt.irv_ts if L1 <= 127 else -1, seed, groups, wpb, 1, L1, stats)
+        assert r >= 0, r
+        assert same(d, o["disp_after_irv"]), (case, L1, seed)
+
+
+def test_clamped_arm_limits_equal_255_in_golden():
+    """The reference clamps arms to MAX_ARM_LENGTH = 255 (cross_aggregator.cpp:151): the golden dumps of cross_L1 = 300 and 1000
+    are those of 255, stage for stage."""
+    import json
+    with open(os.path.join(cases.GOLDEN_DIR, "golden.json")) as f:
+        gold = json.load(f)["cases"]
+    for name, same_as in cases.CLAMPED_CASES.items():
+        assert gold[name] == gold[same_as], name
+
+
+def test_voting_slack_window_guard_on_a_constructed_region(emul):
+    """The decisive changes of a vote lie past the 128 columns the slack count reads per row (tests/cases.py:
+    slack_window_voting_input).  With the budgets on (what the kernel did for every arm limit before irv_slack_mode), the entry's
+    budget of 10 absorbs 73 uncounted fills and its second vote is never taken: a wrong map.  With the product's guard (arm limit
+    255 > IRV_SLACK_MAX_ARM: no budgets) the chain is the reference's region voting, under several work-list layouts."""
+    disp, label, arms, sup_h, opt = cases.slack_window_voting_input()
+    h, w = disp.shape
+    D = opt.max_disparity - opt.min_disparity
+    want = cases.region_voting_reference(disp, label, arms, opt)
+    assert want[0, 0] == 9.0 and disp[0, 0] == np.inf
+    emul.emul_irv_chain3.restype = C.c_long
+
+    def chain(cross_l1, seed, groups, wpb):
+        d, stats = disp.copy(), (C.c_long * 3)()
+        assert emul.emul_irv_chain3(P(d), P(label), P(arms), P(sup_h), w, h, 0, D, opt.irv_ts, C.c_float(opt.irv_th), -1,
+                                    seed, groups, wpb, 1, cross_l1, stats) >= 0
+        return d
+    # the window alone (budgets on: an arm limit the guard lets through, same arms): the 73 fills go uncounted
+    assert not same(chain(48, 1, 1, 1), want)
+    for seed, groups, wpb in ((1, 1, 1), (2, 2, 4), (3, 16, 1)):
+        assert same(chain(opt.cross_L1, seed, groups, wpb), want), (seed, groups, wpb)

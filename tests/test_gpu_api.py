@@ -366,7 +366,8 @@ def test_aggregation_fast_path_equals_direct(hip, oracle, monkeypatch):
 
 
 def test_large_arm_limit_uses_fallback(hip, oracle):
-    """cross_L1 = 120 exceeds the LDS ring budget -> direct kernel; still bit-exact."""
+    """cross_L1 = 120 on a 96 x 64 image: a ring of 241 entries (every arm limit up to 255 runs on the LDS marching ring; no arm can
+    be longer than 95 here, tests/test_gpu_long_arms.py covers arms that reach the limit); bit-exact."""
     A = hip
     from oracle import pyoracle
     left, right, _ = cases.make_case("s2_96x64_d32")

@@ -61,3 +61,38 @@ def test_random_geometries_and_options_equal_oracle(hip, oracle, seed):
                 bad.append(tag + " (Match %d: %d pixels)" % (rep, int((d.view(np.uint32) != o["disp_final"].view(np.uint32)).sum())))
         st.Release()
     assert not bad, bad
+
+
+@pytest.mark.parametrize("seed", [505, 606])
+def test_random_long_arm_limits_equal_oracle(hip, oracle, seed):
+    """Long arm limits (49 / 64 / 128 / 255: past the voting slack count's 128-bit window, rings of up to 511 entries) on flat-patch
+    images whose arms reach them (tests/cases.py: flat_patch_pair): the voting stage in isolation and the whole Match, bit for bit."""
+    A = hip
+    rng = np.random.default_rng(seed)
+    bad = []
+    for k in range(3):
+        w, h = int(rng.integers(300, 700)), int(rng.integers(40, 200))
+        d = int(rng.choice([16, 32, 64]))
+        l1 = int(rng.choice([49, 64, 128, 255]))
+        left, right = cases.flat_patch_pair(w, h, d, seed=int(rng.integers(1, 1 << 30)))
+        opt = pyoracle.Option(max_disparity=d, cross_L1=l1, cross_L2=int(rng.choice([l1 // 2, l1])),
+                              irv_ts=int(rng.choice([0, 5, 20, 45])), irv_th=float(rng.choice([0.1, 0.4, 0.7])))
+        o = oracle.run(left, right, opt)
+        tag = "seed %d case %d: %dx%d D %d L1 %d L2 %d ts %d th %.1f" % (seed, k, w, h, d, l1, opt.cross_L2, opt.irv_ts, opt.irv_th)
+        st = A.ADCensusStereo(device=0)
+        assert st.Initialize(w, h, cases.to_product_option(opt)), tag
+        st.debug_set_images(left, right)
+        st.debug_write(A.BUF_ARMS, o["arms"])
+        st.debug_write(A.BUF_SUPCOUNT_H, o["sup_count_h"])
+        st.debug_write(A.BUF_DISP_LEFT, o["disp_after_lr"])
+        st.debug_write(A.BUF_OUTLIER_LABEL, o["outlier_label"])
+        st.debug_run(A.RUN_REGION_VOTING)
+        got = np.asarray(st.debug_read(A.BUF_DISP_LEFT)).view(np.uint32)
+        if not np.array_equal(got, o["disp_after_irv"].view(np.uint32)):
+            bad.append(tag + " (voting stage: %d pixels)" % int((got != o["disp_after_irv"].view(np.uint32)).sum()))
+        for rep in range(2):
+            dm = st.match(left, right)
+            if not np.array_equal(dm.view(np.uint32), o["disp_final"].view(np.uint32)):
+                bad.append(tag + " (Match %d: %d pixels)" % (rep, int((dm.view(np.uint32) != o["disp_final"].view(np.uint32)).sum())))
+        st.Release()
+    assert not bad, bad

@@ -12,7 +12,12 @@ STAGE_CASES = ["s2_96x64_d32", "q_257x131_d64", "q_20x40_d32", "q_9x20_d8", "q_3
                # min_disparity > 0, 128 < D < 192 (all-padding chunk), D > 256 up to the maximum of 2047, discontinuity adjustment with dmin != 0
                "cone_pos", "q_40x30_pos_wltd", "noise_160x90_d128_pos", "s2_150x100_pos", "s2_200x120_d160",
                "noise_96x50_d160_neg", "s2_360x60_d300", "noise_80x40_d520", "s2_72x48_d1024", "noise_64x24_d1100", "s2_80x20_d2047",
-               "cone_crop_dda_neg", "cone_crop_dda_pos"]
+               "cone_crop_dda_neg", "cone_crop_dda_pos",
+               # long arm limits up to 255 (and the clamp above it), odd arm options and shapes.  (The cases whose 16-bit support
+               # counts wrap, wrap0_320x288_d16 / wrap_320x320_d8, are pinned up to the aggregation: tests/test_gpu_long_arms.py)
+               "flat_640x96_L48", "flat_640x96_L49", "flat_640x96_L64", "flat_640x96_L128", "flat_640x96_L255", "flat_640x96_L300",
+               "flat_640x96_L1000", "flat_560x320_L255", "flat_640x96_L64_L2gt", "flat_640x96_L128_L2zero", "flat_640x96_L128_t2t1",
+               "flat_200x64_L255", "flat_600x1_L255", "flat_1x300_L255"]
 
 
 @pytest.mark.parametrize("name", STAGE_CASES)

@@ -3,7 +3,8 @@
 (oracle/_ref, i.e. the reference's own sources compiled in place with the canonical recipe).
 
 Run in the build container (where /root/reference exists):
-    make -C oracle ref && python tools/make_golden.py
+    make -C oracle ref && python tools/make_golden.py            # every case, image fixtures rewritten
+    python tools/make_golden.py NAME...                            # only these cases, merged into the existing table
 
 Writes
   tests/golden/cone_pair.npz     the Middlebury Cone pair of the reference's Data/ dir as BGR arrays
@@ -33,10 +34,11 @@ def bgr(path):
     return np.ascontiguousarray(np.array(Image.open(path).convert("RGB"))[:, :, ::-1])
 
 
-def main():
+def main(names):
     gold = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gold, exist_ok=True)
-    if os.path.isdir(REF_DATA):
+    table = os.path.join(gold, "golden.json")
+    if not names and os.path.isdir(REF_DATA):
         np.savez_compressed(os.path.join(gold, "cone_pair.npz"),
                             left=bgr(os.path.join(REF_DATA, "Cone", "im2.png")),
                             right=bgr(os.path.join(REF_DATA, "Cone", "im6.png")))
@@ -47,14 +49,20 @@ def main():
             np.savez_compressed(os.path.join(data, name + "_right.npz"), right=bgr(os.path.join(REF_DATA, r)))  # each below 1 MiB)
     ref = pyoracle.load("reference")
     out = {"_generator": "tools/make_golden.py", "_oracle": "oracle/_ref (reference sources, canonical recipe)", "cases": {}}
-    for name in cases.GOLDEN_CASES:
+    if names:
+        unknown = [n for n in names if n not in cases.GOLDEN_CASES]
+        if unknown:
+            raise SystemExit("unknown cases: %s" % unknown)
+        with open(table) as f:
+            out = json.load(f)
+    for name in names or cases.GOLDEN_CASES:
         left, right, opt = cases.make_case(name)
         dumps = ref.run(left, right, opt)
         out["cases"][name] = {k: hashlib.sha256(cases.canonical(k, v, opt).tobytes()).hexdigest() for k, v in dumps.items()}
         print(name, left.shape, "final", out["cases"][name]["disp_final"][:16], flush=True)
-    with open(os.path.join(gold, "golden.json"), "w") as f:
+    with open(table, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
