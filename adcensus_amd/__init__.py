@@ -24,6 +24,10 @@ STAGES = ["cost", "arms", "aggregate", "scanline", "wta", "refine"]
  RUN_INTERPOLATION, RUN_DISCONTINUITY, RUN_MEDIAN) = range(11)
 MAX_DISP_RANGE = 2047
 PAPER_CENSUS5X5, PAPER_SO_SUM, PAPER_RIGHT_ARMS = 1, 2, 4  # adc_set_paper_modes (opt-in, not the reference's behaviour)
+# provenance codes of match_ex (adc_match_ex): code = lr | (fill << PROV_FILL_SHIFT)
+LR_CONSISTENT, LR_MISMATCH, LR_OCCLUSION = 0, 1, 2
+FILL_WTA, FILL_VOTING, FILL_INTERPOLATION, FILL_NONE = 0, 1, 2, 3
+PROV_LR_MASK, PROV_FILL_SHIFT = 3, 2
 
 
 class ADCensusOption(C.Structure):
@@ -76,6 +80,11 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.adc_match_device.argtypes = [vp, vp, vp, vp]
     L.adc_match_device.restype = C.c_int
+    if hasattr(L, "adc_match_ex"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_match_ex.argtypes = [vp, u8p, u8p, vp, vp, vp]
+        L.adc_match_ex.restype = C.c_int
+        L.adc_match_device_ex.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.adc_match_device_ex.restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
     L.adc_stage_name.argtypes = [C.c_int]
@@ -287,6 +296,36 @@ class ADCensusStereo:
         return d
 
     # -- additive API --------------------------------------------------------------------------
+    def MatchEx(self, img_left, img_right, disp_left, provenance=None, confidence=None):
+        """Match plus the optional per-pixel maps (adc_match_ex): provenance uint8 [H][W] (code = lr | fill << 2, LR_* / FILL_*),
+        confidence float32 [H][W]; either may be None (both None: exactly Match).  False where Match is, and on a handle with paper
+        modes set when a map is requested."""
+        if not self._h:
+            return False
+        if img_left is None or img_right is None or disp_left is None:
+            return False
+        l, r = _img(img_left), _img(img_right)
+        n = self.width * self.height
+        assert l.size == n * 3 and r.size == l.size
+        assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        for a, dt in ((provenance, np.uint8), (confidence, np.float32)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
+        return lib().adc_match_ex(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data,
+                                  None if provenance is None else provenance.ctypes.data,
+                                  None if confidence is None else confidence.ctypes.data) == 0
+
+    def match_ex(self, img_left, img_right):
+        """Convenience: returns new (disparity float32, provenance uint8, confidence float32) [H][W] maps; raises on failure."""
+        shp = (self.height, self.width)
+        d, p, c = np.empty(shp, np.float32), np.empty(shp, np.uint8), np.empty(shp, np.float32)
+        if not self.MatchEx(img_left, img_right, d, p, c):
+            raise RuntimeError("MatchEx failed: " + last_error())
+        return d, p, c
+
+    def match_device_ex(self, d_left, d_right, d_disp, d_provenance=None, d_confidence=None):
+        """match_device plus the optional maps into the caller's device buffers (ints or None); asynchronous, call wait()."""
+        return lib().adc_match_device_ex(self._h, d_left, d_right, d_disp, d_provenance, d_confidence) == 0
+
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do
         not overwrite or free them before (the handle keeps no pointer to them afterwards)."""

@@ -173,6 +173,10 @@ struct adc_handle {
     float* async_dst;
     int async_dst_direct; // 0 = via pin_out + host copy, 1 = DMA into the caller's page-locked map, 2 = pageable copy by adc_wait (ADC_HOST_DIRECT)
     void* device_dst;  // adc_match_device: the caller's device buffer (re-filled by the median fallback)
+    uint8_t* x_prov;   // adc_match_ex / adc_match_device_ex: where this Match's provenance / confidence maps go (the caller's device
+    float* x_conf;     // buffers or the scratch below; NULL: not requested); kept until adc_wait, so that its redos write them again
+    uint8_t* xs_prov;  // device scratch of adc_match_ex (host callers), allocated on the first call that needs it
+    float* xs_conf;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -218,6 +222,8 @@ hipError_t adc_launch_wta_left(adc_handle* h);                  // vol_a -> disp
 hipError_t adc_paper_aggregate(adc_handle* h, int iterations);  // k_paper.hip: aggregation limited by both images' arms
 hipError_t adc_paper_accumulate(adc_handle* h, float* acc, const float* src, int first, int last);
 hipError_t adc_launch_lrcheck(adc_handle* h);
+hipError_t adc_launch_confidence(adc_handle* h);                // k_extras.hip: vol_a -> x_conf (heavy stream, behind the WTA)
+hipError_t adc_launch_provenance(adc_handle* h);                // label, disp_l -> x_prov, x_conf = 0 where filled (object stream)
 size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)

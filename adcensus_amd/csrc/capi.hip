@@ -329,7 +329,7 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c};
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -347,6 +347,7 @@ void adc_destroy(adc_handle* h)
 static hipError_t run_refine_tail(adc_handle* h)
 {
     const adc_option& o = h->p.opt;
+    if (h->x_prov || h->x_conf) HIP_OK(adc_launch_provenance(h)); // (adc_match_ex: reads the voted map before interpolation fills it)
     if (o.do_filling && o.do_lr_check) HIP_OK(adc_launch_interpolation(h));
     if (o.do_discontinuity_adjustment) HIP_OK(adc_launch_discontinuity(h));
     HIP_OK(adc_launch_median(h));
@@ -450,6 +451,7 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     }
     MARK(4, h->heavy);
     HIP_OK(adc_launch_wta(h));                   // ComputeDisparity + ComputeDisparityRight, :108-109
+    if (h->x_conf) HIP_OK(adc_launch_confidence(h)); // (adc_match_ex: one more read of the optimised volume)
     MARK(5, h->heavy);
     // maxima + violation flag of this pair, looked at by adc_wait (they seed the next Match's assumption)
     if (h->pin_flags) HIP_OK(hipMemcpyAsync(h->pin_flags + 4, h->armmax, 4 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
@@ -533,6 +535,7 @@ static void abort_match(adc_handle* h)
     h->force_median_fallback = 0;
     h->async_dst = nullptr;
     h->device_dst = nullptr;
+    h->x_prov = nullptr; h->x_conf = nullptr;
     if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
@@ -715,6 +718,7 @@ int adc_wait(adc_handle* h)
         h->async_dst = nullptr;
     }
     h->device_dst = nullptr;
+    h->x_prov = nullptr; h->x_conf = nullptr;
     // adc_match_device BORROWED the caller's device images until here: nothing of the handle may point at them any
     // more (a later debug stage would otherwise read memory the caller has reused or freed)
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) {
@@ -731,6 +735,56 @@ int adc_match(adc_handle* h, const uint8_t* left, const uint8_t* right, float* d
     const int rc = match_async_impl(h, left, right, disp, true);
     if (rc != 0) return rc;
     return adc_wait(h);
+}
+
+// ------------------------------------------------------------------------------ optional per-pixel maps (k_extras.hip)
+// The confidence kernel runs behind the WTA in run_heavy, the provenance kernel at the top of run_refine_tail: every redo of
+// adc_wait goes through one of the two, so the maps always describe the delivered disparity map.
+static bool extras_allowed(adc_handle* h, const char* who)
+{
+    if (!h->paper) return true;
+    g_last_error = std::string(who) + ": provenance / confidence maps are not defined with paper modes set";
+    return false;
+}
+
+int adc_match_ex(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, uint8_t* prov, float* conf)
+{
+    if (!prov && !conf) return adc_match(h, left, right, disp);
+    if (!h || !left || !right || !disp) return 1;
+    if (!extras_allowed(h, "adc_match_ex")) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    if (prov && !h->xs_prov && ADC_HIP(hipMalloc(&h->xs_prov, P)) != hipSuccess) {
+        h->xs_prov = nullptr;
+        set_error("adc_match_ex: provenance scratch", hipGetLastError());
+        return 2;
+    }
+    if (conf && !h->xs_conf && ADC_HIP(hipMalloc(&h->xs_conf, P * 4)) != hipSuccess) {
+        h->xs_conf = nullptr;
+        set_error("adc_match_ex: confidence scratch", hipGetLastError());
+        return 2;
+    }
+    h->x_prov = prov ? h->xs_prov : nullptr;
+    h->x_conf = conf ? h->xs_conf : nullptr;
+    int rc = match_async_impl(h, left, right, disp, true);
+    if (rc == 0) rc = adc_wait(h);
+    h->x_prov = nullptr; h->x_conf = nullptr; // (adc_wait / abort_match have cleared them already)
+    if (rc != 0) return rc;
+    if (prov && ADC_HIP(hipMemcpy(prov, h->xs_prov, P, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_ex: provenance copy-out", hipGetLastError()); return 2; }
+    if (conf && ADC_HIP(hipMemcpy(conf, h->xs_conf, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_ex: confidence copy-out", hipGetLastError()); return 2; }
+    return 0;
+}
+
+int adc_match_device_ex(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, void* d_prov, void* d_conf)
+{
+    if (!d_prov && !d_conf) return adc_match_device(h, d_left, d_right, d_disp);
+    if (!h || !d_left || !d_right || !d_disp) return 1;
+    if (!extras_allowed(h, "adc_match_device_ex")) return 1;
+    h->x_prov = static_cast<uint8_t*>(d_prov);
+    h->x_conf = static_cast<float*>(d_conf);
+    const int rc = adc_match_device(h, d_left, d_right, d_disp);
+    if (rc != 0) { h->x_prov = nullptr; h->x_conf = nullptr; }
+    return rc;
 }
 
 // ------------------------------------------------------------------------------ pair farm

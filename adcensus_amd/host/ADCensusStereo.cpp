@@ -80,6 +80,11 @@ bool ADCensusStereo::MatchAsync(const uint8* l, const uint8* r, float32* d)
     if (!impl_ || !l || !r || !d) return false;
     return adc_match_async(impl_, l, r, d) == 0;
 }
+bool ADCensusStereo::MatchEx(const uint8* l, const uint8* r, float32* d, uint8* provenance, float32* confidence)
+{
+    if (!impl_ || !l || !r || !d) return false;
+    return adc_match_ex(impl_, l, r, d, provenance, confidence) == 0;
+}
 bool ADCensusStereo::Wait() { return impl_ && adc_wait(impl_) == 0; }
 bool ADCensusStereo::SetPaperModes(unsigned modes)
 {

@@ -7,6 +7,9 @@
 //   <out>-c.png      cv::applyColorMap(<out>-d, COLORMAP_JET)
 //   <out>-cloud.txt  "x y |d| r g b" per valid pixel ("%f %f %f %d %d %d", colours of the LEFT image)
 // plus <out>.pfm (raw float32 disparity, for bit-exact comparisons).  PNG coding uses zlib (the image has no OpenCV).
+// --extras (anywhere after the program name) also writes the per-pixel maps of ADCensusStereo::MatchEx:
+//   <out>-prov.png   provenance codes (lr | fill << 2, include/adcensus_c_api.h) as 8-bit gray
+//   <out>-conf.png   uchar(confidence * 255);  <out>-conf.pfm  the float32 confidence
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -18,8 +21,22 @@
 #include "ADCensusStereo.h"
 #include "adc_image_io.h"
 
+static void write_pfm(const std::string& path, const float32* px, int w, int h)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (f) { fprintf(f, "Pf\n%d %d\n-1.0\n", w, h); for (int y = h - 1; y >= 0; y--) fwrite(&px[(size_t)y * w], 4, w, f); fclose(f); }
+}
+
 int main(int argc, char** argv)
 {
+    bool extras = false; // (--extras is taken out of argv: the positional arguments keep their meaning)
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--extras")) {
+            extras = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--;
+            break;
+        }
     // file-format helpers that need no GPU (used by the CPU test tier):
     //   --convert in.{png,ppm} out.png       decode + re-encode (R,G,B)
     //   --colormap in-d.png out-c.png        the JET mapping SaveDisparityMap applies to the grey disparity image
@@ -69,8 +86,12 @@ int main(int argc, char** argv)
     printf("AD-Census Initializing Done! Timing :	%lf s\n\n", std::chrono::duration<double>(t1 - t0).count());
     printf("AD-Census Matching...\n");
     std::vector<float32> disparity((size_t)w * h, 0.0f);
+    std::vector<uint8> provenance(extras ? (size_t)w * h : 0);
+    std::vector<float32> confidence(extras ? (size_t)w * h : 0);
     t0 = std::chrono::steady_clock::now();
-    if (!ad_census.Match(left.data(), right.data(), disparity.data())) { printf("AD-Census matching failed: %s\n", ad_census.LastError()); return -2; }
+    const bool ok = extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
+                           : ad_census.Match(left.data(), right.data(), disparity.data());
+    if (!ok) { printf("AD-Census matching failed: %s\n", ad_census.LastError()); return -2; }
     t1 = std::chrono::steady_clock::now();
     printf("\nAD-Census Matching...Done! Timing :	%lf s\n", std::chrono::duration<double>(t1 - t0).count());
 
@@ -97,7 +118,13 @@ int main(int argc, char** argv)
             }
         fclose(f);
     }
-    f = fopen((out + ".pfm").c_str(), "wb");
-    if (f) { fprintf(f, "Pf\n%d %d\n-1.0\n", w, h); for (int y = h - 1; y >= 0; y--) fwrite(&disparity[(size_t)y * w], 4, w, f); fclose(f); }
+    write_pfm(out + ".pfm", disparity.data(), w, h);
+    if (extras) {
+        std::vector<uint8> conf8((size_t)w * h);
+        for (size_t i = 0; i < conf8.size(); i++) conf8[i] = static_cast<uint8>(confidence[i] * 255);
+        if (!write_png(out + "-prov.png", provenance.data(), w, h, 1) || !write_png(out + "-conf.png", conf8.data(), w, h, 1))
+            printf("cannot write %s-prov.png / -conf.png\n", out.c_str());
+        write_pfm(out + "-conf.pfm", confidence.data(), w, h);
+    }
     return 0;
 }

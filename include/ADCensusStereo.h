@@ -9,7 +9,8 @@
  * the C ABI of include/adcensus_c_api.h (HIP kernels for gfx950); there is no CPU path.
  *
  * Additive members (no reference counterpart): SetDevice, SetVerbose (prints the reference's six stage
- * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait.
+ * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait,
+ * MatchEx (per-pixel provenance and confidence maps next to the disparity).
  */
 #pragma once
 
@@ -42,6 +43,10 @@ public:
     void SetProfiling(bool on);
     bool StageMilliseconds(float ms[6]) const;
     bool MatchAsync(const uint8* img_left, const uint8* img_right, float32* disp_left);
+    /** Match plus optional per-pixel maps (adc_match_ex, include/adcensus_c_api.h): provenance uint8 [H][W], code = lr | fill << 2
+     *  (ADC_LR_* / ADC_FILL_*), and confidence float32 [H][W] in [0, 1]; either may be null (both null: exactly Match).  false
+     *  where Match is false, and when a map is requested with paper modes set. */
+    bool MatchEx(const uint8* img_left, const uint8* img_right, float32* disp_left, uint8* provenance, float32* confidence);
     bool Wait();
     /** Opt-in paper features the reference declares / stores but does not implement (bit 0: 5x5 census, adcensus_types.h:39-42;
      *  bit 1: averaged instead of chained scanline paths; bit 2: right-image arms, cross_aggregator.h:91).  0 (default) = the

@@ -16,6 +16,8 @@
  *
  * Additive entry points (no reference counterpart; they do not change Match semantics):
  *   adc_match_device      device-resident in/out buffers (bench: inputs already in HBM)
+ *   adc_match_ex /        the same Matches with two optional per-pixel maps next to the disparity:
+ *   adc_match_device_ex   provenance (measured or filled, ADC_LR_* / ADC_FILL_*) and confidence
  *   adc_match_async/wait  several objects in flight from one host thread
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
@@ -98,6 +100,40 @@ int adc_match(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, 
  * To overlap several pairs on one GPU, keep several handles in flight from ONE host thread (bench.py --inflight N,
  * adc_farm_* below). */
 int adc_match_device(adc_handle* h, const void* d_bgr_left, const void* d_bgr_right, void* d_disp_left);
+
+/* -------------------------------------------------------------------------------------------
+ * Optional per-pixel outputs: which disparities were measured and which were filled, and how distinct the measured minimum is.
+ *
+ * provenance  uint8 [H][W]:  code = lr | (fill << ADC_PROV_FILL_SHIFT)
+ *   lr   (code & ADC_PROV_LR_MASK)   the LR check's outcome (multistep_refiner.cpp:90-151): ADC_LR_CONSISTENT (also: no LR check
+ *        made), ADC_LR_MISMATCH (includes a winner-takes-all result of +inf), ADC_LR_OCCLUSION
+ *   fill (code >> ADC_PROV_FILL_SHIFT)  where the value came from: ADC_FILL_WTA the pixel's own winner-takes-all disparity (lr ==
+ *        0 and that result finite); ADC_FILL_VOTING region voting; ADC_FILL_INTERPOLATION proper interpolation (lr != 0 with
+ *        do_filling, voting left it +inf); ADC_FILL_NONE nothing filled it (lr != 0 without do_filling; with do_lr_check = 0 a
+ *        winner-takes-all result of +inf, code 12).  The discontinuity adjustment and the median do not change the code.
+ * confidence  float32 [H][W]:  0 wherever fill != ADC_FILL_WTA.  Otherwise, over the pixel's scanline-optimised costs C[d]: c1 =
+ *   min C, d1 = the lowest d with C[d] == c1 (the winner-takes-all's first minimum), c2 = min { C[d] : |d - d1| >= 2 };
+ *   confidence = (c2 - c1) / c2 in f32 (correctly rounded), 0 when c2 == 0, 1 when that set is empty (D == 3, d1 == 1).  In
+ *   [0, 1]; 0 = another disparity at least two steps away is just as good.
+ *
+ * Either map pointer may be NULL; with both NULL the calls are exactly adc_match / adc_match_device.  Return codes are theirs,
+ * plus 1 (with adc_last_error) when a map is requested on a handle with paper modes set.  adc_match_ex allocates device scratch
+ * for the maps on the first call that needs it (freed by adc_destroy).  adc_match_device_ex writes the caller's device buffers
+ * directly and, like adc_match_device, is completed by adc_wait.  adc_match_async and the farm deliver no maps.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_LR_CONSISTENT 0
+#define ADC_LR_MISMATCH 1
+#define ADC_LR_OCCLUSION 2
+#define ADC_FILL_WTA 0
+#define ADC_FILL_VOTING 1
+#define ADC_FILL_INTERPOLATION 2
+#define ADC_FILL_NONE 3
+#define ADC_PROV_LR_MASK 3
+#define ADC_PROV_FILL_SHIFT 2
+int adc_match_ex(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, uint8_t* provenance,
+                 float* confidence);
+int adc_match_device_ex(adc_handle* h, const void* d_bgr_left, const void* d_bgr_right, void* d_disp_left, void* d_provenance,
+                        void* d_confidence);
 
 /* Host buffers, asynchronous (pinned staging inside the handle); adc_wait() completes it and
  * copies the result to disp_left given here. */
