@@ -53,6 +53,40 @@ class ADCensusOption(C.Structure):
             setattr(self, k, v)
 
 
+class Calib(C.Structure):
+    """adc_calib: Middlebury calib.txt convention, Z = baseline * focal_px / (d + doffs)."""
+    _fields_ = [("focal_px", C.c_float), ("baseline", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("doffs", C.c_float)]
+
+
+class Point(C.Structure):
+    """adc_point: 16 bytes."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("r", C.c_uint8), ("g", C.c_uint8), ("b", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class Outputs(C.Structure):
+    """adc_outputs: the request of adc_match_out (host addresses) / adc_match_device_out / adc_reproject_device (device addresses)."""
+    _fields_ = [("calib", C.POINTER(Calib)), ("depth", C.c_void_p), ("cloud", C.c_void_p), ("cloud_capacity", C.c_uint64),
+                ("cloud_count", C.c_void_p), ("disp8", C.c_void_p)]
+
+
+POINT_DTYPE = np.dtype({"names": ["x", "y", "z", "r", "g", "b", "pad"], "formats": ["<f4", "<f4", "<f4", "u1", "u1", "u1", "u1"],
+                        "offsets": [0, 4, 8, 12, 13, 14, 15], "itemsize": 16})
+
+
+def _calib(calib):
+    """None, a Calib, or a sequence (focal_px, baseline, cx, cy, doffs) -> Calib or None."""
+    if calib is None or isinstance(calib, Calib):
+        return calib
+    return Calib(*[float(v) for v in calib])
+
+
+def _outputs(calib, depth, cloud, capacity, cloud_count, disp8):
+    c = _calib(calib)
+    req = Outputs(C.pointer(c) if c is not None else None, depth, cloud, int(capacity), cloud_count, disp8)
+    req._keep = c
+    return req
+
+
 _lib = None
 
 
@@ -85,6 +119,15 @@ def lib():
         L.adc_match_ex.restype = C.c_int
         L.adc_match_device_ex.argtypes = [vp, vp, vp, vp, vp, vp]
         L.adc_match_device_ex.restype = C.c_int
+    if hasattr(L, "adc_match_out"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_match_out.argtypes = [vp, u8p, u8p, vp, C.POINTER(Outputs)]
+        L.adc_match_out.restype = C.c_int
+        L.adc_match_device_out.argtypes = [vp, vp, vp, vp, C.POINTER(Outputs)]
+        L.adc_match_device_out.restype = C.c_int
+        L.adc_reproject_device.argtypes = [vp, vp, vp, C.POINTER(Outputs)]
+        L.adc_reproject_device.restype = C.c_int
+        L.adc_get_cloud_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.adc_get_cloud_count.restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
     L.adc_stage_name.argtypes = [C.c_int]
@@ -325,6 +368,58 @@ class ADCensusStereo:
     def match_device_ex(self, d_left, d_right, d_disp, d_provenance=None, d_confidence=None):
         """match_device plus the optional maps into the caller's device buffers (ints or None); asynchronous, call wait()."""
         return lib().adc_match_device_ex(self._h, d_left, d_right, d_disp, d_provenance, d_confidence) == 0
+
+    def MatchOut(self, img_left, img_right, disp_left, calib=None, depth=None, cloud=None, disp8=None):
+        """Match plus the outputs computed on the device from the final map (adc_match_out) into the caller's arrays: depth
+        float32 [H][W] (needs calib), cloud a POINT_DTYPE array (its length is the capacity), disp8 uint8 [H][W]; any may be None
+        (all None: exactly Match).  False where Match is, and when the request is refused; cloud_count() tells how many points are valid."""
+        if not self._h:
+            return False
+        if img_left is None or img_right is None or disp_left is None:
+            return False
+        l, r = _img(img_left), _img(img_right)
+        n = self.width * self.height
+        assert l.size == n * 3 and r.size == l.size
+        assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        for a, dt in ((depth, np.float32), (disp8, np.uint8)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
+        assert cloud is None or (cloud.dtype == POINT_DTYPE and cloud.flags["C_CONTIGUOUS"])
+        req = _outputs(calib, None if depth is None else depth.ctypes.data, None if cloud is None else cloud.ctypes.data,
+                       0 if cloud is None else cloud.size, None, None if disp8 is None else disp8.ctypes.data)
+        return lib().adc_match_out(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, C.byref(req)) == 0
+
+    def match_out(self, img_left, img_right, calib=None, depth=False, cloud=False, disp8=False):
+        """Convenience: returns (disparity, depth, cloud, disp8) as new numpy arrays, None for what was not asked for; the cloud is a
+        structured array with the adc_point layout (POINT_DTYPE), cut to the number of valid pixels.  Raises on failure."""
+        shp = (self.height, self.width)
+        d = np.empty(shp, np.float32)
+        z = np.empty(shp, np.float32) if depth else None
+        pts = np.empty(shp[0] * shp[1], POINT_DTYPE) if cloud else None
+        g = np.empty(shp, np.uint8) if disp8 else None
+        if not self.MatchOut(img_left, img_right, d, calib, z, pts, g):
+            raise RuntimeError("MatchOut failed: " + last_error())
+        if cloud:
+            pts = pts[:self.cloud_count()].copy()
+        return d, z, pts, g
+
+    def match_device_out(self, d_left, d_right, d_disp, calib=None, d_depth=None, d_cloud=None, cloud_capacity=0, d_cloud_count=None,
+                         d_disp8=None):
+        """match_device plus the outputs into the caller's device buffers (ints or None; d_cloud_count: a uint32 device word);
+        asynchronous, call wait(), then cloud_count()."""
+        req = _outputs(calib, d_depth, d_cloud, cloud_capacity, d_cloud_count, d_disp8)
+        return lib().adc_match_device_out(self._h, d_left, d_right, d_disp, C.byref(req)) == 0
+
+    def reproject_device(self, d_disp, d_left, calib=None, d_depth=None, d_cloud=None, cloud_capacity=0, d_cloud_count=None, d_disp8=None):
+        """The output kernels on any device-resident float32 [H][W] map of this geometry (adc_reproject_device), without a Match;
+        asynchronous, call wait()."""
+        req = _outputs(calib, d_depth, d_cloud, cloud_capacity, d_cloud_count, d_disp8)
+        return lib().adc_reproject_device(self._h, d_disp, d_left, C.byref(req)) == 0
+
+    def cloud_count(self):
+        n = C.c_uint64(0)
+        if lib().adc_get_cloud_count(self._h, C.byref(n)) != 0:
+            raise RuntimeError("adc_get_cloud_count failed")
+        return int(n.value)
 
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do

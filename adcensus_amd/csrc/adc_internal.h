@@ -55,6 +55,20 @@ struct AdcParams {
     adc_option opt;
 };
 
+// One request for the outputs computed from the final map (adc_match_out / adc_match_device_out / adc_reproject_device,
+// k_outputs.hip), validated and resolved to device addresses
+struct AdcOutReq {
+    int active;           // kept until adc_wait, so that its redos (which call enqueue_output again) rewrite the outputs
+    int calibrated;       // calib holds the caller's calibration, fb = focal_px * baseline (one f32 multiply on the host)
+    adc_calib calib;
+    float fb;
+    float* depth;         // device addresses; NULL = not requested
+    void* cloud;
+    uint32_t capacity;    // points the cloud buffer holds
+    uint32_t* cloud_count;
+    uint8_t* disp8;
+};
+
 struct adc_handle {
     AdcParams p;
     int device;
@@ -177,6 +191,12 @@ struct adc_handle {
     float* x_conf;     // buffers or the scratch below; NULL: not requested); kept until adc_wait, so that its redos write them again
     uint8_t* xs_prov;  // device scratch of adc_match_ex (host callers), allocated on the first call that needs it
     float* xs_conf;
+    AdcOutReq out;        // outputs requested with this Match (out.active) -- the caller's device buffers or the scratch below
+    uint32_t* out_words;  // device scratch of k_outputs.hip (min / max words, count, tile counts), allocated on first use
+    float* os_depth;      // device scratch of adc_match_out (host callers), allocated on the first call that needs it
+    void* os_cloud;
+    uint32_t os_cloud_cap; // points os_cloud holds
+    uint8_t* os_disp8;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -224,6 +244,10 @@ hipError_t adc_paper_accumulate(adc_handle* h, float* acc, const float* src, int
 hipError_t adc_launch_lrcheck(adc_handle* h);
 hipError_t adc_launch_confidence(adc_handle* h);                // k_extras.hip: vol_a -> x_conf (heavy stream, behind the WTA)
 hipError_t adc_launch_provenance(adc_handle* h);                // label, disp_l -> x_prov, x_conf = 0 where filled (object stream)
+size_t adc_outputs_scratch_bytes(int W, int H);                 // k_outputs.hip: bytes of out_words
+hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img); // disp -> depth, min / max words, tile counts
+hipError_t adc_launch_out_scan(adc_handle* h);                  // tile counts -> tile bases, count words
+hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img);    // disp, img -> disp8, cloud
 size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)

@@ -195,7 +195,7 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_OK(hipHostMalloc(&h->pin_in, P * 6, hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h->pin_out, P * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h->pin_flags, 64 * sizeof(int32_t), hipHostMallocDefault));
-    memset(h->pin_flags, 0, 64 * sizeof(int32_t)); // [0] median error, [4..7] armmax + violation flag, [16..23] voting state, [32..63] staging of the voting chain's cold block
+    memset(h->pin_flags, 0, 64 * sizeof(int32_t)); // [0] median error, [4..7] armmax + violation flag, [8] cloud count (k_outputs.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
     HIP_OK(hipMemset(h->label, 0, P));
     HIP_OK(hipMemset(h->chg_a, 0, 2 * tiles));
     HIP_OK(hipMemset(h->vol_a, 0, VB));
@@ -329,7 +329,7 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf};
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -502,15 +502,33 @@ static void collect_timings(adc_handle* h)
     }
 }
 
-// the final map -> where the caller wants it (pinned staging for host callers, the caller's device buffer otherwise)
+// depth / point cloud / 8-bit image of h->out from a device-resident map (k_outputs.hip), on the object stream; only what was
+// asked for is launched
+static hipError_t enqueue_outputs(adc_handle* h, const float* disp, const uint8_t* img)
+{
+    const AdcOutReq& r = h->out;
+    if (r.disp8) HIP_OK(hipMemsetAsync(h->out_words, 0, 2 * sizeof(uint32_t), h->stream)); // (the min / max words)
+    HIP_OK(adc_launch_out_measure(h, disp, img));
+    if (r.cloud) {
+        HIP_OK(adc_launch_out_scan(h));
+        HIP_OK(hipMemcpyAsync(h->pin_flags + 8, h->out_words + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream)); // adc_get_cloud_count
+    }
+    if (r.cloud || r.disp8) HIP_OK(adc_launch_out_emit(h, disp, img));
+    return hipSuccess;
+}
+
+// the final map -> where the caller wants it (pinned staging for host callers, the caller's device buffer otherwise), and the
+// outputs computed from it when the Match asked for any (adc_wait comes through here again behind every redo)
 static hipError_t enqueue_output(adc_handle* h)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
-    if (h->async_dst && h->async_dst_direct == 1) return ADC_HIP(hipMemcpyAsync(h->async_dst, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
-    if (h->async_dst && h->async_dst_direct == 2) return hipSuccess; // (pageable, ADC_HOST_DIRECT: copied by adc_wait after the stream has drained)
-    if (h->async_dst) return ADC_HIP(hipMemcpyAsync(h->pin_out, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream));
-    if (h->device_dst) return ADC_HIP(hipMemcpyAsync(h->device_dst, h->disp_l, P * 4, hipMemcpyDeviceToDevice, h->stream));
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (h->async_dst && h->async_dst_direct == 1) e = ADC_HIP(hipMemcpyAsync(h->async_dst, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
+    else if (h->async_dst && h->async_dst_direct == 2) e = hipSuccess; // (pageable, ADC_HOST_DIRECT: copied by adc_wait after the stream has drained)
+    else if (h->async_dst) e = ADC_HIP(hipMemcpyAsync(h->pin_out, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream));
+    else if (h->device_dst) e = ADC_HIP(hipMemcpyAsync(h->device_dst, h->disp_l, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (e == hipSuccess && h->out.active) e = enqueue_outputs(h, h->disp_l, h->img_l);
+    return e;
 }
 
 // A HIP call of a Match failed half-way (the reference's contract: Match returns false and the object stays usable,
@@ -536,6 +554,7 @@ static void abort_match(adc_handle* h)
     h->async_dst = nullptr;
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
+    h->out.active = 0;
     if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
@@ -719,6 +738,7 @@ int adc_wait(adc_handle* h)
     }
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
+    h->out.active = 0;
     // adc_match_device BORROWED the caller's device images until here: nothing of the handle may point at them any
     // more (a later debug stage would otherwise read memory the caller has reused or freed)
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) {
@@ -785,6 +805,117 @@ int adc_match_device_ex(adc_handle* h, const void* d_left, const void* d_right, 
     const int rc = adc_match_device(h, d_left, d_right, d_disp);
     if (rc != 0) { h->x_prov = nullptr; h->x_conf = nullptr; }
     return rc;
+}
+
+// ------------------------------------------------------------------------------ outputs from the final map (k_outputs.hip)
+// Depth, point cloud and 8-bit image are functions of the delivered map only: enqueue_output computes them from disp_l behind the
+// copy of the map, so every redo of adc_wait (which ends in enqueue_output) rewrites them.
+static bool outputs_requested(const adc_outputs* o) { return o && (o->depth || o->cloud || o->disp8); }
+
+// validates a request and resolves it into h->out (not yet active); 0, or 1 (refused, adc_last_error) / 2 (scratch allocation)
+static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who, bool device_pointers)
+{
+    AdcOutReq r;
+    memset(&r, 0, sizeof(r));
+    if (o->calib) {
+        const adc_calib& c = *o->calib;
+        if (!(__builtin_isfinite(c.focal_px) && __builtin_isfinite(c.baseline) && __builtin_isfinite(c.cx) && __builtin_isfinite(c.cy) && __builtin_isfinite(c.doffs))) {
+            g_last_error = std::string(who) + ": the calibration has a non-finite field";
+            return 1;
+        }
+        if (!(c.focal_px > 0.0f)) { g_last_error = std::string(who) + ": the calibration's focal_px must be positive"; return 1; }
+        r.calibrated = 1;
+        r.calib = c;
+        r.fb = c.focal_px * c.baseline;
+    } else if (o->depth) {
+        g_last_error = std::string(who) + ": depth needs a calibration";
+        return 1;
+    }
+    if (device_pointers && o->cloud && ((uintptr_t)o->cloud & 15u)) { g_last_error = std::string(who) + ": the cloud address must be 16-byte aligned"; return 1; }
+    const size_t P = (size_t)h->p.W * h->p.H;
+    r.depth = o->depth;
+    r.cloud = o->cloud;
+    r.capacity = (uint32_t)(o->cloud_capacity < P ? o->cloud_capacity : P); // (there are at most W * H points)
+    r.cloud_count = o->cloud ? o->cloud_count : nullptr;
+    r.disp8 = o->disp8;
+    if (!h->out_words && ADC_HIP(hipMalloc(&h->out_words, adc_outputs_scratch_bytes(h->p.W, h->p.H))) != hipSuccess) {
+        h->out_words = nullptr;
+        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
+        return 2;
+    }
+    h->out = r;
+    return 0;
+}
+
+int adc_match_device_out(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_outputs* out)
+{
+    if (!outputs_requested(out)) return adc_match_device(h, d_left, d_right, d_disp);
+    if (!h || !d_left || !d_right || !d_disp) return 1;
+    hipSetDevice(h->device);
+    int rc = outputs_prepare(h, out, "adc_match_device_out", true);
+    if (rc != 0) return rc;
+    h->out.active = 1;
+    rc = adc_match_device(h, d_left, d_right, d_disp);
+    if (rc != 0) h->out.active = 0;
+    return rc;
+}
+
+int adc_reproject_device(adc_handle* h, const void* d_disp, const void* d_bgr_left, const adc_outputs* out)
+{
+    if (!h || !d_disp || (out && out->cloud && !d_bgr_left)) return 1;
+    if (!outputs_requested(out)) return 0;
+    if (h->out.active) { g_last_error = "adc_reproject_device: a Match with outputs is pending (adc_wait first)"; return 1; }
+    hipSetDevice(h->device);
+    const int rc = outputs_prepare(h, out, "adc_reproject_device", true);
+    if (rc != 0) return rc;
+    // (out.active stays 0: nothing of a later adc_wait may run these again on the handle's own map)
+    if (enqueue_outputs(h, static_cast<const float*>(d_disp), static_cast<const uint8_t*>(d_bgr_left)) != hipSuccess) { abort_match(h); return 2; }
+    return 0;
+}
+
+int adc_match_out(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_outputs* out)
+{
+    if (!outputs_requested(out)) return adc_match(h, left, right, disp);
+    if (!h || !left || !right || !disp) return 1;
+    hipSetDevice(h->device);
+    int rc = outputs_prepare(h, out, "adc_match_out", false);
+    if (rc != 0) return rc;
+    const size_t P = (size_t)h->p.W * h->p.H;
+    const uint32_t cap = h->out.capacity;
+    hipError_t e = hipSuccess;
+    if (out->depth && !h->os_depth && (e = ADC_HIP(hipMalloc(&h->os_depth, P * 4))) != hipSuccess) h->os_depth = nullptr;
+    if (e == hipSuccess && out->disp8 && !h->os_disp8 && (e = ADC_HIP(hipMalloc(&h->os_disp8, P))) != hipSuccess) h->os_disp8 = nullptr;
+    if (e == hipSuccess && out->cloud && (!h->os_cloud || h->os_cloud_cap < cap)) { // (grows with the largest capacity asked for; at least one point)
+        if (h->os_cloud) hipFree(h->os_cloud);
+        h->os_cloud_cap = cap > 0 ? cap : 1;
+        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
+    }
+    if (e != hipSuccess) { set_error("adc_match_out: scratch", hipGetLastError()); return 2; }
+    h->out.depth = out->depth ? h->os_depth : nullptr;
+    h->out.disp8 = out->disp8 ? h->os_disp8 : nullptr;
+    h->out.cloud = out->cloud ? h->os_cloud : nullptr;
+    h->out.cloud_count = nullptr;
+    h->out.active = 1;
+    rc = match_async_impl(h, left, right, disp, true);
+    if (rc == 0) rc = adc_wait(h);
+    h->out.active = 0; // (adc_wait / abort_match have cleared it already)
+    if (rc != 0) return rc;
+    if (out->depth && ADC_HIP(hipMemcpy(out->depth, h->os_depth, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: depth copy-out", hipGetLastError()); return 2; }
+    if (out->disp8 && ADC_HIP(hipMemcpy(out->disp8, h->os_disp8, P, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: image copy-out", hipGetLastError()); return 2; }
+    if (out->cloud) {
+        const uint32_t count = (uint32_t)h->pin_flags[8];
+        const size_t n = count < cap ? count : cap;
+        if (n && ADC_HIP(hipMemcpy(out->cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: cloud copy-out", hipGetLastError()); return 2; }
+        if (out->cloud_count) *out->cloud_count = count;
+    }
+    return 0;
+}
+
+int adc_get_cloud_count(adc_handle* h, uint64_t* count)
+{
+    if (!h || !count || !h->pin_flags) return 1;
+    *count = (uint32_t)h->pin_flags[8];
+    return 0;
 }
 
 // ------------------------------------------------------------------------------ pair farm

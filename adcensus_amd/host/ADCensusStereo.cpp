@@ -85,6 +85,16 @@ bool ADCensusStereo::MatchEx(const uint8* l, const uint8* r, float32* d, uint8* 
     if (!impl_ || !l || !r || !d) return false;
     return adc_match_ex(impl_, l, r, d, provenance, confidence) == 0;
 }
+bool ADCensusStereo::MatchOut(const uint8* l, const uint8* r, float32* d, const adc_outputs* outputs)
+{
+    if (!impl_ || !l || !r || !d) return false;
+    return adc_match_out(impl_, l, r, d, outputs) == 0;
+}
+unsigned long long ADCensusStereo::CloudCount() const
+{
+    uint64_t n = 0;
+    return impl_ && adc_get_cloud_count(impl_, &n) == 0 ? n : 0;
+}
 bool ADCensusStereo::Wait() { return impl_ && adc_wait(impl_) == 0; }
 bool ADCensusStereo::SetPaperModes(unsigned modes)
 {

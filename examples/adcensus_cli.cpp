@@ -10,6 +10,10 @@
 // --extras (anywhere after the program name) also writes the per-pixel maps of ADCensusStereo::MatchEx:
 //   <out>-prov.png   provenance codes (lr | fill << 2, include/adcensus_c_api.h) as 8-bit gray
 //   <out>-conf.png   uchar(confidence * 255);  <out>-conf.pfm  the float32 confidence
+// --calib f,B,cx,cy,doffs (anywhere after the program name; Middlebury calib.txt convention, not together with --extras) also
+// writes the device-side outputs of ADCensusStereo::MatchOut:
+//   <out>-depth.pfm  float32 depth Z = f * B / (|d| + doffs), +inf where invalid
+//   <out>-cloud.ply  binary little-endian PLY of the valid pixels in raster order: x y z float, red green blue uchar
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -19,6 +23,7 @@
 #include <vector>
 
 #include "ADCensusStereo.h"
+#include "adcensus_c_api.h"
 #include "adc_image_io.h"
 
 static void write_pfm(const std::string& path, const float32* px, int w, int h)
@@ -37,6 +42,20 @@ int main(int argc, char** argv)
             argc--;
             break;
         }
+    bool with_calib = false; // (--calib and its value are taken out of argv in the same way)
+    adc_calib calib = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--calib")) {
+            if (i + 1 >= argc || sscanf(argv[i + 1], "%f,%f,%f,%f,%f", &calib.focal_px, &calib.baseline, &calib.cx, &calib.cy, &calib.doffs) != 5) {
+                printf("--calib needs f,B,cx,cy,doffs\n");
+                return -1;
+            }
+            with_calib = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_calib && extras) { printf("--calib and --extras are separate runs\n"); return -1; }
     // file-format helpers that need no GPU (used by the CPU test tier):
     //   --convert in.{png,ppm} out.png       decode + re-encode (R,G,B)
     //   --colormap in-d.png out-c.png        the JET mapping SaveDisparityMap applies to the grey disparity image
@@ -88,8 +107,11 @@ int main(int argc, char** argv)
     std::vector<float32> disparity((size_t)w * h, 0.0f);
     std::vector<uint8> provenance(extras ? (size_t)w * h : 0);
     std::vector<float32> confidence(extras ? (size_t)w * h : 0);
+    std::vector<float32> depth(with_calib ? (size_t)w * h : 0);
+    std::vector<adc_point> cloud(with_calib ? (size_t)w * h : 0);
+    adc_outputs outputs = {&calib, depth.data(), cloud.data(), cloud.size(), nullptr, nullptr};
     t0 = std::chrono::steady_clock::now();
-    const bool ok = extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
+    const bool ok = with_calib ? ad_census.MatchOut(left.data(), right.data(), disparity.data(), &outputs) : extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
                            : ad_census.Match(left.data(), right.data(), disparity.data());
     if (!ok) { printf("AD-Census matching failed: %s\n", ad_census.LastError()); return -2; }
     t1 = std::chrono::steady_clock::now();
@@ -125,6 +147,17 @@ int main(int argc, char** argv)
         if (!write_png(out + "-prov.png", provenance.data(), w, h, 1) || !write_png(out + "-conf.png", conf8.data(), w, h, 1))
             printf("cannot write %s-prov.png / -conf.png\n", out.c_str());
         write_pfm(out + "-conf.pfm", confidence.data(), w, h);
+    }
+    if (with_calib) {
+        write_pfm(out + "-depth.pfm", depth.data(), w, h);
+        const size_t count = (size_t)ad_census.CloudCount();
+        FILE* ply = fopen((out + "-cloud.ply").c_str(), "wb");
+        if (ply) {
+            fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                         "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", count);
+            for (size_t i = 0; i < count; i++) { fwrite(&cloud[i].x, 4, 3, ply); fwrite(&cloud[i].r, 1, 3, ply); }
+            fclose(ply);
+        } else printf("cannot write %s-cloud.ply\n", out.c_str());
     }
     return 0;
 }

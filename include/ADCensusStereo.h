@@ -10,13 +10,15 @@
  *
  * Additive members (no reference counterpart): SetDevice, SetVerbose (prints the reference's six stage
  * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait,
- * MatchEx (per-pixel provenance and confidence maps next to the disparity).
+ * MatchEx (per-pixel provenance and confidence maps next to the disparity), MatchOut (depth, point cloud and 8-bit image computed
+ * on the device from the final map).
  */
 #pragma once
 
 #include "adcensus_types.h"
 
 struct adc_handle;
+struct adc_outputs; // include/adcensus_c_api.h
 
 class ADCensusStereo {
 public:
@@ -47,6 +49,13 @@ public:
      *  (ADC_LR_* / ADC_FILL_*), and confidence float32 [H][W] in [0, 1]; either may be null (both null: exactly Match).  false
      *  where Match is false, and when a map is requested with paper modes set. */
     bool MatchEx(const uint8* img_left, const uint8* img_right, float32* disp_left, uint8* provenance, float32* confidence);
+    /** Match plus the outputs computed on the device from the final map (adc_match_out, include/adcensus_c_api.h: adc_outputs with
+     *  host pointers): metric depth float32 [H][W] (needs a calibration), the point cloud of the valid pixels in raster order, the
+     *  min-max normalised 8-bit image.  A null request or one that asks for nothing is exactly Match.  false where Match is
+     *  false, and when the request is refused (depth without a calibration, focal_px <= 0, a non-finite calibration field). */
+    bool MatchOut(const uint8* img_left, const uint8* img_right, float32* disp_left, const adc_outputs* outputs);
+    /** Valid pixels of the last MatchOut that asked for a cloud (whatever the capacity was). */
+    unsigned long long CloudCount() const;
     bool Wait();
     /** Opt-in paper features the reference declares / stores but does not implement (bit 0: 5x5 census, adcensus_types.h:39-42;
      *  bit 1: averaged instead of chained scanline paths; bit 2: right-image arms, cross_aggregator.h:91).  0 (default) = the

@@ -18,6 +18,8 @@
  *   adc_match_device      device-resident in/out buffers (bench: inputs already in HBM)
  *   adc_match_ex /        the same Matches with two optional per-pixel maps next to the disparity:
  *   adc_match_device_ex   provenance (measured or filled, ADC_LR_* / ADC_FILL_*) and confidence
+ *   adc_match_out /       the same Matches with outputs computed on the device from the final map: metric depth, a point
+ *   adc_match_device_out  cloud in raster order, the min-max normalised 8-bit image; adc_reproject_device: the same from any map
  *   adc_match_async/wait  several objects in flight from one host thread
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
@@ -134,6 +136,61 @@ int adc_match_ex(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_righ
                  float* confidence);
 int adc_match_device_ex(adc_handle* h, const void* d_bgr_left, const void* d_bgr_right, void* d_disp_left, void* d_provenance,
                         void* d_confidence);
+
+/* -------------------------------------------------------------------------------------------
+ * Outputs computed on the device from the final left-view disparity map (behind the median): what the reference's demo derives
+ * on the host after every Match (main.cpp:180-230), plus metric depth.  d = the pixel's final disparity, a = |d| (both reference
+ * functions take abs first).  All arithmetic is IEEE binary32, one rounding per operation, nothing fused, divisions correctly
+ * rounded; tests/outputs_ref.py holds the same definitions in numpy.
+ *
+ * adc_calib  Middlebury calib.txt convention, Z = baseline * focal_px / (d + doffs).  fb = focal_px * baseline is one f32 multiply.
+ * disp8   uint8 [H][W], SaveDisparityMap's image: mn = float(W), mx = -float(W), then min / max of a over the pixels with
+ *         a != +inf; pixel = uint8((a - mn) / (mx - mn) * 255) (truncating), 0 where a == +inf, 0 everywhere when !(mx > mn).
+ *         Does not look at the calibration.
+ * depth   float32 [H][W], needs a calibration: s = a + doffs; valid <=> a finite and s > 0; valid: fb / s, otherwise +inf
+ *         (Invalid_Float).
+ * cloud   adc_point per valid pixel, in raster order (row by row, then by column: SaveDisparityCloud's rows).  r, g, b from the left
+ *         image (stored B,G,R), pad = 0.  Without a calibration: (x, y, z) = (float(x), float(y), a), valid <=> a != +inf -- the
+ *         reference's rows.  With one: validity and Z as for depth, X = ((float(x) - cx) * Z) / focal_px, Y = ((float(y) - cy) * Z) /
+ *         focal_px (a pixel stays valid where fb / s overflows).  The first min(count, cloud_capacity) points are written and
+ *         nothing behind them; W * H points always suffice.  count = valid pixels, whatever the capacity: adc_get_cloud_count
+ *         after adc_wait, and -- when cloud_count is given -- a uint32 at that device address, written on the stream (a GPU
+ *         consumer need not synchronise).  cloud_capacity = 0 with a non-NULL cloud counts only.
+ *
+ * Any output pointer may be NULL (cloud_count is looked at only with a cloud); with a NULL request or none of depth / cloud /
+ * disp8 the Match calls are exactly adc_match / adc_match_device.  Refused with 1 and adc_last_error, before anything is
+ * enqueued: depth without a calibration; a calibration with focal_px <= 0 or a non-finite field; a device cloud address that is
+ * not 16-byte aligned.  Paper modes do not matter.  Otherwise the return codes are those of adc_match / adc_match_device.
+ *
+ * adc_match_device_out  asynchronous, completed by adc_wait; the pointers of the request are DEVICE addresses, written directly;
+ *                       the borrow rules of adc_match_device (the request struct itself is read before the call returns).
+ * adc_match_out         synchronous, HOST pointers; device scratch is allocated on the first call that needs it (freed by
+ *                       adc_destroy); copies out min(count, capacity) points; cloud_count is a host uint32 here.
+ * adc_reproject_device  the same kernels on any device-resident float32 [H][W] map of the handle's geometry, without a Match
+ *                       (d_bgr_left is needed for a cloud only); completed by adc_wait.  Refused while a Match with outputs is
+ *                       pending.  A caller of adc_match_device_ex gets depth and points this way.
+ * Every redo adc_wait can take rewrites the outputs from the map it delivers.  adc_match_async and the farm deliver none.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct adc_calib {
+    float focal_px, baseline, cx, cy, doffs;
+} adc_calib;
+typedef struct adc_point {
+    float x, y, z;
+    uint8_t r, g, b, pad;
+} adc_point; /* 16 bytes */
+typedef struct adc_outputs {
+    const adc_calib* calib; /* NULL: no calibration */
+    float* depth;
+    adc_point* cloud;
+    uint64_t cloud_capacity; /* points */
+    uint32_t* cloud_count;
+    uint8_t* disp8;
+} adc_outputs;
+int adc_match_out(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, const adc_outputs* out);
+int adc_match_device_out(adc_handle* h, const void* d_bgr_left, const void* d_bgr_right, void* d_disp_left, const adc_outputs* out);
+int adc_reproject_device(adc_handle* h, const void* d_disp, const void* d_bgr_left, const adc_outputs* out);
+/* Valid pixels of the last cloud request on this handle that adc_wait (or adc_match_out) has completed. */
+int adc_get_cloud_count(adc_handle* h, uint64_t* count);
 
 /* Host buffers, asynchronous (pinned staging inside the handle); adc_wait() completes it and
  * copies the result to disp_left given here. */
