@@ -28,6 +28,7 @@ PAPER_CENSUS5X5, PAPER_SO_SUM, PAPER_RIGHT_ARMS = 1, 2, 4  # adc_set_paper_modes
 LR_CONSISTENT, LR_MISMATCH, LR_OCCLUSION = 0, 1, 2
 FILL_WTA, FILL_VOTING, FILL_INTERPOLATION, FILL_NONE = 0, 1, 2, 3
 PROV_LR_MASK, PROV_FILL_SHIFT = 3, 2
+PROV_SPECKLE = 0x10  # set by a Match with the speckle filter on, at the pixels the filter removed (ADC_PROV_SPECKLE)
 
 
 class ADCensusOption(C.Structure):
@@ -128,6 +129,15 @@ def lib():
         L.adc_reproject_device.restype = C.c_int
         L.adc_get_cloud_count.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.adc_get_cloud_count.restype = C.c_int
+    if hasattr(L, "adc_set_speckle_filter"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_set_speckle_filter.argtypes = [vp, i32, C.c_float]
+        L.adc_set_speckle_filter.restype = C.c_int
+        L.adc_filter_speckles_device.argtypes = [vp, vp, i32, C.c_float, vp]
+        L.adc_filter_speckles_device.restype = C.c_int
+        L.adc_get_speckle_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.adc_get_speckle_stats.restype = C.c_int
+        L.adc_farm_set_speckle_filter.argtypes = [vp, i32, C.c_float]
+        L.adc_farm_set_speckle_filter.restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
     L.adc_stage_name.argtypes = [C.c_int]
@@ -262,6 +272,11 @@ class PairFarm:
             raise RuntimeError("adc_farm_drain failed: " + last_error())
         self._keep.clear()
         return n
+
+    def set_speckle_filter(self, max_size, max_diff):
+        """The speckle filter of ADCensusStereo.set_speckle_filter on every pipeline (adc_farm_set_speckle_filter); drain() first."""
+        if lib().adc_farm_set_speckle_filter(self._f, int(max_size), float(max_diff)) != 0:
+            raise RuntimeError("adc_farm_set_speckle_filter failed: " + last_error())
 
     def close(self):
         if self._f:
@@ -420,6 +435,47 @@ class ADCensusStereo:
         if lib().adc_get_cloud_count(self._h, C.byref(n)) != 0:
             raise RuntimeError("adc_get_cloud_count failed")
         return int(n.value)
+
+    def set_speckle_filter(self, max_size, max_diff):
+        """Every later match of this object (all entry points) delivers its map with the 4-connected components (neighbours within
+        max_diff) of at most max_size pixels set to +inf (adc_set_speckle_filter); max_size <= 0 switches the filter off.  Raises
+        when refused (max_diff negative or not finite, a Match pending) or on a HIP failure."""
+        if lib().adc_set_speckle_filter(self._h, int(max_size), float(max_diff)) != 0:
+            raise RuntimeError("adc_set_speckle_filter failed: " + last_error())
+
+    def filter_speckles_device(self, d_disp, max_size, max_diff, d_labels=None):
+        """The filter's kernels on any device-resident float32 [H][W] map of this geometry, in place (adc_filter_speckles_device);
+        d_labels: int32 [H][W] device buffer or None; asynchronous, call wait(), then speckle_stats()."""
+        return lib().adc_filter_speckles_device(self._h, d_disp, int(max_size), float(max_diff), d_labels) == 0
+
+    def filter_speckles(self, disp, max_size, max_diff, labels=False):
+        """Host convenience: uploads a float32 [H][W] map, filters it on the device, downloads it.  Returns the filtered map, or
+        (map, labels int32 [H][W]) with labels=True; speckle_stats() has the counts.  Raises on failure."""
+        d = np.ascontiguousarray(disp, dtype=np.float32)
+        assert d.shape == (self.height, self.width), (d.shape, (self.height, self.width))
+        L = lib()
+        pd = L.adc_device_malloc(d.nbytes)
+        pl = L.adc_device_malloc(d.nbytes) if labels else None
+        try:
+            if not pd or (labels and not pl) or L.adc_memcpy_h2d(pd, d.ctypes.data, d.nbytes) != 0:
+                raise RuntimeError("filter_speckles: device buffer")
+            if not (self.filter_speckles_device(pd, max_size, max_diff, pl) and self.wait()):
+                raise RuntimeError("adc_filter_speckles_device failed: " + last_error())
+            out = np.empty_like(d)
+            lab = np.empty(d.shape, np.int32) if labels else None
+            if L.adc_memcpy_d2h(out.ctypes.data, pd, out.nbytes) != 0 or (labels and L.adc_memcpy_d2h(lab.ctypes.data, pl, lab.nbytes) != 0):
+                raise RuntimeError("filter_speckles: download")
+        finally:
+            L.adc_device_free(pd)
+            L.adc_device_free(pl)
+        return (out, lab) if labels else out
+
+    def speckle_stats(self):
+        """(components, removed components, removed pixels) of the last filtered match / filter call that wait() has completed."""
+        c, rc, rp = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        if lib().adc_get_speckle_stats(self._h, C.byref(c), C.byref(rc), C.byref(rp)) != 0:
+            raise RuntimeError("adc_get_speckle_stats failed")
+        return int(c.value), int(rc.value), int(rp.value)
 
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do

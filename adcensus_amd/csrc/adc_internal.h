@@ -197,6 +197,11 @@ struct adc_handle {
     void* os_cloud;
     uint32_t os_cloud_cap; // points os_cloud holds
     uint8_t* os_disp8;
+    // optional speckle filter (k_speckle.hip; off = sp_max_size <= 0: nothing of it is enqueued)
+    int32_t sp_max_size;  // handle state (adc_set_speckle_filter): every later Match filters its delivered map
+    float sp_max_diff;
+    int32_t* sp_parent;   // device scratch, allocated on first use: parent [P], size [P], then the three stat words
+    float* sp_map;        // the filtered map of a Match (out of place: a redo of adc_wait may patch disp_l only in part)
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -248,6 +253,11 @@ size_t adc_outputs_scratch_bytes(int W, int H);                 // k_outputs.hip
 hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img); // disp -> depth, min / max words, tile counts
 hipError_t adc_launch_out_scan(adc_handle* h);                  // tile counts -> tile bases, count words
 hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img);    // disp, img -> disp8, cloud
+size_t adc_speckle_scratch_words(int W, int H);                 // k_speckle.hip: int32 words of sp_parent
+hipError_t adc_launch_speckle_runs(adc_handle* h, const float* src, float max_diff);    // src -> row runs in parent, size = 0, stat words = 0
+hipError_t adc_launch_speckle_merge(adc_handle* h, const float* src, float max_diff);   // unions across rows and 64-pixel pieces
+hipError_t adc_launch_speckle_flatten(adc_handle* h, int32_t* labels);                  // parent = root (-> labels, may be NULL), sizes, components
+hipError_t adc_launch_speckle_apply(adc_handle* h, const float* src, float* dst, uint8_t* prov, int max_size); // small components -> +inf
 size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)

@@ -195,7 +195,7 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_OK(hipHostMalloc(&h->pin_in, P * 6, hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h->pin_out, P * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h->pin_flags, 64 * sizeof(int32_t), hipHostMallocDefault));
-    memset(h->pin_flags, 0, 64 * sizeof(int32_t)); // [0] median error, [4..7] armmax + violation flag, [8] cloud count (k_outputs.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
+    memset(h->pin_flags, 0, 64 * sizeof(int32_t)); // [0] median error, [4..7] armmax + violation flag, [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
     HIP_OK(hipMemset(h->label, 0, P));
     HIP_OK(hipMemset(h->chg_a, 0, 2 * tiles));
     HIP_OK(hipMemset(h->vol_a, 0, VB));
@@ -329,7 +329,7 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8};
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->sp_parent, h->sp_map};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -517,17 +517,36 @@ static hipError_t enqueue_outputs(adc_handle* h, const float* disp, const uint8_
     return hipSuccess;
 }
 
+// The speckle filter (k_speckle.hip) on a device-resident map: four launches with geometry-only grids, then the three stat words
+// on their way to pin_flags[9..11] (adc_get_speckle_stats).  dst == src filters in place; max_size <= 0 only labels.
+static hipError_t enqueue_speckle(adc_handle* h, const float* src, float* dst, int32_t max_size, float max_diff, int32_t* labels, uint8_t* prov)
+{
+    const size_t P = (size_t)h->p.W * h->p.H;
+    HIP_OK(adc_launch_speckle_runs(h, src, max_diff));
+    HIP_OK(adc_launch_speckle_merge(h, src, max_diff));
+    HIP_OK(adc_launch_speckle_flatten(h, labels));
+    if (max_size > 0) HIP_OK(adc_launch_speckle_apply(h, src, dst, prov, max_size));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + 9, h->sp_parent + 2 * P, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+// the map a Match delivers: the filter's own copy when the speckle filter is on (out of place: the median's fallbacks in
+// adc_wait rewrite disp_l from the unfiltered intermediate, and nothing of a redo may ever see a map with the filter's holes)
+static const float* delivered_map(const adc_handle* h) { return h->sp_max_size > 0 ? h->sp_map : h->disp_l; }
+
 // the final map -> where the caller wants it (pinned staging for host callers, the caller's device buffer otherwise), and the
 // outputs computed from it when the Match asked for any (adc_wait comes through here again behind every redo)
 static hipError_t enqueue_output(adc_handle* h)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
     hipError_t e = hipSuccess;
-    if (h->async_dst && h->async_dst_direct == 1) e = ADC_HIP(hipMemcpyAsync(h->async_dst, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
+    if (h->sp_max_size > 0 && (e = enqueue_speckle(h, h->disp_l, h->sp_map, h->sp_max_size, h->sp_max_diff, nullptr, h->x_prov)) != hipSuccess) return e;
+    const float* map = delivered_map(h);
+    if (h->async_dst && h->async_dst_direct == 1) e = ADC_HIP(hipMemcpyAsync(h->async_dst, map, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
     else if (h->async_dst && h->async_dst_direct == 2) e = hipSuccess; // (pageable, ADC_HOST_DIRECT: copied by adc_wait after the stream has drained)
-    else if (h->async_dst) e = ADC_HIP(hipMemcpyAsync(h->pin_out, h->disp_l, P * 4, hipMemcpyDeviceToHost, h->stream));
-    else if (h->device_dst) e = ADC_HIP(hipMemcpyAsync(h->device_dst, h->disp_l, P * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (e == hipSuccess && h->out.active) e = enqueue_outputs(h, h->disp_l, h->img_l);
+    else if (h->async_dst) e = ADC_HIP(hipMemcpyAsync(h->pin_out, map, P * 4, hipMemcpyDeviceToHost, h->stream));
+    else if (h->device_dst) e = ADC_HIP(hipMemcpyAsync(h->device_dst, map, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (e == hipSuccess && h->out.active) e = enqueue_outputs(h, map, h->img_l);
     return e;
 }
 
@@ -555,7 +574,7 @@ static void abort_match(adc_handle* h)
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
     h->out.active = 0;
-    if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; }
+    if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
 }
@@ -730,7 +749,7 @@ int adc_wait(adc_handle* h)
     else if (h->med_seg_off > 0 && h->med_seg_last <= 1) h->med_seg_off--; // (whole rows again because a segment seam had failed)
     if (h->async_dst) {
         if (h->async_dst_direct == 2) {
-            if (ADC_HIP(hipMemcpy(h->async_dst, h->disp_l, (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
+            if (ADC_HIP(hipMemcpy(h->async_dst, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
         } else if (h->async_dst_direct == 0) {
             memcpy(h->async_dst, h->pin_out, (size_t)h->p.W * h->p.H * 4);
         }
@@ -918,6 +937,72 @@ int adc_get_cloud_count(adc_handle* h, uint64_t* count)
     return 0;
 }
 
+// ------------------------------------------------------------------------------ speckle filter (k_speckle.hip)
+// Handle state; enqueue_output runs the filter on disp_l into sp_map in front of the copy-out and the outputs, so every redo
+// of adc_wait (each ends in enqueue_output) refilters the recomputed map.
+static bool speckle_args_ok(float max_diff, const char* who)
+{
+    if (__builtin_isfinite(max_diff) && max_diff >= 0.0f) return true;
+    g_last_error = std::string(who) + ": max_diff must be finite and >= 0";
+    return false;
+}
+
+// first use: parent / size / stat words, and (for the Matches) the filtered map
+static int speckle_scratch(adc_handle* h, bool with_map, const char* who)
+{
+    const size_t P = (size_t)h->p.W * h->p.H;
+    if (!h->sp_parent && ADC_HIP(hipMalloc(&h->sp_parent, adc_speckle_scratch_words(h->p.W, h->p.H) * sizeof(int32_t))) != hipSuccess) {
+        h->sp_parent = nullptr;
+        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
+        return 2;
+    }
+    if (with_map && !h->sp_map && ADC_HIP(hipMalloc(&h->sp_map, P * 4)) != hipSuccess) {
+        h->sp_map = nullptr;
+        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
+        return 2;
+    }
+    return 0;
+}
+
+static bool match_in_flight(const adc_handle* h) { return h->match_pending || h->async_dst || h->device_dst || h->out.active; }
+
+int adc_set_speckle_filter(adc_handle* h, int32_t max_size, float max_diff)
+{
+    if (!h) return 1;
+    if (!speckle_args_ok(max_diff, "adc_set_speckle_filter")) return 1;
+    if (match_in_flight(h)) { g_last_error = "adc_set_speckle_filter: a Match is pending (adc_wait first)"; return 1; }
+    if (max_size <= 0) { h->sp_max_size = 0; h->sp_max_diff = 0.0f; return 0; }
+    hipSetDevice(h->device);
+    const int rc = speckle_scratch(h, true, "adc_set_speckle_filter");
+    if (rc != 0) return rc;
+    h->sp_max_size = max_size;
+    h->sp_max_diff = max_diff;
+    return 0;
+}
+
+int adc_filter_speckles_device(adc_handle* h, void* d_disp_inout, int32_t max_size, float max_diff, void* d_labels)
+{
+    if (!h) return 1;
+    if (!d_disp_inout) { g_last_error = "adc_filter_speckles_device: null map"; return 1; }
+    if (!speckle_args_ok(max_diff, "adc_filter_speckles_device")) return 1;
+    if (max_size <= 0 && !d_labels) return 0;
+    hipSetDevice(h->device);
+    const int rc = speckle_scratch(h, false, "adc_filter_speckles_device");
+    if (rc != 0) return rc;
+    float* map = static_cast<float*>(d_disp_inout);
+    if (enqueue_speckle(h, map, map, max_size, max_diff, static_cast<int32_t*>(d_labels), nullptr) != hipSuccess) { abort_match(h); return 2; }
+    return 0;
+}
+
+int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed_components, uint32_t* removed_pixels)
+{
+    if (!h || !h->pin_flags) return 1;
+    if (components) *components = (uint32_t)h->pin_flags[9];
+    if (removed_components) *removed_components = (uint32_t)h->pin_flags[10];
+    if (removed_pixels) *removed_pixels = (uint32_t)h->pin_flags[11];
+    return 0;
+}
+
 // ------------------------------------------------------------------------------ pair farm
 struct adc_farm {
     std::vector<adc_handle*> pipes;
@@ -1003,6 +1088,19 @@ int64_t adc_farm_drain(adc_farm* f)
         if (farm_collect(f, best) != 0) return -1;
     }
     return f->delivered;
+}
+
+int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff)
+{
+    if (!f) return 1;
+    if (!speckle_args_ok(max_diff, "adc_farm_set_speckle_filter")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++)
+        if (f->in_flight[i]) { g_last_error = "adc_farm_set_speckle_filter: a pair is in flight (adc_farm_drain first)"; return 1; }
+    for (size_t i = 0; i < f->pipes.size(); i++) {
+        const int rc = adc_set_speckle_filter(f->pipes[i], max_size, max_diff);
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------ misc plumbing

@@ -30,7 +30,7 @@ static bool default_verbose()
     const char* e = getenv("ADC_VERBOSE");
     return e ? atoi(e) != 0 : true;
 }
-ADCensusStereo::ADCensusStereo() : impl_(nullptr), device_(-1), verbose_(default_verbose()), profiling_(false), paper_(0) {}
+ADCensusStereo::ADCensusStereo() : impl_(nullptr), device_(-1), verbose_(default_verbose()), profiling_(false), paper_(0), speckle_size_(0), speckle_diff_(0.0f) {}
 ADCensusStereo::~ADCensusStereo() { Release(); }
 
 void ADCensusStereo::Release()
@@ -48,6 +48,7 @@ bool ADCensusStereo::Initialize(const sint32& width, const sint32& height, const
     if (profiling_) adc_set_profiling(impl_, 1);
     if (verbose_) adc_set_verbose(impl_, 1);
     if (paper_ && adc_set_paper_modes(impl_, paper_) != 0) return false;
+    if (speckle_size_ > 0 && adc_set_speckle_filter(impl_, speckle_size_, speckle_diff_) != 0) return false;
     return true;
 }
 
@@ -100,5 +101,13 @@ bool ADCensusStereo::SetPaperModes(unsigned modes)
 {
     paper_ = modes;
     return impl_ ? adc_set_paper_modes(impl_, modes) == 0 : true; // (before Initialize: applied there)
+}
+bool ADCensusStereo::SetSpeckleFilter(int max_size, float max_diff)
+{
+    if (impl_ && adc_set_speckle_filter(impl_, max_size, max_diff) != 0) return false;
+    if (!impl_ && !(max_diff >= 0.0f && max_diff <= 3.402823466e38f)) return false; // (before Initialize: checked here, applied there)
+    speckle_size_ = max_size > 0 ? max_size : 0;
+    speckle_diff_ = max_size > 0 ? max_diff : 0.0f;
+    return true;
 }
 const char* ADCensusStereo::LastError() const { return adc_last_error(); }

@@ -14,6 +14,9 @@
 // writes the device-side outputs of ADCensusStereo::MatchOut:
 //   <out>-depth.pfm  float32 depth Z = f * B / (|d| + doffs), +inf where invalid
 //   <out>-cloud.ply  binary little-endian PLY of the valid pixels in raster order: x y z float, red green blue uchar
+// --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
+// components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
+// the filtered map; without the flag the files are what they were.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -51,6 +54,20 @@ int main(int argc, char** argv)
                 return -1;
             }
             with_calib = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    int speckle_size = 0; // (--speckle and its value likewise; checked before anything touches a device)
+    float speckle_diff = 0.f;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--speckle")) {
+            char tail = 0;
+            if (i + 1 >= argc || sscanf(argv[i + 1], "%d,%f%c", &speckle_size, &speckle_diff, &tail) != 2 || speckle_size <= 0 ||
+                !std::isfinite(speckle_diff) || speckle_diff < 0.f) {
+                printf("--speckle needs SIZE,DIFF (SIZE > 0 pixels, DIFF >= 0 and finite)\n");
+                return -1;
+            }
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2;
             break;
@@ -103,6 +120,7 @@ int main(int argc, char** argv)
     if (!ad_census.Initialize(w, h, ad_option)) { printf("AD-Census initialisation failed: %s\n", ad_census.LastError()); return -2; }
     auto t1 = std::chrono::steady_clock::now();
     printf("AD-Census Initializing Done! Timing :	%lf s\n\n", std::chrono::duration<double>(t1 - t0).count());
+    if (speckle_size > 0 && !ad_census.SetSpeckleFilter(speckle_size, speckle_diff)) { printf("speckle filter refused: %s\n", ad_census.LastError()); return -2; }
     printf("AD-Census Matching...\n");
     std::vector<float32> disparity((size_t)w * h, 0.0f);
     std::vector<uint8> provenance(extras ? (size_t)w * h : 0);

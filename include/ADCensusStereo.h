@@ -11,7 +11,7 @@
  * Additive members (no reference counterpart): SetDevice, SetVerbose (prints the reference's six stage
  * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait,
  * MatchEx (per-pixel provenance and confidence maps next to the disparity), MatchOut (depth, point cloud and 8-bit image computed
- * on the device from the final map).
+ * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default).
  */
 #pragma once
 
@@ -61,6 +61,11 @@ public:
      *  bit 1: averaged instead of chained scanline paths; bit 2: right-image arms, cross_aggregator.h:91).  0 (default) = the
      *  reference's behaviour; anything else changes the results by definition.  Call after Initialize. */
     bool SetPaperModes(unsigned modes);
+    /** Optional speckle filter (adc_set_speckle_filter, include/adcensus_c_api.h): every later Match / MatchAsync / MatchEx / MatchOut
+     *  delivers the map with every 4-connected component (neighbours within max_diff) of at most max_size pixels set to
+     *  Invalid_Float; the outputs of MatchOut come from the filtered map.  max_size <= 0 (default) = off.  false: max_diff negative
+     *  or not finite, a Match pending, or a HIP failure.  May be called before Initialize (applied there). */
+    bool SetSpeckleFilter(int max_size, float max_diff);
     const char* LastError() const;
 
 private:
@@ -69,4 +74,6 @@ private:
     int device_;
     bool verbose_, profiling_;
     unsigned paper_;
+    int speckle_size_;
+    float speckle_diff_;
 };

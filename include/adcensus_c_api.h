@@ -192,6 +192,41 @@ int adc_reproject_device(adc_handle* h, const void* d_disp, const void* d_bgr_le
 /* Valid pixels of the last cloud request on this handle that adc_wait (or adc_match_out) has completed. */
 int adc_get_cloud_count(adc_handle* h, uint64_t* count);
 
+/* -------------------------------------------------------------------------------------------
+ * Optional speckle filter on the device: drops the small islands of the final left-view map (OpenCV's filterSpeckles, the
+ * speckleWindowSize / speckleRange pair of StereoBM / SGBM), behind the median and in front of the copy of the map to the caller
+ * and of the outputs above -- depth, cloud and disp8 of a filtered Match come from the filtered map.  OFF by default: without a
+ * call of adc_set_speckle_filter every Match is exactly what it was.  tests/speckle_ref.py holds the definition in numpy:
+ *
+ *   valid      a pixel whose value is finite (+inf is Invalid_Float; NaN and -inf of a caller's own map are invalid too and are
+ *              left untouched)
+ *   joined     two 4-neighbours p, q, both valid, with fabsf(d[p] - d[q]) <= max_diff (one binary32 subtraction; signs kept)
+ *   component  a class of the transitive closure of "joined" (a smooth ramp is ONE component however far its ends are apart)
+ *   label      int32: raster index y * W + x of the component's first pixel in raster order; -1 at invalid pixels
+ *   filter     every pixel of a component of size <= max_size becomes +inf; everything else keeps its bits
+ *   stats      components, removed components, removed pixels (uint32 each)
+ * Integer logic over one exact float comparison: results are defined bit for bit.
+ *
+ * adc_set_speckle_filter      handle state, like adc_set_paper_modes: every later Match through every entry point (adc_match,
+ *                             _async, _device, _ex, _device_ex, _out, _device_out) delivers the filtered map, also behind every
+ *                             redo adc_wait can take.  max_size <= 0 switches the filter off again.  Device scratch (12 bytes per
+ *                             pixel) is allocated by the first call that switches it on and freed by adc_destroy.  With the filter
+ *                             on, adc_match_ex / adc_match_device_ex set ADC_PROV_SPECKLE in the provenance code of the pixels
+ *                             the filter removed (confidence is left as computed).  Paper modes do not matter.
+ * adc_filter_speckles_device  the same kernels on any device-resident float32 [H][W] map of the handle's geometry, IN PLACE,
+ *                             asynchronous on the handle's stream, completed by adc_wait (the counterpart of
+ *                             adc_reproject_device).  d_labels: int32 [H][W] device buffer for the labels, or NULL.  max_size <= 0
+ *                             with d_labels labels without filtering (without d_labels: nothing to do, 0).
+ * adc_get_speckle_stats       of the last filtered Match / filter call that adc_wait has completed; any pointer may be NULL.
+ * adc_farm_set_speckle_filter all pipelines of a farm.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued or changed (NULL handle / map, max_diff negative or not finite,
+ * the setters while a Match / a pair is in flight); 2 on a HIP failure.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_PROV_SPECKLE (0x10) /* above the four bits of lr and fill */
+int adc_set_speckle_filter(adc_handle* h, int32_t max_size, float max_diff);
+int adc_filter_speckles_device(adc_handle* h, void* d_disp_inout, int32_t max_size, float max_diff, void* d_labels);
+int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed_components, uint32_t* removed_pixels);
+
 /* Host buffers, asynchronous (pinned staging inside the handle); adc_wait() completes it and
  * copies the result to disp_left given here. */
 int adc_match_async(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left);
@@ -228,6 +263,8 @@ int adc_farm_submit(adc_farm* f, const uint8_t* bgr_left, const uint8_t* bgr_rig
 int adc_farm_wait(adc_farm* f, uint64_t ticket);
 /* Completes everything submitted so far; returns the number of pairs delivered since creation, negative on failure. */
 int64_t adc_farm_drain(adc_farm* f);
+/* adc_set_speckle_filter on every pipeline of the farm (above); 1 while a pair is in flight (adc_farm_drain first). */
+int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
