@@ -29,6 +29,9 @@ LR_CONSISTENT, LR_MISMATCH, LR_OCCLUSION = 0, 1, 2
 FILL_WTA, FILL_VOTING, FILL_INTERPOLATION, FILL_NONE = 0, 1, 2, 3
 PROV_LR_MASK, PROV_FILL_SHIFT = 3, 2
 PROV_SPECKLE = 0x10  # set by a Match with the speckle filter on, at the pixels the filter removed (ADC_PROV_SPECKLE)
+PIX_BGR8, PIX_RGB8, PIX_GRAY8, PIX_BGRA8 = 0, 1, 2, 3  # adc_raw_format.format (ADC_PIX_*)
+PIX_BYTES = {PIX_BGR8: 3, PIX_RGB8: 3, PIX_GRAY8: 1, PIX_BGRA8: 4}
+SIDE_LEFT, SIDE_RIGHT = 0, 1  # ADC_SIDE_*
 
 
 class ADCensusOption(C.Structure):
@@ -68,6 +71,34 @@ class Outputs(C.Structure):
     """adc_outputs: the request of adc_match_out (host addresses) / adc_match_device_out / adc_reproject_device (device addresses)."""
     _fields_ = [("calib", C.POINTER(Calib)), ("depth", C.c_void_p), ("cloud", C.c_void_p), ("cloud_capacity", C.c_uint64),
                 ("cloud_count", C.c_void_p), ("disp8", C.c_void_p)]
+
+
+class RawFormat(C.Structure):
+    """adc_raw_format: geometry of the raw images of one side while rectification is on (pitch_bytes 0: tightly packed rows)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch_bytes", C.c_int32), ("format", C.c_int32)]
+
+    def __init__(self, width=0, height=0, pitch_bytes=0, format=PIX_BGR8):
+        super().__init__(int(width), int(height), int(pitch_bytes) or int(width) * PIX_BYTES.get(int(format), 0), int(format))
+
+    @property
+    def nbytes(self):
+        return self.height * self.pitch_bytes
+
+
+class CameraModel(C.Structure):
+    """adc_camera_model: intrinsics, Brown-Conrady distortion, rectifying rotation R (9 values, row-major), new intrinsics."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+                ("R", C.c_float * 9),
+                ("new_fx", C.c_float), ("new_fy", C.c_float), ("new_cx", C.c_float), ("new_cy", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.R = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, (C.c_float * 9)(*[float(x) for x in v]) if k == "R" else float(v))
 
 
 POINT_DTYPE = np.dtype({"names": ["x", "y", "z", "r", "g", "b", "pad"], "formats": ["<f4", "<f4", "<f4", "u1", "u1", "u1", "u1"],
@@ -138,6 +169,17 @@ def lib():
         L.adc_get_speckle_stats.restype = C.c_int
         L.adc_farm_set_speckle_filter.argtypes = [vp, i32, C.c_float]
         L.adc_farm_set_speckle_filter.restype = C.c_int
+    if hasattr(L, "adc_set_rectify_maps"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        for prefix in ("adc_", "adc_farm_"):
+            getattr(L, prefix + "set_rectify_maps").argtypes = [vp, C.c_int, C.POINTER(RawFormat), vp, vp]
+            getattr(L, prefix + "set_rectify_model").argtypes = [vp, C.c_int, C.POINTER(RawFormat), C.POINTER(CameraModel)]
+            getattr(L, prefix + "clear_rectify").argtypes = [vp]
+            for name in ("set_rectify_maps", "set_rectify_model", "clear_rectify"):
+                getattr(L, prefix + name).restype = C.c_int
+        L.adc_get_rectify_maps.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.adc_get_rectify_maps.restype = C.c_int
+        L.adc_rectify_device.argtypes = [vp, C.c_int, vp, vp]
+        L.adc_rectify_device.restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
     L.adc_stage_name.argtypes = [C.c_int]
@@ -225,6 +267,33 @@ def _img(a):
     return a
 
 
+def _maps(map_x, map_y, width, height):
+    mx, my = np.ascontiguousarray(map_x, dtype=np.float32), np.ascontiguousarray(map_y, dtype=np.float32)
+    assert mx.shape == (height, width) and my.shape == (height, width), (mx.shape, my.shape, (height, width))
+    return mx, my
+
+
+class _RectifyState:
+    """What a Python object remembers of the rectification it has set: the raw geometry per side, for the size asserts of its
+    entry points (the library keeps the real state)."""
+
+    def __init__(self):
+        self.raw = [None, None]
+
+    def set(self, side, raw):
+        self.raw[int(side)] = RawFormat(raw.width, raw.height, raw.pitch_bytes, raw.format)
+
+    def clear(self):
+        self.raw = [None, None]
+
+    def on(self):
+        return self.raw[0] is not None and self.raw[1] is not None
+
+    def sizes(self, plain):
+        """bytes the left / right image argument of a match must have"""
+        return (self.raw[0].nbytes, self.raw[1].nbytes) if self.on() else (plain, plain)
+
+
 class PreviousPairFailed(RuntimeError):
     """adc_farm_submit returned ADC_FARM_PREVIOUS_FAILED: the pair that occupied the pipeline before (`failed_ticket`) failed
     while it was collected; the NEW pair is in flight all the same and `ticket` is its ticket."""
@@ -245,10 +314,11 @@ class PairFarm:
         if not self._f:
             raise RuntimeError("adc_farm_create failed: " + last_error())
         self._keep = {}
+        self._rect = _RectifyState()
 
     def submit(self, img_left, img_right, disp_left):
         l, r = _img(img_left), _img(img_right)
-        assert l.size == self.width * self.height * 3 and r.size == l.size
+        assert (l.size, r.size) == self._rect.sizes(self.width * self.height * 3)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == self.width * self.height
         t = C.c_uint64(0)
         rc = lib().adc_farm_submit(self._f, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, C.byref(t))
@@ -278,6 +348,24 @@ class PairFarm:
         if lib().adc_farm_set_speckle_filter(self._f, int(max_size), float(max_diff)) != 0:
             raise RuntimeError("adc_farm_set_speckle_filter failed: " + last_error())
 
+    def set_rectify_maps(self, side, raw, map_x, map_y):
+        """ADCensusStereo.set_rectify_maps on every pipeline (adc_farm_set_rectify_maps); drain() first."""
+        mx, my = _maps(map_x, map_y, self.width, self.height)
+        if lib().adc_farm_set_rectify_maps(self._f, int(side), C.byref(raw), mx.ctypes.data, my.ctypes.data) != 0:
+            raise RuntimeError("adc_farm_set_rectify_maps failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def set_rectify_model(self, side, raw, model):
+        """ADCensusStereo.set_rectify_model on every pipeline (adc_farm_set_rectify_model); drain() first."""
+        if lib().adc_farm_set_rectify_model(self._f, int(side), C.byref(raw), C.byref(model)) != 0:
+            raise RuntimeError("adc_farm_set_rectify_model failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def clear_rectify(self):
+        if lib().adc_farm_clear_rectify(self._f) != 0:
+            raise RuntimeError("adc_farm_clear_rectify failed: " + last_error())
+        self._rect.clear()
+
     def close(self):
         if self._f:
             lib().adc_farm_destroy(self._f)
@@ -303,6 +391,7 @@ class ADCensusStereo:
         self._device = device
         self.width = self.height = 0
         self.option = None
+        self._rect = _RectifyState()
 
     # -- lifetime ------------------------------------------------------------------------------
     def Initialize(self, width, height, option):
@@ -310,6 +399,7 @@ class ADCensusStereo:
         self.width, self.height, self.option = int(width), int(height), option
         h = lib().adc_create(int(width), int(height), C.byref(option), int(self._device))
         self._h = h
+        self._rect.clear()  # (a new handle: rectification is off)
         return bool(h)
 
     def Reset(self, width, height, option):
@@ -342,7 +432,7 @@ class ADCensusStereo:
         if img_left is None or img_right is None or disp_left is None:
             return False  # :74-76
         l, r = _img(img_left), _img(img_right)
-        assert l.size == self.width * self.height * 3 and r.size == l.size
+        assert (l.size, r.size) == self._rect.sizes(self.width * self.height * 3)  # (rectification on: the raw sizes)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == self.width * self.height
         return lib().adc_match(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data) == 0
 
@@ -364,7 +454,7 @@ class ADCensusStereo:
             return False
         l, r = _img(img_left), _img(img_right)
         n = self.width * self.height
-        assert l.size == n * 3 and r.size == l.size
+        assert (l.size, r.size) == self._rect.sizes(n * 3)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
         for a, dt in ((provenance, np.uint8), (confidence, np.float32)):
             assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
@@ -394,7 +484,7 @@ class ADCensusStereo:
             return False
         l, r = _img(img_left), _img(img_right)
         n = self.width * self.height
-        assert l.size == n * 3 and r.size == l.size
+        assert (l.size, r.size) == self._rect.sizes(n * 3)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
         for a, dt in ((depth, np.float32), (disp8, np.uint8)):
             assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
@@ -476,6 +566,62 @@ class ADCensusStereo:
         if lib().adc_get_speckle_stats(self._h, C.byref(c), C.byref(rc), C.byref(rp)) != 0:
             raise RuntimeError("adc_get_speckle_stats failed")
         return int(c.value), int(rc.value), int(rp.value)
+
+    # -- rectification of raw images in front of the match (adc_set_rectify_*) -------------------
+    def set_rectify_maps(self, side, raw, map_x, map_y):
+        """Declares the raw images of one side (SIDE_LEFT / SIDE_RIGHT) as `raw` (a RawFormat) and their rectification as the float32
+        [H][W] maps of source coordinates (as cv::initUndistortRectifyMap gives them).  Once both sides are set, EVERY match entry point
+        of this object takes raw images (raw.nbytes bytes each) and matches their rectified versions.  Raises when refused or on a
+        HIP failure."""
+        mx, my = _maps(map_x, map_y, self.width, self.height)
+        if lib().adc_set_rectify_maps(self._h, int(side), C.byref(raw), mx.ctypes.data, my.ctypes.data) != 0:
+            raise RuntimeError("adc_set_rectify_maps failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def set_rectify_model(self, side, raw, model):
+        """The same with the maps computed on the device from a CameraModel (adc_set_rectify_model)."""
+        if lib().adc_set_rectify_model(self._h, int(side), C.byref(raw), C.byref(model)) != 0:
+            raise RuntimeError("adc_set_rectify_model failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def clear_rectify(self):
+        """Rectification off again: the entry points take rectified [H][W][3] BGR images (adc_clear_rectify)."""
+        if lib().adc_clear_rectify(self._h) != 0:
+            raise RuntimeError("adc_clear_rectify failed: " + last_error())
+        self._rect.clear()
+
+    def rectify_maps(self, side):
+        """(map_x float32, map_y float32, valid uint8) [H][W] in use for a side (adc_get_rectify_maps); raises when the side is not set."""
+        shp = (self.height, self.width)
+        mx, my, v = np.empty(shp, np.float32), np.empty(shp, np.float32), np.empty(shp, np.uint8)
+        if lib().adc_get_rectify_maps(self._h, int(side), mx.ctypes.data, my.ctypes.data, v.ctypes.data) != 0:
+            raise RuntimeError("adc_get_rectify_maps failed: " + last_error())
+        return mx, my, v
+
+    def rectify_device(self, side, d_raw, d_bgr_out):
+        """The remap alone on device buffers (ints): raw image of the side's geometry -> [H][W][3] BGR (adc_rectify_device);
+        asynchronous, call wait()."""
+        return lib().adc_rectify_device(self._h, int(side), d_raw, d_bgr_out) == 0
+
+    def rectify(self, raw, side):
+        """Host convenience: uploads one raw image of the side's geometry, remaps it on the device, returns uint8 [H][W][3] BGR."""
+        a = _img(raw)
+        fmt = self._rect.raw[int(side)]
+        assert fmt is not None and a.size == fmt.nbytes, (None if fmt is None else fmt.nbytes, a.size)
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        L = lib()
+        pr, po = L.adc_device_malloc(a.nbytes), L.adc_device_malloc(out.nbytes)
+        try:
+            if not pr or not po or L.adc_memcpy_h2d(pr, a.ctypes.data, a.nbytes) != 0:
+                raise RuntimeError("rectify: device buffer")
+            if not (self.rectify_device(side, pr, po) and self.wait()):
+                raise RuntimeError("adc_rectify_device failed: " + last_error())
+            if L.adc_memcpy_d2h(out.ctypes.data, po, out.nbytes) != 0:
+                raise RuntimeError("rectify: download")
+        finally:
+            L.adc_device_free(pr)
+            L.adc_device_free(po)
+        return out
 
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do

@@ -69,6 +69,19 @@ struct AdcOutReq {
     uint8_t* disp8;
 };
 
+// One side of the optional rectification (k_rectify.hip): the declared geometry of the raw images, and what the set call made of
+// the maps.  The [H][W] buffers are allocated by the first set call of a handle (both sides at once), the raw buffer grows with the
+// largest geometry declared; adc_destroy frees them.
+struct AdcRectSide {
+    int set;              // a set call has succeeded for this side (adc_clear_rectify / a failed set call: 0)
+    adc_raw_format fmt;
+    uint32_t* rec;        // uint2 per destination pixel: {xi | yi << 16, ax | ay << 8 | flags << 16}
+    float *mx, *my;       // the float maps (the caller's, or the model's): adc_get_rectify_maps
+    uint8_t* valid;       // 1 where every tap with a nonzero weight lies inside the source
+    uint8_t* raw;         // device copy of the raw image of the host entry points
+    size_t raw_cap;       // bytes raw holds
+};
+
 struct adc_handle {
     AdcParams p;
     int device;
@@ -202,6 +215,10 @@ struct adc_handle {
     float sp_max_diff;
     int32_t* sp_parent;   // device scratch, allocated on first use: parent [P], size [P], then the three stat words
     float* sp_map;        // the filtered map of a Match (out of place: a redo of adc_wait may patch disp_l only in part)
+    // optional rectification of raw images in front of the Match (k_rectify.hip; on = both sides set, off: nothing of it is enqueued)
+    AdcRectSide rect[2];  // ADC_SIDE_LEFT, ADC_SIDE_RIGHT
+    uint8_t* pin_raw;     // pinned staging of the two raw images (left at 0, right behind it)
+    size_t pin_raw_cap;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -258,6 +275,9 @@ hipError_t adc_launch_speckle_runs(adc_handle* h, const float* src, float max_di
 hipError_t adc_launch_speckle_merge(adc_handle* h, const float* src, float max_diff);   // unions across rows and 64-pixel pieces
 hipError_t adc_launch_speckle_flatten(adc_handle* h, int32_t* labels);                  // parent = root (-> labels, may be NULL), sizes, components
 hipError_t adc_launch_speckle_apply(adc_handle* h, const float* src, float* dst, uint8_t* prov, int max_size); // small components -> +inf
+hipError_t adc_launch_rect_model_maps(adc_handle* h, int side, const adc_camera_model* m); // k_rectify.hip: model -> rect[side].mx / my
+hipError_t adc_launch_rect_pack(adc_handle* h, int side);                                   // mx / my -> records, valid map
+hipError_t adc_launch_rect_remap(adc_handle* h, int side, const uint8_t* raw, uint8_t* bgr_out); // raw image -> [H][W][3] BGR
 size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)

@@ -329,8 +329,10 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->sp_parent, h->sp_map};
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->sp_parent, h->sp_map,
+                    h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw};
     for (void* b : bufs) if (b) hipFree(b);
+    if (h->pin_raw) hipHostFree(h->pin_raw);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
     if (h->pin_flags) hipHostFree(h->pin_flags);
@@ -550,6 +552,30 @@ static hipError_t enqueue_output(adc_handle* h)
     return e;
 }
 
+// Optional rectification (k_rectify.hip): 0 off (no side set: the entry points take rectified W x H BGR images), 1 on (both sides
+// set: they take raw images of the declared geometries), -1 exactly one side set (a Match is refused)
+static int rectify_state(const adc_handle* h)
+{
+    const int n = (h->rect[0].set ? 1 : 0) + (h->rect[1].set ? 1 : 0);
+    return n == 2 ? 1 : (n == 0 ? 0 : -1);
+}
+static bool rectify_refused(const adc_handle* h, const char* who)
+{
+    if (rectify_state(h) >= 0) return false;
+    g_last_error = std::string(who) + ": rectification is set for one side only (set the other side, or adc_clear_rectify)";
+    return true;
+}
+static size_t raw_bytes(const adc_raw_format& f) { return (size_t)f.height * (size_t)f.pitch_bytes; }
+// both raw images -> the handle's own W x H BGR buffers, on the object stream in front of run_pipeline.  Out of place: a redo of
+// adc_wait finds the rectified pair still there (nothing downstream writes the image buffers)
+static hipError_t enqueue_rectify(adc_handle* h, const void* raw_l, const void* raw_r)
+{
+    HIP_OK(adc_launch_rect_remap(h, ADC_SIDE_LEFT, static_cast<const uint8_t*>(raw_l), h->img_l_own));
+    HIP_OK(adc_launch_rect_remap(h, ADC_SIDE_RIGHT, static_cast<const uint8_t*>(raw_r), h->img_r_own));
+    h->bgrx_valid = 0;
+    return hipSuccess;
+}
+
 // A HIP call of a Match failed half-way (the reference's contract: Match returns false and the object stays usable,
 // ADCensusStereo.cpp:71-76).  Whatever was already enqueued is drained, every per-Match flag of the handle goes back to its idle
 // value -- a later Match must not find a half-described predecessor: a pending voting chain, a dropped aggregation pass the
@@ -582,11 +608,20 @@ static void abort_match(adc_handle* h)
 int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, void* d_disp)
 {
     if (!h || !d_left || !d_right || !d_disp) return 1; // ADCensusStereo.cpp:71-76
+    if (rectify_refused(h, "adc_match_device")) return 1;
     hipSetDevice(h->device);
+    if (rectify_state(h) > 0) {
+        // rectification on: the caller's RAW images are read by the remap only (borrowed until adc_wait all the same), the Match
+        // runs on the handle's own buffers
+        h->img_l = h->img_l_own;
+        h->img_r = h->img_r_own;
+        if (enqueue_rectify(h, d_left, d_right) != hipSuccess) { abort_match(h); return 2; }
+    } else {
     // the caller's device images are BORROWED until adc_wait returns (like the reference borrows the host pointers for the
     // duration of Match, ADCensusStereo.cpp:78-79): no copy
     h->img_l = const_cast<uint8_t*>(static_cast<const uint8_t*>(d_left));
     h->img_r = const_cast<uint8_t*>(static_cast<const uint8_t*>(d_right));
+    }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
     h->device_dst = d_disp;
     h->async_dst = nullptr;
@@ -597,10 +632,16 @@ int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, voi
 static int match_async_impl(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, bool sync_call)
 {
     if (!h || !left || !right || !disp) return 1;
+    if (rectify_refused(h, "adc_match")) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
     h->img_l = h->img_l_own;
     h->img_r = h->img_r_own;
+    // rectification on: what is uploaded are the two RAW images (height * pitch_bytes each) into the raw buffers, through the raw
+    // staging; the remap then writes the own buffers.  Off: nl == nr == 3 * P into the image buffers, as ever
+    const bool rect = rectify_state(h) > 0;
+    const size_t nl = rect ? raw_bytes(h->rect[0].fmt) : P * 3, nr = rect ? raw_bytes(h->rect[1].fmt) : P * 3;
+    uint8_t *const dst_l = rect ? h->rect[0].raw : h->img_l, *const dst_r = rect ? h->rect[1].raw : h->img_r, *const pin = rect ? h->pin_raw : h->pin_in;
     // Synchronous adc_match only (the caller cannot touch its buffers before the call returns): hand the pageable pointers to
     // the runtime (its own chunked staging / pin-in-place: measured 145 vs 140 pairs/s at 1080p; ADC_HOST_DIRECT=0 switches it
     // off).  The asynchronous entry points promise "the images may be reused as soon as the call returns", so they always
@@ -611,31 +652,32 @@ static int match_async_impl(adc_handle* h, const uint8_t* left, const uint8_t* r
     // copy: the asynchronous entry points (adc_match_async, adc_farm_submit) promise that the caller may refill its images as
     // soon as the call returns, so they always stage the inputs (a DMA still in flight would read the refilled pixels).  The
     // OUTPUT map of a registered range is written in place by every entry point (it is the caller's until adc_wait anyway).
-    const bool reg_in = sync_call && host_registered(left, P * 3) && host_registered(right, P * 3);
+    const bool reg_in = sync_call && host_registered(left, nl) && host_registered(right, nr);
     // (Round 6, measured and NOT adopted: left image first, the kernels that need only the left image -- arms, support counts,
     // aggregation records -- enqueued, the right image on a second stream behind an event.  Pageable buffers: no gain; buffers the
     // caller registered: 192 -> 180 pairs/s -- the cross-stream dependency costs more than the ~0.1 ms of overlap it buys,
     // profiles/r6_ab_upload_overlap.txt.)
     const uint8_t *lsrc = left, *rsrc = right;
     if (!(reg_in || direct)) { // staging: the second image is copied while the first one is on the bus
-        memcpy(h->pin_in, left, P * 3);
-        lsrc = h->pin_in;
+        memcpy(pin, left, nl);
+        lsrc = pin;
     }
     // (reg_in / direct: DMA from the caller's memory -- page-locked by the caller: asynchronous; pageable: the runtime stages)
-    if (ADC_HIP(hipMemcpyAsync(h->img_l, lsrc, P * 3, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
+    if (ADC_HIP(hipMemcpyAsync(dst_l, lsrc, nl, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
         set_error("adc_match: upload of the left image", hipGetLastError());
         abort_match(h);
         return 2;
     }
     if (!(reg_in || direct)) {
-        memcpy(h->pin_in + P * 3, right, P * 3);
-        rsrc = h->pin_in + P * 3;
+        memcpy(pin + nl, right, nr);
+        rsrc = pin + nl;
     }
-    if (ADC_HIP(hipMemcpyAsync(h->img_r, rsrc, P * 3, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
+    if (ADC_HIP(hipMemcpyAsync(dst_r, rsrc, nr, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
         set_error("adc_match: upload of the right image", hipGetLastError());
         abort_match(h);
         return 2;
     }
+    if (rect && enqueue_rectify(h, dst_l, dst_r) != hipSuccess) { abort_match(h); return 2; }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
     h->async_dst = disp;
     h->async_dst_direct = host_registered(disp, P * 4) ? 1 : (direct ? 2 : 0);
@@ -1003,6 +1045,138 @@ int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed
     return 0;
 }
 
+// ------------------------------------------------------------------------------ rectification (k_rectify.hip)
+// Handle state per side.  A set call brings the float maps to the device (the caller's, or the model's computed there), packs them
+// into the records of the hot kernel and the valid map, and waits: the entry points above find everything ready.
+static int rect_bpp(int format) { return format == ADC_PIX_GRAY8 ? 1 : (format == ADC_PIX_BGRA8 ? 4 : 3); }
+
+static int rect_args_ok(adc_handle* h, int side, const adc_raw_format* f, const void* a, const void* b, const char* who)
+{
+    if (!h || !f || !a || !b) return 0;
+    const char* why = nullptr;
+    if (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) why = "side must be ADC_SIDE_LEFT or ADC_SIDE_RIGHT";
+    else if (f->format < ADC_PIX_BGR8 || f->format > ADC_PIX_BGRA8) why = "unknown pixel format";
+    else if (f->width < 1 || f->width > 32767 || f->height < 1 || f->height > 32767) why = "raw width / height must be 1..32767";
+    else if ((long long)f->pitch_bytes < (long long)f->width * rect_bpp(f->format)) why = "pitch_bytes is smaller than a row";
+    else if ((long long)f->height * (long long)f->pitch_bytes > 2147483647LL) why = "a raw image must be smaller than 2 GiB";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) g_last_error = std::string(who) + ": " + why;
+    return why ? 0 : 1;
+}
+
+// first set call of a handle: the [H][W] buffers of both sides; every set call: raw buffer and raw staging large enough
+static hipError_t rect_buffers(adc_handle* h, int side, const adc_raw_format* f)
+{
+    const size_t P = (size_t)h->p.W * h->p.H;
+    for (int s = 0; s < 2; s++) {
+        AdcRectSide& r = h->rect[s];
+        if (!r.rec) HIP_OK(hipMalloc(&r.rec, P * 8));
+        if (!r.mx) HIP_OK(hipMalloc(&r.mx, P * 4));
+        if (!r.my) HIP_OK(hipMalloc(&r.my, P * 4));
+        if (!r.valid) HIP_OK(hipMalloc(&r.valid, P));
+    }
+    AdcRectSide& r = h->rect[side];
+    const size_t n = raw_bytes(*f);
+    if (r.raw_cap < n) {
+        if (r.raw) hipFree(r.raw);
+        r.raw = nullptr; r.raw_cap = 0;
+        HIP_OK(hipMalloc(&r.raw, n));
+        r.raw_cap = n;
+    }
+    const size_t other = h->rect[side ^ 1].set ? raw_bytes(h->rect[side ^ 1].fmt) : n; // (sized for two raw images)
+    if (h->pin_raw_cap < n + other) {
+        if (h->pin_raw) hipHostFree(h->pin_raw);
+        h->pin_raw = nullptr; h->pin_raw_cap = 0;
+        HIP_OK(hipHostMalloc(&h->pin_raw, n + other, hipHostMallocDefault));
+        h->pin_raw_cap = n + other;
+    }
+    return hipSuccess;
+}
+
+static hipError_t rect_install(adc_handle* h, int side, const adc_raw_format* f, const float* map_x, const float* map_y, const adc_camera_model* model)
+{
+    const size_t P = (size_t)h->p.W * h->p.H;
+    const hipError_t eb = rect_buffers(h, side, f); // (every HIP call in there is hooked itself)
+    if (eb != hipSuccess) return eb;
+    AdcRectSide& r = h->rect[side];
+    r.fmt = *f;
+    if (model) HIP_OK(adc_launch_rect_model_maps(h, side, model));
+    else {
+        HIP_OK(hipMemcpyAsync(r.mx, map_x, P * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_OK(hipMemcpyAsync(r.my, map_y, P * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_OK(adc_launch_rect_pack(h, side));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return hipSuccess;
+}
+
+static int rect_set(adc_handle* h, int side, const adc_raw_format* f, const float* map_x, const float* map_y, const adc_camera_model* model, const char* who)
+{
+    hipSetDevice(h->device);
+    h->rect[side].set = 0; // (a failure below leaves this side unset: its records may be half written)
+    if (rect_install(h, side, f, map_x, map_y, model) != hipSuccess) {
+        const std::string keep = std::string(who) + ": " + g_last_error;
+        abort_match(h); // (drains the stream; no Match was pending)
+        g_last_error = keep;
+        return 2;
+    }
+    h->rect[side].set = 1;
+    return 0;
+}
+
+int adc_set_rectify_maps(adc_handle* h, int side, const adc_raw_format* raw, const float* map_x, const float* map_y)
+{
+    if (!rect_args_ok(h, side, raw, map_x, map_y, "adc_set_rectify_maps")) return 1;
+    return rect_set(h, side, raw, map_x, map_y, nullptr, "adc_set_rectify_maps");
+}
+
+int adc_set_rectify_model(adc_handle* h, int side, const adc_raw_format* raw, const adc_camera_model* model)
+{
+    if (!rect_args_ok(h, side, raw, model, model, "adc_set_rectify_model")) return 1;
+    const float* v = &model->fx;
+    bool finite = true;
+    for (size_t i = 0; i < sizeof(adc_camera_model) / sizeof(float); i++) finite = finite && __builtin_isfinite(v[i]);
+    if (!finite || model->fx == 0.0f || model->fy == 0.0f || model->new_fx == 0.0f || model->new_fy == 0.0f) {
+        g_last_error = "adc_set_rectify_model: every value must be finite, and fx, fy, new_fx, new_fy nonzero";
+        return 1;
+    }
+    return rect_set(h, side, raw, nullptr, nullptr, model, "adc_set_rectify_model");
+}
+
+int adc_clear_rectify(adc_handle* h)
+{
+    if (!h) return 1;
+    if (match_in_flight(h)) { g_last_error = "adc_clear_rectify: a Match is pending (adc_wait first)"; return 1; }
+    h->rect[0].set = 0;
+    h->rect[1].set = 0;
+    return 0;
+}
+
+int adc_get_rectify_maps(adc_handle* h, int side, float* map_x, float* map_y, uint8_t* valid)
+{
+    if (!h || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT)) return 1;
+    const AdcRectSide& r = h->rect[side];
+    if (!r.set) { g_last_error = "adc_get_rectify_maps: this side is not set"; return 1; }
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = ADC_HIP(hipStreamSynchronize(h->stream));
+    if (e == hipSuccess && map_x) e = ADC_HIP(hipMemcpy(map_x, r.mx, P * 4, hipMemcpyDeviceToHost));
+    if (e == hipSuccess && map_y) e = ADC_HIP(hipMemcpy(map_y, r.my, P * 4, hipMemcpyDeviceToHost));
+    if (e == hipSuccess && valid) e = ADC_HIP(hipMemcpy(valid, r.valid, P, hipMemcpyDeviceToHost));
+    if (e != hipSuccess) { set_error("adc_get_rectify_maps", e); return 2; }
+    return 0;
+}
+
+int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_out)
+{
+    if (!h || !d_raw || !d_bgr_out || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT)) return 1;
+    if (!h->rect[side].set) { g_last_error = "adc_rectify_device: this side is not set"; return 1; }
+    hipSetDevice(h->device);
+    const hipError_t e = ADC_HIP(adc_launch_rect_remap(h, side, static_cast<const uint8_t*>(d_raw), static_cast<uint8_t*>(d_bgr_out)));
+    if (e != hipSuccess) { set_error("adc_rectify_device", e); abort_match(h); return 2; }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------ pair farm
 struct adc_farm {
     std::vector<adc_handle*> pipes;
@@ -1100,6 +1274,38 @@ int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff)
         const int rc = adc_set_speckle_filter(f->pipes[i], max_size, max_diff);
         if (rc != 0) return rc;
     }
+    return 0;
+}
+
+static bool farm_idle(adc_farm* f, const char* who)
+{
+    for (size_t i = 0; i < f->pipes.size(); i++)
+        if (f->in_flight[i]) { g_last_error = std::string(who) + ": a pair is in flight (adc_farm_drain first)"; return false; }
+    return true;
+}
+int adc_farm_set_rectify_maps(adc_farm* f, int side, const adc_raw_format* raw, const float* map_x, const float* map_y)
+{
+    if (!f || !raw || !map_x || !map_y || !farm_idle(f, "adc_farm_set_rectify_maps")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++) {
+        const int rc = adc_set_rectify_maps(f->pipes[i], side, raw, map_x, map_y);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+int adc_farm_set_rectify_model(adc_farm* f, int side, const adc_raw_format* raw, const adc_camera_model* model)
+{
+    if (!f || !raw || !model || !farm_idle(f, "adc_farm_set_rectify_model")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++) {
+        const int rc = adc_set_rectify_model(f->pipes[i], side, raw, model);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+int adc_farm_clear_rectify(adc_farm* f)
+{
+    if (!f || !farm_idle(f, "adc_farm_clear_rectify")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++)
+        if (adc_clear_rectify(f->pipes[i]) != 0) return 1;
     return 0;
 }
 

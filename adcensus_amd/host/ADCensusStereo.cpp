@@ -4,7 +4,19 @@
 #include "ADCensusStereo.h"
 #include "adcensus_c_api.h"
 
+#include <math.h>
 #include <stdlib.h>
+#include <new>
+#include <vector>
+
+// what SetRectifyMaps / SetRectifyModel were given for one side: applied by Initialize, and again by every Reset
+struct ADCensusStereo::RectifySide {
+    adc_raw_format raw;
+    bool is_model;
+    adc_camera_model model;
+    std::vector<float> map_x, map_y;
+    sint32 map_w, map_h;
+};
 
 static adc_option to_c(const ADCensusOption& o)
 {
@@ -30,8 +42,16 @@ static bool default_verbose()
     const char* e = getenv("ADC_VERBOSE");
     return e ? atoi(e) != 0 : true;
 }
-ADCensusStereo::ADCensusStereo() : impl_(nullptr), device_(-1), verbose_(default_verbose()), profiling_(false), paper_(0), speckle_size_(0), speckle_diff_(0.0f) {}
-ADCensusStereo::~ADCensusStereo() { Release(); }
+ADCensusStereo::ADCensusStereo() : impl_(nullptr), device_(-1), verbose_(default_verbose()), profiling_(false), paper_(0), speckle_size_(0), speckle_diff_(0.0f), width_(0), height_(0)
+{
+    rect_[0] = rect_[1] = nullptr;
+}
+ADCensusStereo::~ADCensusStereo()
+{
+    Release();
+    delete rect_[0];
+    delete rect_[1];
+}
 
 void ADCensusStereo::Release()
 {
@@ -45,10 +65,13 @@ bool ADCensusStereo::Initialize(const sint32& width, const sint32& height, const
     const adc_option c = to_c(option);
     impl_ = adc_create(width, height, &c, device_);
     if (!impl_) return false;
+    width_ = width; height_ = height;
     if (profiling_) adc_set_profiling(impl_, 1);
     if (verbose_) adc_set_verbose(impl_, 1);
     if (paper_ && adc_set_paper_modes(impl_, paper_) != 0) return false;
     if (speckle_size_ > 0 && adc_set_speckle_filter(impl_, speckle_size_, speckle_diff_) != 0) return false;
+    for (int side = 0; side < 2; side++)
+        if (rect_[side] && !ApplyRectify(side)) return false;
     return true;
 }
 
@@ -109,5 +132,72 @@ bool ADCensusStereo::SetSpeckleFilter(int max_size, float max_diff)
     speckle_size_ = max_size > 0 ? max_size : 0;
     speckle_diff_ = max_size > 0 ? max_diff : 0.0f;
     return true;
+}
+
+static bool raw_format_ok(const adc_raw_format* f)
+{
+    if (!f || f->format < ADC_PIX_BGR8 || f->format > ADC_PIX_BGRA8) return false;
+    const int bpp = f->format == ADC_PIX_GRAY8 ? 1 : (f->format == ADC_PIX_BGRA8 ? 4 : 3);
+    return f->width >= 1 && f->width <= 32767 && f->height >= 1 && f->height <= 32767 && (long long)f->pitch_bytes >= (long long)f->width * bpp &&
+           (long long)f->height * f->pitch_bytes <= 2147483647LL;
+}
+bool ADCensusStereo::ApplyRectify(int side)
+{
+    const RectifySide& r = *rect_[side];
+    if (r.is_model) return adc_set_rectify_model(impl_, side, &r.raw, &r.model) == 0;
+    if (r.map_w != width_ || r.map_h != height_) return false; // (the maps have the rectified size)
+    return adc_set_rectify_maps(impl_, side, &r.raw, r.map_x.data(), r.map_y.data()) == 0;
+}
+bool ADCensusStereo::SetRectifyMaps(int side, const adc_raw_format* raw, const float32* map_x, const float32* map_y, sint32 map_width, sint32 map_height)
+{
+    if ((side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) || !raw_format_ok(raw) || !map_x || !map_y || map_width < 1 || map_height < 1) return false;
+    if (impl_ && (map_width != width_ || map_height != height_)) return false;
+    RectifySide* r = new (std::nothrow) RectifySide();
+    if (!r) return false;
+    const size_t n = (size_t)map_width * (size_t)map_height;
+    r->raw = *raw; r->is_model = false; r->map_w = map_width; r->map_h = map_height;
+    r->map_x.assign(map_x, map_x + n);
+    r->map_y.assign(map_y, map_y + n);
+    RectifySide* old = rect_[side];
+    rect_[side] = r;
+    if (impl_ && !ApplyRectify(side)) { rect_[side] = old; delete r; return false; } // (the library's state for this side is unchanged or unset; see adc_last_error)
+    delete old;
+    return true;
+}
+bool ADCensusStereo::SetRectifyModel(int side, const adc_raw_format* raw, const adc_camera_model* model)
+{
+    if ((side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) || !raw_format_ok(raw) || !model) return false;
+    const float* v = &model->fx;
+    for (size_t i = 0; i < sizeof(adc_camera_model) / sizeof(float); i++)
+        if (!std::isfinite(v[i])) return false;
+    if (model->fx == 0.0f || model->fy == 0.0f || model->new_fx == 0.0f || model->new_fy == 0.0f) return false;
+    RectifySide* r = new (std::nothrow) RectifySide();
+    if (!r) return false;
+    r->raw = *raw; r->is_model = true; r->model = *model; r->map_w = r->map_h = 0;
+    RectifySide* old = rect_[side];
+    rect_[side] = r;
+    if (impl_ && !ApplyRectify(side)) { rect_[side] = old; delete r; return false; }
+    delete old;
+    return true;
+}
+bool ADCensusStereo::ClearRectify()
+{
+    if (impl_ && adc_clear_rectify(impl_) != 0) return false;
+    delete rect_[0];
+    delete rect_[1];
+    rect_[0] = rect_[1] = nullptr;
+    return true;
+}
+bool ADCensusStereo::Rectify(int side, const uint8* raw, uint8* bgr_out)
+{
+    if (!impl_ || !raw || !bgr_out || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) || !rect_[side]) return false;
+    const size_t n_raw = (size_t)rect_[side]->raw.height * (size_t)rect_[side]->raw.pitch_bytes, n_out = (size_t)width_ * (size_t)height_ * 3;
+    void* d_raw = adc_device_malloc(n_raw);
+    void* d_out = adc_device_malloc(n_out);
+    const bool ok = d_raw && d_out && adc_memcpy_h2d(d_raw, raw, n_raw) == 0 && adc_rectify_device(impl_, side, d_raw, d_out) == 0 && adc_wait(impl_) == 0 &&
+                    adc_memcpy_d2h(bgr_out, d_out, n_out) == 0;
+    adc_device_free(d_raw);
+    adc_device_free(d_out);
+    return ok;
 }
 const char* ADCensusStereo::LastError() const { return adc_last_error(); }

@@ -17,6 +17,13 @@
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
+// --rectify LEFT.txt,RIGHT.txt (anywhere after the program name) declares the two images RAW camera frames and rectifies them on the
+// device in front of the Match (ADCensusStereo::SetRectifyModel).  Each file holds one camera as key=value lines ('#' starts a
+// comment): width height pitch format (BGR8 RGB8 GRAY8 BGRA8: the layout the loaded pixels are repacked into before they are
+// handed over) fx fy cx cy k1 k2 p1 p2 k3 R (nine values, row-major) new_fx new_fy new_cx new_cy, each exactly once, and optionally
+// rect_width rect_height (the rectified size, default: the raw size; both files must agree).  A malformed flag or file is refused
+// while the arguments are parsed.  Every file of the run then comes from the rectified pair, and the run also writes
+//   <out>-rect-left.png  <out>-rect-right.png   the rectified images
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -28,6 +35,91 @@
 #include "ADCensusStereo.h"
 #include "adcensus_c_api.h"
 #include "adc_image_io.h"
+
+struct RectifyFile { adc_raw_format raw; adc_camera_model model; int rect_w, rect_h; };
+
+// one camera file of --rectify; false (with the reason in `why`) unless every key is there exactly once and every value parses
+static bool parse_rectify_file(const std::string& path, RectifyFile& out, std::string& why)
+{
+    static const char* const keys[] = {"width", "height", "pitch", "format", "fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "R",
+                                       "new_fx", "new_fy", "new_cx", "new_cy", "rect_width", "rect_height"};
+    const int nkeys = 20, required = 18;
+    int seen[20] = {0};
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) { why = "cannot read " + path; return false; }
+    memset(&out, 0, sizeof(out));
+    char line[1024];
+    bool ok = true;
+    while (ok && fgets(line, sizeof(line), f)) {
+        std::string t(line);
+        const size_t hash = t.find('#');
+        if (hash != std::string::npos) t.resize(hash);
+        while (!t.empty() && strchr(" \t\r\n", t.back())) t.pop_back();
+        size_t b = 0;
+        while (b < t.size() && (t[b] == ' ' || t[b] == '\t')) b++;
+        t = t.substr(b);
+        if (t.empty()) continue;
+        const size_t eq = t.find('=');
+        if (eq == std::string::npos) { why = path + ": not a key=value line: " + t; ok = false; break; }
+        std::string key = t.substr(0, eq), val = t.substr(eq + 1);
+        while (!key.empty() && (key.back() == ' ' || key.back() == '\t')) key.pop_back();
+        int k = -1;
+        for (int i = 0; i < nkeys; i++) if (key == keys[i]) k = i;
+        if (k < 0) { why = path + ": unknown key " + key; ok = false; break; }
+        if (seen[k]++) { why = path + ": key given twice: " + key; ok = false; break; }
+        char tail = 0;
+        if (k == 3) { // format: a name or its number
+            while (!val.empty() && (val[0] == ' ' || val[0] == '\t')) val.erase(0, 1);
+            static const char* const names[] = {"BGR8", "RGB8", "GRAY8", "BGRA8"};
+            int fmt = -1;
+            for (int i = 0; i < 4; i++) if (val == names[i] || (val.size() == 1 && val[0] == '0' + i)) fmt = i;
+            if (fmt < 0) { why = path + ": format must be BGR8, RGB8, GRAY8 or BGRA8"; ok = false; break; }
+            out.raw.format = fmt;
+        } else if (k == 13) { // R: nine values
+            for (char& c : val) if (c == ',') c = ' ';
+            float* R = out.model.R;
+            if (sscanf(val.c_str(), "%f %f %f %f %f %f %f %f %f %c", R, R + 1, R + 2, R + 3, R + 4, R + 5, R + 6, R + 7, R + 8, &tail) != 9) { why = path + ": R needs nine values"; ok = false; break; }
+        } else if (k <= 2 || k >= 18) { // integers
+            int v = 0;
+            if (sscanf(val.c_str(), "%d %c", &v, &tail) != 1) { why = path + ": " + key + " needs an integer"; ok = false; break; }
+            if (k == 0) out.raw.width = v; else if (k == 1) out.raw.height = v; else if (k == 2) out.raw.pitch_bytes = v; else if (k == 18) out.rect_w = v; else out.rect_h = v;
+        } else { // floats
+            float v = 0.f;
+            if (sscanf(val.c_str(), "%f %c", &v, &tail) != 1) { why = path + ": " + key + " needs a number"; ok = false; break; }
+            float* const dst[] = {&out.model.fx, &out.model.fy, &out.model.cx, &out.model.cy, &out.model.k1, &out.model.k2, &out.model.p1, &out.model.p2, &out.model.k3,
+                                  nullptr, &out.model.new_fx, &out.model.new_fy, &out.model.new_cx, &out.model.new_cy};
+            *dst[k - 4] = v;
+        }
+    }
+    fclose(f);
+    if (!ok) return false;
+    for (int i = 0; i < required; i++) if (!seen[i]) { why = path + ": key missing: " + keys[i]; return false; }
+    if (seen[18] != seen[19]) { why = path + ": rect_width and rect_height come together"; return false; }
+    if (!seen[18]) { out.rect_w = out.raw.width; out.rect_h = out.raw.height; }
+    const int bpp = out.raw.format == ADC_PIX_GRAY8 ? 1 : (out.raw.format == ADC_PIX_BGRA8 ? 4 : 3);
+    if (out.raw.width < 1 || out.raw.width > 32767 || out.raw.height < 1 || out.raw.height > 32767 || (long long)out.raw.pitch_bytes < (long long)out.raw.width * bpp ||
+        (long long)out.raw.height * out.raw.pitch_bytes > 2147483647LL || out.rect_w < 1 || out.rect_h < 1) { why = path + ": width / height / pitch out of range"; return false; }
+    const float* v = &out.model.fx;
+    for (size_t i = 0; i < sizeof(adc_camera_model) / sizeof(float); i++) if (!std::isfinite(v[i])) { why = path + ": every value must be finite"; return false; }
+    if (out.model.fx == 0.f || out.model.fy == 0.f || out.model.new_fx == 0.f || out.model.new_fy == 0.f) { why = path + ": fx, fy, new_fx, new_fy must not be 0"; return false; }
+    return true;
+}
+
+// tightly packed B,G,R pixels -> the declared raw layout (GRAY8 takes B; alpha and row padding are 0)
+static std::vector<uint8> pack_raw(const std::vector<uint8>& bgr, const adc_raw_format& f)
+{
+    std::vector<uint8> raw((size_t)f.height * f.pitch_bytes, 0);
+    for (int y = 0; y < f.height; y++)
+        for (int x = 0; x < f.width; x++) {
+            const uint8* p = &bgr[((size_t)y * f.width + x) * 3];
+            uint8* q = &raw[(size_t)y * f.pitch_bytes];
+            if (f.format == ADC_PIX_GRAY8) q[x] = p[0];
+            else if (f.format == ADC_PIX_RGB8) { q[3 * x] = p[2]; q[3 * x + 1] = p[1]; q[3 * x + 2] = p[0]; }
+            else if (f.format == ADC_PIX_BGRA8) { q[4 * x] = p[0]; q[4 * x + 1] = p[1]; q[4 * x + 2] = p[2]; }
+            else { q[3 * x] = p[0]; q[3 * x + 1] = p[1]; q[3 * x + 2] = p[2]; }
+        }
+    return raw;
+}
 
 static void write_pfm(const std::string& path, const float32* px, int w, int h)
 {
@@ -72,6 +164,25 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
+    RectifyFile rect_file[2];
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--rectify")) {
+            std::string why = "--rectify needs LEFT.txt,RIGHT.txt";
+            bool ok = i + 1 < argc;
+            if (ok) {
+                const std::string v(argv[i + 1]);
+                const size_t comma = v.find(',');
+                ok = comma != std::string::npos && comma > 0 && comma + 1 < v.size() && v.find(',', comma + 1) == std::string::npos;
+                ok = ok && parse_rectify_file(v.substr(0, comma), rect_file[0], why) && parse_rectify_file(v.substr(comma + 1), rect_file[1], why);
+                if (ok && (rect_file[0].rect_w != rect_file[1].rect_w || rect_file[0].rect_h != rect_file[1].rect_h)) { ok = false; why = "the two files differ in the rectified size"; }
+            }
+            if (!ok) { printf("--rectify refused: %s\n", why.c_str()); return -1; }
+            with_rectify = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     if (with_calib && extras) { printf("--calib and --extras are separate runs\n"); return -1; }
     // file-format helpers that need no GPU (used by the CPU test tier):
     //   --convert in.{png,ppm} out.png       decode + re-encode (R,G,B)
@@ -98,9 +209,19 @@ int main(int argc, char** argv)
         printf("cannot read the image pair (8-bit PNG or binary PPM)\n"); // main.cpp:50-53
         return -1;
     }
-    if (w != w2 || h != h2) {
+    if (!with_rectify && (w != w2 || h != h2)) {
         printf("the two images differ in size\n"); // main.cpp:54-57
         return -1;
+    }
+    if (with_rectify) { // the loaded pixels become the raw frames of the declared layout; from here on w x h is the rectified size
+        if (w != rect_file[0].raw.width || h != rect_file[0].raw.height || w2 != rect_file[1].raw.width || h2 != rect_file[1].raw.height) {
+            printf("--rectify: an image does not have the size its camera file declares\n");
+            return -1;
+        }
+        left = pack_raw(left, rect_file[0].raw);
+        right = pack_raw(right, rect_file[1].raw);
+        w = rect_file[0].rect_w;
+        h = rect_file[0].rect_h;
     }
     printf("Done!\n");
     ADCensusOption ad_option;                               // main.cpp:80-92
@@ -121,6 +242,21 @@ int main(int argc, char** argv)
     auto t1 = std::chrono::steady_clock::now();
     printf("AD-Census Initializing Done! Timing :	%lf s\n\n", std::chrono::duration<double>(t1 - t0).count());
     if (speckle_size > 0 && !ad_census.SetSpeckleFilter(speckle_size, speckle_diff)) { printf("speckle filter refused: %s\n", ad_census.LastError()); return -2; }
+    std::vector<uint8> rect_left; // (the rectified left image: the colours of the cloud file)
+    if (with_rectify) {
+        std::vector<uint8> rect_right((size_t)w * h * 3, 0), rgb((size_t)w * h * 3);
+        rect_left.assign((size_t)w * h * 3, 0);
+        if (!ad_census.SetRectifyModel(ADC_SIDE_LEFT, &rect_file[0].raw, &rect_file[0].model) || !ad_census.SetRectifyModel(ADC_SIDE_RIGHT, &rect_file[1].raw, &rect_file[1].model) ||
+            !ad_census.Rectify(ADC_SIDE_LEFT, left.data(), rect_left.data()) || !ad_census.Rectify(ADC_SIDE_RIGHT, right.data(), rect_right.data())) {
+            printf("rectification refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        for (int side = 0; side < 2; side++) {
+            const std::vector<uint8>& img = side ? rect_right : rect_left;
+            for (size_t i = 0; i < (size_t)w * h; i++) { rgb[3 * i] = img[3 * i + 2]; rgb[3 * i + 1] = img[3 * i + 1]; rgb[3 * i + 2] = img[3 * i]; }
+            if (!write_png(out + (side ? "-rect-right.png" : "-rect-left.png"), rgb.data(), w, h, 3)) printf("cannot write %s-rect-*.png\n", out.c_str());
+        }
+    }
     printf("AD-Census Matching...\n");
     std::vector<float32> disparity((size_t)w * h, 0.0f);
     std::vector<uint8> provenance(extras ? (size_t)w * h : 0);
@@ -153,7 +289,7 @@ int main(int argc, char** argv)
             for (int j = 0; j < w; j++) {
                 const float32 a = fabsf(disparity[(size_t)i * w + j]);
                 if (a == Invalid_Float) continue;
-                const uint8* p = &left[((size_t)i * w + j) * 3];
+                const uint8* p = with_rectify ? &rect_left[((size_t)i * w + j) * 3] : &left[((size_t)i * w + j) * 3];
                 fprintf(f, "%f %f %f %d %d %d\n", float32(j), float32(i), a, p[2], p[1], p[0]);
             }
         fclose(f);

@@ -11,7 +11,8 @@
  * Additive members (no reference counterpart): SetDevice, SetVerbose (prints the reference's six stage
  * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait,
  * MatchEx (per-pixel provenance and confidence maps next to the disparity), MatchOut (depth, point cloud and 8-bit image computed
- * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default).
+ * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default),
+ * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default).
  */
 #pragma once
 
@@ -19,6 +20,8 @@
 
 struct adc_handle;
 struct adc_outputs; // include/adcensus_c_api.h
+struct adc_raw_format;
+struct adc_camera_model;
 
 class ADCensusStereo {
 public:
@@ -66,6 +69,18 @@ public:
      *  Invalid_Float; the outputs of MatchOut come from the filtered map.  max_size <= 0 (default) = off.  false: max_diff negative
      *  or not finite, a Match pending, or a HIP failure.  May be called before Initialize (applied there). */
     bool SetSpeckleFilter(int max_size, float max_diff);
+    /** Optional rectification on the device (adc_set_rectify_maps / adc_set_rectify_model, include/adcensus_c_api.h).  Once BOTH sides
+     *  (ADC_SIDE_LEFT, ADC_SIDE_RIGHT) are set, every Match / MatchAsync / MatchEx / MatchOut takes img_left / img_right as RAW images
+     *  of the declared geometry (raw->height * raw->pitch_bytes bytes each) and matches their rectified W x H versions.  The maps are
+     *  float32 [map_height][map_width] source coordinates and must have the size given to Initialize.  false: a refused argument, a
+     *  Match pending, a HIP failure.  May be called before Initialize: checked as far as possible, copied, applied there
+     *  (Initialize then returns false when the library refuses them). */
+    bool SetRectifyMaps(int side, const adc_raw_format* raw, const float32* map_x, const float32* map_y, sint32 map_width, sint32 map_height);
+    bool SetRectifyModel(int side, const adc_raw_format* raw, const adc_camera_model* model);
+    /** Both sides unset: Match takes rectified W x H BGR images again. */
+    bool ClearRectify();
+    /** The remap alone, host to host: raw image of the side's geometry -> uint8 [H][W][3] BGR.  Needs Initialize and the side set. */
+    bool Rectify(int side, const uint8* raw, uint8* bgr_out);
     const char* LastError() const;
 
 private:
@@ -76,4 +91,8 @@ private:
     unsigned paper_;
     int speckle_size_;
     float speckle_diff_;
+    struct RectifySide; // what was set for a side (kept for Initialize / Reset)
+    RectifySide* rect_[2];
+    sint32 width_, height_;
+    bool ApplyRectify(int side);
 };

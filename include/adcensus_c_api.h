@@ -266,6 +266,62 @@ int64_t adc_farm_drain(adc_farm* f);
 /* adc_set_speckle_filter on every pipeline of the farm (above); 1 while a pair is in flight (adc_farm_drain first). */
 int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff);
 
+/* -------------------------------------------------------------------------------------------
+ * Optional rectification of raw camera images on the device (k_rectify.hip), off by default.  Handle state like the speckle filter:
+ * once BOTH sides are set, EVERY match entry point (adc_match, _async, _device, _ex, _device_ex, _out, _device_out,
+ * adc_farm_submit) takes its left / right arguments as RAW source images of the declared geometry -- height * pitch_bytes bytes each,
+ * host or device like the entry point's images were -- remaps each into the handle's own W x H BGR buffers and matches those.
+ * Everything downstream (the map, depth, cloud colours, 8-bit image, speckle filter, every redo of adc_wait) sees the rectified
+ * pair.  With exactly one side set a Match is refused (1).  A handle that never had a side set does exactly what it did before.
+ *
+ * The remap, per destination pixel, from float32 maps map_x / map_y [H][W] (source coordinates, as cv::initUndistortRectifyMap
+ * produces them): outside (B = G = R = 0, valid = 0) when !(fabsf(mx) < 32768) or !(fabsf(my) < 32768), NaN and +-inf included;
+ * otherwise X = (int)rintf(mx * 32), xi = X >> 5, ax = X & 31, Y / yi / ay likewise; taps (yi, xi), (yi, xi+1), (yi+1, xi), (yi+1, xi+1)
+ * with the integer weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax*ay; a tap outside the source contributes 0 (constant border);
+ * out = (sum of w * p + 512) >> 10 per channel; valid = 1 iff every tap with a nonzero weight is inside.  Integer arithmetic behind
+ * the two float operations: tests/rectify_ref.py is the definition, the kernels match it bit for bit.  By construction these are the
+ * weights of cv::remap with INTER_LINEAR and BORDER_CONSTANT (INTER_BITS = 5).
+ *
+ * adc_set_rectify_model computes the maps on the device from one camera: xn = (u - new_cx) / new_fx, yn = (v - new_cy) / new_fy;
+ * (X, Y, Wc) = R^T (xn, yn, 1); x = X / Wc, y = Y / Wc; r2 = x*x + y*y; rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ * xd = (x rad + (2 p1) x y) + p2 (r2 + 2 x*x); yd = (y rad + p1 (r2 + 2 y*y)) + (2 p2) x y; mx = fx xd + cx, my = fy yd + cy --
+ * float32, one rounding per operation, in that order (Brown-Conrady, R the rectifying rotation, row-major).  Deriving R and the new
+ * intrinsics from a stereo calibration is the caller's business.
+ *
+ * Set calls return 0; 1 for a NULL argument, a bad side or format, width / height outside [1, 32767], pitch_bytes < width * bytes per
+ * pixel, height * pitch_bytes > 2^31 - 1, a model with a non-finite value or fx, fy, new_fx, new_fy == 0, or a Match pending
+ * (adc_wait first); 2 for a HIP failure (that side is then unset, the handle stays usable).  Synchronous.  The first set call
+ * allocates the feature's buffers (adc_create allocates none of them); adc_destroy frees them.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_PIX_BGR8 0   /* 3 bytes per pixel: B, G, R */
+#define ADC_PIX_RGB8 1   /* 3 bytes per pixel: R, G, B */
+#define ADC_PIX_GRAY8 2  /* 1 byte per pixel: B = G = R */
+#define ADC_PIX_BGRA8 3  /* 4 bytes per pixel: B, G, R, alpha (ignored) */
+#define ADC_SIDE_LEFT 0
+#define ADC_SIDE_RIGHT 1
+typedef struct adc_raw_format { int32_t width, height, pitch_bytes, format; } adc_raw_format;
+typedef struct adc_camera_model {
+    float fx, fy, cx, cy;          /* intrinsics of the raw camera */
+    float k1, k2, p1, p2, k3;      /* Brown-Conrady distortion */
+    float R[9];                    /* rectifying rotation, row-major */
+    float new_fx, new_fy, new_cx, new_cy; /* intrinsics of the rectified W x H image */
+} adc_camera_model;
+/* map_x / map_y: host float32 [H][W] (H, W of adc_create); they may hold anything, NaN and inf included. */
+int adc_set_rectify_maps(adc_handle* h, int side, const adc_raw_format* raw, const float* map_x, const float* map_y);
+int adc_set_rectify_model(adc_handle* h, int side, const adc_raw_format* raw, const adc_camera_model* model);
+/* Both sides unset: the entry points take rectified W x H BGR images again.  1: NULL handle or a Match pending. */
+int adc_clear_rectify(adc_handle* h);
+/* The float maps in use for a side (the caller's, or the model's) and the valid map, to host buffers [H][W]; any may be NULL.
+ * Synchronous.  1: NULL handle, bad side, side not set; 2: HIP failure. */
+int adc_get_rectify_maps(adc_handle* h, int side, float* map_x, float* map_y, uint8_t* valid);
+/* The remap alone: device-resident raw image of the side's geometry -> device-resident [H][W][3] BGR.  Asynchronous on the handle's
+ * stream (adc_wait completes it); both buffers are the caller's.  1: NULL argument, bad side, side not set; 2: HIP failure. */
+int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_out);
+/* The same setters on every pipeline of a farm; 1 while a pair is in flight (adc_farm_drain first). */
+int adc_farm_set_rectify_maps(adc_farm* f, int side, const adc_raw_format* raw, const float* map_x, const float* map_y);
+int adc_farm_set_rectify_model(adc_farm* f, int side, const adc_raw_format* raw, const adc_camera_model* model);
+int adc_farm_clear_rectify(adc_farm* f);
+
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
  * Level 2 records only the marks around the aggregation launches (adc_aggregate_info: the live duration of the roofline kernel) and
