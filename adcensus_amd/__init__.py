@@ -32,6 +32,10 @@ PROV_SPECKLE = 0x10  # set by a Match with the speckle filter on, at the pixels 
 PIX_BGR8, PIX_RGB8, PIX_GRAY8, PIX_BGRA8 = 0, 1, 2, 3  # adc_raw_format.format (ADC_PIX_*)
 PIX_BYTES = {PIX_BGR8: 3, PIX_RGB8: 3, PIX_GRAY8: 1, PIX_BGRA8: 4}
 SIDE_LEFT, SIDE_RIGHT = 0, 1  # ADC_SIDE_*
+GT_U8, GT_U16, GT_F32 = 0, 1, 2  # adc_gt.format (ADC_GT_*)
+GT_DTYPES = {GT_U8: np.uint8, GT_U16: np.uint16, GT_F32: np.float32}
+EVAL_MAX_THRESHOLDS, EVAL_ERR_BINS, EVAL_CONF_BINS = 4, 256, 256
+EVAL_KNOWN, EVAL_VALID, EVAL_BAD, EVAL_OCCLUDED = 1, 2, 4, 8  # bits of the class map (ADC_EVAL_*)
 
 
 class ADCensusOption(C.Structure):
@@ -99,6 +103,60 @@ class CameraModel(C.Structure):
             if not hasattr(self, k):
                 raise AttributeError(k)
             setattr(self, k, (C.c_float * 9)(*[float(x) for x in v]) if k == "R" else float(v))
+
+
+class GroundTruth(C.Structure):
+    """adc_gt: one view's ground truth as the caller holds it (host array, ADC_GT_* format, row pitch in bytes, scale)."""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_int32), ("pitch_bytes", C.c_int32), ("scale", C.c_float), ("reserved_", C.c_int32)]
+
+    def __init__(self, array=None, scale=1.0, format=None, pitch_bytes=0):
+        """array: a 2-D uint8 / uint16 / float32 numpy array (kept alive by this object); its row stride becomes the pitch."""
+        super().__init__()
+        if array is not None:
+            a = np.asarray(array)
+            if format is None:
+                format = {np.dtype(np.uint8): GT_U8, np.dtype(np.uint16): GT_U16, np.dtype(np.float32): GT_F32}[a.dtype]
+            if a.ndim != 2 or a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize:
+                a = np.ascontiguousarray(a)
+            self._keep = a
+            self.data = a.ctypes.data
+            pitch_bytes = pitch_bytes or a.strides[0]
+        self.format, self.pitch_bytes, self.scale = int(0 if format is None else format), int(pitch_bytes), float(scale)
+
+
+class EvalParams(C.Structure):
+    """adc_eval_params: up to EVAL_MAX_THRESHOLDS bad-pixel thresholds (finite, >= 0)."""
+    _fields_ = [("n_thresholds", C.c_int32), ("thresholds", C.c_float * EVAL_MAX_THRESHOLDS)]
+
+    def __init__(self, thresholds=(1.0,)):
+        super().__init__()
+        ts = [float(t) for t in thresholds]
+        self.n_thresholds = len(ts)  # (more than four: the library refuses the call)
+        for k, t in enumerate(ts[:EVAL_MAX_THRESHOLDS]):
+            self.thresholds[k] = t
+
+
+class EvalMaskStats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("bad", C.c_uint64 * EVAL_MAX_THRESHOLDS), ("sum_err_q", C.c_uint64),
+                ("sum_sq_err_q", C.c_uint64), ("err_hist", C.c_uint64 * EVAL_ERR_BINS)]
+
+
+class EvalFillStats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("bad", C.c_uint64 * EVAL_MAX_THRESHOLDS), ("sum_err_q", C.c_uint64)]
+
+
+class EvalReport(C.Structure):
+    """adc_eval_report: integer counters (all / nonocc masks, the four fill classes, confidence bins) and the echo of the request;
+    adcensus_amd.evaluation.summarize turns it into rates, mean, RMS and the sparsification curve."""
+    _fields_ = [("all", EvalMaskStats), ("nonocc", EvalMaskStats), ("by_fill", EvalFillStats * 4), ("speckle_removed_known", C.c_uint64),
+                ("conf_pixels", C.c_uint64 * EVAL_CONF_BINS), ("conf_bad", C.c_uint64 * EVAL_CONF_BINS),
+                ("thresholds", C.c_float * EVAL_MAX_THRESHOLDS), ("n_thresholds", C.c_int32), ("occ_thres", C.c_float),
+                ("has_right_gt", C.c_uint8), ("has_nonocc_mask", C.c_uint8), ("has_provenance", C.c_uint8), ("has_confidence", C.c_uint8),
+                ("reserved_", C.c_int32)]
+
+    def words(self):
+        """The counters in declaration order as a uint64 array (everything in front of the echo)."""
+        return np.frombuffer(bytes(self), np.uint64, EvalReport.thresholds.offset // 8).copy()
 
 
 POINT_DTYPE = np.dtype({"names": ["x", "y", "z", "r", "g", "b", "pad"], "formats": ["<f4", "<f4", "<f4", "u1", "u1", "u1", "u1"],
@@ -180,6 +238,14 @@ def lib():
         L.adc_get_rectify_maps.restype = C.c_int
         L.adc_rectify_device.argtypes = [vp, C.c_int, vp, vp]
         L.adc_rectify_device.restype = C.c_int
+    if hasattr(L, "adc_set_ground_truth"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_set_ground_truth.argtypes = [vp, C.POINTER(GroundTruth), C.POINTER(GroundTruth), vp, C.c_float]
+        L.adc_clear_ground_truth.argtypes = [vp]
+        L.adc_evaluate_device.argtypes = [vp, vp, vp, vp, C.POINTER(EvalParams), vp, vp]
+        L.adc_evaluate.argtypes = [vp, vp, vp, vp, C.POINTER(EvalParams), vp, vp, C.POINTER(EvalReport)]
+        L.adc_get_eval_report.argtypes = [vp, C.POINTER(EvalReport)]
+        for name in ("adc_set_ground_truth", "adc_clear_ground_truth", "adc_evaluate_device", "adc_evaluate", "adc_get_eval_report"):
+            getattr(L, name).restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
     L.adc_stage_name.argtypes = [C.c_int]
@@ -622,6 +688,61 @@ class ADCensusStereo:
             L.adc_device_free(pr)
             L.adc_device_free(po)
         return out
+
+    # -- evaluation against ground truth (adc_set_ground_truth / adc_evaluate*) ---------------------
+    def set_ground_truth(self, left, right=None, nonocc=None, occ_thres=1.0, scale=1.0):
+        """Sets the ground truth every later evaluate / evaluate_device of this object scores against.  left / right: a GroundTruth, or a
+        2-D uint8 / uint16 / float32 array (then `scale` applies: disparity = value / scale, 0 = unknown in the integer formats);
+        right may be None; nonocc: an optional uint8 [H][W] mask (nonzero = non-occluded) used when there is no right view.  Raises
+        when refused or on a HIP failure."""
+        gl = left if isinstance(left, GroundTruth) else GroundTruth(left, scale)
+        gr = right if right is None or isinstance(right, GroundTruth) else GroundTruth(right, scale)
+        m = None
+        if nonocc is not None:
+            m = np.ascontiguousarray(nonocc, dtype=np.uint8)
+            assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        for g in (gl, gr):
+            a = getattr(g, "_keep", None)
+            assert g is None or a is None or a.shape == (self.height, self.width), (a.shape, (self.height, self.width))
+        if lib().adc_set_ground_truth(self._h, C.byref(gl), None if gr is None else C.byref(gr), None if m is None else m.ctypes.data,
+                                      float(occ_thres)) != 0:
+            raise RuntimeError("adc_set_ground_truth failed: " + last_error())
+
+    def clear_ground_truth(self):
+        if lib().adc_clear_ground_truth(self._h) != 0:
+            raise RuntimeError("adc_clear_ground_truth failed: " + last_error())
+
+    def evaluate_device(self, d_disp, d_provenance=None, d_confidence=None, thresholds=(1.0,), d_err=None, d_class=None):
+        """Scores a device-resident float32 [H][W] map (ints: device addresses; provenance uint8, confidence float32, err float32 and
+        class uint8 [H][W] or None) against the ground truth set (adc_evaluate_device); asynchronous, call wait(), then eval_report().
+        False when refused (no ground truth, a Match pending, bad thresholds, confidence without provenance) or on a HIP failure."""
+        params = thresholds if isinstance(thresholds, EvalParams) else EvalParams(thresholds)
+        return lib().adc_evaluate_device(self._h, d_disp, d_provenance, d_confidence, C.byref(params), d_err, d_class) == 0
+
+    def evaluate(self, disp, provenance=None, confidence=None, thresholds=(1.0,), err=True, cls=True):
+        """Host convenience (adc_evaluate): scores a float32 [H][W] numpy map; returns (EvalReport, err float32 [H][W] or None, class
+        uint8 [H][W] or None).  Raises on failure."""
+        shp = (self.height, self.width)
+        d = np.ascontiguousarray(disp, dtype=np.float32)
+        p = None if provenance is None else np.ascontiguousarray(provenance, dtype=np.uint8)
+        c = None if confidence is None else np.ascontiguousarray(confidence, dtype=np.float32)
+        for a in (d, p, c):
+            assert a is None or a.shape == shp, (a.shape, shp)
+        e = np.empty(shp, np.float32) if err else None
+        k = np.empty(shp, np.uint8) if cls else None
+        params = thresholds if isinstance(thresholds, EvalParams) else EvalParams(thresholds)
+        rep = EvalReport()
+        if lib().adc_evaluate(self._h, d.ctypes.data, None if p is None else p.ctypes.data, None if c is None else c.ctypes.data, C.byref(params),
+                              None if e is None else e.ctypes.data, None if k is None else k.ctypes.data, C.byref(rep)) != 0:
+            raise RuntimeError("adc_evaluate failed: " + last_error())
+        return rep, e, k
+
+    def eval_report(self):
+        """The EvalReport of the last evaluation wait() has completed (adc_get_eval_report)."""
+        rep = EvalReport()
+        if lib().adc_get_eval_report(self._h, C.byref(rep)) != 0:
+            raise RuntimeError("adc_get_eval_report failed: " + last_error())
+        return rep
 
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do

@@ -219,6 +219,26 @@ struct adc_handle {
     AdcRectSide rect[2];  // ADC_SIDE_LEFT, ADC_SIDE_RIGHT
     uint8_t* pin_raw;     // pinned staging of the two raw images (left at 0, right behind it)
     size_t pin_raw_cap;
+    // optional evaluation against ground truth (k_eval.hip; nothing of it exists before the first adc_set_ground_truth)
+    int ev_set;               // ground truth is set (adc_clear_ground_truth / a failed set call: 0)
+    int ev_has_right, ev_has_mask; // where the occlusion byte map came from (neither: occlusion is not defined, the map is all 0)
+    float ev_occ_thres;
+    int ev_cus;               // CUs of the device: the measure kernel's grid is a fixed multiple of it
+    float* ev_g[2];           // decoded ground truth of the left / right view, unknown = +inf
+    uint8_t* ev_occ;          // 1 = known and non-occluded
+    uint8_t* ev_raw;          // device copy of the caller's raw array being decoded (one at a time), then of the mask
+    size_t ev_raw_cap;
+    uint64_t* ev_rep;         // the report words the measure kernel adds to (adc_eval_report without its echo)
+    uint64_t* ev_pin;         // pinned: read-back of the report words, enqueued behind the kernel
+    int ev_pending;           // an evaluation was enqueued; adc_wait moves ev_pin and ev_echo into ev_report
+    adc_eval_report ev_echo;  // the echo fields of the evaluation enqueued last
+    adc_eval_report ev_report; // adc_get_eval_report
+    int ev_report_valid;
+    float* evs_disp;          // device scratch of adc_evaluate (host callers), each allocated on the first call that needs it
+    uint8_t* evs_prov;
+    float* evs_conf;
+    float* evs_err;
+    uint8_t* evs_cls;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -278,6 +298,10 @@ hipError_t adc_launch_speckle_apply(adc_handle* h, const float* src, float* dst,
 hipError_t adc_launch_rect_model_maps(adc_handle* h, int side, const adc_camera_model* m); // k_rectify.hip: model -> rect[side].mx / my
 hipError_t adc_launch_rect_pack(adc_handle* h, int side);                                   // mx / my -> records, valid map
 hipError_t adc_launch_rect_remap(adc_handle* h, int side, const uint8_t* raw, uint8_t* bgr_out); // raw image -> [H][W][3] BGR
+size_t adc_eval_report_words(void);                             // k_eval.hip: uint64 words of ev_rep / ev_pin
+hipError_t adc_launch_eval_gt(adc_handle* h, int side, int format, int pitch, float scale); // ev_raw -> ev_g[side]
+hipError_t adc_launch_eval_occ(adc_handle* h, int mode, float occ_thres);                   // 1: ev_g[0], ev_g[1] -> ev_occ; 2: ev_g[0], mask in ev_raw -> ev_occ
+hipError_t adc_launch_eval_measure(adc_handle* h, const float* disp, const uint8_t* prov, const float* conf, const float* thresholds, float* err, uint8_t* cls);
 size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)

@@ -330,8 +330,10 @@ void adc_destroy(adc_handle* h)
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
                     h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->sp_parent, h->sp_map,
-                    h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw};
+                    h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw,
+                    h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls};
     for (void* b : bufs) if (b) hipFree(b);
+    if (h->ev_pin) hipHostFree(h->ev_pin);
     if (h->pin_raw) hipHostFree(h->pin_raw);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -600,6 +602,7 @@ static void abort_match(adc_handle* h)
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
     h->out.active = 0;
+    h->ev_pending = 0;
     if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
@@ -800,6 +803,12 @@ int adc_wait(adc_handle* h)
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
     h->out.active = 0;
+    if (h->ev_pending) { // an evaluation has completed: its report words have arrived in the pinned block (adc_get_eval_report)
+        h->ev_report = h->ev_echo;
+        memcpy(&h->ev_report, h->ev_pin, adc_eval_report_words() * sizeof(uint64_t));
+        h->ev_report_valid = 1;
+        h->ev_pending = 0;
+    }
     // adc_match_device BORROWED the caller's device images until here: nothing of the handle may point at them any
     // more (a later debug stage would otherwise read memory the caller has reused or freed)
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) {
@@ -1174,6 +1183,216 @@ int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_o
     hipSetDevice(h->device);
     const hipError_t e = ADC_HIP(adc_launch_rect_remap(h, side, static_cast<const uint8_t*>(d_raw), static_cast<uint8_t*>(d_bgr_out)));
     if (e != hipSuccess) { set_error("adc_rectify_device", e); abort_match(h); return 2; }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ evaluation against ground truth (k_eval.hip)
+// Handle state like the rectification: a set call uploads the caller's arrays one after the other into one raw buffer, decodes each
+// into its float map, builds the occlusion byte map and waits.  An evaluation is a memset of the report words, one kernel and the
+// read-back of the words into a pinned block, all on the object stream; adc_wait moves the block into the handle's report.
+static int gt_bpp(int format) { return format == ADC_GT_U8 ? 1 : (format == ADC_GT_U16 ? 2 : 4); }
+
+// 0 = usable; otherwise the reason.  pitch_out: the row pitch in bytes (0 in the struct: tightly packed)
+static const char* gt_check(const adc_handle* h, const adc_gt* g, bool geometry, int* pitch_out)
+{
+    if (!g->data) return "null ground-truth array";
+    if (g->format != ADC_GT_U8 && g->format != ADC_GT_U16 && g->format != ADC_GT_F32) return "unknown ground-truth format";
+    if (!(__builtin_isfinite(g->scale) && g->scale > 0.0f)) return "scale must be finite and > 0";
+    if (g->pitch_bytes < 0) return "pitch_bytes is negative";
+    if (!geometry) return nullptr;
+    const long long row = (long long)h->p.W * gt_bpp(g->format);
+    const long long pitch = g->pitch_bytes ? (long long)g->pitch_bytes : row;
+    if (pitch < row) return "pitch_bytes is smaller than a row";
+    if (pitch * (long long)h->p.H > 2147483647LL) return "a ground-truth array must be smaller than 2 GiB";
+    *pitch_out = (int)pitch;
+    return nullptr;
+}
+
+static hipError_t gt_buffers(adc_handle* h, size_t raw_bytes)
+{
+    const size_t P = (size_t)h->p.W * h->p.H;
+    if (!h->ev_cus) {
+        int cus = 0;
+        HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        h->ev_cus = cus > 0 ? cus : 1;
+    }
+    for (int s = 0; s < 2; s++) if (!h->ev_g[s]) HIP_OK(hipMalloc(&h->ev_g[s], P * 4));
+    if (!h->ev_occ) HIP_OK(hipMalloc(&h->ev_occ, P));
+    if (!h->ev_rep) HIP_OK(hipMalloc(&h->ev_rep, adc_eval_report_words() * sizeof(uint64_t)));
+    if (!h->ev_pin) HIP_OK(hipHostMalloc(&h->ev_pin, adc_eval_report_words() * sizeof(uint64_t), hipHostMallocDefault));
+    if (h->ev_raw_cap < raw_bytes) {
+        if (h->ev_raw) hipFree(h->ev_raw);
+        h->ev_raw = nullptr; h->ev_raw_cap = 0;
+        HIP_OK(hipMalloc(&h->ev_raw, raw_bytes));
+        h->ev_raw_cap = raw_bytes;
+    }
+    return hipSuccess;
+}
+
+static hipError_t gt_install(adc_handle* h, const adc_gt* left, int pitch_l, const adc_gt* right, int pitch_r, const uint8_t* nonocc, float occ_thres)
+{
+    const size_t P = (size_t)h->p.W * h->p.H, H = (size_t)h->p.H;
+    // (the caller's last row need not be padded to the pitch: H - 1 pitches and one row are read)
+    const size_t bytes_l = (size_t)pitch_l * (H - 1) + (size_t)h->p.W * gt_bpp(left->format);
+    const size_t bytes_r = right ? (size_t)pitch_r * (H - 1) + (size_t)h->p.W * gt_bpp(right->format) : 0;
+    size_t need = bytes_l > bytes_r ? bytes_l : bytes_r;
+    if (!right && nonocc && P > need) need = P;
+    const hipError_t eb = gt_buffers(h, need); // (every HIP call in there is hooked itself)
+    if (eb != hipSuccess) return eb;
+    // (the stream is drained between the uploads: the raw buffer is reused, and a pageable source must not be read after the call)
+    HIP_OK(hipMemcpyAsync(h->ev_raw, left->data, bytes_l, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(adc_launch_eval_gt(h, 0, left->format, pitch_l, left->scale));
+    if (right) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        HIP_OK(hipMemcpyAsync(h->ev_raw, right->data, bytes_r, hipMemcpyHostToDevice, h->stream));
+        HIP_OK(adc_launch_eval_gt(h, 1, right->format, pitch_r, right->scale));
+        HIP_OK(adc_launch_eval_occ(h, 1, occ_thres));
+    } else if (nonocc) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        HIP_OK(hipMemcpyAsync(h->ev_raw, nonocc, P, hipMemcpyHostToDevice, h->stream));
+        HIP_OK(adc_launch_eval_occ(h, 2, occ_thres));
+    } else {
+        HIP_OK(hipMemsetAsync(h->ev_occ, 0, P, h->stream));
+    }
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return hipSuccess;
+}
+
+int adc_set_ground_truth(adc_handle* h, const adc_gt* left, const adc_gt* right, const uint8_t* nonocc, float occ_thres)
+{
+    if (!h) { g_last_error = "adc_set_ground_truth: null handle"; return 1; }
+    if (!left) { g_last_error = "adc_set_ground_truth: null left ground truth"; return 1; }
+    int pitch_l = 0, pitch_r = 0;
+    const char* why = gt_check(h, left, false, &pitch_l);
+    if (!why && right) why = gt_check(h, right, false, &pitch_r);
+    if (!why && !(__builtin_isfinite(occ_thres) && occ_thres >= 0.0f)) why = "occ_thres must be finite and >= 0";
+    if (!why && match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (!why) why = gt_check(h, left, true, &pitch_l);
+    if (!why && right) why = gt_check(h, right, true, &pitch_r);
+    if (why) { g_last_error = std::string("adc_set_ground_truth: ") + why; return 1; }
+    hipSetDevice(h->device);
+    h->ev_set = 0; // (a failure below leaves ground truth unset: the maps may be half written)
+    if (gt_install(h, left, pitch_l, right, pitch_r, nonocc, occ_thres) != hipSuccess) {
+        const std::string keep = "adc_set_ground_truth: " + g_last_error;
+        abort_match(h); // (drains the stream; no Match was pending)
+        g_last_error = keep;
+        return 2;
+    }
+    h->ev_has_right = right ? 1 : 0;
+    h->ev_has_mask = (!right && nonocc) ? 1 : 0;
+    h->ev_occ_thres = occ_thres;
+    h->ev_set = 1;
+    return 0;
+}
+
+int adc_clear_ground_truth(adc_handle* h)
+{
+    if (!h) { g_last_error = "adc_clear_ground_truth: null handle"; return 1; }
+    if (match_in_flight(h)) { g_last_error = "adc_clear_ground_truth: a Match is pending (adc_wait first)"; return 1; }
+    h->ev_set = 0;
+    return 0;
+}
+
+// validates an evaluation request; fills the four thresholds the kernel takes (unused: +inf).  0, or 1 with adc_last_error
+static int eval_check(adc_handle* h, const void* disp, const void* prov, const void* conf, const adc_eval_params* params, float* t, int* n_out, const char* who)
+{
+    const char* why = nullptr;
+    int n = 1;
+    t[0] = 1.0f;
+    if (!h) why = "null handle";
+    else if (!disp) why = "null map";
+    else if (params && (params->n_thresholds < 0 || params->n_thresholds > ADC_EVAL_MAX_THRESHOLDS)) why = "at most 4 thresholds";
+    else if (conf && !prov) why = "a confidence map needs a provenance map";
+    if (!why && params) {
+        n = params->n_thresholds;
+        for (int k = 0; k < n; k++) {
+            t[k] = params->thresholds[k];
+            if (!(__builtin_isfinite(t[k]) && t[k] >= 0.0f)) why = "a threshold must be finite and >= 0";
+        }
+    }
+    if (!why && !h->ev_set) why = "no ground truth set (adc_set_ground_truth)";
+    if (!why && match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    for (int k = n; k < ADC_EVAL_MAX_THRESHOLDS; k++) t[k] = ADC_INVALID_FLOAT;
+    *n_out = n;
+    return 0;
+}
+
+static hipError_t enqueue_evaluation(adc_handle* h, const float* disp, const uint8_t* prov, const float* conf, const float* t, float* err, uint8_t* cls)
+{
+    const size_t bytes = adc_eval_report_words() * sizeof(uint64_t);
+    HIP_OK(hipMemsetAsync(h->ev_rep, 0, bytes, h->stream));
+    HIP_OK(adc_launch_eval_measure(h, disp, prov, conf, t, err, cls));
+    HIP_OK(hipMemcpyAsync(h->ev_pin, h->ev_rep, bytes, hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+static int evaluate_device_impl(adc_handle* h, const void* d_disp, const void* d_prov, const void* d_conf, const float* t, int n, void* d_err, void* d_class,
+                                const char* who)
+{
+    hipSetDevice(h->device);
+    if (enqueue_evaluation(h, static_cast<const float*>(d_disp), static_cast<const uint8_t*>(d_prov), static_cast<const float*>(d_conf), t,
+                           static_cast<float*>(d_err), static_cast<uint8_t*>(d_class)) != hipSuccess) {
+        const std::string keep = std::string(who) + ": " + g_last_error;
+        abort_match(h);
+        g_last_error = keep;
+        return 2;
+    }
+    memset(&h->ev_echo, 0, sizeof(h->ev_echo));
+    for (int k = 0; k < n; k++) h->ev_echo.thresholds[k] = t[k];
+    h->ev_echo.n_thresholds = n;
+    h->ev_echo.occ_thres = h->ev_occ_thres;
+    h->ev_echo.has_right_gt = (uint8_t)h->ev_has_right;
+    h->ev_echo.has_nonocc_mask = (uint8_t)h->ev_has_mask;
+    h->ev_echo.has_provenance = d_prov ? 1 : 0;
+    h->ev_echo.has_confidence = d_conf ? 1 : 0;
+    h->ev_pending = 1;
+    return 0;
+}
+
+int adc_evaluate_device(adc_handle* h, const void* d_disp, const void* d_provenance, const void* d_confidence, const adc_eval_params* params,
+                        void* d_err, void* d_class)
+{
+    float t[ADC_EVAL_MAX_THRESHOLDS];
+    int n = 0;
+    if (eval_check(h, d_disp, d_provenance, d_confidence, params, t, &n, "adc_evaluate_device") != 0) return 1;
+    return evaluate_device_impl(h, d_disp, d_provenance, d_confidence, t, n, d_err, d_class, "adc_evaluate_device");
+}
+
+int adc_evaluate(adc_handle* h, const float* disp, const uint8_t* provenance, const float* confidence, const adc_eval_params* params, float* err,
+                 uint8_t* eval_class, adc_eval_report* out)
+{
+    float t[ADC_EVAL_MAX_THRESHOLDS];
+    int n = 0;
+    if (eval_check(h, disp, provenance, confidence, params, t, &n, "adc_evaluate") != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = hipSuccess;
+    if (!h->evs_disp && (e = ADC_HIP(hipMalloc(&h->evs_disp, P * 4))) != hipSuccess) h->evs_disp = nullptr;
+    if (e == hipSuccess && provenance && !h->evs_prov && (e = ADC_HIP(hipMalloc(&h->evs_prov, P))) != hipSuccess) h->evs_prov = nullptr;
+    if (e == hipSuccess && confidence && !h->evs_conf && (e = ADC_HIP(hipMalloc(&h->evs_conf, P * 4))) != hipSuccess) h->evs_conf = nullptr;
+    if (e == hipSuccess && err && !h->evs_err && (e = ADC_HIP(hipMalloc(&h->evs_err, P * 4))) != hipSuccess) h->evs_err = nullptr;
+    if (e == hipSuccess && eval_class && !h->evs_cls && (e = ADC_HIP(hipMalloc(&h->evs_cls, P))) != hipSuccess) h->evs_cls = nullptr;
+    if (e != hipSuccess) { set_error("adc_evaluate: scratch", e); (void)hipGetLastError(); return 2; }
+    e = ADC_HIP(hipMemcpy(h->evs_disp, disp, P * 4, hipMemcpyHostToDevice));
+    if (e == hipSuccess && provenance) e = ADC_HIP(hipMemcpy(h->evs_prov, provenance, P, hipMemcpyHostToDevice));
+    if (e == hipSuccess && confidence) e = ADC_HIP(hipMemcpy(h->evs_conf, confidence, P * 4, hipMemcpyHostToDevice));
+    if (e != hipSuccess) { set_error("adc_evaluate: upload", e); (void)hipGetLastError(); return 2; }
+    int rc = evaluate_device_impl(h, h->evs_disp, provenance ? h->evs_prov : nullptr, confidence ? h->evs_conf : nullptr, t, n, err ? h->evs_err : nullptr,
+                                  eval_class ? h->evs_cls : nullptr, "adc_evaluate");
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (err && (e = ADC_HIP(hipMemcpy(err, h->evs_err, P * 4, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_evaluate: error map copy-out", e); return 2; }
+    if (eval_class && (e = ADC_HIP(hipMemcpy(eval_class, h->evs_cls, P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_evaluate: class map copy-out", e); return 2; }
+    if (out) *out = h->ev_report;
+    return 0;
+}
+
+int adc_get_eval_report(adc_handle* h, adc_eval_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_eval_report: null argument"; return 1; }
+    if (!h->ev_report_valid) { g_last_error = "adc_get_eval_report: no evaluation has completed on this handle"; return 1; }
+    *out = h->ev_report;
     return 0;
 }
 

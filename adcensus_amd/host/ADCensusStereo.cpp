@@ -200,4 +200,15 @@ bool ADCensusStereo::Rectify(int side, const uint8* raw, uint8* bgr_out)
     adc_device_free(d_out);
     return ok;
 }
+bool ADCensusStereo::SetGroundTruth(const adc_gt* left, const adc_gt* right, const uint8* nonocc, float32 occ_thres)
+{
+    return impl_ && adc_set_ground_truth(impl_, left, right, nonocc, occ_thres) == 0;
+}
+bool ADCensusStereo::ClearGroundTruth() { return impl_ && adc_clear_ground_truth(impl_) == 0; }
+bool ADCensusStereo::Evaluate(const float32* disp, const uint8* provenance, const float32* confidence, const adc_eval_params* params, float32* err,
+                              uint8* eval_class, adc_eval_report* report)
+{
+    return impl_ && adc_evaluate(impl_, disp, provenance, confidence, params, err, eval_class, report) == 0;
+}
+bool ADCensusStereo::EvalReport(adc_eval_report* report) const { return impl_ && adc_get_eval_report(impl_, report) == 0; }
 const char* ADCensusStereo::LastError() const { return adc_last_error(); }

@@ -24,6 +24,14 @@
 // rect_width rect_height (the rectified size, default: the raw size; both files must agree).  A malformed flag or file is refused
 // while the arguments are parsed.  Every file of the run then comes from the rectified pair, and the run also writes
 //   <out>-rect-left.png  <out>-rect-right.png   the rectified images
+// --gt LEFT[,RIGHT],SCALE [--bad T0[,T1..]] (anywhere after the program name) scores the map against ground truth on the device
+// (ADCensusStereo::SetGroundTruth / Evaluate): LEFT / RIGHT are the left- / right-view disparities as 8-bit gray PNG (0 = unknown) or
+// PFM, disparity = value / SCALE (Middlebury: 4 for Cone, 2 for Cloth3 / Wood2, 1 for PFM); with RIGHT the non-occluded mask comes
+// from the cross-check of the two.  --bad gives up to four thresholds (default 1).  A malformed flag is refused while the arguments
+// are parsed.  With --extras the provenance and confidence maps are scored too (one row per fill class, the confidence's
+// sparsification area); with --speckle the filtered map is what is scored.  Prints one table and writes
+//   <out>-err.pfm    float32 |d - ground truth|, +inf where unknown or invalid
+//   <out>-bad.png    the class map coloured: black unknown, blue invalid, grey good, red bad (darker / orange where occluded)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -121,6 +129,60 @@ static std::vector<uint8> pack_raw(const std::vector<uint8>& bgr, const adc_raw_
     return raw;
 }
 
+// PFM ("Pf", one channel) -> rows top-down; false unless the header and the payload are complete
+static bool load_pfm(const std::string& path, std::vector<float32>& px, int& w, int& h)
+{
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    char magic[3] = {0};
+    float scale = 0.f;
+    bool ok = fscanf(f, "%2s %d %d %f", magic, &w, &h, &scale) == 4 && !strcmp(magic, "Pf") && w > 0 && h > 0 && (long long)w * h <= (1LL << 30) && fgetc(f) != EOF;
+    if (ok) {
+        px.resize((size_t)w * h);
+        for (int y = h - 1; ok && y >= 0; y--) ok = fread(&px[(size_t)y * w], 4, (size_t)w, f) == (size_t)w;
+        if (ok && scale > 0.f) // big-endian payload
+            for (float32& v : px) { uint8 b[4]; memcpy(b, &v, 4); const uint8 r[4] = {b[3], b[2], b[1], b[0]}; memcpy(&v, r, 4); }
+    }
+    fclose(f);
+    return ok;
+}
+
+// one view's ground truth from an 8-bit gray PNG or a PFM of w x h pixels
+struct GtImage { std::vector<uint8> u8; std::vector<float32> f32; adc_gt gt; };
+static bool load_gt(const std::string& path, float scale, int w, int h, GtImage& out, std::string& why)
+{
+    int gw = 0, gh = 0;
+    memset(&out.gt, 0, sizeof(out.gt));
+    out.gt.scale = scale;
+    if (path.size() > 4 && path.substr(path.size() - 4) == ".pfm") {
+        if (!load_pfm(path, out.f32, gw, gh)) { why = "cannot read " + path + " (one-channel PFM)"; return false; }
+        out.gt.data = out.f32.data();
+        out.gt.format = ADC_GT_F32;
+    } else {
+        std::vector<uint8> bgr;
+        if (!load_image(path.c_str(), bgr, gw, gh)) { why = "cannot read " + path + " (8-bit gray PNG or PFM)"; return false; }
+        out.u8.resize((size_t)gw * gh);
+        for (size_t i = 0; i < out.u8.size(); i++) {
+            if (bgr[3 * i] != bgr[3 * i + 1] || bgr[3 * i] != bgr[3 * i + 2]) { why = path + " is not a gray image"; return false; }
+            out.u8[i] = bgr[3 * i];
+        }
+        out.gt.data = out.u8.data();
+        out.gt.format = ADC_GT_U8;
+    }
+    if (gw != w || gh != h) { why = path + " does not have the size of the images"; return false; }
+    return true;
+}
+
+static void print_eval_row(const char* name, uint64_t pixels, uint64_t invalid, const uint64_t* bad, int n, uint64_t sum_q, const uint64_t* sum_sq_q)
+{
+    const double valid = (double)(pixels - invalid);
+    printf("%-14s %9llu %8.2f", name, (unsigned long long)pixels, pixels ? 100.0 * (double)invalid / (double)pixels : 0.0);
+    for (int k = 0; k < n; k++) printf(" %9.2f", pixels ? 100.0 * (double)bad[k] / (double)pixels : 0.0);
+    printf(" %8.4f", valid > 0 ? (double)sum_q / 1024.0 / valid : 0.0);
+    if (sum_sq_q) printf(" %8.4f", valid > 0 ? sqrt((double)*sum_sq_q / (1024.0 * 1024.0) / valid) : 0.0);
+    printf("\n");
+}
+
 static void write_pfm(const std::string& path, const float32* px, int w, int h)
 {
     FILE* f = fopen(path.c_str(), "wb");
@@ -183,6 +245,53 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_gt = false; // (--gt / --bad and their values likewise; the syntax is checked here, the files are read behind the images)
+    std::string gt_path[2];
+    float gt_scale = 0.f;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--gt")) {
+            bool ok = i + 1 < argc;
+            if (ok) {
+                std::vector<std::string> parts;
+                std::string v(argv[i + 1]);
+                size_t at = 0, comma;
+                while ((comma = v.find(',', at)) != std::string::npos) { parts.push_back(v.substr(at, comma - at)); at = comma + 1; }
+                parts.push_back(v.substr(at));
+                char tail = 0;
+                ok = (parts.size() == 2 || parts.size() == 3) && !parts[0].empty() && (parts.size() == 2 || !parts[1].empty()) &&
+                     sscanf(parts.back().c_str(), "%f%c", &gt_scale, &tail) == 1 && std::isfinite(gt_scale) && gt_scale > 0.f;
+                if (ok) { gt_path[0] = parts[0]; if (parts.size() == 3) gt_path[1] = parts[1]; }
+            }
+            if (!ok) { printf("--gt refused: it needs LEFT[,RIGHT],SCALE (8-bit gray PNG or PFM; SCALE finite and > 0)\n"); return -1; }
+            with_gt = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    adc_eval_params eval_params = {1, {1.0f, 0.f, 0.f, 0.f}};
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--bad")) {
+            bool ok = i + 1 < argc && with_gt;
+            int n = 0;
+            if (ok) {
+                const char* p = argv[i + 1];
+                while (ok) {
+                    char* end = nullptr;
+                    const float t = strtof(p, &end);
+                    ok = end != p && n < ADC_EVAL_MAX_THRESHOLDS && std::isfinite(t) && t >= 0.f && (*end == ',' || *end == 0);
+                    if (!ok) break;
+                    eval_params.thresholds[n++] = t;
+                    if (*end == 0) break;
+                    p = end + 1;
+                }
+            }
+            if (!ok) { printf("--bad refused: it needs --gt and T0[,T1..] (one to four thresholds, finite and >= 0)\n"); return -1; }
+            eval_params.n_thresholds = n;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_calib && with_gt) { printf("--calib and --gt are separate runs\n"); return -1; }
     if (with_calib && extras) { printf("--calib and --extras are separate runs\n"); return -1; }
     // file-format helpers that need no GPU (used by the CPU test tier):
     //   --convert in.{png,ppm} out.png       decode + re-encode (R,G,B)
@@ -222,6 +331,14 @@ int main(int argc, char** argv)
         right = pack_raw(right, rect_file[1].raw);
         w = rect_file[0].rect_w;
         h = rect_file[0].rect_h;
+    }
+    GtImage gt_img[2];
+    if (with_gt) {
+        std::string why;
+        if (!load_gt(gt_path[0], gt_scale, w, h, gt_img[0], why) || (!gt_path[1].empty() && !load_gt(gt_path[1], gt_scale, w, h, gt_img[1], why))) {
+            printf("--gt refused: %s\n", why.c_str());
+            return -1;
+        }
     }
     printf("Done!\n");
     ADCensusOption ad_option;                               // main.cpp:80-92
@@ -301,6 +418,54 @@ int main(int argc, char** argv)
         if (!write_png(out + "-prov.png", provenance.data(), w, h, 1) || !write_png(out + "-conf.png", conf8.data(), w, h, 1))
             printf("cannot write %s-prov.png / -conf.png\n", out.c_str());
         write_pfm(out + "-conf.pfm", confidence.data(), w, h);
+    }
+    if (with_gt) {
+        std::vector<float32> err((size_t)w * h);
+        std::vector<uint8> cls((size_t)w * h), rgb((size_t)w * h * 3);
+        adc_eval_report rep;
+        if (!ad_census.SetGroundTruth(&gt_img[0].gt, gt_path[1].empty() ? nullptr : &gt_img[1].gt, nullptr, 1.0f) ||
+            !ad_census.Evaluate(disparity.data(), extras ? provenance.data() : nullptr, extras ? confidence.data() : nullptr, &eval_params, err.data(), cls.data(), &rep)) {
+            printf("evaluation refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        const int n = rep.n_thresholds;
+        printf("\nEvaluation against %s (scale %g)%s\n%-14s %9s %8s", gt_path[0].c_str(), gt_scale, rep.has_right_gt ? ", non-occluded by cross-check within 1 px" : "",
+               "mask", "pixels", "invalid%");
+        for (int k = 0; k < n; k++) printf(" bad>%-4g%%", rep.thresholds[k]);
+        printf(" %8s %8s\n", "mean", "rms");
+        print_eval_row("all", rep.all.pixels, rep.all.invalid, rep.all.bad, n, rep.all.sum_err_q, &rep.all.sum_sq_err_q);
+        if (rep.has_right_gt) print_eval_row("nonocc", rep.nonocc.pixels, rep.nonocc.invalid, rep.nonocc.bad, n, rep.nonocc.sum_err_q, &rep.nonocc.sum_sq_err_q);
+        if (rep.has_provenance) {
+            static const char* const names[4] = {"fill:wta", "fill:voting", "fill:interp", "fill:none"};
+            for (int f = 0; f < 4; f++) print_eval_row(names[f], rep.by_fill[f].pixels, rep.by_fill[f].invalid, rep.by_fill[f].bad, n, rep.by_fill[f].sum_err_q, nullptr);
+            if (speckle_size > 0) printf("known pixels removed by the speckle filter: %llu\n", (unsigned long long)rep.speckle_removed_known);
+        }
+        if (rep.has_confidence && n > 0) { // sparsification: bins from low confidence up, error rate of the pixels that remain
+            double total = 0, total_bad = 0, removed = 0, removed_bad = 0, area = 0, x0 = 0, y0 = 0;
+            for (int b = 0; b < ADC_EVAL_CONF_BINS; b++) { total += (double)rep.conf_pixels[b]; total_bad += (double)rep.conf_bad[b]; }
+            y0 = total > 0 ? total_bad / total : 0;
+            for (int b = 0; b < ADC_EVAL_CONF_BINS && total > 0; b++) {
+                removed += (double)rep.conf_pixels[b];
+                removed_bad += (double)rep.conf_bad[b];
+                const double x1 = removed / total, y1 = total - removed > 0 ? (total_bad - removed_bad) / (total - removed) : 0;
+                area += (x1 - x0) * (y0 + y1) / 2;
+                x0 = x1; y0 = y1;
+            }
+            printf("confidence: sparsification area %.4f (random ranking %.4f) over %.0f measured pixels, bad > %g\n", area, total > 0 ? total_bad / total : 0, total,
+                   rep.thresholds[0]);
+        }
+        for (size_t i = 0; i < cls.size(); i++) {
+            const uint8 c = cls[i];
+            const bool occ = (c & ADC_EVAL_OCCLUDED) != 0;
+            uint8 r = 0, g = 0, b = 0;
+            if (!(c & ADC_EVAL_KNOWN)) { }
+            else if (!(c & ADC_EVAL_VALID)) { b = 255; }
+            else if (c & ADC_EVAL_BAD) { r = 255; g = occ ? 160 : 0; }
+            else { r = g = b = occ ? 140 : 220; }
+            rgb[3 * i] = r; rgb[3 * i + 1] = g; rgb[3 * i + 2] = b;
+        }
+        write_pfm(out + "-err.pfm", err.data(), w, h);
+        if (!write_png(out + "-bad.png", rgb.data(), w, h, 3)) printf("cannot write %s-bad.png\n", out.c_str());
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

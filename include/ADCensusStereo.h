@@ -12,7 +12,8 @@
  * timing lines, ADCensusStereo.cpp:88-129: ON by default like the reference, ADC_VERBOSE=0 or SetVerbose(false) turns them off), StageMilliseconds, MatchAsync/Wait,
  * MatchEx (per-pixel provenance and confidence maps next to the disparity), MatchOut (depth, point cloud and 8-bit image computed
  * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default),
- * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default).
+ * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default),
+ * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device).
  */
 #pragma once
 
@@ -22,6 +23,9 @@ struct adc_handle;
 struct adc_outputs; // include/adcensus_c_api.h
 struct adc_raw_format;
 struct adc_camera_model;
+struct adc_gt;
+struct adc_eval_params;
+struct adc_eval_report;
 
 class ADCensusStereo {
 public:
@@ -81,6 +85,21 @@ public:
     bool ClearRectify();
     /** The remap alone, host to host: raw image of the side's geometry -> uint8 [H][W][3] BGR.  Needs Initialize and the side set. */
     bool Rectify(int side, const uint8* raw, uint8* bgr_out);
+    /** Optional evaluation against ground truth on the device (adc_set_ground_truth / adc_evaluate, include/adcensus_c_api.h): the
+     *  ground truth of the left view, optionally of the right view (occlusion by cross-check within occ_thres) or a non-occlusion
+     *  mask, all host arrays.  Needs Initialize; Initialize / Reset drop it (it belongs to the matcher object underneath).  false: a
+     *  refused argument, a Match pending, a HIP failure. */
+    bool SetGroundTruth(const adc_gt* left, const adc_gt* right, const uint8* nonocc, float32 occ_thres);
+    bool ClearGroundTruth();
+    /** Scores a float32 [H][W] host map (any map of this geometry: a Match result, a filtered one, another matcher's) against the
+     *  ground truth set: integer report (bad pixels per threshold, error sums, histograms; all / non-occluded / per provenance fill
+     *  class / per confidence bin), optionally the per-pixel error and class maps.  provenance, confidence, params (one threshold of
+     *  1.0), err, eval_class and report may be null.  false where the library refuses (no ground truth, confidence without
+     *  provenance, a bad threshold) and on a HIP failure. */
+    bool Evaluate(const float32* disp, const uint8* provenance, const float32* confidence, const adc_eval_params* params, float32* err,
+                  uint8* eval_class, adc_eval_report* report);
+    /** The report of the last evaluation completed on this object. */
+    bool EvalReport(adc_eval_report* report) const;
     const char* LastError() const;
 
 private:

@@ -322,6 +322,110 @@ int adc_farm_set_rectify_maps(adc_farm* f, int side, const adc_raw_format* raw, 
 int adc_farm_set_rectify_model(adc_farm* f, int side, const adc_raw_format* raw, const adc_camera_model* model);
 int adc_farm_clear_rectify(adc_farm* f);
 
+/* -------------------------------------------------------------------------------------------
+ * Optional evaluation of a disparity map against ground truth on the device (k_eval.hip): Middlebury's evaldisp figures -- bad-pixel
+ * counts, error sums, all pixels and non-occluded pixels -- split by the provenance classes and binned by the confidence of
+ * adc_match_ex.  Off by default: a handle that never gets ground truth does exactly what it did before.  Every result is an integer;
+ * tests/eval_ref.py holds the same definition in numpy and the kernels match it bit for bit.  All float arithmetic is IEEE binary32,
+ * one rounding per operation, nothing fused, divisions correctly rounded.
+ *
+ * Ground truth g [H][W] of a side, from the caller's array (adc_gt: address, format, row pitch in bytes, scale):
+ *   ADC_GT_U8 / ADC_GT_U16  value v == 0: unknown; otherwise g = float(v) / scale (the Middlebury PNG convention: scale 4 for Cone,
+ *                           2 for Cloth3 and Wood2; ADC_GT_U16 with scale 256 is KITTI's encoding)
+ *   ADC_GT_F32              g = v / scale (PFM ground truth, scale 1)
+ *   In every format a quotient that is not finite (a v that is NaN or +-inf, an overflow) is unknown.  Unknown is stored as +inf.
+ *   scale must be finite and > 0, pitch_bytes >= W * bytes per value (0: tightly packed), H * pitch_bytes <= 2^31 - 1.
+ * Occlusion is defined only with right-view ground truth gr or a caller mask:
+ *   with gr:    a known pixel (x, y) is non-occluded iff r = rintf(g) (ties to even) has |r| <= 2^30, xr = x - (int)r lies in [0, W),
+ *               gr[y][xr] is known and fabsf(gr[y][xr] - g) <= occ_thres
+ *   otherwise:  a caller-given uint8 [H][W] mask (tightly packed), nonzero = non-occluded
+ *   masks:      all = known; nonocc = known and non-occluded (empty when neither source is present)
+ * Per pixel, with d the evaluated map (signed, not |d|): valid = d finite; for a known and valid pixel e = fabsf(d - g) and
+ *   eq = (uint32)rintf(fminf(e, 2048.0f) * 1024.0f)   (1/1024 pixel, clamped at 2048 pixels: the product is exact, rintf is the only
+ *   rounding, and the means agree with float arithmetic to four digits)
+ * Report (adc_eval_report; uint64 counters):
+ *   all, nonocc     pixels of the mask; invalid = those with !valid; bad[k] = valid ones with e > thresholds[k] (a float compare on e,
+ *                   e == t is not bad; unused k: 0); sum_err_q = sum of eq and sum_sq_err_q = sum of eq * eq (modulo 2^64) over the
+ *                   valid ones; err_hist[min(eq >> 8, 255)] (bins of 1/4 pixel, the last one open) over the valid ones
+ *   by_fill[f]      pixels, invalid, bad[k], sum_err_q as above over the `all` mask, for the pixels whose provenance code has
+ *                   fill = (code >> ADC_PROV_FILL_SHIFT) & 3 equal to f (ADC_FILL_*); all zero without a provenance map.  A pixel
+ *                   with ADC_PROV_SPECKLE stays in its fill class and also counts in speckle_removed_known (if known)
+ *   conf_pixels[b], conf_bad[b]   over the pixels that are known, valid and fill == ADC_FILL_WTA: c = confidence * 256.0f,
+ *                   b = 0 when !(c >= 0), 255 when c >= 255, otherwise (int)c; conf_bad counts e > thresholds[0].  All zero unless
+ *                   BOTH a provenance and a confidence map are given
+ *   and an echo: the thresholds, occ_thres, which inputs were present
+ * Per-pixel outputs, both optional:
+ *   err    float32 [H][W]: e, +inf where unknown or !valid
+ *   class  uint8 [H][W]: ADC_EVAL_KNOWN | ADC_EVAL_VALID (d finite, known or not) | ADC_EVAL_BAD (known, valid, e > thresholds[0]) |
+ *          ADC_EVAL_OCCLUDED (known, occlusion defined, not non-occluded)
+ * Rates, mean (sum_err_q / 1024 / valid pixels), RMS and the sparsification curve of the confidence are the caller's arithmetic on these
+ * integers (adcensus_amd/evaluation.py: summarize; the CLI's table); they are not part of the ABI.
+ *
+ * adc_set_ground_truth   HOST pointers, synchronous: uploads, decodes, builds the occlusion byte map.  right may be NULL, nonocc may be
+ *                        NULL (right wins when both are given); occ_thres finite and >= 0 (Middlebury: 1.0).  The first call on a
+ *                        handle allocates the feature's device buffers (adc_create allocates none of them), adc_destroy frees them.
+ * adc_clear_ground_truth back to "no ground truth" (the buffers stay until adc_destroy).
+ * adc_evaluate_device    scores any device-resident float32 [H][W] map of the handle's geometry; d_provenance (uint8 [H][W]),
+ *                        d_confidence (float32 [H][W]), d_err, d_class are device addresses or NULL; params NULL = one threshold, 1.0.
+ *                        Asynchronous on the handle's stream, completed by adc_wait (the report travels through a pinned read-back
+ *                        behind the kernel).  REFUSED while a Match is pending: a redo of adc_wait would rewrite the map behind the
+ *                        evaluation (adc_wait first).
+ * adc_evaluate           the same with HOST pointers, synchronous; device scratch is allocated on the first call that needs it (freed
+ *                        by adc_destroy); out may be NULL.
+ * adc_get_eval_report    the report of the last evaluation that adc_wait (or adc_evaluate) has completed.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued or changed (NULL handle / map / left ground truth, an unknown format, a
+ * bad scale, occ_thres or pitch, more than ADC_EVAL_MAX_THRESHOLDS thresholds, a threshold negative or not finite, a confidence map
+ * without a provenance map, no ground truth set, a Match pending); 2 on a HIP failure (a failed set call leaves ground truth unset,
+ * the handle stays usable).  There is no farm entry point: ground truth differs per pair.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_GT_U8 0
+#define ADC_GT_U16 1
+#define ADC_GT_F32 2
+#define ADC_EVAL_MAX_THRESHOLDS 4
+#define ADC_EVAL_ERR_BINS 256
+#define ADC_EVAL_CONF_BINS 256
+#define ADC_EVAL_KNOWN 1
+#define ADC_EVAL_VALID 2
+#define ADC_EVAL_BAD 4
+#define ADC_EVAL_OCCLUDED 8
+typedef struct adc_gt {
+    const void* data;
+    int32_t format;      /* ADC_GT_* */
+    int32_t pitch_bytes; /* 0: tightly packed rows */
+    float scale;
+    int32_t reserved_;
+} adc_gt;
+typedef struct adc_eval_params {
+    int32_t n_thresholds; /* 0 .. ADC_EVAL_MAX_THRESHOLDS */
+    float thresholds[ADC_EVAL_MAX_THRESHOLDS];
+} adc_eval_params;
+typedef struct adc_eval_mask_stats {
+    uint64_t pixels, invalid, bad[ADC_EVAL_MAX_THRESHOLDS], sum_err_q, sum_sq_err_q;
+    uint64_t err_hist[ADC_EVAL_ERR_BINS];
+} adc_eval_mask_stats;
+typedef struct adc_eval_fill_stats {
+    uint64_t pixels, invalid, bad[ADC_EVAL_MAX_THRESHOLDS], sum_err_q;
+} adc_eval_fill_stats;
+typedef struct adc_eval_report {
+    adc_eval_mask_stats all, nonocc;
+    adc_eval_fill_stats by_fill[4]; /* ADC_FILL_WTA, _VOTING, _INTERPOLATION, _NONE */
+    uint64_t speckle_removed_known;
+    uint64_t conf_pixels[ADC_EVAL_CONF_BINS], conf_bad[ADC_EVAL_CONF_BINS];
+    /* echo of the request */
+    float thresholds[ADC_EVAL_MAX_THRESHOLDS];
+    int32_t n_thresholds;
+    float occ_thres;
+    uint8_t has_right_gt, has_nonocc_mask, has_provenance, has_confidence;
+    int32_t reserved_;
+} adc_eval_report;
+int adc_set_ground_truth(adc_handle* h, const adc_gt* left, const adc_gt* right, const uint8_t* nonocc, float occ_thres);
+int adc_clear_ground_truth(adc_handle* h);
+int adc_evaluate_device(adc_handle* h, const void* d_disp, const void* d_provenance, const void* d_confidence,
+                        const adc_eval_params* params, void* d_err, void* d_class);
+int adc_evaluate(adc_handle* h, const float* disp, const uint8_t* provenance, const float* confidence, const adc_eval_params* params,
+                 float* err, uint8_t* eval_class, adc_eval_report* out);
+int adc_get_eval_report(adc_handle* h, adc_eval_report* out);
+
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
  * Level 2 records only the marks around the aggregation launches (adc_aggregate_info: the live duration of the roofline kernel) and
