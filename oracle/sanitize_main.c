@@ -2,13 +2,32 @@
  * adc_oracle_match of whichever oracle it is linked with, for the ASAN / UBSAN builds (`make -C oracle asan`): the port
  * (adcensus_port.c) and, where /root/reference exists, the reference's own sources behind ref_driver.cpp.  Exit code 0 and no
  * sanitizer report = clean on this input (min_disparity = 0; the reference's documented out-of-bounds read for
- * min_disparity > 0, ADCensusStereo.cpp:296-300, is not provoked). */
+ * min_disparity > 0, ADCensusStereo.cpp:296-300, is not provoked).
+ * Arguments: option overrides as field=value (lambda_ad, lambda_census, cross_L1, cross_L2, cross_t1, cross_t2, so_p1, so_p2, so_tso,
+ * irv_ts, irv_th, lrcheck_thres), e.g. `sanitize_port so_p1=-1 so_p2=-3`; an unknown field or a malformed value is exit code 4. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "oracle_abi.h"
 
-int main(void)
+static int override(adc_option* o, const char* arg)
+{
+    const char* eq = strchr(arg, '=');
+    char* end = NULL;
+    if (!eq || eq == arg || !eq[1]) return 0;
+    const size_t n = (size_t)(eq - arg);
+    const double v = strtod(eq + 1, &end);
+    if (*end) return 0;
+#define INT_FIELD(f) if (n == strlen(#f) && !strncmp(arg, #f, n)) { o->f = (int32_t)v; return (double)(int32_t)v == v; }
+#define FLT_FIELD(f) if (n == strlen(#f) && !strncmp(arg, #f, n)) { o->f = (float)v; return 1; }
+    INT_FIELD(lambda_ad) INT_FIELD(lambda_census) INT_FIELD(cross_L1) INT_FIELD(cross_L2) INT_FIELD(cross_t1) INT_FIELD(cross_t2)
+    FLT_FIELD(so_p1) FLT_FIELD(so_p2) INT_FIELD(so_tso) INT_FIELD(irv_ts) FLT_FIELD(irv_th) FLT_FIELD(lrcheck_thres)
+#undef INT_FIELD
+#undef FLT_FIELD
+    return 0;
+}
+
+int main(int argc, char** argv)
 {
     const int W = 96, H = 64, D = 24;
     uint8_t* l = (uint8_t*)malloc((size_t)W * H * 3);
@@ -32,6 +51,8 @@ int main(void)
     opt.min_disparity = 0; opt.max_disparity = D; opt.lambda_ad = 10.0f; opt.lambda_census = 30.0f; opt.cross_L1 = 34; opt.cross_L2 = 17;
     opt.cross_t1 = 20; opt.cross_t2 = 6; opt.so_p1 = 1.0f; opt.so_p2 = 3.0f; opt.so_tso = 15; opt.irv_ts = 20; opt.irv_th = 0.4f;
     opt.lrcheck_thres = 1.0f; opt.do_lr_check = 1; opt.do_filling = 1; opt.do_discontinuity_adjustment = 1;
+    for (int i = 1; i < argc; i++)
+        if (!override(&opt, argv[i])) { printf("bad option override: %s\n", argv[i]); free(l); free(r); return 4; }
     const size_t P = (size_t)W * H;
     adc_oracle_dump d;
     memset(&d, 0, sizeof(d));

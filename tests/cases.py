@@ -196,6 +196,124 @@ _CASES = {
     "wrap0_320x288_d16": (lambda: flat_block_pair(320, 288, 256, -4, seed=51), _long(255, d=16)),
     "wrap_320x320_d8": (lambda: flat_block_pair(320, 320, 300, -3, seed=52), _long(255, d=8)),
 }
+
+# ---- the option space (opt_<set>_<pair>[_r]) -------------------------------------------------------------------------------------
+# Extreme and ordinary-but-untested values of the twelve numeric option fields, one field group per set, everything else default.
+# The reference validates nothing but the disparity range, so every value here is a legal input; its behaviour on all of them is
+# defined (a UBSAN build of its sources runs them clean, tests/test_sanitize.py) and the port restates it bit for bit.
+# Deliberately NOT covered: lambda_ad <= 0 / lambda_census <= 0 (the reference divides by zero: sign and payload of the resulting
+# NaN are nothing to pin bit for bit) and NaN thresholds.
+# Pairs, all seeded and small: s2 = structured 96x64, q = quantized noise 70x45 (arms <= 1 under default options: the sets that
+# need regions -- scanline threshold, voting -- do not use it), flat = flat patches 160x48 (arms that reach the limit), s2w =
+# structured 160x48 with D = 128 (two disparities per lane: class offsets, fused cost windows and the fused tail are per-VPL
+# code), n2w = uniform noise 160x48 with D = 128 (arms of 0..1: the only pair on which the last aggregation pass moves into the first
+# scanline pass, k_scanline_seg_agg, which needs horizontal arms <= 3; 160 columns are the fewest that allow two row segments).
+# s2x = structured 160x40 with D = 64 = the padded range: wide enough for whole interior chunks of the scanline kernels, whose class
+# rule is a form of its own (adc_so_class_offsets_interior) -- the scanline threshold sets use it.
+# "_r" = the range [-5, 27) with the discontinuity adjustment on.
+OPT_PAIRS = {
+    "s2": (lambda: workloads.structured_pair(96, 64, 32, seed=11), dict(max_disparity=32)),
+    "q": (lambda: workloads.quantized_noise_pair(70, 45, 32, seed=5, levels=16), dict(max_disparity=32)),
+    "flat": (lambda: flat_patch_pair(160, 48, 16, seed=3, patch_w=(20, 80), patch_h=(8, 30)), dict(max_disparity=32)),
+    "s2w": (lambda: workloads.structured_pair(160, 48, 128, seed=61), dict(max_disparity=128)),
+    "n2w": (lambda: workloads.noise_pair(160, 48, seed=71), dict(max_disparity=128)),
+    "s2x": (lambda: workloads.structured_pair(160, 40, 64, seed=81), dict(max_disparity=64)),
+    # flat patches of 6..30 x 4..12 pixels in bands of 3..10 rows: regions that mix several disparities (votes whose winning share
+    # stays below the default irv_th) and arms that end between cross_L2 and cross_L1 on a colour step between cross_t2 and cross_t1
+    "fs": (lambda: flat_patch_pair(160, 48, 16, seed=1, patch_w=(6, 30), patch_h=(4, 12), band_h=(3, 10)), dict(max_disparity=32)),
+    "fs4": (lambda: flat_patch_pair(160, 48, 16, seed=4, patch_w=(6, 30), patch_h=(4, 12), band_h=(3, 10)), dict(max_disparity=32)),
+}
+_OPT_R = dict(min_disparity=-5, max_disparity=27, do_discontinuity_adjustment=1)
+# family -> (stage a set of the family must change against the default options, pair tags it runs on)
+OPT_FAMILIES = {
+    "cost": ("cost_init", ["s2", "flat", "s2w", "n2w"]),
+    "penalty": ("cost_so", ["s2", "flat", "s2w", "n2w", "s2_r"]),
+    "tso": ("cost_so", ["s2", "flat", "s2w", "n2w", "s2x", "s2_r"]),
+    "arm_t": ("arms", ["s2", "flat", "q"]),
+    "arm_l": ("arms", ["s2", "flat", "q"]),
+    "voting": ("disp_after_irv", ["s2", "flat", "flat_r"]),
+    "lr": ("outlier_label", ["s2", "flat", "q"]),
+}
+# set -> (family, option fields[, pair tags of its own: where the family's pairs cannot show the set -- arms of at most 1 (q) never
+# reach cross_L2, the colour steps of the large flat patches lie on one side of cross_t2, and no region of s2 / flat votes with
+# a winning share below the default irv_th])
+OPT_SETS = {
+    "lam_1_1": ("cost", dict(lambda_ad=1, lambda_census=1)),
+    "lam_2_200": ("cost", dict(lambda_ad=2, lambda_census=200)),
+    "lam_255_3": ("cost", dict(lambda_ad=255, lambda_census=3)),
+    "lam_1000_1000": ("cost", dict(lambda_ad=1000, lambda_census=1000)),
+    "p_zero": ("penalty", dict(so_p1=0.0, so_p2=0.0)),
+    "p1_gt_p2": ("penalty", dict(so_p1=3.0, so_p2=1.0)),
+    "p_small": ("penalty", dict(so_p1=0.01, so_p2=0.03)),
+    "p_big": ("penalty", dict(so_p1=100.0, so_p2=300.0)),
+    "p_1e5": ("penalty", dict(so_p1=1e5, so_p2=3e5)),
+    "p_neg": ("penalty", dict(so_p1=-1.0, so_p2=-3.0)),
+    "tso_m3": ("tso", dict(so_tso=-3)),
+    "tso_0": ("tso", dict(so_tso=0)),
+    "tso_1": ("tso", dict(so_tso=1)),
+    "tso_255": ("tso", dict(so_tso=255)),
+    "tso_256": ("tso", dict(so_tso=256)),
+    "tso_1000": ("tso", dict(so_tso=1000)),
+    "t1_m4": ("arm_t", dict(cross_t1=-4)),
+    "t1_0": ("arm_t", dict(cross_t1=0)),
+    "t1_1": ("arm_t", dict(cross_t1=1)),
+    "t1_255": ("arm_t", dict(cross_t1=255)),
+    "t1t2_256": ("arm_t", dict(cross_t1=256, cross_t2=256)),
+    "t2_0": ("arm_t", dict(cross_t2=0), ["s2", "flat", "fs"]),
+    "t2_1000": ("arm_t", dict(cross_t2=1000), ["s2", "fs"]),
+    "L1_m5": ("arm_l", dict(cross_L1=-5)),
+    "L1_0": ("arm_l", dict(cross_L1=0)),
+    "L1_2": ("arm_l", dict(cross_L1=2), ["s2", "flat", "fs"]),
+    "L1_1_L2_0": ("arm_l", dict(cross_L1=1, cross_L2=0)),
+    "L2_m3": ("arm_l", dict(cross_L2=-3), ["s2", "q", "fs"]),
+    "L2_100000": ("arm_l", dict(cross_L2=100000), ["s2", "fs"]),
+    "ts_m1": ("voting", dict(irv_ts=-1)),
+    "ts_1": ("voting", dict(irv_ts=1)),
+    "ts_100000": ("voting", dict(irv_ts=100000)),
+    "th_m05": ("voting", dict(irv_th=-0.5), ["fs", "fs4", "fs4_r"]),
+    "th_0": ("voting", dict(irv_th=0.0), ["fs", "fs4", "fs4_r"]),
+    "th_099": ("voting", dict(irv_th=0.99)),
+    "th_1": ("voting", dict(irv_th=1.0)),
+    "th_5": ("voting", dict(irv_th=5.0)),
+    "lr_m1": ("lr", dict(lrcheck_thres=-1.0)),
+    "lr_0": ("lr", dict(lrcheck_thres=0.0)),
+    "lr_03": ("lr", dict(lrcheck_thres=0.3)),
+    "lr_1e9": ("lr", dict(lrcheck_thres=1e9)),
+}
+# sets that the reference makes equal by construction (every colour step is >= 0 > so_tso and <= 255 < so_tso; the arm limit is
+# clamped to >= 0; no colour difference is < cross_t1 <= 0; a winning share is > 0 and <= 1): equal stage for stage, pair by pair
+OPT_EQUAL_SETS = {"tso_m3": "tso_0", "tso_1000": "tso_256", "L1_m5": "L1_0", "t1_m4": "t1_0", "th_m05": "th_0", "th_5": "th_1"}
+
+
+def _opt_case(pair_tag, fields):
+    pair, _, r = pair_tag.partition("_")
+    build, kw = OPT_PAIRS[pair]
+    return build, dict(kw, **(_OPT_R if r else {}), **fields)
+
+
+OPT_DEFAULTS = {}   # case name -> the case of the same pair and range under default options
+OPT_TARGET = {}     # case name -> stage its set must change against OPT_DEFAULTS[name]
+OPT_CASES = {fam: [] for fam in OPT_FAMILIES}  # family -> case names
+_OPT_DEFAULT_TAGS = ("s2", "q", "flat", "s2w", "n2w", "s2x", "fs", "fs4", "s2_r", "flat_r", "fs4_r")
+for _tag in _OPT_DEFAULT_TAGS:
+    _CASES["opt_default_" + _tag] = _opt_case(_tag, {})
+for _set, (_fam, _fields, *_own) in OPT_SETS.items():
+    for _tag in (_own[0] if _own else OPT_FAMILIES[_fam][1]):
+        _name = "opt_%s_%s" % (_set, _tag)
+        _CASES[_name] = _opt_case(_tag, _fields)
+        OPT_DEFAULTS[_name] = "opt_default_" + _tag
+        OPT_TARGET[_name] = OPT_FAMILIES[_fam][0]
+        OPT_CASES[_fam].append(_name)
+OPT_DEFAULT_CASES = ["opt_default_" + t for t in _OPT_DEFAULT_TAGS]
+OPT_ALL_CASES = [n for fam in OPT_FAMILIES for n in OPT_CASES[fam]]
+# the penalty sets whose path costs need not converge within the scanline segments' 64-column warm-up (gpu_harness.stage_report)
+OPT_SEAMS_MAY_FAIL = [n for n in OPT_CASES["penalty"] if n.startswith(("opt_p_big_", "opt_p_1e5_", "opt_p_neg_"))]
+# ... and the one cost case that is the same thing from the other side: lambda = (1, 1) on uniform noise saturates the cost (44 % of the
+# aggregated volume is exactly 2.0 and no pixel's costs spread by more than 1.0 = so_p1), so a path never takes the branch that
+# forgets where it started -- whatever the warm-up length.  Its seams DO fail on the MI355X (profiles/README.md); the whole-row redo
+# is exact.  (On the structured and flat pairs the same lambda leaves contrast, and the seams hold.)
+OPT_SEAMS_MAY_FAIL.append("opt_lam_1_1_n2w")
+
 GOLDEN_CASES = list(_CASES.keys())
 # subset that the CPU-only tier recomputes with the port (kept small: the whole CPU suite must run in minutes)
 FAST_CASES = ["cone_crop_d40", "s2_96x64_d32", "q_257x131_d64", "q_20x40_d32", "q_9x20_d8", "q_30x7_d8", "q_1x40_d8",
@@ -206,6 +324,7 @@ FAST_CASES = ["cone_crop_d40", "s2_96x64_d32", "q_257x131_d64", "q_20x40_d32", "
               "flat_640x96_L48", "flat_640x96_L49", "flat_640x96_L64", "flat_640x96_L128", "flat_640x96_L255", "flat_640x96_L1000",
               "flat_640x96_L64_L2gt", "flat_640x96_L128_L2zero", "flat_640x96_L128_t2t1", "flat_200x64_L255", "flat_600x1_L255",
               "flat_1x300_L255"]
+FAST_CASES += OPT_DEFAULT_CASES + OPT_ALL_CASES  # (the option space: about 0.1 s each)
 # named long-arm cases that the reference's arm clamp (MAX_ARM_LENGTH = 255) makes equal, stage for stage
 CLAMPED_CASES = {"flat_640x96_L300": "flat_640x96_L255", "flat_640x96_L1000": "flat_640x96_L255"}
 

@@ -30,9 +30,11 @@ def diff(got, want):
     return n, first
 
 
-def stage_report(left, right, opt, o, device=0, paper_modes=0):
+def stage_report(left, right, opt, o, device=0, paper_modes=0, seams_may_fail=False):
     """o = oracle dump dict (all stages). Returns {stage: {"bad": n, "total": N, "first": ...}}.
-    paper_modes: opt-in paper features set on the handle (then `o` must come from the port oracle run with the same modes)."""
+    paper_modes: opt-in paper features set on the handle (then `o` must come from the port oracle run with the same modes).
+    seams_may_fail: do not assert that every scanline seam held (SO_SEAMS_HOLD_UP_TO_L1 was measured with the default penalties;
+    how fast a path forgets its start depends on so_p1 / so_p2) -- the whole-row redo must be exact all the same."""
     h, w = left.shape[:2]
     st = A.ADCensusStereo(device=device)
     popt = cases.to_product_option(opt)
@@ -104,7 +106,7 @@ def stage_report(left, right, opt, o, device=0, paper_modes=0):
         import os
         rep["cost_so"]["segments"] = st.debug_counter(5)
         rep["cost_so"]["seam_fails"] = 1 if seam_error else (st.debug_counter(6) if st.debug_counter(5) > 1 else 0)
-        if int(os.environ.get("ADC_SO_WARM", "64")) >= 64 and min(opt.cross_L1, 255) <= SO_SEAMS_HOLD_UP_TO_L1:
+        if int(os.environ.get("ADC_SO_WARM", "64")) >= 64 and min(opt.cross_L1, 255) <= SO_SEAMS_HOLD_UP_TO_L1 and not seams_may_fail:
             assert rep["cost_so"]["seam_fails"] == 0, rep["cost_so"]
 
         # production form of the scanline stage: the last pass also delivers the left-view winner-takes-all

@@ -49,6 +49,30 @@ def test_initialize_rejects_bad_arguments():
     assert not st.Match(np.zeros((10, 10, 3), np.uint8), np.zeros((10, 10, 3), np.uint8), np.zeros((10, 10), np.float32))
 
 
+def _option_sets():
+    from tests import cases
+    return sorted(cases.OPT_SETS)
+
+
+@pytest.mark.parametrize("name", _option_sets())
+def test_create_accepts_every_option_extreme(name):
+    """The reference validates nothing but the size and the disparity range, and neither does adc_create: every set of the option
+    space (tests/cases.py: OPT_SETS) passes the argument checks.  With a device the handle is created; without one the refusal is
+    the missing device -- which is checked AFTER the arguments -- and names no option field."""
+    import adcensus_amd
+    from tests import cases
+    fields = cases.OPT_SETS[name][1]
+    st = adcensus_amd.ADCensusStereo()
+    ok = st.Initialize(32, 32, adcensus_amd.ADCensusOption(max_disparity=32, **fields))
+    if adcensus_amd.device_count() > 0:
+        assert ok, adcensus_amd.last_error()
+        st.Release()
+    else:
+        err = adcensus_amd.last_error()
+        assert not ok and ("no HIP device" in err or "hipSetDevice" in err), err
+        assert not any(f in err for f in fields), err
+
+
 def test_no_cpu_fallback_without_device():
     """Without a GPU the product must FAIL (never silently compute on the CPU)."""
     import adcensus_amd

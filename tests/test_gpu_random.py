@@ -96,3 +96,63 @@ def test_random_long_arm_limits_equal_oracle(hip, oracle, seed):
                 bad.append(tag + " (Match %d: %d pixels)" % (rep, int((dm.view(np.uint32) != o["disp_final"].view(np.uint32)).sum())))
         st.Release()
     assert not bad, bad
+
+
+# the whole option hull: every numeric field from a list that holds the extremes of the option space (tests/cases.py: OPT_SETS)
+# and ordinary values in between.  (lambda_* > 0: the reference divides by them.)
+HULL = {
+    "lambda_ad": [1, 2, 10, 10, 255, 1000], "lambda_census": [1, 3, 30, 30, 200, 1000],
+    "cross_L1": [-5, 0, 1, 2, 9, 17, 34, 34], "cross_L2": [-3, 0, 1, 8, 17, 17, 100000],
+    "cross_t1": [-4, 0, 1, 8, 20, 20, 40, 255, 256], "cross_t2": [0, 1, 6, 6, 12, 256, 1000],
+    "so_p1": [0.0, 0.01, 0.8, 1.0, 1.0, 3.0, 100.0, 1e5, -1.0], "so_p2": [0.0, 0.03, 1.0, 2.5, 3.0, 3.0, 300.0, 3e5, -3.0],
+    "so_tso": [-3, 0, 1, 11, 15, 15, 255, 256, 1000],
+    "irv_ts": [-1, 0, 1, 5, 20, 20, 45, 100000], "irv_th": [-0.5, 0.0, 0.1, 0.4, 0.4, 0.7, 0.99, 1.0, 5.0],
+    "lrcheck_thres": [-1.0, 0.0, 0.3, 0.5, 1.0, 1.0, 2.0, 1e9],
+}
+HULL_SEEDS = [1101, 1202, 1303, 1404]
+
+
+def draw_hull(rng):
+    """Geometry and pair as in _draw (whose own sequence stays what it is), then all twelve numeric fields from HULL."""
+    pair, opt = _draw(rng)
+    for field, values in HULL.items():
+        v = rng.choice(values)
+        setattr(opt, field, float(v) if isinstance(values[0], float) else int(v))
+    return pair, opt
+
+
+def hull_tag(seed, k, shape, opt):
+    return "seed %d case %d: %dx%d [%d, %d) lambda %d/%d L %d/%d t %d/%d P %g/%g tso %d ts %d th %g lr %g" % (
+        seed, k, shape[1], shape[0], opt.min_disparity, opt.max_disparity, opt.lambda_ad, opt.lambda_census, opt.cross_L1, opt.cross_L2,
+        opt.cross_t1, opt.cross_t2, opt.so_p1, opt.so_p2, opt.so_tso, opt.irv_ts, opt.irv_th, opt.lrcheck_thres)
+
+
+@pytest.mark.parametrize("seed", HULL_SEEDS)
+def test_random_draws_over_the_option_hull_equal_oracle(hip, oracle, seed):
+    """4 seeds x 6 draws over the whole option hull (tests/test_oracle.py runs the same draws for port == reference, so they are
+    known to be defined behaviour): the voting stage in isolation and two Matches, bit for bit."""
+    A = hip
+    rng = np.random.default_rng(seed)
+    bad = []
+    for k in range(6):
+        (left, right), opt = draw_hull(rng)
+        h, w = left.shape[:2]
+        o = oracle.run(left, right, opt)
+        tag = hull_tag(seed, k, left.shape, opt)
+        st = A.ADCensusStereo(device=0)
+        assert st.Initialize(w, h, cases.to_product_option(opt)), tag + ": " + A.last_error()
+        st.debug_set_images(left, right)
+        st.debug_write(A.BUF_ARMS, o["arms"])
+        st.debug_write(A.BUF_SUPCOUNT_H, o["sup_count_h"])
+        st.debug_write(A.BUF_DISP_LEFT, o["disp_after_lr"])
+        st.debug_write(A.BUF_OUTLIER_LABEL, o["outlier_label"])
+        st.debug_run(A.RUN_REGION_VOTING)
+        got = np.asarray(st.debug_read(A.BUF_DISP_LEFT)).view(np.uint32)
+        if not np.array_equal(got, o["disp_after_irv"].view(np.uint32)):
+            bad.append(tag + " (voting stage: %d pixels)" % int((got != o["disp_after_irv"].view(np.uint32)).sum()))
+        for rep in range(2):
+            d = st.match(left, right)
+            if not np.array_equal(d.view(np.uint32), o["disp_final"].view(np.uint32)):
+                bad.append(tag + " (Match %d: %d pixels)" % (rep, int((d.view(np.uint32) != o["disp_final"].view(np.uint32)).sum())))
+        st.Release()
+    assert not bad, bad

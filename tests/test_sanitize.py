@@ -34,14 +34,44 @@ def _run(cmd, ok=True):
     return r
 
 
-def test_oracles_under_sanitizers():
+@pytest.fixture(scope="module")
+def oracle_asan():
     _make(os.path.join(ROOT, "oracle"))
+    ref = os.path.join(ROOT, "oracle", "_ref", "sanitize_ref")
+    if os.path.isdir("/root/reference/AD-Census"):
+        assert os.path.exists(ref)
+    return [os.path.join(ROOT, "oracle", "_port", "sanitize_port")] + ([ref] if os.path.exists(ref) else [])
+
+
+def test_oracles_under_sanitizers(oracle_asan):
     out = _run([os.path.join(ROOT, "oracle", "_port", "sanitize_port")]).stdout
     assert "match == staged run: yes" in out
     ref = os.path.join(ROOT, "oracle", "_ref", "sanitize_ref")
     if os.path.isdir("/root/reference/AD-Census"):
         assert os.path.exists(ref)
         assert "match == staged run: yes" in _run([ref]).stdout
+
+
+def _option_sets():
+    from tests import cases
+    return sorted(cases.OPT_SETS)
+
+
+@pytest.mark.parametrize("name", _option_sets())
+def test_oracles_under_sanitizers_per_option_set(oracle_asan, name):
+    """Every set of the option space (tests/cases.py: OPT_SETS) on the driver's built-in pair, under ASAN + UBSAN: the port, and the
+    reference's own sources where they exist -- signed overflow, out-of-range float-to-int conversions, out-of-bounds table reads
+    and divisions by zero that an extreme option value could provoke are reports, and a report is a failure."""
+    from tests import cases
+    args = ["%s=%r" % kv for kv in cases.OPT_SETS[name][1].items()]
+    outs = [_run([exe] + args).stdout for exe in oracle_asan]
+    assert all("match == staged run: yes" in o for o in outs), outs
+
+
+def test_sanitize_driver_rejects_unknown_overrides(oracle_asan):
+    """A misspelt field must not silently run the default options."""
+    for arg in ("no_such_field=1", "so_tso=1.5", "so_p1=", "irv_th=0.4x"):
+        assert _run([oracle_asan[0], arg], ok=False).returncode == 4, arg
 
 
 def test_cli_and_facade_under_sanitizers(cli_asan, tmp_path):
