@@ -30,7 +30,19 @@ FILL_WTA, FILL_VOTING, FILL_INTERPOLATION, FILL_NONE = 0, 1, 2, 3
 PROV_LR_MASK, PROV_FILL_SHIFT = 3, 2
 PROV_SPECKLE = 0x10  # set by a Match with the speckle filter on, at the pixels the filter removed (ADC_PROV_SPECKLE)
 PIX_BGR8, PIX_RGB8, PIX_GRAY8, PIX_BGRA8 = 0, 1, 2, 3  # adc_raw_format.format (ADC_PIX_*)
-PIX_BYTES = {PIX_BGR8: 3, PIX_RGB8: 3, PIX_GRAY8: 1, PIX_BGRA8: 4}
+PIX_GRAY16 = 0x10  # camera layouts (include/adcensus_c_api.h); codes 4..15 stay invalid
+PIX_BAYER_RGGB8, PIX_BAYER_GRBG8, PIX_BAYER_GBRG8, PIX_BAYER_BGGR8 = 0x20, 0x21, 0x22, 0x23
+PIX_BAYER_RGGB16, PIX_BAYER_GRBG16, PIX_BAYER_GBRG16, PIX_BAYER_BGGR16 = 0x30, 0x31, 0x32, 0x33
+PIX_YUYV, PIX_UYVY, PIX_NV12 = 0x40, 0x41, 0x42
+# bytes per pixel of a row (NV12: of a luma row; its chroma plane follows, RawFormat.nbytes)
+PIX_BYTES = {PIX_BGR8: 3, PIX_RGB8: 3, PIX_GRAY8: 1, PIX_BGRA8: 4, PIX_GRAY16: 2, PIX_YUYV: 2, PIX_UYVY: 2, PIX_NV12: 1,
+             PIX_BAYER_RGGB8: 1, PIX_BAYER_GRBG8: 1, PIX_BAYER_GBRG8: 1, PIX_BAYER_BGGR8: 1,
+             PIX_BAYER_RGGB16: 2, PIX_BAYER_GRBG16: 2, PIX_BAYER_GBRG16: 2, PIX_BAYER_BGGR16: 2}
+
+
+def pix_bits(fmt, bits):
+    """ADC_PIX_BITS: the format word of a 16-bit layout with its significant bits (9..16; 0 = 16)."""
+    return int(fmt) | (int(bits) << 8)
 SIDE_LEFT, SIDE_RIGHT = 0, 1  # ADC_SIDE_*
 GT_U8, GT_U16, GT_F32 = 0, 1, 2  # adc_gt.format (ADC_GT_*)
 GT_DTYPES = {GT_U8: np.uint8, GT_U16: np.uint16, GT_F32: np.float32}
@@ -82,11 +94,12 @@ class RawFormat(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch_bytes", C.c_int32), ("format", C.c_int32)]
 
     def __init__(self, width=0, height=0, pitch_bytes=0, format=PIX_BGR8):
-        super().__init__(int(width), int(height), int(pitch_bytes) or int(width) * PIX_BYTES.get(int(format), 0), int(format))
+        super().__init__(int(width), int(height), int(pitch_bytes) or int(width) * PIX_BYTES.get(int(format) & 0xff, 0), int(format))
 
     @property
     def nbytes(self):
-        return self.height * self.pitch_bytes
+        luma = self.height * self.pitch_bytes
+        return luma // 2 * 3 if (self.format & 0xff) == PIX_NV12 else luma  # (NV12: the chroma plane behind the luma plane)
 
 
 class CameraModel(C.Structure):
@@ -234,6 +247,10 @@ def lib():
             getattr(L, prefix + "clear_rectify").argtypes = [vp]
             for name in ("set_rectify_maps", "set_rectify_model", "clear_rectify"):
                 getattr(L, prefix + name).restype = C.c_int
+        if hasattr(L, "adc_set_input_format"):
+            for name in ("adc_set_input_format", "adc_farm_set_input_format"):
+                getattr(L, name).argtypes = [vp, C.c_int, C.POINTER(RawFormat)]
+                getattr(L, name).restype = C.c_int
         L.adc_get_rectify_maps.argtypes = [vp, C.c_int, vp, vp, vp]
         L.adc_get_rectify_maps.restype = C.c_int
         L.adc_rectify_device.argtypes = [vp, C.c_int, vp, vp]
@@ -425,6 +442,12 @@ class PairFarm:
         """ADCensusStereo.set_rectify_model on every pipeline (adc_farm_set_rectify_model); drain() first."""
         if lib().adc_farm_set_rectify_model(self._f, int(side), C.byref(raw), C.byref(model)) != 0:
             raise RuntimeError("adc_farm_set_rectify_model failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def set_input_format(self, side, raw):
+        """ADCensusStereo.set_input_format on every pipeline (adc_farm_set_input_format); drain() first."""
+        if lib().adc_farm_set_input_format(self._f, int(side), C.byref(raw)) != 0:
+            raise RuntimeError("adc_farm_set_input_format failed: " + last_error())
         self._rect.set(side, raw)
 
     def clear_rectify(self):
@@ -648,6 +671,14 @@ class ADCensusStereo:
         """The same with the maps computed on the device from a CameraModel (adc_set_rectify_model)."""
         if lib().adc_set_rectify_model(self._h, int(side), C.byref(raw), C.byref(model)) != 0:
             raise RuntimeError("adc_set_rectify_model failed: " + last_error())
+        self._rect.set(side, raw)
+
+    def set_input_format(self, side, raw):
+        """Conversion only, for frames that are already rectified: declares the frames of one side as `raw` (a RawFormat of the object's
+        width and height in any PIX_* layout -- Bayer, YUYV / UYVY, NV12, 16-bit, or one of the 8-bit ones) without maps
+        (adc_set_input_format).  It sets the side like set_rectify_maps / set_rectify_model; any mix of the three works."""
+        if lib().adc_set_input_format(self._h, int(side), C.byref(raw)) != 0:
+            raise RuntimeError("adc_set_input_format failed: " + last_error())
         self._rect.set(side, raw)
 
     def clear_rectify(self):

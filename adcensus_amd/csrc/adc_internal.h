@@ -73,8 +73,9 @@ struct AdcOutReq {
 // the maps.  The [H][W] buffers are allocated by the first set call of a handle (both sides at once), the raw buffer grows with the
 // largest geometry declared; adc_destroy frees them.
 struct AdcRectSide {
-    int set;              // a set call has succeeded for this side (adc_clear_rectify / a failed set call: 0)
-    adc_raw_format fmt;
+    int set;              // a set call has succeeded for this side: 1 with maps, 2 conversion only (adc_set_input_format);
+                          // adc_clear_rectify / a failed set call: 0
+    adc_raw_format fmt;   // as declared: .format may carry the significant bits (ADC_PIX_BITS)
     uint32_t* rec;        // uint2 per destination pixel: {xi | yi << 16, ax | ay << 8 | flags << 16}
     float *mx, *my;       // the float maps (the caller's, or the model's): adc_get_rectify_maps
     uint8_t* valid;       // 1 where every tap with a nonzero weight lies inside the source
@@ -298,6 +299,11 @@ hipError_t adc_launch_speckle_apply(adc_handle* h, const float* src, float* dst,
 hipError_t adc_launch_rect_model_maps(adc_handle* h, int side, const adc_camera_model* m); // k_rectify.hip: model -> rect[side].mx / my
 hipError_t adc_launch_rect_pack(adc_handle* h, int side);                                   // mx / my -> records, valid map
 hipError_t adc_launch_rect_remap(adc_handle* h, int side, const uint8_t* raw, uint8_t* bgr_out); // raw image -> [H][W][3] BGR
+hipError_t adc_launch_rect_convert(adc_handle* h, int side, const uint8_t* raw, uint8_t* bgr_out); // the same without maps (set == 2)
+// the layout behind a format word: code without the bits, bytes per sample row element, 16-bit samples
+static inline int adc_pix_code(int format) { return format & 0xff; }
+static inline bool adc_pix_is16(int format) { const int c = format & 0xff; return c == ADC_PIX_GRAY16 || (c >= ADC_PIX_BAYER_RGGB16 && c <= ADC_PIX_BAYER_BGGR16); }
+static inline int adc_pix_shift(int format) { const int b = (format >> 8) & 0xff; return adc_pix_is16(format) ? (b ? b : 16) - 8 : 0; }
 size_t adc_eval_report_words(void);                             // k_eval.hip: uint64 words of ev_rep / ev_pin
 hipError_t adc_launch_eval_gt(adc_handle* h, int side, int format, int pitch, float scale); // ev_raw -> ev_g[side]
 hipError_t adc_launch_eval_occ(adc_handle* h, int mode, float occ_thres);                   // 1: ev_g[0], ev_g[1] -> ev_occ; 2: ev_g[0], mask in ev_raw -> ev_occ

@@ -567,13 +567,30 @@ static bool rectify_refused(const adc_handle* h, const char* who)
     g_last_error = std::string(who) + ": rectification is set for one side only (set the other side, or adc_clear_rectify)";
     return true;
 }
-static size_t raw_bytes(const adc_raw_format& f) { return (size_t)f.height * (size_t)f.pitch_bytes; }
+// bytes of one raw image: NV12 carries its chroma plane (height / 2 rows of the same pitch) behind the luma plane
+static size_t raw_bytes(const adc_raw_format& f)
+{
+    const size_t luma = (size_t)f.height * (size_t)f.pitch_bytes;
+    return adc_pix_code(f.format) == ADC_PIX_NV12 ? luma / 2 * 3 : luma;
+}
+// one side's raw image -> a W x H BGR buffer: through the maps, or (adc_set_input_format) the conversion alone
+static hipError_t launch_rect_side(adc_handle* h, int side, const uint8_t* raw, uint8_t* out)
+{
+    return h->rect[side].set == 2 ? adc_launch_rect_convert(h, side, raw, out) : adc_launch_rect_remap(h, side, raw, out);
+}
+// the 16-bit layouts are read as 16-bit words: an odd device address is refused at the call that receives it
+static bool raw_address_refused(const adc_handle* h, int side, const void* d_raw, const char* who)
+{
+    if (!adc_pix_is16(h->rect[side].fmt.format) || ((uintptr_t)d_raw & 1u) == 0) return false;
+    g_last_error = std::string(who) + ": the device address of a 16-bit raw image must be even";
+    return true;
+}
 // both raw images -> the handle's own W x H BGR buffers, on the object stream in front of run_pipeline.  Out of place: a redo of
 // adc_wait finds the rectified pair still there (nothing downstream writes the image buffers)
 static hipError_t enqueue_rectify(adc_handle* h, const void* raw_l, const void* raw_r)
 {
-    HIP_OK(adc_launch_rect_remap(h, ADC_SIDE_LEFT, static_cast<const uint8_t*>(raw_l), h->img_l_own));
-    HIP_OK(adc_launch_rect_remap(h, ADC_SIDE_RIGHT, static_cast<const uint8_t*>(raw_r), h->img_r_own));
+    HIP_OK(launch_rect_side(h, ADC_SIDE_LEFT, static_cast<const uint8_t*>(raw_l), h->img_l_own));
+    HIP_OK(launch_rect_side(h, ADC_SIDE_RIGHT, static_cast<const uint8_t*>(raw_r), h->img_r_own));
     h->bgrx_valid = 0;
     return hipSuccess;
 }
@@ -612,6 +629,7 @@ int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, voi
 {
     if (!h || !d_left || !d_right || !d_disp) return 1; // ADCensusStereo.cpp:71-76
     if (rectify_refused(h, "adc_match_device")) return 1;
+    if (rectify_state(h) > 0 && (raw_address_refused(h, 0, d_left, "adc_match_device") || raw_address_refused(h, 1, d_right, "adc_match_device"))) return 1;
     hipSetDevice(h->device);
     if (rectify_state(h) > 0) {
         // rectification on: the caller's RAW images are read by the remap only (borrowed until adc_wait all the same), the Match
@@ -1057,27 +1075,49 @@ int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed
 // ------------------------------------------------------------------------------ rectification (k_rectify.hip)
 // Handle state per side.  A set call brings the float maps to the device (the caller's, or the model's computed there), packs them
 // into the records of the hot kernel and the valid map, and waits: the entry points above find everything ready.
-static int rect_bpp(int format) { return format == ADC_PIX_GRAY8 ? 1 : (format == ADC_PIX_BGRA8 ? 4 : 3); }
+// bytes per pixel of a row (NV12: of a luma row); 0: not a layout (codes 4..15 and everything between the groups stay invalid)
+static int rect_bpp(int format)
+{
+    const int c = adc_pix_code(format);
+    if (c == ADC_PIX_BGR8 || c == ADC_PIX_RGB8) return 3;
+    if (c == ADC_PIX_BGRA8) return 4;
+    if (c == ADC_PIX_GRAY8 || c == ADC_PIX_NV12 || (c >= ADC_PIX_BAYER_RGGB8 && c <= ADC_PIX_BAYER_BGGR8)) return 1;
+    if (c == ADC_PIX_GRAY16 || c == ADC_PIX_YUYV || c == ADC_PIX_UYVY || (c >= ADC_PIX_BAYER_RGGB16 && c <= ADC_PIX_BAYER_BGGR16)) return 2;
+    return 0;
+}
+// the format word and the parity rules of its layout; nullptr: fine
+static const char* rect_format_why(const adc_raw_format* f)
+{
+    const int c = adc_pix_code(f->format), bits = (f->format >> 8) & 0xff;
+    if (f->format < 0 || f->format > 0xffff || rect_bpp(f->format) == 0) return "unknown pixel format";
+    if (bits != 0 && !(adc_pix_is16(f->format) && bits >= 9 && bits <= 16)) return "unknown pixel format (significant bits: 9..16, 16-bit layouts only)";
+    if (adc_pix_is16(f->format) && (f->pitch_bytes & 1)) return "pitch_bytes of a 16-bit layout must be even";
+    if (c >= ADC_PIX_BAYER_RGGB8 && c <= ADC_PIX_BAYER_BGGR16 && (f->width < 2 || f->height < 2)) return "a Bayer image needs width and height >= 2";
+    if ((c == ADC_PIX_YUYV || c == ADC_PIX_UYVY || c == ADC_PIX_NV12) && (f->width & 1)) return "the width of a YUV layout must be even";
+    if (c == ADC_PIX_NV12 && (f->height & 1)) return "the height of an NV12 image must be even";
+    return nullptr;
+}
 
 static int rect_args_ok(adc_handle* h, int side, const adc_raw_format* f, const void* a, const void* b, const char* who)
 {
     if (!h || !f || !a || !b) return 0;
     const char* why = nullptr;
     if (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) why = "side must be ADC_SIDE_LEFT or ADC_SIDE_RIGHT";
-    else if (f->format < ADC_PIX_BGR8 || f->format > ADC_PIX_BGRA8) why = "unknown pixel format";
+    else if (f->format < 0 || f->format > 0xffff || rect_bpp(f->format) == 0) why = "unknown pixel format";
     else if (f->width < 1 || f->width > 32767 || f->height < 1 || f->height > 32767) why = "raw width / height must be 1..32767";
     else if ((long long)f->pitch_bytes < (long long)f->width * rect_bpp(f->format)) why = "pitch_bytes is smaller than a row";
-    else if ((long long)f->height * (long long)f->pitch_bytes > 2147483647LL) why = "a raw image must be smaller than 2 GiB";
+    else if ((why = rect_format_why(f)) != nullptr) {}
+    else if ((long long)raw_bytes(*f) > 2147483647LL) why = "a raw image must be smaller than 2 GiB";
     else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
     if (why) g_last_error = std::string(who) + ": " + why;
     return why ? 0 : 1;
 }
 
 // first set call of a handle: the [H][W] buffers of both sides; every set call: raw buffer and raw staging large enough
-static hipError_t rect_buffers(adc_handle* h, int side, const adc_raw_format* f)
+static hipError_t rect_buffers(adc_handle* h, int side, const adc_raw_format* f, bool maps)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
-    for (int s = 0; s < 2; s++) {
+    for (int s = 0; maps && s < 2; s++) { // (conversion only: no records, no maps, no valid map)
         AdcRectSide& r = h->rect[s];
         if (!r.rec) HIP_OK(hipMalloc(&r.rec, P * 8));
         if (!r.mx) HIP_OK(hipMalloc(&r.mx, P * 4));
@@ -1105,7 +1145,7 @@ static hipError_t rect_buffers(adc_handle* h, int side, const adc_raw_format* f)
 static hipError_t rect_install(adc_handle* h, int side, const adc_raw_format* f, const float* map_x, const float* map_y, const adc_camera_model* model)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
-    const hipError_t eb = rect_buffers(h, side, f); // (every HIP call in there is hooked itself)
+    const hipError_t eb = rect_buffers(h, side, f, true); // (every HIP call in there is hooked itself)
     if (eb != hipSuccess) return eb;
     AdcRectSide& r = h->rect[side];
     r.fmt = *f;
@@ -1152,6 +1192,26 @@ int adc_set_rectify_model(adc_handle* h, int side, const adc_raw_format* raw, co
     return rect_set(h, side, raw, nullptr, nullptr, model, "adc_set_rectify_model");
 }
 
+int adc_set_input_format(adc_handle* h, int side, const adc_raw_format* raw)
+{
+    if (!rect_args_ok(h, side, raw, raw, raw, "adc_set_input_format")) return 1;
+    if (raw->width != h->p.W || raw->height != h->p.H) {
+        g_last_error = "adc_set_input_format: width / height must be the handle's (frames of another geometry need adc_set_rectify_*)";
+        return 1;
+    }
+    hipSetDevice(h->device);
+    h->rect[side].set = 0;
+    if (rect_buffers(h, side, raw, false) != hipSuccess) { // raw buffer and raw staging of the host entry points
+        const std::string keep = "adc_set_input_format: " + g_last_error;
+        abort_match(h);
+        g_last_error = keep;
+        return 2;
+    }
+    h->rect[side].fmt = *raw;
+    h->rect[side].set = 2;
+    return 0;
+}
+
 int adc_clear_rectify(adc_handle* h)
 {
     if (!h) return 1;
@@ -1166,6 +1226,7 @@ int adc_get_rectify_maps(adc_handle* h, int side, float* map_x, float* map_y, ui
     if (!h || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT)) return 1;
     const AdcRectSide& r = h->rect[side];
     if (!r.set) { g_last_error = "adc_get_rectify_maps: this side is not set"; return 1; }
+    if (r.set == 2) { g_last_error = "adc_get_rectify_maps: this side converts only (adc_set_input_format): there are no maps"; return 1; }
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
     hipError_t e = ADC_HIP(hipStreamSynchronize(h->stream));
@@ -1180,8 +1241,9 @@ int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_o
 {
     if (!h || !d_raw || !d_bgr_out || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT)) return 1;
     if (!h->rect[side].set) { g_last_error = "adc_rectify_device: this side is not set"; return 1; }
+    if (raw_address_refused(h, side, d_raw, "adc_rectify_device")) return 1;
     hipSetDevice(h->device);
-    const hipError_t e = ADC_HIP(adc_launch_rect_remap(h, side, static_cast<const uint8_t*>(d_raw), static_cast<uint8_t*>(d_bgr_out)));
+    const hipError_t e = ADC_HIP(launch_rect_side(h, side, static_cast<const uint8_t*>(d_raw), static_cast<uint8_t*>(d_bgr_out)));
     if (e != hipSuccess) { set_error("adc_rectify_device", e); abort_match(h); return 2; }
     return 0;
 }
@@ -1520,6 +1582,16 @@ int adc_farm_set_rectify_model(adc_farm* f, int side, const adc_raw_format* raw,
     }
     return 0;
 }
+int adc_farm_set_input_format(adc_farm* f, int side, const adc_raw_format* raw)
+{
+    if (!f || !raw || !farm_idle(f, "adc_farm_set_input_format")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++) {
+        const int rc = adc_set_input_format(f->pipes[i], side, raw);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 int adc_farm_clear_rectify(adc_farm* f)
 {
     if (!f || !farm_idle(f, "adc_farm_clear_rectify")) return 1;

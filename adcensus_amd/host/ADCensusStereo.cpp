@@ -13,6 +13,7 @@
 struct ADCensusStereo::RectifySide {
     adc_raw_format raw;
     bool is_model;
+    bool convert_only; // SetInputFormat: no maps at all
     adc_camera_model model;
     std::vector<float> map_x, map_y;
     sint32 map_w, map_h;
@@ -134,16 +135,33 @@ bool ADCensusStereo::SetSpeckleFilter(int max_size, float max_diff)
     return true;
 }
 
+// the argument rules of the set calls (include/adcensus_c_api.h), checked here as well: before Initialize there is no library state to ask
+static long long raw_image_bytes(const adc_raw_format* f)
+{
+    const long long luma = (long long)f->height * f->pitch_bytes;
+    return (f->format & 0xff) == ADC_PIX_NV12 ? luma / 2 * 3 : luma;
+}
 static bool raw_format_ok(const adc_raw_format* f)
 {
-    if (!f || f->format < ADC_PIX_BGR8 || f->format > ADC_PIX_BGRA8) return false;
-    const int bpp = f->format == ADC_PIX_GRAY8 ? 1 : (f->format == ADC_PIX_BGRA8 ? 4 : 3);
-    return f->width >= 1 && f->width <= 32767 && f->height >= 1 && f->height <= 32767 && (long long)f->pitch_bytes >= (long long)f->width * bpp &&
-           (long long)f->height * f->pitch_bytes <= 2147483647LL;
+    if (!f || f->format < 0 || f->format > 0xffff) return false;
+    const int c = f->format & 0xff, bits = (f->format >> 8) & 0xff;
+    const bool bayer8 = c >= ADC_PIX_BAYER_RGGB8 && c <= ADC_PIX_BAYER_BGGR8, bayer16 = c >= ADC_PIX_BAYER_RGGB16 && c <= ADC_PIX_BAYER_BGGR16;
+    const bool wide = c == ADC_PIX_GRAY16 || bayer16, yuv = c == ADC_PIX_YUYV || c == ADC_PIX_UYVY || c == ADC_PIX_NV12;
+    int bpp = 0;
+    if (c == ADC_PIX_BGR8 || c == ADC_PIX_RGB8) bpp = 3;
+    else if (c == ADC_PIX_BGRA8) bpp = 4;
+    else if (c == ADC_PIX_GRAY8 || c == ADC_PIX_NV12 || bayer8) bpp = 1;
+    else if (wide || c == ADC_PIX_YUYV || c == ADC_PIX_UYVY) bpp = 2;
+    if (bpp == 0 || (bits != 0 && !(wide && bits >= 9 && bits <= 16))) return false;
+    if (!(f->width >= 1 && f->width <= 32767 && f->height >= 1 && f->height <= 32767 && (long long)f->pitch_bytes >= (long long)f->width * bpp)) return false;
+    if ((wide && (f->pitch_bytes & 1)) || ((bayer8 || bayer16) && (f->width < 2 || f->height < 2))) return false;
+    if ((yuv && (f->width & 1)) || (c == ADC_PIX_NV12 && (f->height & 1))) return false;
+    return raw_image_bytes(f) <= 2147483647LL;
 }
 bool ADCensusStereo::ApplyRectify(int side)
 {
     const RectifySide& r = *rect_[side];
+    if (r.convert_only) return adc_set_input_format(impl_, side, &r.raw) == 0; // (refuses a geometry other than width_ x height_)
     if (r.is_model) return adc_set_rectify_model(impl_, side, &r.raw, &r.model) == 0;
     if (r.map_w != width_ || r.map_h != height_) return false; // (the maps have the rectified size)
     return adc_set_rectify_maps(impl_, side, &r.raw, r.map_x.data(), r.map_y.data()) == 0;
@@ -155,7 +173,7 @@ bool ADCensusStereo::SetRectifyMaps(int side, const adc_raw_format* raw, const f
     RectifySide* r = new (std::nothrow) RectifySide();
     if (!r) return false;
     const size_t n = (size_t)map_width * (size_t)map_height;
-    r->raw = *raw; r->is_model = false; r->map_w = map_width; r->map_h = map_height;
+    r->raw = *raw; r->is_model = false; r->convert_only = false; r->map_w = map_width; r->map_h = map_height;
     r->map_x.assign(map_x, map_x + n);
     r->map_y.assign(map_y, map_y + n);
     RectifySide* old = rect_[side];
@@ -173,7 +191,20 @@ bool ADCensusStereo::SetRectifyModel(int side, const adc_raw_format* raw, const 
     if (model->fx == 0.0f || model->fy == 0.0f || model->new_fx == 0.0f || model->new_fy == 0.0f) return false;
     RectifySide* r = new (std::nothrow) RectifySide();
     if (!r) return false;
-    r->raw = *raw; r->is_model = true; r->model = *model; r->map_w = r->map_h = 0;
+    r->raw = *raw; r->is_model = true; r->convert_only = false; r->model = *model; r->map_w = r->map_h = 0;
+    RectifySide* old = rect_[side];
+    rect_[side] = r;
+    if (impl_ && !ApplyRectify(side)) { rect_[side] = old; delete r; return false; }
+    delete old;
+    return true;
+}
+bool ADCensusStereo::SetInputFormat(int side, const adc_raw_format* raw)
+{
+    if ((side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) || !raw_format_ok(raw)) return false;
+    if (impl_ && (raw->width != width_ || raw->height != height_)) return false;
+    RectifySide* r = new (std::nothrow) RectifySide();
+    if (!r) return false;
+    r->raw = *raw; r->is_model = false; r->convert_only = true; r->map_w = r->map_h = 0;
     RectifySide* old = rect_[side];
     rect_[side] = r;
     if (impl_ && !ApplyRectify(side)) { rect_[side] = old; delete r; return false; }
@@ -191,7 +222,7 @@ bool ADCensusStereo::ClearRectify()
 bool ADCensusStereo::Rectify(int side, const uint8* raw, uint8* bgr_out)
 {
     if (!impl_ || !raw || !bgr_out || (side != ADC_SIDE_LEFT && side != ADC_SIDE_RIGHT) || !rect_[side]) return false;
-    const size_t n_raw = (size_t)rect_[side]->raw.height * (size_t)rect_[side]->raw.pitch_bytes, n_out = (size_t)width_ * (size_t)height_ * 3;
+    const size_t n_raw = (size_t)raw_image_bytes(&rect_[side]->raw), n_out = (size_t)width_ * (size_t)height_ * 3;
     void* d_raw = adc_device_malloc(n_raw);
     void* d_out = adc_device_malloc(n_out);
     const bool ok = d_raw && d_out && adc_memcpy_h2d(d_raw, raw, n_raw) == 0 && adc_rectify_device(impl_, side, d_raw, d_out) == 0 && adc_wait(impl_) == 0 &&

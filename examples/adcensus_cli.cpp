@@ -24,6 +24,13 @@
 // rect_width rect_height (the rectified size, default: the raw size; both files must agree).  A malformed flag or file is refused
 // while the arguments are parsed.  Every file of the run then comes from the rectified pair, and the run also writes
 //   <out>-rect-left.png  <out>-rect-right.png   the rectified images
+// --raw FMT,W,H[,PITCH[,BITS]] (anywhere after the program name) declares the two image arguments headerless binary camera frames of
+// that layout instead of image files: FMT one of BGR8 RGB8 GRAY8 BGRA8 GRAY16 BAYER_RGGB8 BAYER_GRBG8 BAYER_GBRG8 BAYER_BGGR8
+// BAYER_RGGB16 BAYER_GRBG16 BAYER_GBRG16 BAYER_BGGR16 YUYV UYVY NV12, W x H the frame size, PITCH the bytes of a row (default:
+// tightly packed), BITS the significant bits of a 16-bit layout (9..16, default 16).  Each file must hold exactly one frame.  Without
+// --rectify the frames are already rectified and are only converted on the device (ADCensusStereo::SetInputFormat); with --rectify
+// FMT,W,H,PITCH are the raw geometry of both cameras (the camera files' width and height must agree, their pitch and format are
+// superseded).  A malformed flag is refused while the arguments are parsed.  The run also writes <out>-rect-left.png / -right.png.
 // --gt LEFT[,RIGHT],SCALE [--bad T0[,T1..]] (anywhere after the program name) scores the map against ground truth on the device
 // (ADCensusStereo::SetGroundTruth / Evaluate): LEFT / RIGHT are the left- / right-view disparities as 8-bit gray PNG (0 = unknown) or
 // PFM, disparity = value / SCALE (Middlebury: 4 for Cone, 2 for Cloth3 / Wood2, 1 for PFM); with RIGHT the non-occluded mask comes
@@ -111,6 +118,61 @@ static bool parse_rectify_file(const std::string& path, RectifyFile& out, std::s
     for (size_t i = 0; i < sizeof(adc_camera_model) / sizeof(float); i++) if (!std::isfinite(v[i])) { why = path + ": every value must be finite"; return false; }
     if (out.model.fx == 0.f || out.model.fy == 0.f || out.model.new_fx == 0.f || out.model.new_fy == 0.f) { why = path + ": fx, fy, new_fx, new_fy must not be 0"; return false; }
     return true;
+}
+
+static long long raw_frame_bytes(const adc_raw_format& f)
+{
+    const long long luma = (long long)f.height * f.pitch_bytes;
+    return (f.format & 0xff) == ADC_PIX_NV12 ? luma / 2 * 3 : luma;
+}
+
+// the value of --raw; false (with the reason in `why`) unless it names a layout and a geometry the library accepts
+static bool parse_raw_flag(const std::string& v, adc_raw_format& out, std::string& why)
+{
+    static const struct { const char* name; int code, bpp; } layouts[] = {
+        {"BGR8", ADC_PIX_BGR8, 3}, {"RGB8", ADC_PIX_RGB8, 3}, {"GRAY8", ADC_PIX_GRAY8, 1}, {"BGRA8", ADC_PIX_BGRA8, 4}, {"GRAY16", ADC_PIX_GRAY16, 2},
+        {"BAYER_RGGB8", ADC_PIX_BAYER_RGGB8, 1}, {"BAYER_GRBG8", ADC_PIX_BAYER_GRBG8, 1}, {"BAYER_GBRG8", ADC_PIX_BAYER_GBRG8, 1}, {"BAYER_BGGR8", ADC_PIX_BAYER_BGGR8, 1},
+        {"BAYER_RGGB16", ADC_PIX_BAYER_RGGB16, 2}, {"BAYER_GRBG16", ADC_PIX_BAYER_GRBG16, 2}, {"BAYER_GBRG16", ADC_PIX_BAYER_GBRG16, 2}, {"BAYER_BGGR16", ADC_PIX_BAYER_BGGR16, 2},
+        {"YUYV", ADC_PIX_YUYV, 2}, {"UYVY", ADC_PIX_UYVY, 2}, {"NV12", ADC_PIX_NV12, 1}};
+    std::vector<std::string> parts;
+    size_t at = 0, comma;
+    while ((comma = v.find(',', at)) != std::string::npos) { parts.push_back(v.substr(at, comma - at)); at = comma + 1; }
+    parts.push_back(v.substr(at));
+    why = "it needs FMT,W,H[,PITCH[,BITS]]";
+    if (parts.size() < 3 || parts.size() > 5) return false;
+    int code = -1, bpp = 0;
+    for (const auto& l : layouts) if (parts[0] == l.name) { code = l.code; bpp = l.bpp; }
+    if (code < 0) { why = "unknown layout " + parts[0]; return false; }
+    int n[4] = {0, 0, 0, 0}; // W, H, PITCH, BITS
+    for (size_t i = 1; i < parts.size(); i++) {
+        char tail = 0;
+        if (sscanf(parts[i].c_str(), "%d%c", &n[i - 1], &tail) != 1 || n[i - 1] < 0) { why = "not a number: " + parts[i]; return false; }
+    }
+    const bool wide = bpp == 2 && code != ADC_PIX_YUYV && code != ADC_PIX_UYVY, yuv = code == ADC_PIX_YUYV || code == ADC_PIX_UYVY || code == ADC_PIX_NV12;
+    const bool bayer = code >= ADC_PIX_BAYER_RGGB8 && code <= ADC_PIX_BAYER_BGGR16;
+    if (n[0] < 1 || n[0] > 32767 || n[1] < 1 || n[1] > 32767) { why = "W and H must be 1..32767"; return false; }
+    if (parts.size() < 4 || n[2] == 0) n[2] = n[0] * bpp;
+    if (n[2] < n[0] * bpp) { why = "PITCH is smaller than a row"; return false; }
+    if (n[3] != 0 && !(wide && n[3] >= 9 && n[3] <= 16)) { why = "BITS must be 9..16 and belongs to a 16-bit layout"; return false; }
+    if (wide && (n[2] & 1)) { why = "PITCH of a 16-bit layout must be even"; return false; }
+    if (bayer && (n[0] < 2 || n[1] < 2)) { why = "a Bayer frame needs W and H >= 2"; return false; }
+    if ((yuv && (n[0] & 1)) || (code == ADC_PIX_NV12 && (n[1] & 1))) { why = "W (NV12: and H) of a YUV layout must be even"; return false; }
+    out.width = n[0]; out.height = n[1]; out.pitch_bytes = n[2]; out.format = ADC_PIX_BITS(code, n[3]);
+    if (raw_frame_bytes(out) > 2147483647LL) { why = "a frame must be smaller than 2 GiB"; return false; }
+    return true;
+}
+
+// one headerless frame: the file must hold exactly the declared bytes
+static bool load_raw_frame(const char* path, const adc_raw_format& f, std::vector<uint8>& out)
+{
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return false;
+    const size_t n = (size_t)raw_frame_bytes(f);
+    out.assign(n, 0);
+    uint8 extra = 0;
+    const bool ok = fread(out.data(), 1, n, fp) == n && fread(&extra, 1, 1, fp) == 0;
+    fclose(fp);
+    return ok;
 }
 
 // tightly packed B,G,R pixels -> the declared raw layout (GRAY8 takes B; alpha and row padding are 0)
@@ -245,6 +307,23 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_raw = false; // (--raw and its value likewise)
+    adc_raw_format raw_fmt = {0, 0, 0, 0};
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--raw")) {
+            std::string why = "it needs FMT,W,H[,PITCH[,BITS]]";
+            bool ok = i + 1 < argc && parse_raw_flag(argv[i + 1], raw_fmt, why);
+            if (ok && with_rectify && (rect_file[0].raw.width != raw_fmt.width || rect_file[0].raw.height != raw_fmt.height ||
+                                       rect_file[1].raw.width != raw_fmt.width || rect_file[1].raw.height != raw_fmt.height)) {
+                ok = false; why = "W x H is not the raw size of the camera files of --rectify";
+            }
+            if (!ok) { printf("--raw refused: %s\n", why.c_str()); return -1; }
+            with_raw = true;
+            if (with_rectify) rect_file[0].raw = rect_file[1].raw = raw_fmt;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     bool with_gt = false; // (--gt / --bad and their values likewise; the syntax is checked here, the files are read behind the images)
     std::string gt_path[2];
     float gt_scale = 0.f;
@@ -314,7 +393,14 @@ int main(int argc, char** argv)
     printf("Image Loading...");
     std::vector<uint8> left, right;
     int w = 0, h = 0, w2 = 0, h2 = 0;
-    if (!load_image(argv[1], left, w, h) || !load_image(argv[2], right, w2, h2)) {
+    if (with_raw) {
+        if (!load_raw_frame(argv[1], raw_fmt, left) || !load_raw_frame(argv[2], raw_fmt, right)) {
+            printf("cannot read the frame pair (--raw: each file holds exactly one frame of %lld bytes)\n", raw_frame_bytes(raw_fmt));
+            return -1;
+        }
+        w = w2 = raw_fmt.width;
+        h = h2 = raw_fmt.height;
+    } else if (!load_image(argv[1], left, w, h) || !load_image(argv[2], right, w2, h2)) {
         printf("cannot read the image pair (8-bit PNG or binary PPM)\n"); // main.cpp:50-53
         return -1;
     }
@@ -327,8 +413,10 @@ int main(int argc, char** argv)
             printf("--rectify: an image does not have the size its camera file declares\n");
             return -1;
         }
-        left = pack_raw(left, rect_file[0].raw);
-        right = pack_raw(right, rect_file[1].raw);
+        if (!with_raw) { // (--raw: the files are the frames already)
+            left = pack_raw(left, rect_file[0].raw);
+            right = pack_raw(right, rect_file[1].raw);
+        }
         w = rect_file[0].rect_w;
         h = rect_file[0].rect_h;
     }
@@ -360,10 +448,12 @@ int main(int argc, char** argv)
     printf("AD-Census Initializing Done! Timing :	%lf s\n\n", std::chrono::duration<double>(t1 - t0).count());
     if (speckle_size > 0 && !ad_census.SetSpeckleFilter(speckle_size, speckle_diff)) { printf("speckle filter refused: %s\n", ad_census.LastError()); return -2; }
     std::vector<uint8> rect_left; // (the rectified left image: the colours of the cloud file)
-    if (with_rectify) {
+    if (with_rectify || with_raw) {
         std::vector<uint8> rect_right((size_t)w * h * 3, 0), rgb((size_t)w * h * 3);
         rect_left.assign((size_t)w * h * 3, 0);
-        if (!ad_census.SetRectifyModel(ADC_SIDE_LEFT, &rect_file[0].raw, &rect_file[0].model) || !ad_census.SetRectifyModel(ADC_SIDE_RIGHT, &rect_file[1].raw, &rect_file[1].model) ||
+        const bool set = with_rectify ? ad_census.SetRectifyModel(ADC_SIDE_LEFT, &rect_file[0].raw, &rect_file[0].model) && ad_census.SetRectifyModel(ADC_SIDE_RIGHT, &rect_file[1].raw, &rect_file[1].model)
+                                      : ad_census.SetInputFormat(ADC_SIDE_LEFT, &raw_fmt) && ad_census.SetInputFormat(ADC_SIDE_RIGHT, &raw_fmt);
+        if (!set ||
             !ad_census.Rectify(ADC_SIDE_LEFT, left.data(), rect_left.data()) || !ad_census.Rectify(ADC_SIDE_RIGHT, right.data(), rect_right.data())) {
             printf("rectification refused: %s\n", ad_census.LastError());
             return -2;
@@ -406,7 +496,7 @@ int main(int argc, char** argv)
             for (int j = 0; j < w; j++) {
                 const float32 a = fabsf(disparity[(size_t)i * w + j]);
                 if (a == Invalid_Float) continue;
-                const uint8* p = with_rectify ? &rect_left[((size_t)i * w + j) * 3] : &left[((size_t)i * w + j) * 3];
+                const uint8* p = (with_rectify || with_raw) ? &rect_left[((size_t)i * w + j) * 3] : &left[((size_t)i * w + j) * 3];
                 fprintf(f, "%f %f %f %d %d %d\n", float32(j), float32(i), a, p[2], p[1], p[0]);
             }
         fclose(f);

@@ -81,6 +81,11 @@ public:
      *  (Initialize then returns false when the library refuses them). */
     bool SetRectifyMaps(int side, const adc_raw_format* raw, const float32* map_x, const float32* map_y, sint32 map_width, sint32 map_height);
     bool SetRectifyModel(int side, const adc_raw_format* raw, const adc_camera_model* model);
+    /** Conversion only, for cameras whose frames are already rectified (adc_set_input_format): declares the frames of one side as `raw`
+     *  -- any ADC_PIX_* layout: Bayer, YUYV / UYVY, NV12, 16-bit, or an 8-bit one; raw->width / height must be the size given to
+     *  Initialize -- without maps.  It sets the side like the two calls above (any mix works).  May be called before Initialize: checked
+     *  as far as possible, kept, applied there. */
+    bool SetInputFormat(int side, const adc_raw_format* raw);
     /** Both sides unset: Match takes rectified W x H BGR images again. */
     bool ClearRectify();
     /** The remap alone, host to host: raw image of the side's geometry -> uint8 [H][W][3] BGR.  Needs Initialize and the side set. */

@@ -289,7 +289,7 @@ int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff);
  * intrinsics from a stereo calibration is the caller's business.
  *
  * Set calls return 0; 1 for a NULL argument, a bad side or format, width / height outside [1, 32767], pitch_bytes < width * bytes per
- * pixel, height * pitch_bytes > 2^31 - 1, a model with a non-finite value or fx, fy, new_fx, new_fy == 0, or a Match pending
+ * pixel, an image larger than 2^31 - 1 bytes, a parity rule of the layout (below) broken, a model with a non-finite value or fx, fy, new_fx, new_fy == 0, or a Match pending
  * (adc_wait first); 2 for a HIP failure (that side is then unset, the handle stays usable).  Synchronous.  The first set call
  * allocates the feature's buffers (adc_create allocates none of them); adc_destroy frees them.
  * ------------------------------------------------------------------------------------------- */
@@ -297,6 +297,37 @@ int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff);
 #define ADC_PIX_RGB8 1   /* 3 bytes per pixel: R, G, B */
 #define ADC_PIX_GRAY8 2  /* 1 byte per pixel: B = G = R */
 #define ADC_PIX_BGRA8 3  /* 4 bytes per pixel: B, G, R, alpha (ignored) */
+/* Camera layouts (codes 4..15 stay invalid).  Each is DECODED to the virtual 8-bit B, G, R source image V the remap takes its taps
+ * from; the tap weights, the rounding, the constant border and the valid map are those above.  All integer, >> arithmetic:
+ *   16-bit samples  little-endian; s = min(255, v >> (bits - 8)), bits = the significant bits given with ADC_PIX_BITS (9..16, 0 = 16);
+ *                   everything below works on s.  pitch_bytes must be even, a device address of such an image must be even
+ *   GRAY16          B = G = R = s
+ *   BAYER_*         the four letters are the colours of pixels (0,0), (0,1), (1,0), (1,1); width, height >= 2.  Bilinear: S(y, x) is
+ *                   the sample at coordinates reflected into the image without repeating the edge (-1 -> 1, n -> n - 2).  Red / blue
+ *                   site: own colour S(y,x), green (S(y-1,x) + S(y+1,x) + S(y,x-1) + S(y,x+1) + 2) >> 2, the other colour the same of
+ *                   the four diagonal neighbours.  Green site: green S(y,x), the colour of the left / right neighbours
+ *                   (S(y,x-1) + S(y,x+1) + 1) >> 1, of the upper / lower neighbours (S(y-1,x) + S(y+1,x) + 1) >> 1.  The reflection
+ *                   belongs to the decode of a tap INSIDE the source; a tap outside still contributes 0
+ *   YUYV, UYVY      row bytes Y0 U Y1 V / U Y0 V Y1 per pixel pair, width even.  BT.601 limited range, the pair's own chroma:
+ *                   c = Y - 16, d = U - 128, e = V - 128; R = clip8((298c + 409e + 128) >> 8),
+ *                   G = clip8((298c - 100d - 208e + 128) >> 8), B = clip8((298c + 516d + 128) >> 8)
+ *   NV12            luma plane [height][pitch_bytes], at byte offset height * pitch_bytes the chroma plane [height / 2][pitch_bytes]
+ *                   of U, V pairs: pixel (y, x) reads U = C[y >> 1][2 * (x >> 1)] and V behind it; width and height even; the image
+ *                   is height * pitch_bytes * 3 / 2 bytes (that product is what must stay <= 2^31 - 1).  Same matrix as YUYV */
+#define ADC_PIX_GRAY16 0x10       /* 2 bytes per pixel */
+#define ADC_PIX_BAYER_RGGB8 0x20  /* 1 byte per pixel */
+#define ADC_PIX_BAYER_GRBG8 0x21
+#define ADC_PIX_BAYER_GBRG8 0x22
+#define ADC_PIX_BAYER_BGGR8 0x23
+#define ADC_PIX_BAYER_RGGB16 0x30 /* 2 bytes per pixel */
+#define ADC_PIX_BAYER_GRBG16 0x31
+#define ADC_PIX_BAYER_GBRG16 0x32
+#define ADC_PIX_BAYER_BGGR16 0x33
+#define ADC_PIX_YUYV 0x40         /* 2 bytes per pixel */
+#define ADC_PIX_UYVY 0x41         /* 2 bytes per pixel */
+#define ADC_PIX_NV12 0x42         /* 1 byte per pixel of luma (pitch_bytes >= width), plus the chroma plane */
+/* the format word of a 16-bit layout with its significant bits (9..16; 0 = 16); any nonzero value on an 8-bit layout is refused */
+#define ADC_PIX_BITS(fmt, bits) ((fmt) | ((bits) << 8))
 #define ADC_SIDE_LEFT 0
 #define ADC_SIDE_RIGHT 1
 typedef struct adc_raw_format { int32_t width, height, pitch_bytes, format; } adc_raw_format;
@@ -321,6 +352,14 @@ int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_o
 int adc_farm_set_rectify_maps(adc_farm* f, int side, const adc_raw_format* raw, const float* map_x, const float* map_y);
 int adc_farm_set_rectify_model(adc_farm* f, int side, const adc_raw_format* raw, const adc_camera_model* model);
 int adc_farm_clear_rectify(adc_farm* f);
+/* Conversion only, for cameras whose frames are already rectified: declares the frames of one side as `raw` (any ADC_PIX_* layout;
+ * raw->width / height must be the handle's W / H) without maps.  It sets the side like the two calls above (any mix of the three
+ * works, each side has its own layout); for such a side the handle's image is the decoded V itself -- bit for bit what the remap
+ * delivers under the identity map -- computed by a kernel that reads no map records and writes no valid map.  adc_rectify_device on
+ * such a side runs the conversion alone, adc_get_rectify_maps returns 1 (there are no maps), adc_clear_rectify unsets it.  Returns as
+ * the set calls above; 1 also for a geometry other than the handle's. */
+int adc_set_input_format(adc_handle* h, int side, const adc_raw_format* raw);
+int adc_farm_set_input_format(adc_farm* f, int side, const adc_raw_format* raw);
 
 /* -------------------------------------------------------------------------------------------
  * Optional evaluation of a disparity map against ground truth on the device (k_eval.hip): Middlebury's evaldisp figures -- bad-pixel

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Is the device code of the working tree the same as at another commit?  Compiles the nine translation units of
-adcensus_amd/csrc to gfx950 assembly with the product flags at both revisions (a temporary git worktree for the other one) and
+"""Is the device code of the working tree the same as at another commit?  Compiles the translation units of
+adcensus_amd/csrc listed below (or those named behind the commit) to gfx950 assembly with the product flags at both revisions (a temporary git worktree for the other one) and
 compares them, ignoring comments, debug locations and the per-build `__hip_cuid_*` symbol.
-    python tools/device_code_diff.py <commit>
+    python tools/device_code_diff.py <commit> [unit ...]      e.g. ... HEAD k_rectify
 (Used at the end of round 3: everything after the last GPU-validated commit, 13c55c7, changed tests, tools, documents and added
 unused inline functions to adc_device_fn.h -- the generated code of all nine units is identical.)"""
 import os
@@ -12,7 +12,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = ["capi", "k_cost", "k_arms", "k_aggregate", "k_scanline", "k_wta", "k_refine", "k_voting", "k_paper"]
+SRCS = ["capi", "k_cost", "k_arms", "k_aggregate", "k_scanline", "k_wta", "k_refine", "k_voting", "k_paper", "k_rectify"]
 
 
 def isa(root, stem, out):
@@ -40,7 +40,7 @@ def main():
     subprocess.run(["git", "-C", ROOT, "worktree", "add", "-q", other, commit], check=True)
     same = True
     try:
-        for s in SRCS:
+        for s in (sys.argv[2:] or SRCS):
             a, b = isa(other, s, os.path.join(tmp, "a_%s.s" % s)), isa(ROOT, s, os.path.join(tmp, "b_%s.s" % s))
             if a == b:
                 print("%-12s identical" % s)

@@ -3,6 +3,7 @@
 
     python tools/rectify_timing.py [--alternations 5] [--reps 10] [--sizes 1920x1080,1242x375] [--workloads structured,noise]
                                    [--disp 128] [--out FILE]
+    python tools/rectify_timing.py --rawfmt [--alternations 3] [--batch 20] [--out profiles/rawfmt_timing.md]
 
 Per size:
   * k_rect_remap alone, per source format, on the example lens model (tests/rectify_ref.py: example_model, source = destination size
@@ -12,6 +13,13 @@ Per size:
   * per workload, device-resident inputs and outputs, each Match timed on the host from enqueue to adc_wait on ONE handle:
     `--alternations` rounds of `--reps` plain adc_match_device on the rectified pair, then `--reps` with rectification on and the
     raw pair; the figure is the median over rounds of (on - off).  The same for the host entry point adc_match (pageable arrays).
+`--rawfmt` (a run of its own): every source layout at 1920 x 1080 -> 1920 x 1080 -- the remap under the example lens model and the
+conversion-only kernel (adc_set_input_format), each timed from HIP events on the handle's stream around `--batch` launches, in
+`--alternations` (at least three) interleaved repetitions of the whole list in one process, next to the BGR8 remap (whose generated code
+is the parent revision's) and the best adc_device_copy_kernel_ms; then adc_match host to host in pairs/s on the structured pair handed
+over as BGR8 (plain), as BAYER_RGGB8 and as NV12 through adc_set_input_format, interleaved the same way.  Writes a markdown table with
+the priced bytes per destination pixel (remap: 8 record + 1 valid + 3 out + the source footprint; conversion: source + 3) and the clock
+state as far as it can be read to `--out` (default profiles/rawfmt_timing.md).
 One JSON line at the end.  Under `rocprofv3 --kernel-trace --stats -- python tools/rectify_timing.py --trace-only on|off` one process
 runs a few Matches with rectification on (the table lists k_rect_*) or on a handle that never had a side set (the parent's kernels).
 The clock state is not read."""
@@ -160,6 +168,150 @@ def trace_only(w, h, d, form):
         L.adc_device_free(b)
 
 
+# layout name -> (format word, source bytes per pixel)
+RAW_LAYOUTS = [("BGR8", 0, 3.0), ("RGB8", 1, 3.0), ("GRAY8", 2, 1.0), ("BGRA8", 3, 4.0), ("GRAY16/12", 0x10 | (12 << 8), 2.0),
+               ("BAYER_RGGB8", 0x20, 1.0), ("BAYER_GRBG8", 0x21, 1.0), ("BAYER_GBRG8", 0x22, 1.0), ("BAYER_BGGR8", 0x23, 1.0),
+               ("BAYER_RGGB16/12", 0x30 | (12 << 8), 2.0), ("BAYER_GRBG16/10", 0x31 | (10 << 8), 2.0), ("BAYER_GBRG16/12", 0x32 | (12 << 8), 2.0),
+               ("BAYER_BGGR16/10", 0x33 | (10 << 8), 2.0), ("YUYV", 0x40, 2.0), ("UYVY", 0x41, 2.0), ("NV12", 0x42, 1.5)]
+
+
+class _Events:
+    """HIP events on a handle's stream (adc_get_stream), through the runtime library the product library is linked with"""
+
+    def __init__(self, stream):
+        import ctypes as C
+        self.C, self.hip, self.stream = C, C.CDLL("libamdhip64.so"), C.c_void_p(stream)
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        assert self.hip.hipEventCreate(C.byref(self.a)) == 0 and self.hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def ms(self, fn):
+        assert self.hip.hipEventRecord(self.a, self.stream) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.b, self.stream) == 0 and self.hip.hipEventSynchronize(self.b) == 0
+        t = self.C.c_float(0)
+        assert self.hip.hipEventElapsedTime(self.C.byref(t), self.a, self.b) == 0
+        return float(t.value)
+
+
+def _clock_state():
+    import subprocess
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks", "--showperflevel"], capture_output=True, text=True, timeout=60)
+        keep = [l.strip() for l in r.stdout.splitlines() if "GPU[0]" in l and ("sclk" in l or "mclk" in l or "fclk" in l or "Performance" in l)]
+        return keep or ["not readable (rocm-smi printed nothing for GPU[0])"]
+    except Exception as exc:  # noqa: BLE001
+        return ["not readable (%s)" % exc]
+
+
+def rawfmt(alternations, batch, out_path):
+    import ctypes as C
+    import adcensus_amd as A
+    from adcensus_amd import workloads
+    from tests import rawfmt_ref as RF
+    from tests import rectify_ref as RR
+    L = A.lib()
+    L.adc_get_stream.restype = C.c_void_p
+    L.adc_get_stream.argtypes = [C.c_void_p]
+    w, h, d = 1920, 1080, 128
+    P = w * h
+    alternations = max(3, alternations)
+    clocks = [_clock_state()]
+    st = A.ADCensusStereo(device=0)
+    assert st.Initialize(w, h, A.ADCensusOption(max_disparity=d)), A.last_error()
+    ev = _Events(L.adc_get_stream(st._h))
+    left, right = workloads.structured_pair(w, h, d, seed=777)
+    model = A.CameraModel(**RR.example_model(w, h, w, h))
+    po = L.adc_device_malloc(3 * P)
+    frames = {}
+    for name, word, _ in RAW_LAYOUTS:
+        raw = RF.pack(left, word)
+        p = L.adc_device_malloc(raw.nbytes)
+        assert p and L.adc_memcpy_h2d(p, raw.ctypes.data, raw.nbytes) == 0
+        frames[name] = (p, A.RawFormat(w, h, 0, word))
+    cb = 16 << 20
+    ca, cbuf = L.adc_device_malloc(cb), L.adc_device_malloc(cb)
+    times = {name: {"remap": [], "convert": []} for name, _, _ in RAW_LAYOUTS}
+    copies = []
+
+    def launches(p):
+        for _ in range(batch):
+            assert st.rectify_device(A.SIDE_LEFT, p, po), A.last_error()
+
+    for _ in range(alternations):
+        for name, _, _ in RAW_LAYOUTS:
+            p, rf = frames[name]
+            for kind in ("remap", "convert"):
+                if kind == "remap":
+                    st.set_rectify_model(A.SIDE_LEFT, rf, model)
+                else:
+                    st.set_input_format(A.SIDE_LEFT, rf)
+                launches(p)
+                assert st.wait()
+                times[name][kind].append(ev.ms(lambda: launches(p)) / batch)
+                assert st.wait()
+        copies.append(float(L.adc_device_copy_kernel_ms(ca, cbuf, cb, 20)))
+    valid = None
+    st.set_rectify_model(A.SIDE_LEFT, frames["BGR8"][1], model)
+    valid = float(st.rectify_maps(A.SIDE_LEFT)[2].mean())
+    st.clear_rectify()
+    # ---- the upload effect: adc_match host to host, the same frames as BGR8 (plain), BAYER_RGGB8 and NV12
+    pairs = {"BGR8 (plain)": (None, np.ascontiguousarray(left), np.ascontiguousarray(right))}
+    for name, word in (("BAYER_RGGB8", 0x20), ("NV12", 0x42)):
+        pairs[name] = (A.RawFormat(w, h, 0, word), RF.pack(left, word), RF.pack(right, word))
+    out = np.empty((h, w), np.float32)
+    rates = {name: [] for name in pairs}
+    reps = 10
+    for _ in range(alternations):
+        for name, (rf, l, r) in pairs.items():
+            st.clear_rectify()
+            if rf is not None:
+                st.set_input_format(0, rf)
+                st.set_input_format(1, rf)
+            for _ in range(3):
+                assert st.Match(l, r, out), A.last_error()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                assert st.Match(l, r, out), A.last_error()
+            rates[name].append(reps / (time.perf_counter() - t0))
+    st.Release()
+    for p in [po, ca, cbuf] + [f[0] for f in frames.values()]:
+        L.adc_device_free(p)
+    clocks.append(_clock_state())
+    # ---- the report
+    copy_ms = min(copies)
+    copy_tbs = 2 * cb / (copy_ms * 1e-3) / 1e12
+    base = min(times["BGR8"]["remap"])
+    lines = ["# Camera layouts: remap and conversion-only kernels, 1920 x 1080 -> 1920 x 1080", "",
+             "`python tools/rectify_timing.py --rawfmt --alternations %d --batch %d`: HIP events on the handle's stream around %d launches, "
+             "%d interleaved repetitions of the whole list in one process on one box; the figure is the best repetition, the spread is max / min - 1 "
+             "over the repetitions.  Example lens model, %.2f %% of the destination valid.  Priced bytes per destination pixel: remap 8 (record) + 1 (valid) + 3 (out) + source, "
+             "conversion source + 3.  The BGR8 remap is the parent revision's kernel (identical generated code)." % (alternations, batch, batch, alternations, 100 * valid), "",
+             "Best device copy (adc_device_copy_kernel_ms, %d MiB): %.1f us, %.2f TB/s (read + written)." % (cb >> 20, 1e3 * copy_ms, copy_tbs), "",
+             "Clock state before: " + "; ".join(clocks[0]), "", "Clock state after: " + "; ".join(clocks[1]), "",
+             "| layout | remap us | spread | priced B/px | priced TB/s | vs BGR8 remap | convert us | spread | priced B/px | priced TB/s |", "|---|---|---|---|---|---|---|---|---|---|"]
+    table, slow = {}, []
+    for name, _, src in RAW_LAYOUTS:
+        r, c = times[name]["remap"], times[name]["convert"]
+        rb, cbp = 12.0 + src, src + 3.0
+        table[name] = {"remap_us": [round(1e3 * t, 2) for t in r], "convert_us": [round(1e3 * t, 2) for t in c], "remap_bytes_per_px": rb, "convert_bytes_per_px": cbp}
+        rate = base / min(r)
+        if rate < 0.5:
+            slow.append(name)
+        lines.append("| %s | %.1f | %.0f %% | %.1f | %.2f | %.2f x | %.1f | %.0f %% | %.1f | %.2f |" % (
+            name, 1e3 * min(r), 100 * (max(r) / min(r) - 1), rb, rb * P / (min(r) * 1e-3) / 1e12, rate, 1e3 * min(c), 100 * (max(c) / min(c) - 1), cbp,
+            cbp * P / (min(c) * 1e-3) / 1e12))
+    lines += ["", "Layouts below half of the BGR8 remap's rate (pixels per second): " + (", ".join(slow) if slow else "none") + ".", "",
+              "## adc_match host to host, structured 1080p pair, D = 128 (pairs/s, %d Matches per figure)" % reps, "",
+              "| input | uploaded bytes per pair | pairs/s per repetition | best |", "|---|---|---|---|"]
+    for name, (rf, l, r) in pairs.items():
+        lines.append("| %s | %d | %s | %.1f |" % (name, l.nbytes + r.nbytes, ", ".join("%.1f" % v for v in rates[name]), max(rates[name])))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines), flush=True)
+    print(json.dumps({"rawfmt_timing": {"kernels": table, "copy_us": [round(1e3 * c, 2) for c in copies], "match_pairs_per_s": rates, "clocks": clocks}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--alternations", type=int, default=5)
@@ -170,7 +322,11 @@ def main():
     ap.add_argument("--disp", type=int, default=128)
     ap.add_argument("--out", default=None, help="also write the report lines to this file")
     ap.add_argument("--trace-only", default=None, choices=["on", "off"])
+    ap.add_argument("--rawfmt", action="store_true", help="the camera layouts at 1920x1080 (a run of its own)")
     a = ap.parse_args()
+    if a.rawfmt:
+        rawfmt(a.alternations if a.alternations != 5 else 3, a.batch if a.batch != 50 else 20, a.out or os.path.join(ROOT, "profiles", "rawfmt_timing.md"))
+        return
     lines, out = [], {"remap": {}, "match": []}
     for size in a.sizes.split(","):
         w, h = (int(v) for v in size.split("x"))
