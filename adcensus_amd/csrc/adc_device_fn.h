@@ -29,6 +29,20 @@ ADC_HD int adc_iabs(int a) { return a < 0 ? -a : a; }
 ADC_HD int adc_imax(int a, int b) { return a > b ? a : b; }
 ADC_HD int adc_imin(int a, int b) { return a < b ? a : b; }
 
+// Does an aggregation pass along the direction of record rec = {arm_lo, arm_hi, count16} (k_make_records) CHANGE the pixel?
+// Arms 0/0 make the ordered sum 0.0f + x, which is x bit for bit (no volume a regular pass reads holds -0.0f: each was produced
+// by a sum that starts at +0.0f), and a count of 1 makes the division x / 1.  divide = the launch contains a dividing pass (a
+// pass pair always does; both of its passes run along the same direction on the same record).  The sparse launches
+// (k_agg_march<.., SPARSE>) store, and k_agg_apply copies back, exactly the pixels for which this holds.
+ADC_HD bool adc_rec_changes_pixel(uint32_t rec, bool divide) { return (rec & 0xFFFFu) != 0u || (divide && (rec >> 16) != 1u); }
+// record densities (pixels with adc_rec_changes_pixel(rec, true) per direction) are counted into sharded words behind the arm
+// maxima: word of direction c, shard s = armmax[ADC_NZ_BASE + (c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE] (one cache line each:
+// a single word takes ~90 atomics per microsecond, a 1080p image has 8100 workgroups)
+#define ADC_NZ_BASE 32
+#define ADC_NZ_SHARDS 16
+#define ADC_NZ_STRIDE 32
+#define ADC_ARMMAX_WORDS (ADC_NZ_BASE + 2 * ADC_NZ_SHARDS * ADC_NZ_STRIDE)
+
 // gray = uint8(r*0.299 + g*0.587 + b*0.114), operands in double, left to right, truncation
 // (cost_computor.cpp:66-69).  Unfused: 3 mul + 2 add.
 ADC_HD uint8_t adc_gray(uint8_t b, uint8_t g, uint8_t r)

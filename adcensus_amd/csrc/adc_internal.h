@@ -83,6 +83,7 @@ struct AdcRectSide {
     size_t raw_cap;       // bytes raw holds
 };
 
+#define ADC_PIN_ARM 64 // pin_flags[ADC_PIN_ARM + i] = armmax[i] of the last Match (one copy at the end of the heavy stream)
 struct adc_handle {
     AdcParams p;
     int device;
@@ -100,7 +101,8 @@ struct adc_handle {
     uint64_t *census_l, *census_r;
     uint8_t* arms;
     uint16_t *sup_h, *sup_v;
-    int* armmax;             // [0] max horizontal arm, [1] max vertical arm of the current left image
+    int* armmax;             // [0] max horizontal arm, [1] max vertical arm of the current left image, [2] failed seams, [3] ring too
+                             // shallow, [ADC_NZ_BASE..] sharded record densities (ADC_ARMMAX_WORDS words, adc_device_fn.h)
     uint32_t *rec_h, *rec_v; // packed {arm_lo, arm_hi, divisor} per pixel, line-major (rec_v transposed)
     uint32_t *rec2_h, *rec2_v; // uint2 {arm_lo | span<<8 | divisor<<16, RN(1/divisor)}: records of the register-ring kernels
     float* agg_sink;           // 256 KiB scratch: store target of the halo steps of a pass pair (k_aggregate_rr.h)
@@ -158,6 +160,14 @@ struct adc_handle {
     int fuse_agg_so;      // set by the pipeline: the last aggregation pass may move into the first scanline pass (short-arm plan)
     int so_agg_fused;     // adc_launch_aggregate did so: vol_a holds the volume BEFORE that pass (consumed by the scanline stage)
     int agg_so_fusions;   // Matches that ran that way
+    // Sparse small-ring launches (k_aggregate.hip): chosen per direction from the density of pass-changing records the handle
+    // last saw (k_make_records counts them behind the arm maxima; they reach the host like the maxima do)
+    int32_t* pin_nz;      // the sharded density words of the last Match inside pin_flags (pin_flags + ADC_PIN_ARM + ADC_NZ_BASE; ADC_NZ_*: adc_device_fn.h)
+    long long rec_nz_host[2]; // pixels with a pass-changing horizontal / vertical record, previous Match (or read back: debug surface)
+    int rec_nz_known;     // rec_nz_host is valid
+    int in_redo;          // adc_wait is redoing a Match (no sparse launches there)
+    int agg_sparse_last;  // the last aggregation run used sparse launches (pass timings are then not priced as read V + write V)
+    int agg_sparse_launches; // sparse launches of this handle
     int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     float* med_hand;      // banded median: per-band hand-off rows [bands][med_hpitch], indexed by wavefront level
     int med_hpitch;
@@ -267,6 +277,7 @@ hipError_t adc_launch_gray_census(adc_handle* h);
 hipError_t adc_launch_cost(adc_handle* h, float* vol_out);
 hipError_t adc_launch_cost_records(adc_handle* h);
 int adc_agg_small_L(const adc_handle* h);
+double adc_agg_sparse_density(void); // density of pass-changing records up to which a direction's small-ring launches run sparse
 hipError_t adc_launch_arms(adc_handle* h); // arms, support counts, colour-difference maps (= _left + _rest)
 hipError_t adc_launch_arms_left(adc_handle* h); // what needs only the left image: packed pixels, arms, maxima, support counts
 hipError_t adc_launch_sup_counts(adc_handle* h); // support counts + region boxes from the arms in HBM (debug surface)

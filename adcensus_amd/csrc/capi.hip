@@ -131,7 +131,7 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_OK(hipMalloc(&h->arms, P * 4));
     HIP_OK(hipMalloc(&h->sup_h, P * 2));
     HIP_OK(hipMalloc(&h->sup_v, P * 2));
-    HIP_OK(hipMalloc(&h->armmax, 4 * sizeof(int)));
+    HIP_OK(hipMalloc(&h->armmax, ADC_ARMMAX_WORDS * sizeof(int)));
     HIP_OK(hipMalloc(&h->rec_h, P * 4));
     HIP_OK(hipMalloc(&h->rec_v, P * 4));
     HIP_OK(hipMalloc(&h->rec2_h, P * 8));
@@ -194,8 +194,10 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_OK(hipMalloc(&h->edge, P));
     HIP_OK(hipHostMalloc(&h->pin_in, P * 6, hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h->pin_out, P * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc(&h->pin_flags, 64 * sizeof(int32_t), hipHostMallocDefault));
-    memset(h->pin_flags, 0, 64 * sizeof(int32_t)); // [0] median error, [4..7] armmax + violation flag, [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
+    // (one block: the 64 flag words, then the mirror of the device's armmax words -- maxima, speculation flags, record densities)
+    HIP_OK(hipHostMalloc(&h->pin_flags, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t), hipHostMallocDefault));
+    h->pin_nz = h->pin_flags + ADC_PIN_ARM + ADC_NZ_BASE; // record densities (k_make_records)
+    memset(h->pin_flags, 0, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t)); // [0] median error, [ADC_PIN_ARM..] mirror of the armmax words (maxima, failed seams, violation flag, record densities), [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
     HIP_OK(hipMemset(h->label, 0, P));
     HIP_OK(hipMemset(h->chg_a, 0, 2 * tiles));
     HIP_OK(hipMemset(h->vol_a, 0, VB));
@@ -425,10 +427,10 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
         // ADC_AGG_HOST_ARMS=1: read the two maxima back instead (one early host synchronisation, the round-1 behaviour).
         static const bool host_arms = [] { const char* e = getenv("ADC_AGG_HOST_ARMS"); return e ? atoi(e) != 0 : false; }();
         if (host_arms && h->pin_flags) {
-            HIP_OK(hipMemcpyAsync(h->pin_flags + 4, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
+            HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_ARM, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
             HIP_OK(hipStreamSynchronize(h->heavy));
-            h->armmax_host[0] = h->pin_flags[4];
-            h->armmax_host[1] = h->pin_flags[5];
+            h->armmax_host[0] = h->pin_flags[ADC_PIN_ARM + 0];
+            h->armmax_host[1] = h->pin_flags[ADC_PIN_ARM + 1];
             h->armmax_valid = 1;
         } else {
             h->armmax_valid = h->arm_known ? 2 : 3;
@@ -458,7 +460,9 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     if (h->x_conf) HIP_OK(adc_launch_confidence(h)); // (adc_match_ex: one more read of the optimised volume)
     MARK(5, h->heavy);
     // maxima + violation flag of this pair, looked at by adc_wait (they seed the next Match's assumption)
-    if (h->pin_flags) HIP_OK(hipMemcpyAsync(h->pin_flags + 4, h->armmax, 4 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
+    // ... together with its record densities, which seed the next Match's choice between dense and sparse small-ring launches
+    // (ONE copy of all armmax words; a redo that restarts at the aggregation makes no records: the words are still this pair's)
+    if (h->pin_flags) HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_ARM, h->armmax, ADC_ARMMAX_WORDS * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
     HIP_OK(hipEventRecord(h->ev_heavy_done, h->heavy));
     if (h->heavy != h->stream) HIP_OK(hipStreamWaitEvent(h->stream, h->ev_heavy_done, 0));
 #undef MARK
@@ -494,6 +498,7 @@ static void collect_timings(adc_handle* h)
     // average duration of a REGULAR aggregation pass (read V + write V); a fused first pass (write-only) is left out
     const int first = h->agg_first_fused ? 1 : 0;
     if (h->agg_dual_last) h->agg_pass_ms = 0.f; // (two plans were enqueued: the marks bracket launches that may have been skipped)
+    else if (h->agg_sparse_last) h->agg_pass_ms = 0.f; // (sparse launches do not move read V + write V: no roofline figure for them)
     else if (h->agg_launches > first && hipEventElapsedTime(&tot, h->ev_agg[first], h->ev_agg[h->agg_launches]) == hipSuccess)
         h->agg_pass_ms = tot / (float)(h->agg_launches - first);
     if (h->verbose) { // the reference's stage lines (ADCensusStereo.cpp:88-129)
@@ -612,6 +617,8 @@ static void abort_match(adc_handle* h)
     h->fuse_cost = 0; h->fuse_agg_so = 0; h->fuse_wta = 0;
     h->armmax_valid = 0;
     h->agg_gate = 0;
+    h->in_redo = 0;
+    h->rec_nz_known = 0;
     h->wta_left_done = 0;
     h->timings_pending = false;
     h->force_median_fallback = 0;
@@ -620,7 +627,7 @@ static void abort_match(adc_handle* h)
     h->x_prov = nullptr; h->x_conf = nullptr;
     h->out.active = 0;
     h->ev_pending = 0;
-    if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[4] = h->pin_flags[5] = h->pin_flags[6] = h->pin_flags[7] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
+    if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
 }
@@ -741,38 +748,48 @@ int adc_wait(adc_handle* h)
     // (1) the aggregation assumed the arm maxima of the previous Match; a longer arm raised the flag and the pass was
     //     skipped: redo with the full ring (valid for every image).
     // (1b) a row of the scanline passes was cut into segments and a segment's warm-up did not reach the state of the full
-    //     pass (pin_flags[6] = seams that failed): redo with whole rows, and keep them for the next Matches.
+    //     pass (pin_flags[ADC_PIN_ARM + 2] = seams that failed): redo with whole rows, and keep them for the next Matches.
     //     Both redos restart at the aggregation when its first pass computes the matching cost itself (the default): the
     //     pixel records, arms and aggregation records of this pair are still in HBM; otherwise the whole Match runs again
     //     (the inputs are still there).  EVERY redo runs whole scanline rows: its volume differs from the first run's when the
     //     aggregation was skipped, so a seam could fail there that did not fail before (round-4 advisor finding) -- and the
     //     seam count is looked at again behind the redo.
     if (h->pin_flags) {
-        for (int attempt = 0; attempt < 2 && (h->pin_flags[7] != 0 || h->pin_flags[6] != 0); attempt++) {
+        for (int attempt = 0; attempt < 2 && (h->pin_flags[ADC_PIN_ARM + 3] != 0 || h->pin_flags[ADC_PIN_ARM + 2] != 0); attempt++) {
             // (round-5 advisor finding) a too-shallow ring skipped aggregation passes: the row passes and their seam check then ran
             // on a stale volume -- a seam that failed THERE says nothing about this image and must not cost 64 Matches of whole
             // rows (which would also switch the fused tail pass off); the redo re-checks the seams on the real volume
-            if (h->pin_flags[7] != 0) { h->arm_redos++; h->arm_known = 0; }
-            else if (h->pin_flags[6] != 0) { h->so_seam_redos++; h->so_seg_off = 64; }
+            if (h->pin_flags[ADC_PIN_ARM + 3] != 0) { h->arm_redos++; h->arm_known = 0; }
+            else if (h->pin_flags[ADC_PIN_ARM + 2] != 0) { h->so_seam_redos++; h->so_seg_off = 64; }
             if (h->so_seg_off < 1) h->so_seg_off = 1; // whole rows in every redo
             const bool partial = h->agg_first_fused != 0 && !(h->paper & ADC_PAPER_RIGHT_ARMS);
             if (partial) h->redo_partial++;
+            h->in_redo = 1;
             hipError_t e = run_pipeline(h, partial);
+            h->in_redo = 0;
             if (e == hipSuccess) e = enqueue_output(h);
             if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
             if (e != hipSuccess) { set_error("adc_wait: redo (full aggregation ring / whole scanline rows)", e); abort_match(h); return 2; }
         }
-        if (h->pin_flags[7] != 0 || h->pin_flags[6] != 0) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
-        h->armmax_host[0] = h->pin_flags[4];
-        h->armmax_host[1] = h->pin_flags[5];
+        if (h->pin_flags[ADC_PIN_ARM + 3] != 0 || h->pin_flags[ADC_PIN_ARM + 2] != 0) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
+        h->armmax_host[0] = h->pin_flags[ADC_PIN_ARM + 0];
+        h->armmax_host[1] = h->pin_flags[ADC_PIN_ARM + 1];
         h->arm_known = 1;
+        if (h->pin_nz && h->match_pending) {
+            for (int c = 0; c < 2; c++) {
+                long long n = 0;
+                for (int s = 0; s < ADC_NZ_SHARDS; s++) n += h->pin_nz[(c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE];
+                h->rec_nz_host[c] = n;
+            }
+            h->rec_nz_known = 1;
+        }
         if (h->match_pending && h->so_seg_off > 0) h->so_seg_off--; // (whole rows for a while after a failed seam)
         if (h->match_pending) { // (once per Match: a second adc_wait without a Match in between must not count again)
             // which plan did this image need?  Consecutive Matches that need different plans = a mixed stream: the next 64
             // Matches enqueue both plans and let the device choose (k_aggregate.hip) instead of assuming and redoing
             const int small_L = adc_agg_small_L(h);
-            const int plan = (h->pin_flags[4] <= small_L && h->pin_flags[5] <= small_L) ? 1 : 2;
-            if (plan == 1) { h->armmax_small[0] = h->pin_flags[4] > 0 ? h->pin_flags[4] : 1; h->armmax_small[1] = h->pin_flags[5] > 0 ? h->pin_flags[5] : 1; }
+            const int plan = (h->pin_flags[ADC_PIN_ARM + 0] <= small_L && h->pin_flags[ADC_PIN_ARM + 1] <= small_L) ? 1 : 2;
+            if (plan == 1) { h->armmax_small[0] = h->pin_flags[ADC_PIN_ARM + 0] > 0 ? h->pin_flags[ADC_PIN_ARM + 0] : 1; h->armmax_small[1] = h->pin_flags[ADC_PIN_ARM + 1] > 0 ? h->pin_flags[ADC_PIN_ARM + 1] : 1; }
             if (h->agg_last_plan != 0 && plan != h->agg_last_plan) { h->agg_switches++; h->agg_dual = 64; }
             else if (h->agg_dual > 0) h->agg_dual--;
             h->agg_last_plan = plan;
@@ -1773,12 +1790,23 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
     case ADC_RUN_COST: e = adc_launch_cost(h, h->vol_a); break;
     case ADC_RUN_ARMS: e = adc_launch_arms(h); break;
     case ADC_RUN_AGGREGATE: // arg = iterations (default 4); arg >= 100: first pass with the fused cost computation
-        e = adc_launch_records(h); // (needs ADC_RUN_GRAY_CENSUS before; reads the images instead of ADC_BUF_COST_INIT)
+        e = hipMemsetAsync(h->armmax + ADC_NZ_BASE, 0, 2 * ADC_NZ_SHARDS * ADC_NZ_STRIDE * sizeof(int), h->heavy); // (the record densities: counted below)
+        if (e == hipSuccess) e = adc_launch_records(h); // (needs ADC_RUN_GRAY_CENSUS before; reads the images instead of ADC_BUF_COST_INIT)
         // arg >= 200: additionally read the maximum arms back (needs ADC_RUN_ARMS before) so that the launcher picks
         // the ring depth on the host and fuses same-direction pass pairs -- the production pipeline's path
         if (e == hipSuccess && arg >= 200) {
             e = hipMemcpy(h->armmax_host, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost);
             h->armmax_valid = e == hipSuccess ? 1 : 0;
+            // ... and the record densities of THIS image (the pipeline assumes the previous Match's)
+            if (e == hipSuccess && h->pin_nz) e = hipMemcpyAsync(h->pin_nz, h->armmax + ADC_NZ_BASE, 2 * ADC_NZ_SHARDS * ADC_NZ_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, h->heavy);
+            if (e == hipSuccess && h->pin_nz) e = hipStreamSynchronize(h->heavy);
+            if (e == hipSuccess && h->pin_nz) {
+                for (int c = 0; c < 2; c++) {
+                    h->rec_nz_host[c] = 0;
+                    for (int s = 0; s < ADC_NZ_SHARDS; s++) h->rec_nz_host[c] += h->pin_nz[(c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE];
+                }
+                h->rec_nz_known = 1;
+            }
             arg -= 200;
         }
         if (e == hipSuccess && arg >= 100) {
@@ -1853,6 +1881,10 @@ int64_t adc_debug_counter(adc_handle* h, int which)
     case 11: return h->redo_partial;  // redos that restarted at the aggregation (not the whole Match)
     case 12: return h->agg_dual;      // > 0: the next Match enqueues both plans
     case 13: return h->agg_so_fusions; // Matches whose last aggregation pass ran inside the first scanline pass
+    case 16: return h->agg_sparse_launches; // small-ring aggregation launches that ran in their sparse form (+ k_agg_apply)
+    case 17: return (int64_t)(adc_agg_sparse_density() * 1e6 + 0.5); // density threshold of the sparse form, parts per million of the pixels
+    case 18: return h->rec_nz_known ? h->rec_nz_host[0] : -1; // pixels with a pass-changing horizontal record the handle last saw
+    case 19: return h->rec_nz_known ? h->rec_nz_host[1] : -1; // ... vertical record
     case 14: return h->irv_xcd_mode;   // the voting chain sweeps band -> XCD (the mapping was probed on this device)
     case 15: return h->med_seg_last;   // column segments per band link of the last banded median launch (1: whole rows)
     case 3: return h->irv_budget;

@@ -182,7 +182,11 @@ __device__ __forceinline__ float agg_reg_sum(float acc, int idx, int cnt)
     return acc;
 }
 
-template <bool VERT, bool DIVIDE, bool SMALL, bool COSTIN, bool PAIR, int VPL, bool REGRING>
+// SPARSE (small ring, volume input): the launch issues the volume store of an output only when the pixel's own record
+// makes a pass change it (adc_rec_changes_pixel) -- every other output is bit for bit what the launch READ at that index, so
+// the result of the launch is "src with the stored pixels replaced"; k_agg_apply copies those back into src behind it.
+// Loads, rings, sums, division, segments and halos are the dense form's.
+template <bool VERT, bool DIVIDE, bool SMALL, bool COSTIN, bool PAIR, int VPL, bool REGRING, bool SPARSE = false>
 __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, float* __restrict__ dst,
                                                const uint32_t* __restrict__ rec, // {lo, hi, count16} per pixel, line-major
                                                int W, int H, int Dp, int L, int seg_len, int nseg, int per_xcd,
@@ -193,6 +197,7 @@ __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, fl
     static_assert(!COSTIN || (!VERT && !DIVIDE), "the fused cost is for the first (row, non-dividing) pass");
     static_assert(!PAIR || (DIVIDE && !COSTIN), "a fused pair = dividing pass + the following non-dividing pass");
     static_assert(VPL == 1 || (VPL == 2 && SMALL && !COSTIN), "two disparities per lane: small ring, no fused cost");
+    static_assert(!SPARSE || (SMALL && !COSTIN && !REGRING), "sparse stores: the regular small-ring launches");
     typedef typename AggT<VPL>::V V;
     const V vzero = (V)(0.0f);
     // small_variant >= 0 (host does not know the arms, debug path): two launches per pass, the window depth follows
@@ -299,7 +304,7 @@ __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, fl
             acc2_ = agg_sum<SMALL, V>(vzero, ring2 + i2_ * 64, k1_);                              \
             if (k_ > k1_) acc2_ = agg_sum<SMALL, V>(acc2_, ring2, k_ - k1_);                      \
         }                                                                                         \
-        ADC_VOL_STORE(reinterpret_cast<V*>(dpn), acc2_);                                          \
+        if (!SPARSE || adc_rec_changes_pixel(r2_, true)) ADC_VOL_STORE(reinterpret_cast<V*>(dpn), acc2_); \
         dpn += fstep;                                                                             \
         slot2_s = slot2_s + 1 == R ? 0 : slot2_s + 1;                                             \
     } while (0)
@@ -314,7 +319,7 @@ __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, fl
             mcur++;                                                                               \
             if (s_ >= s0 && s_ < s1) AGG_EMIT2();                                                 \
         } else {                                                                                  \
-            ADC_VOL_STORE(reinterpret_cast<V*>(dpn), (ACC));                                      \
+            if (!SPARSE || adc_rec_changes_pixel((RECV), DIVIDE)) ADC_VOL_STORE(reinterpret_cast<V*>(dpn), (ACC)); \
             dpn += fstep;                                                                         \
         }                                                                                         \
     } while (0)
@@ -516,15 +521,16 @@ __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, fl
         // first iteration: the younger ops are the prologue loads of slots U+1.. (2 each) and the U steps
         // already done (3 each): 2*(AGG_PF-1-U) + 3*U = 2*AGG_PF - 2 + U
         static_assert(AGG_PF == 8, "the peeled first iteration below is written for AGG_PF == 8");
-        // (PAIR: a step may issue no store at all, so only the loads are counted -- a lower bound is always safe)
-        AGG_STEP(0, 14); AGG_STEP(1, PAIR ? 14 : 15); AGG_STEP(2, PAIR ? 14 : 16); AGG_STEP(3, PAIR ? 14 : 17);
-        AGG_STEP(4, PAIR ? 14 : 18); AGG_STEP(5, PAIR ? 14 : 19); AGG_STEP(6, PAIR ? 14 : 20); AGG_STEP(7, PAIR ? 14 : 21);
+        // (PAIR, SPARSE: a step may issue no store at all, so only the loads are counted -- a lower bound is always safe)
+        constexpr bool NOST = PAIR || SPARSE;
+        AGG_STEP(0, 14); AGG_STEP(1, NOST ? 14 : 15); AGG_STEP(2, NOST ? 14 : 16); AGG_STEP(3, NOST ? 14 : 17);
+        AGG_STEP(4, NOST ? 14 : 18); AGG_STEP(5, NOST ? 14 : 19); AGG_STEP(6, NOST ? 14 : 20); AGG_STEP(7, NOST ? 14 : 21);
         j += AGG_PF;
         // steady state: younger ops = this slot's own store + 3 per younger step = 3*(AGG_PF-1)+1; we wait for
         // <= 3*(AGG_PF-1) outstanding (one stricter).  vmcnt retires in order (loads and stores) on gfx9-family.
         for (; j + 2 * AGG_PF <= hi; j += AGG_PF) {
 #pragma unroll
-            for (int u = 0; u < AGG_PF; u++) AGG_STEP(u, PAIR ? 2 * (AGG_PF - 1) : 3 * (AGG_PF - 1));
+            for (int u = 0; u < AGG_PF; u++) AGG_STEP(u, NOST ? 2 * (AGG_PF - 1) : 3 * (AGG_PF - 1));
         }
 #undef AGG_STEP
         // the AGG_PF entries still in flight are entries j .. j+AGG_PF-1 (all < hi)
@@ -581,14 +587,42 @@ __device__ __forceinline__ void agg_march_body(const float* __restrict__ src, fl
 #undef AGG_COST
 }
 
-template <bool VERT, bool DIVIDE, bool SMALL, bool COSTIN, bool PAIR, int VPL = 1>
+template <bool VERT, bool DIVIDE, bool SMALL, bool COSTIN, bool PAIR, int VPL = 1, bool SPARSE = false>
 __global__ __launch_bounds__(64) void k_agg_march(const float* __restrict__ src, float* __restrict__ dst,
                                                   const uint32_t* __restrict__ rec, int W, int H, int Dp, int L, int seg_len,
                                                   int nseg, int per_xcd, const int* __restrict__ armmax, int small_variant,
                                                   int small_L, AggCostIn ci)
 {
-    agg_march_body<VERT, DIVIDE, SMALL, COSTIN, PAIR, VPL, false>(src, dst, rec, W, H, Dp, L, seg_len, nseg, per_xcd, armmax,
-                                                                  small_variant, small_L, ci);
+    agg_march_body<VERT, DIVIDE, SMALL, COSTIN, PAIR, VPL, false, SPARSE>(src, dst, rec, W, H, Dp, L, seg_len, nseg, per_xcd, armmax,
+                                                                          small_variant, small_L, ci);
+}
+
+// Behind a sparse launch: the outputs it stored (into the OTHER volume, at their own index -- the waves of neighbouring
+// segments read each other's halos, so the launch itself must not write the volume it reads) go back into the volume the launch
+// read, which then holds the whole result.  A wave takes 64 consecutive records of the direction's line-major record set (one
+// coalesced load), and copies the Dp floats of every pixel whose record passes the launch's own predicate.  Runs after every
+// kernel of the launch (stream order) with the same assumption gate, so it moves nothing when the launch was skipped.
+template <bool VERT>
+__global__ __launch_bounds__(256) void k_agg_apply(const float* __restrict__ from, float* __restrict__ to,
+                                                   const uint32_t* __restrict__ rec, int W, int H, int Dp, int divide,
+                                                   const int* __restrict__ armmax, int small_variant, int small_L)
+{
+    if (agg_gate_skip(armmax, small_variant, small_L, VERT)) return;
+    const int lane = threadIdx.x & 63;
+    const long long P = (long long)W * H;
+    const long long i = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane; // record index: y * W + x, or x * H + y
+    const bool take = i < P && adc_rec_changes_pixel(rec[i < P ? i : 0], divide != 0);
+    unsigned long long todo = __ballot(take);
+    const long long i0 = i - lane;
+    while (todo) {
+        const int b = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const long long r = i0 + b;
+        const long long pix = VERT ? (r % H) * W + r / H : r;
+        const float* f = from + pix * Dp;
+        float* t = to + pix * Dp;
+        for (int d = lane; d < Dp; d += 64) t[d] = f[d];
+    }
 }
 
 // full ring in registers (2L+1 <= AGG_RING_REGS): the compiler keeps to v0..v55, ring 1 owns v56..v127, ring 2 (pairs)
@@ -703,15 +737,44 @@ static int agg_assumed_depth(const adc_handle* h, bool vert)
 
 // which: 0 = the host does not know the arms: launch the full-ring and the small-ring variant, the kernel decides;
 //        1 = small ring only, 2 = full ring only (the host has read armmax).  PAIR needs which == 1.
+// two disparities per lane with the small ring (ADC_AGG_VPL2: 1 = every small-ring launch, 2 = pass pairs only, 0 = off)
+static bool agg_small_vpl2(const adc_handle* h, bool pair)
+{
+    static const int vpl2_env = env_int("ADC_AGG_VPL2", 1);
+    return (vpl2_env == 1 || (vpl2_env == 2 && pair)) && h->p.Dp % 128 == 0;
+}
+
+// Largest fraction of pixels with a pass-changing record (per direction, of the previous Match) up to which the small-ring
+// launches of that direction run in their sparse form: half of the measured break-even density against the dense form (0.211
+// on 1080p noise pairs with planted copies: tools/gpu_sparse_sweep.py, profiles/sparse_agg_density_sweep.md;
+// ADC_AGG_SPARSE_DENSITY overrides the value, read per call: the sweep and the tests vary it).
+#define AGG_SPARSE_MAX_DENSITY 0.105
+double adc_agg_sparse_density(void)
+{
+    const char* e = getenv("ADC_AGG_SPARSE_DENSITY");
+    return e ? atof(e) : AGG_SPARSE_MAX_DENSITY;
+}
+// Does a small-ring launch of this direction run sparse?  Only in the plain short-arm plan of the pipeline (arms read back or
+// assumed, one plan enqueued, not a redo), with two disparities per lane, when the record density the handle last saw is low.
+// Both forms give the same bits for every image: a wrong guess costs time, never a redo.  ADC_AGG_SPARSE=0 switches it off.
+static bool agg_sparse_wanted(const adc_handle* h, bool vert, bool pair)
+{
+    const char* e = getenv("ADC_AGG_SPARSE"); // (read per call: the tests switch it within one process)
+    if (e && atoi(e) == 0) return false;
+    if (h->agg_gate || h->in_redo || !(h->armmax_valid == 1 || h->armmax_valid == 2) || !h->rec_nz_known) return false;
+    if (!agg_small_vpl2(h, pair)) return false;
+    return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_sparse_density() * (double)h->p.W * (double)h->p.H;
+}
+
+// sparse: small-ring launch in its sparse form + k_agg_apply (the result is then in src, not in dst); which == 1 only
 template <bool VERT, bool DIVIDE, bool COSTIN = false, bool PAIR = false>
-static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int which = 0)
+static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int which = 0, bool sparse = false)
 {
     const AdcParams& p = h->p;
     const int L = adc_imax(0, adc_imin(p.opt.cross_L1, 255)); // (a ring of 2 * 255 + 1 entries of 256 bytes fits the 160 KiB of LDS: every arm limit marches)
     const int N = VERT ? p.H : p.W;
     const int small_L = adc_agg_small_L(h);
-    // two disparities per lane with the small ring (ADC_AGG_VPL2=0 switches it off)
-    static const int vpl2_env = env_int("ADC_AGG_VPL2", 1); // 1 = every small-ring launch, 2 = pass pairs only
+    if (sparse && (COSTIN || which != 1 || !agg_small_vpl2(h, PAIR))) return hipErrorInvalidValue; // (agg_sparse_wanted)
     for (int variant = 0; variant < 2; variant++) { // 0: full ring, 1: small ring (exits unless every arm <= small_L)
         if (variant == 1 && (small_L <= 0 || small_L >= L)) break;
         if ((which == 1 && variant == 0 && small_L > 0 && small_L < L) || (which == 2 && variant == 1)) continue;
@@ -725,7 +788,7 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
         // ... as VGPR pairs, two disparities per lane (k_aggregate_rr2.h; ADC_AGG_RR2=0: the one-float register ring)
         static const bool rr2_env = env_int("ADC_AGG_RR2", 1) != 0;
         const bool rr2 = regring && rr2_env && !PAIR && p.Dp % 128 == 0 && 2 * Lv + 1 <= RR2_SLOTS;
-        const int vpl = rr2 ? 2 : ((variant == 1 && !COSTIN && (vpl2_env == 1 || (vpl2_env == 2 && PAIR)) && p.Dp % 128 == 0) ? 2 : 1);
+        const int vpl = rr2 ? 2 : ((variant == 1 && !COSTIN && agg_small_vpl2(h, PAIR)) ? 2 : 1);
         const long long nlines = (long long)(VERT ? p.W : p.H) * (p.Dp / (64 * vpl));
         const size_t ring_bytes = regring ? 0 : (size_t)(2 * Lv + 1) * 64 * sizeof(float) * vpl;
         const size_t ldsv = ring_bytes + (COSTIN ? (768 + 64) * sizeof(float) : 0) + ((PAIR && !regring) ? ring_bytes + (2 * Lv + 1) * 4 + 64 : 0);
@@ -752,6 +815,8 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
             h->agg_kernel = rr2 ? "k_agg_rr2 (register ring of VGPR pairs, 2 disparities per lane, one pass per launch)"
                           : regring ? (PAIR ? "k_agg_regring_pair (two register rings, dividing pass + next first pass per launch)"
                                             : "k_agg_regring (register ring, 1 disparity per lane, one pass per launch)")
+                          : (variant && sparse) ? (PAIR ? "k_agg_march<.., PAIR, SPARSE> + k_agg_apply (LDS small rings: dividing pass + next first pass per launch, only changed pixels stored)"
+                                                        : "k_agg_march<.., SMALL, SPARSE> + k_agg_apply (LDS small ring, one pass per launch, only changed pixels stored)")
                           : variant ? (PAIR ? "k_agg_march<.., PAIR> (LDS small rings: dividing pass + next first pass per launch)"
                                             : "k_agg_march<.., SMALL> (LDS small ring, one pass per launch)")
                                     : "k_agg_march (LDS full ring, one pass per launch)";
@@ -781,9 +846,19 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
                                    reinterpret_cast<const uint2*>(VERT ? h->rec2_v : h->rec2_h), p.W, p.H, p.Dp, Lv, seg_len, nseg,
                                    per_xcd, h->armmax, sv, sl, h->agg_sink);
         } else if (variant && vpl == 2) {
-            if constexpr (!COSTIN)
-                hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                                   VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
+            if constexpr (!COSTIN) {
+                if (sparse) {
+                    hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2, true>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
+                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
+                    const long long P = (long long)p.W * p.H;
+                    hipLaunchKernelGGL((k_agg_apply<VERT>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->heavy, dst, const_cast<float*>(src),
+                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, (DIVIDE || PAIR) ? 1 : 0, h->armmax, sv, sl);
+                    h->agg_sparse_launches++;
+                    h->agg_sparse_last = 1;
+                } else
+                    hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
+                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
+            }
         } else if (variant)
             hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, COSTIN, PAIR>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
                                VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
@@ -849,9 +924,15 @@ static hipError_t agg_sequence(adc_handle* h, int iterations, bool dry, bool fir
                 if (fused) {
                     swap = !first_into_cur;
                     if (!dry) e = launch_pass<false, false, true>(h, cur, swap ? oth : cur, which_h);
-                } else if (!dry) e = launch_pass<false, false>(h, cur, oth, which_h);
-            } else if (!dry) {
-                e = launch_pass<true, false>(h, cur, oth, which_v);
+                } else {
+                    const bool sp = which_h == 1 && agg_sparse_wanted(h, false, false);
+                    if (!dry) e = launch_pass<false, false>(h, cur, oth, which_h, sp);
+                    swap = !sp; // (a sparse launch leaves its result in the volume it read)
+                }
+            } else {
+                const bool sp = which_v == 1 && agg_sparse_wanted(h, true, false);
+                if (!dry) e = launch_pass<true, false>(h, cur, oth, which_v, sp);
+                swap = !sp;
             }
             if (swap) { float* t = cur; cur = oth; oth = t; }
             launch++;
@@ -871,16 +952,17 @@ static hipError_t agg_sequence(adc_handle* h, int iterations, bool dry, bool fir
         }
         const bool pair = pair_env && marching && k + 1 < iterations &&
                           (wsec == 1 || (wsec == 2 && (pair_full >= 2 || (pair_full == 1 && regring_fits))));
+        const bool sparse = wsec == 1 && agg_sparse_wanted(h, hf, pair); // (the second pass runs across the first: vertical after hf)
         if (!dry) {
             if (hf) {
-                if (pair) e = launch_pass<true, true, false, true>(h, cur, oth, wsec);
-                else e = launch_pass<true, true>(h, cur, oth, which_v); // / sup_h
+                if (pair) e = launch_pass<true, true, false, true>(h, cur, oth, wsec, sparse);
+                else e = launch_pass<true, true>(h, cur, oth, which_v, sparse); // / sup_h
             } else {
-                if (pair) e = launch_pass<false, true, false, true>(h, cur, oth, wsec);
-                else e = launch_pass<false, true>(h, cur, oth, which_h); // / sup_v
+                if (pair) e = launch_pass<false, true, false, true>(h, cur, oth, wsec, sparse);
+                else e = launch_pass<false, true>(h, cur, oth, which_h, sparse); // / sup_v
             }
         }
-        { float* t = cur; cur = oth; oth = t; }
+        if (!sparse) { float* t = cur; cur = oth; oth = t; } // (a sparse launch leaves its result in the volume it read)
         launch++;
         passes += pair ? 2 : 1;
         second_done = pair;
@@ -919,6 +1001,7 @@ hipError_t adc_launch_aggregate(adc_handle* h, int iterations)
     }
     h->agg_first_fused = 0;
     h->agg_dual_last = 0;
+    h->agg_sparse_last = 0;
     h->so_agg_fused = 0; // (round-5 advisor finding: a Match that failed between this stage and the scanline stage must not leave it set)
     hipError_t e = hipSuccess;
     AggSeq seq;

@@ -146,21 +146,42 @@ __global__ __launch_bounds__(256) void k_color_diffs(const uint8_t* __restrict__
 __global__ __launch_bounds__(256) void k_make_records(const uchar4* __restrict__ arms, const uint16_t* __restrict__ sup_h,
                                                       const uint16_t* __restrict__ sup_v, uint32_t* __restrict__ rec_h,
                                                       uint32_t* __restrict__ rec_v, uint2* __restrict__ rec2_h,
-                                                      uint2* __restrict__ rec2_v, int W, int H, int L)
+                                                      uint2* __restrict__ rec2_v, int W, int H, int L, int* __restrict__ armmax)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
+    __shared__ int snz[2];
+    if (threadIdx.x < 2) snz[threadIdx.x] = 0;
+    __syncthreads();
+    bool nzh = false, nzv = false;
+    if (x < W && y < H) {
     const size_t p = (size_t)y * W + x;
     const uchar4 a = arms[p];
     const uint32_t ch = sup_h[p], cv = sup_v[p];
-    rec_h[p] = (uint32_t)a.x | ((uint32_t)a.y << 8) | (cv << 16);
-    rec_v[(size_t)x * H + y] = (uint32_t)a.z | ((uint32_t)a.w << 8) | (ch << 16);
+    const uint32_t rh = (uint32_t)a.x | ((uint32_t)a.y << 8) | (cv << 16);
+    const uint32_t rv = (uint32_t)a.z | ((uint32_t)a.w << 8) | (ch << 16);
+    rec_h[p] = rh;
+    rec_v[(size_t)x * H + y] = rv;
+    nzh = adc_rec_changes_pixel(rh, true);
+    nzv = adc_rec_changes_pixel(rv, true);
     if (rec2_h) {
         const uint32_t nh = (uint32_t)a.x + a.y + 1u, nv = (uint32_t)a.z + a.w + 1u;
         const uint32_t bias = (uint32_t)L + 1u;
         rec2_h[p] = make_uint2((((uint32_t)a.x + bias) & 255u) | ((nh & 255u) << 8) | (cv << 16), __float_as_uint(1.0f / (float)cv));
         rec2_v[(size_t)x * H + y] = make_uint2((((uint32_t)a.z + bias) & 255u) | ((nv & 255u) << 8) | (ch << 16), __float_as_uint(1.0f / (float)ch));
+    }
+    }
+    // pixels per direction whose record makes a pass change them (the sparse aggregation launches are chosen from these
+    // densities, k_aggregate.hip): one count per wave into LDS, one atomic per workgroup and direction into a sharded word
+    const int ch_ = __popcll(__ballot(nzh)), cv_ = __popcll(__ballot(nzv));
+    if ((threadIdx.x & 63) == 0) {
+        if (ch_) atomicAdd(&snz[0], ch_);
+        if (cv_) atomicAdd(&snz[1], cv_);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && snz[threadIdx.x] != 0) {
+        const int shard = (int)((blockIdx.y * gridDim.x + blockIdx.x) % ADC_NZ_SHARDS);
+        atomicAdd(&armmax[ADC_NZ_BASE + ((int)threadIdx.x * ADC_NZ_SHARDS + shard) * ADC_NZ_STRIDE], snz[threadIdx.x]);
     }
 }
 
@@ -170,7 +191,7 @@ hipError_t adc_launch_records(adc_handle* h)
     dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, 1), block(256, 1, 1);
     hipLaunchKernelGGL(k_make_records, grid, block, 0, h->heavy, reinterpret_cast<const uchar4*>(h->arms), h->sup_h, h->sup_v,
                        h->rec_h, h->rec_v, reinterpret_cast<uint2*>(h->rec2_h), reinterpret_cast<uint2*>(h->rec2_v), p.W, p.H,
-                       adc_imax(0, adc_imin(p.opt.cross_L1, 255)));
+                       adc_imax(0, adc_imin(p.opt.cross_L1, 255)), h->armmax);
     return hipGetLastError();
 }
 
@@ -181,7 +202,8 @@ hipError_t adc_launch_arms_left(adc_handle* h)
 {
     const AdcParams& p = h->p;
     dim3 grid((p.W + 63) / 64, (p.H + 3) / 4, 1), block(256, 1, 1);
-    hipMemsetAsync(h->armmax, 0, 4 * sizeof(int), h->heavy); // [0],[1] maxima, [3] "assumed ring depth too small" flag (k_aggregate.hip)
+    // [0],[1] maxima, [3] "assumed ring depth too small" flag (k_aggregate.hip), [ADC_NZ_BASE..] record densities (k_make_records)
+    hipMemsetAsync(h->armmax, 0, ADC_ARMMAX_WORDS * sizeof(int), h->heavy);
     hipLaunchKernelGGL(k_pack_bgr, dim3((p.W * p.H + 255) / 256), dim3(256), 0, h->heavy, h->img_l, h->bgrx_l, p.W * p.H);
     h->bgrx_valid = 1;
     hipLaunchKernelGGL(k_build_arms, grid, block, 0, h->heavy, h->bgrx_l, reinterpret_cast<uchar4*>(h->arms), p.W, p.H,
