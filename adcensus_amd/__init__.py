@@ -89,6 +89,43 @@ class Outputs(C.Structure):
                 ("cloud_count", C.c_void_p), ("disp8", C.c_void_p)]
 
 
+class Products(C.Structure):
+    """adc_products: every optional product of one Match -- provenance / confidence (adc_match_ex), an embedded Outputs (adc_match_out)
+    and the 16-bit fixed-point map disp16 with its scale.  Host addresses for adc_match_products / adc_match_async_products /
+    adc_farm_submit_products, device addresses for adc_match_device_products.  from_arrays() builds one from numpy arrays and keeps
+    them alive."""
+    _fields_ = [("provenance", C.c_void_p), ("confidence", C.c_void_p), ("out", Outputs), ("disp16", C.c_void_p),
+                ("disp16_scale", C.c_float), ("reserved_", C.c_uint32)]
+
+    @classmethod
+    def from_addresses(cls, provenance=None, confidence=None, calib=None, depth=None, cloud=None, cloud_capacity=0, cloud_count=None,
+                       disp8=None, disp16=None, disp16_scale=256.0):
+        c = _calib(calib)
+        req = cls(provenance, confidence, Outputs(C.pointer(c) if c is not None else None, depth, cloud, int(cloud_capacity), cloud_count, disp8),
+                  disp16, float(disp16_scale), 0)
+        req._keep = [c]
+        return req
+
+    @classmethod
+    def from_arrays(cls, provenance=None, confidence=None, calib=None, depth=None, cloud=None, disp8=None, disp16=None, disp16_scale=256.0):
+        """Host request from C-contiguous numpy arrays (None: not requested): provenance uint8, confidence float32, depth float32, disp8
+        uint8, disp16 uint16 [H][W]; cloud a POINT_DTYPE array whose length is the capacity.  With a cloud, `count` (a uint32 array of one
+        element, written at delivery) is part of the request."""
+        for a, dt in ((provenance, np.uint8), (confidence, np.float32), (depth, np.float32), (disp8, np.uint8), (disp16, np.uint16), (cloud, POINT_DTYPE)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"]), dt
+        count = np.zeros(1, np.uint32) if cloud is not None else None
+        adr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        req = cls.from_addresses(adr(provenance), adr(confidence), calib, adr(depth), adr(cloud), 0 if cloud is None else cloud.size, adr(count),
+                                 adr(disp8), adr(disp16), disp16_scale)
+        req._keep += [provenance, confidence, depth, cloud, disp8, disp16, count]
+        req.count = count
+        return req
+
+    def sizes_ok(self, n):
+        """every map array from_arrays() was given holds n elements"""
+        return all(a is None or a.dtype == POINT_DTYPE or a.size in (1, n) for a in getattr(self, "_keep", [])[1:])
+
+
 class RawFormat(C.Structure):
     """adc_raw_format: geometry of the raw images of one side while rectification is on (pitch_bytes 0: tightly packed rows)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch_bytes", C.c_int32), ("format", C.c_int32)]
@@ -231,6 +268,14 @@ def lib():
         L.adc_reproject_device.restype = C.c_int
         L.adc_get_cloud_count.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.adc_get_cloud_count.restype = C.c_int
+    if hasattr(L, "adc_match_products"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        for name in ("adc_match_products", "adc_match_async_products", "adc_match_device_products"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, C.POINTER(Products)]
+            getattr(L, name).restype = C.c_int
+        L.adc_farm_submit_products.argtypes = [vp, u8p, u8p, vp, C.POINTER(Products), C.POINTER(C.c_uint64)]
+        L.adc_farm_submit_products.restype = C.c_int
+        L.adc_disp16_device.argtypes = [vp, vp, C.c_float, vp]
+        L.adc_disp16_device.restype = C.c_int
     if hasattr(L, "adc_set_speckle_filter"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_speckle_filter.argtypes = [vp, i32, C.c_float]
         L.adc_set_speckle_filter.restype = C.c_int
@@ -399,16 +444,22 @@ class PairFarm:
         self._keep = {}
         self._rect = _RectifyState()
 
-    def submit(self, img_left, img_right, disp_left):
+    def submit(self, img_left, img_right, disp_left, products=None):
+        """products: a Products with HOST addresses (Products.from_arrays) or None; its arrays are delivered with the map, in
+        submission order (adc_farm_submit_products), and are kept alive until then."""
         l, r = _img(img_left), _img(img_right)
         assert (l.size, r.size) == self._rect.sizes(self.width * self.height * 3)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == self.width * self.height
         t = C.c_uint64(0)
-        rc = lib().adc_farm_submit(self._f, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, C.byref(t))
+        if products is None:
+            rc = lib().adc_farm_submit(self._f, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, C.byref(t))
+        else:
+            assert products.sizes_ok(self.width * self.height)
+            rc = lib().adc_farm_submit_products(self._f, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, C.byref(products), C.byref(t))
         if rc not in (0, 3):
             raise RuntimeError("adc_farm_submit failed (%d): %s" % (rc, last_error()))
         ticket = int(t.value)
-        self._keep[ticket] = disp_left  # the output array must stay alive until the pair is delivered
+        self._keep[ticket] = (disp_left, products)  # the output arrays must stay alive until the pair is delivered
         self._keep.pop(ticket - self.pipelines, None)  # submit() has just delivered the pair that held this pipeline before
         if rc == 3:  # ADC_FARM_PREVIOUS_FAILED: the new pair IS in flight (ticket), the pipeline's previous pair failed
             raise PreviousPairFailed(ticket, ticket - self.pipelines, "adc_farm_submit: " + last_error())
@@ -608,6 +659,70 @@ class ADCensusStereo:
         asynchronous, call wait()."""
         req = _outputs(calib, d_depth, d_cloud, cloud_capacity, d_cloud_count, d_disp8)
         return lib().adc_reproject_device(self._h, d_disp, d_left, C.byref(req)) == 0
+
+    # -- every product from one Match (adc_*_products) --------------------------------------------
+    def MatchProducts(self, img_left, img_right, disp_left, products):
+        """Match plus every product the request asks for (adc_match_products; a Products with HOST addresses, e.g. Products.from_arrays),
+        synchronous.  None or an empty request: exactly Match.  False where Match is, and when the request is refused."""
+        if not self._h or img_left is None or img_right is None or disp_left is None:
+            return False
+        l, r = _img(img_left), _img(img_right)
+        n = self.width * self.height
+        assert (l.size, r.size) == self._rect.sizes(n * 3)
+        assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        assert products is None or products.sizes_ok(n)
+        return lib().adc_match_products(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, None if products is None else C.byref(products)) == 0
+
+    def _product_arrays(self, calib, provenance, confidence, depth, cloud, disp8, disp16_scale, cloud_capacity):
+        shp = (self.height, self.width)
+        new = lambda on, dt: np.empty(shp, dt) if on else None  # noqa: E731
+        cap = shp[0] * shp[1] if cloud_capacity is None else int(cloud_capacity)
+        return Products.from_arrays(new(provenance, np.uint8), new(confidence, np.float32), calib, new(depth, np.float32),
+                                    np.empty(cap, POINT_DTYPE) if cloud else None, new(disp8, np.uint8), new(disp16_scale is not None, np.uint16),
+                                    256.0 if disp16_scale is None else disp16_scale)
+
+    @staticmethod
+    def _product_dict(disp, req):
+        """what a delivered request holds, as a dict of arrays (only what was asked for); the cloud is cut to the points written"""
+        c, prov, conf, depth, cloud, disp8, disp16, count = req._keep
+        out = {"disparity": disp}
+        for name, a in (("provenance", prov), ("confidence", conf), ("depth", depth), ("disp8", disp8), ("disp16", disp16)):
+            if a is not None:
+                out[name] = a
+        if cloud is not None:
+            out["cloud_count"] = int(count[0])
+            out["cloud"] = cloud[:min(int(count[0]), cloud.size)]
+        return out
+
+    def match_products(self, img_left, img_right, calib=None, provenance=False, confidence=False, depth=False, cloud=False, disp8=False,
+                       disp16_scale=None, cloud_capacity=None):
+        """Convenience: one synchronous Match, returns a dict of new arrays -- "disparity" and whatever was asked for: "provenance",
+        "confidence", "depth" (needs calib), "cloud" (POINT_DTYPE, cut to the points written) with "cloud_count", "disp8", "disp16"
+        (disp16_scale: the fixed-point scale, None = not requested).  Raises on failure."""
+        d = np.empty((self.height, self.width), np.float32)
+        req = self._product_arrays(calib, provenance, confidence, depth, cloud, disp8, disp16_scale, cloud_capacity)
+        if not self.MatchProducts(img_left, img_right, d, req):
+            raise RuntimeError("MatchProducts failed: " + last_error())
+        return self._product_dict(d, req)
+
+    def match_async_products(self, img_left, img_right, disp_left, products):
+        """match_async plus the products of the request (HOST addresses; adc_match_async_products): only enqueues, wait() delivers the
+        map and every product.  The images may be reused at once; disp_left and the request's arrays are kept alive until wait()."""
+        l, r = _img(img_left), _img(img_right)
+        assert products is None or products.sizes_ok(self.width * self.height)
+        self._keep = (l, r, disp_left, products)
+        return lib().adc_match_async_products(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data,
+                                              None if products is None else C.byref(products)) == 0
+
+    def match_device_products(self, d_left, d_right, d_disp, products):
+        """match_device plus the products of the request into the caller's DEVICE buffers (Products.from_addresses);
+        asynchronous, call wait(), then cloud_count()."""
+        return lib().adc_match_device_products(self._h, d_left, d_right, d_disp, None if products is None else C.byref(products)) == 0
+
+    def disp16_device(self, d_disp, scale, d_disp16):
+        """The 16-bit fixed-point kernel alone on any device-resident float32 [H][W] map of this geometry (adc_disp16_device);
+        d_disp16: uint16 [H][W] device buffer; asynchronous, call wait()."""
+        return lib().adc_disp16_device(self._h, d_disp, float(scale), d_disp16) == 0
 
     def cloud_count(self):
         n = C.c_uint64(0)

@@ -69,6 +69,25 @@ struct AdcOutReq {
     uint8_t* disp8;
 };
 
+// The host side of a products Match (adc_match_products / adc_match_async_products / adc_farm_submit_products): where adc_wait
+// delivers each product.  The kernels write the handle's device scratch (xs_*, os_*); enqueue_output sends every map behind them to
+// its pinned staging block (or straight into a destination the caller has registered), adc_wait copies staging -> caller and, once
+// the count is known, the first min(count, capacity) points of the cloud.
+#define ADC_PROD_MAPS 5 // provenance, confidence, depth, disp8, disp16
+struct AdcProdMap {
+    void* dst;         // the caller's host buffer; NULL = not requested
+    const void* dev;   // the device scratch it comes from
+    size_t bytes;
+    int direct;        // dst lies in a registered range: the stream writes it in place
+};
+struct AdcProdReq {
+    int active;        // kept until adc_wait (its redos send the maps again), forgotten by abort_match
+    AdcProdMap map[ADC_PROD_MAPS];
+    adc_point* cloud;  // host
+    uint32_t capacity;
+    uint32_t* cloud_count; // host word, written at delivery
+};
+
 // One side of the optional rectification (k_rectify.hip): the declared geometry of the raw images, and what the set call made of
 // the maps.  The [H][W] buffers are allocated by the first set call of a handle (both sides at once), the raw buffer grows with the
 // largest geometry declared; adc_destroy frees them.
@@ -221,6 +240,11 @@ struct adc_handle {
     void* os_cloud;
     uint32_t os_cloud_cap; // points os_cloud holds
     uint8_t* os_disp8;
+    uint16_t* x_disp16;   // adc_*_products: where this Match's 16-bit map goes (the caller's device buffer or the scratch below; NULL:
+    float x_disp16_scale; // not requested); kept until adc_wait, so that its redos write it again
+    uint16_t* os_disp16;  // device scratch of the host products calls, allocated on the first call that needs it
+    AdcProdReq prod;      // host delivery of the products Match in flight (prod.active)
+    void* ps_map[ADC_PROD_MAPS]; // pinned staging of the asynchronous host delivery, each allocated by the first call that needs it
     // optional speckle filter (k_speckle.hip; off = sp_max_size <= 0: nothing of it is enqueued)
     int32_t sp_max_size;  // handle state (adc_set_speckle_filter): every later Match filters its delivered map
     float sp_max_diff;
@@ -302,6 +326,7 @@ size_t adc_outputs_scratch_bytes(int W, int H);                 // k_outputs.hip
 hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img); // disp -> depth, min / max words, tile counts
 hipError_t adc_launch_out_scan(adc_handle* h);                  // tile counts -> tile bases, count words
 hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img);    // disp, img -> disp8, cloud
+hipError_t adc_launch_disp16(adc_handle* h, const float* disp, float scale, uint16_t* out);                  // disp -> 16-bit fixed point (k_disp16)
 size_t adc_speckle_scratch_words(int W, int H);                 // k_speckle.hip: int32 words of sp_parent
 hipError_t adc_launch_speckle_runs(adc_handle* h, const float* src, float max_diff);    // src -> row runs in parent, size = 0, stat words = 0
 hipError_t adc_launch_speckle_merge(adc_handle* h, const float* src, float max_diff);   // unions across rows and 64-pixel pieces

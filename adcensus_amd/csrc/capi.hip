@@ -331,11 +331,12 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->sp_parent, h->sp_map,
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->os_disp16, h->sp_parent, h->sp_map,
                     h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw,
                     h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->ev_pin) hipHostFree(h->ev_pin);
+    for (void* b : h->ps_map) if (b) hipHostFree(b);
     if (h->pin_raw) hipHostFree(h->pin_raw);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -556,6 +557,13 @@ static hipError_t enqueue_output(adc_handle* h)
     else if (h->async_dst) e = ADC_HIP(hipMemcpyAsync(h->pin_out, map, P * 4, hipMemcpyDeviceToHost, h->stream));
     else if (h->device_dst) e = ADC_HIP(hipMemcpyAsync(h->device_dst, map, P * 4, hipMemcpyDeviceToDevice, h->stream));
     if (e == hipSuccess && h->out.active) e = enqueue_outputs(h, map, h->img_l);
+    if (e == hipSuccess && h->x_disp16) e = ADC_HIP(adc_launch_disp16(h, map, h->x_disp16_scale, h->x_disp16));
+    // a products Match of a host caller: every map product behind the kernel that wrote it (the provenance map behind the speckle
+    // filter's mark) -> its pinned staging, or straight into a destination the caller has registered
+    for (int i = 0; e == hipSuccess && h->prod.active && i < ADC_PROD_MAPS; i++) {
+        const AdcProdMap& m = h->prod.map[i];
+        if (m.dst) e = ADC_HIP(hipMemcpyAsync(m.direct ? m.dst : h->ps_map[i], m.dev, m.bytes, hipMemcpyDeviceToHost, h->stream));
+    }
     return e;
 }
 
@@ -626,6 +634,8 @@ static void abort_match(adc_handle* h)
     h->device_dst = nullptr;
     h->x_prov = nullptr; h->x_conf = nullptr;
     h->out.active = 0;
+    h->x_disp16 = nullptr;
+    h->prod.active = 0;
     h->ev_pending = 0;
     if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
@@ -836,7 +846,20 @@ int adc_wait(adc_handle* h)
         h->async_dst = nullptr;
     }
     h->device_dst = nullptr;
+    if (h->prod.active) { // a products Match of a host caller: staging -> the caller's buffers, then the points that exist
+        const AdcProdReq r = h->prod;
+        for (int i = 0; i < ADC_PROD_MAPS; i++)
+            if (r.map[i].dst && !r.map[i].direct) memcpy(r.map[i].dst, h->ps_map[i], r.map[i].bytes);
+        if (r.cloud || r.cloud_count) {
+            const uint32_t count = (uint32_t)h->pin_flags[8];
+            const size_t n = count < r.capacity ? count : r.capacity;
+            if (n && r.cloud && ADC_HIP(hipMemcpy(r.cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: cloud copy-out", hipGetLastError()); abort_match(h); return 2; }
+            if (r.cloud_count) *r.cloud_count = count;
+        }
+        h->prod.active = 0;
+    }
     h->x_prov = nullptr; h->x_conf = nullptr;
+    h->x_disp16 = nullptr;
     h->out.active = 0;
     if (h->ev_pending) { // an evaluation has completed: its report words have arrived in the pinned block (adc_get_eval_report)
         h->ev_report = h->ev_echo;
@@ -1023,6 +1046,134 @@ int adc_get_cloud_count(adc_handle* h, uint64_t* count)
     return 0;
 }
 
+// ------------------------------------------------------------------------------ every product through one request (adc_products)
+// One path for the four Match entry points: the request is validated and resolved into the per-Match state the kernels already look
+// at (x_prov / x_conf, out, x_disp16), the host callers additionally into prod (where adc_wait delivers).  Everything is enqueued by
+// the existing stages and by enqueue_output, so every redo of adc_wait rewrites every product from the map it delivers.
+static bool match_in_flight(const adc_handle* h);
+static bool products_requested(const adc_products* p) { return p && (p->provenance || p->confidence || outputs_requested(&p->out) || p->disp16); }
+
+static void products_forget(adc_handle* h)
+{
+    h->x_prov = nullptr; h->x_conf = nullptr;
+    h->out.active = 0;
+    h->x_disp16 = nullptr;
+    h->prod.active = 0;
+}
+
+// what all three forms refuse; 0, or 1 (adc_last_error) / 2 (scratch of the outputs).  On 0 h->out holds the resolved outputs (inactive).
+static int products_check(adc_handle* h, const adc_products* p, const char* who, bool device_pointers)
+{
+    if (match_in_flight(h)) { g_last_error = std::string(who) + ": a Match is pending (adc_wait first)"; return 1; }
+    if ((p->provenance || p->confidence) && !extras_allowed(h, who)) return 1;
+    if (p->disp16 && !(__builtin_isfinite(p->disp16_scale) && p->disp16_scale > 0.0f)) { g_last_error = std::string(who) + ": disp16_scale must be finite and > 0"; return 1; }
+    if (p->disp16 && device_pointers && ((uintptr_t)p->disp16 & 1u)) { g_last_error = std::string(who) + ": the device address of disp16 must be even"; return 1; }
+    if (outputs_requested(&p->out)) return outputs_prepare(h, &p->out, who, device_pointers);
+    memset(&h->out, 0, sizeof(h->out));
+    return 0;
+}
+
+int adc_match_device_products(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_products* p)
+{
+    if (!products_requested(p)) return adc_match_device(h, d_left, d_right, d_disp);
+    if (!h || !d_left || !d_right || !d_disp) return 1;
+    hipSetDevice(h->device);
+    int rc = products_check(h, p, "adc_match_device_products", true);
+    if (rc != 0) return rc;
+    h->x_prov = p->provenance;
+    h->x_conf = p->confidence;
+    h->out.active = outputs_requested(&p->out) ? 1 : 0;
+    h->x_disp16 = p->disp16;
+    h->x_disp16_scale = p->disp16_scale;
+    rc = adc_match_device(h, d_left, d_right, d_disp);
+    if (rc != 0) products_forget(h);
+    return rc;
+}
+
+// first use of a product by a host caller: its device scratch and its pinned staging block
+static hipError_t products_map_buffers(adc_handle* h, int i, void** dev, size_t bytes, bool staged)
+{
+    if (!*dev) {
+        const hipError_t e = ADC_HIP(hipMalloc(dev, bytes));
+        if (e != hipSuccess) { *dev = nullptr; return e; }
+    }
+    if (staged && !h->ps_map[i]) {
+        const hipError_t e = ADC_HIP(hipHostMalloc(&h->ps_map[i], bytes, hipHostMallocDefault));
+        if (e != hipSuccess) { h->ps_map[i] = nullptr; return e; }
+    }
+    return hipSuccess;
+}
+
+static int match_products_impl(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p, bool sync_call, const char* who)
+{
+    if (!h || !left || !right || !disp) return 1;
+    hipSetDevice(h->device);
+    int rc = products_check(h, p, who, false);
+    if (rc != 0) return rc;
+    const size_t P = (size_t)h->p.W * h->p.H;
+    AdcProdReq r;
+    memset(&r, 0, sizeof(r));
+    void* host[ADC_PROD_MAPS] = {p->provenance, p->confidence, p->out.depth, p->out.disp8, p->disp16};
+    void** dev[ADC_PROD_MAPS] = {(void**)&h->xs_prov, (void**)&h->xs_conf, (void**)&h->os_depth, (void**)&h->os_disp8, (void**)&h->os_disp16};
+    const size_t bytes[ADC_PROD_MAPS] = {P, P * 4, P * 4, P, P * 2};
+    hipError_t e = hipSuccess;
+    for (int i = 0; e == hipSuccess && i < ADC_PROD_MAPS; i++) {
+        if (!host[i]) continue;
+        r.map[i].dst = host[i];
+        r.map[i].bytes = bytes[i];
+        r.map[i].direct = host_registered(host[i], bytes[i]) ? 1 : 0;
+        e = products_map_buffers(h, i, dev[i], bytes[i], !r.map[i].direct);
+        r.map[i].dev = *dev[i];
+    }
+    const uint32_t cap = h->out.capacity;
+    if (e == hipSuccess && p->out.cloud && (!h->os_cloud || h->os_cloud_cap < cap)) { // (grows with the largest capacity asked for; at least one point)
+        if (h->os_cloud) hipFree(h->os_cloud);
+        h->os_cloud_cap = cap > 0 ? cap : 1;
+        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
+    }
+    if (e != hipSuccess) { set_error((std::string(who) + ": scratch").c_str(), e); (void)hipGetLastError(); return 2; }
+    if (p->out.cloud) { r.cloud = p->out.cloud; r.capacity = cap; r.cloud_count = p->out.cloud_count; }
+    h->x_prov = p->provenance ? h->xs_prov : nullptr;
+    h->x_conf = p->confidence ? h->xs_conf : nullptr;
+    h->out.depth = p->out.depth ? h->os_depth : nullptr;
+    h->out.disp8 = p->out.disp8 ? h->os_disp8 : nullptr;
+    h->out.cloud = p->out.cloud ? h->os_cloud : nullptr;
+    h->out.cloud_count = nullptr;
+    h->out.active = outputs_requested(&p->out) ? 1 : 0;
+    h->x_disp16 = p->disp16 ? h->os_disp16 : nullptr;
+    h->x_disp16_scale = p->disp16_scale;
+    r.active = 1;
+    h->prod = r;
+    rc = match_async_impl(h, left, right, disp, sync_call);
+    if (rc != 0) products_forget(h);
+    return rc;
+}
+
+int adc_match_async_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
+{
+    if (!products_requested(p)) return adc_match_async(h, left, right, disp);
+    return match_products_impl(h, left, right, disp, p, false, "adc_match_async_products");
+}
+
+int adc_match_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
+{
+    if (!products_requested(p)) return adc_match(h, left, right, disp);
+    const int rc = match_products_impl(h, left, right, disp, p, true, "adc_match_products");
+    return rc != 0 ? rc : adc_wait(h);
+}
+
+int adc_disp16_device(adc_handle* h, const void* d_disp, float scale, void* d_disp16)
+{
+    if (!h) return 1;
+    if (!d_disp || !d_disp16) { g_last_error = "adc_disp16_device: null map"; return 1; }
+    if (!(__builtin_isfinite(scale) && scale > 0.0f)) { g_last_error = "adc_disp16_device: scale must be finite and > 0"; return 1; }
+    if ((uintptr_t)d_disp16 & 1u) { g_last_error = "adc_disp16_device: the device address of disp16 must be even"; return 1; }
+    hipSetDevice(h->device);
+    const hipError_t e = ADC_HIP(adc_launch_disp16(h, static_cast<const float*>(d_disp), scale, static_cast<uint16_t*>(d_disp16)));
+    if (e != hipSuccess) { set_error("adc_disp16_device", e); abort_match(h); return 2; }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------ speckle filter (k_speckle.hip)
 // Handle state; enqueue_output runs the filter on disp_l into sp_map in front of the copy-out and the outputs, so every redo
 // of adc_wait (each ends in enqueue_output) refilters the recomputed map.
@@ -1050,7 +1201,7 @@ static int speckle_scratch(adc_handle* h, bool with_map, const char* who)
     return 0;
 }
 
-static bool match_in_flight(const adc_handle* h) { return h->match_pending || h->async_dst || h->device_dst || h->out.active; }
+static bool match_in_flight(const adc_handle* h) { return h->match_pending || h->async_dst || h->device_dst || h->out.active || h->prod.active || h->x_disp16; }
 
 int adc_set_speckle_filter(adc_handle* h, int32_t max_size, float max_diff)
 {
@@ -1513,9 +1664,13 @@ static int farm_collect(adc_farm* f, size_t slot)
     if (rc == 0) f->delivered++;
     return rc;
 }
-int adc_farm_submit(adc_farm* f, const uint8_t* left, const uint8_t* right, float* disp, uint64_t* ticket)
+static int farm_submit_impl(adc_farm* f, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* products, uint64_t* ticket)
 {
     if (!f || !left || !right || !disp) return 1;
+    if (products && products->out.cloud && !products->out.cloud_count) { // (there is no per-ticket getter: the count travels with the pair)
+        g_last_error = "adc_farm_submit_products: a cloud needs cloud_count";
+        return 1;
+    }
     const uint64_t t = f->next_ticket;
     const size_t slot = (size_t)((t - 1) % f->pipes.size());
     // the pipeline's previous pair (if any) must be delivered before its staging is reused.  When THAT pair failed, the new
@@ -1524,7 +1679,7 @@ int adc_farm_submit(adc_farm* f, const uint8_t* left, const uint8_t* right, floa
     const uint64_t prev = f->in_flight[slot];
     const int rc_prev = farm_collect(f, slot);
     const std::string prev_error = rc_prev != 0 ? g_last_error : std::string();
-    int rc = adc_match_async(f->pipes[slot], left, right, disp);
+    int rc = products ? adc_match_async_products(f->pipes[slot], left, right, disp, products) : adc_match_async(f->pipes[slot], left, right, disp);
     if (rc != 0) {
         // nothing was enqueued; when the pipeline's previous pair failed as well, say so first (its output is invalid too)
         if (rc_prev != 0)
@@ -1540,6 +1695,14 @@ int adc_farm_submit(adc_farm* f, const uint8_t* left, const uint8_t* right, floa
         return ADC_FARM_PREVIOUS_FAILED;
     }
     return 0;
+}
+int adc_farm_submit(adc_farm* f, const uint8_t* left, const uint8_t* right, float* disp, uint64_t* ticket)
+{
+    return farm_submit_impl(f, left, right, disp, nullptr, ticket);
+}
+int adc_farm_submit_products(adc_farm* f, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* products, uint64_t* ticket)
+{
+    return farm_submit_impl(f, left, right, disp, products, ticket);
 }
 int adc_farm_wait(adc_farm* f, uint64_t ticket)
 {

@@ -7,6 +7,7 @@
 //   k_out_scan      one workgroup: exclusive scan of the tile counts (a few thousand) in place, total -> the count words
 //   k_out_emit      reads the map again: the 8-bit image from the finished min / max, the points behind their tile's base
 // Only what was asked for runs: depth alone is the first launch, the image alone the first and the third.
+// A fourth kernel, k_disp16, is independent of the three: the map in 16-bit fixed point (adc_products.disp16).
 //
 // Arithmetic: IEEE binary32, one rounding per operation (-ffp-contract=off, pragma in adc_device_fn.h), correctly rounded
 // divisions.  a = |d|.  The min / max use that for non-negative floats (and +inf is excluded, a >= +0) the unsigned order of
@@ -213,6 +214,59 @@ __global__ __launch_bounds__(OUT_WG) void k_out_emit(const OutArgs g)
         }
         pos += (uint32_t)__popcll(m);
     }
+}
+
+// The 16-bit fixed-point map (include/adcensus_c_api.h: adc_products.disp16): a = |d|; not finite -> 0; otherwise
+// (uint16_t)fminf(fmaxf(a * scale, 1.0f), 65535.0f) -- one multiply, one rounding; an overflowing product is +inf and saturates.
+// A streaming kernel of its own: 4 bytes in, 2 bytes out per pixel, nothing shared between lanes.
+__device__ __forceinline__ uint16_t disp16_pixel(float d, float scale)
+{
+    const float a = __builtin_fabsf(d);
+    if (!__builtin_isfinite(a)) return 0;
+    const float p = a * scale;
+    return (uint16_t)fminf(fmaxf(p, 1.0f), 65535.0f);
+}
+
+typedef float disp16_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned short disp16_u4 __attribute__((ext_vector_type(4)));
+#define DISP16_WG 256
+#define DISP16_PER_LANE 4
+
+// vec (uniform): disp is 16-byte and out 8-byte aligned -- a lane owns 4 consecutive pixels, one 16-byte load and one 8-byte store;
+// the lane that holds the end of the map walks its pixels one by one.  Otherwise the element-wise form: lane l of a workgroup
+// owns pixels base + l, base + 256 + l, ... of the workgroup's 1024.
+__global__ __launch_bounds__(DISP16_WG) void k_disp16(const float* __restrict__ disp, uint16_t* __restrict__ out, int P, float scale, int vec)
+{
+    const int base = (int)blockIdx.x * (DISP16_WG * DISP16_PER_LANE);
+    if (vec) {
+        const int i = base + (int)threadIdx.x * DISP16_PER_LANE;
+        if (i + DISP16_PER_LANE <= P) {
+            const disp16_f4 v = *reinterpret_cast<const disp16_f4*>(disp + i);
+            disp16_u4 r;
+            r.x = disp16_pixel(v.x, scale);
+            r.y = disp16_pixel(v.y, scale);
+            r.z = disp16_pixel(v.z, scale);
+            r.w = disp16_pixel(v.w, scale);
+            *reinterpret_cast<disp16_u4*>(out + i) = r;
+        } else {
+            for (int k = i; k < P; k++) out[k] = disp16_pixel(disp[k], scale);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < DISP16_PER_LANE; k++) {
+        const int i = base + k * DISP16_WG + (int)threadIdx.x;
+        if (i < P) out[i] = disp16_pixel(disp[i], scale);
+    }
+}
+
+hipError_t adc_launch_disp16(adc_handle* h, const float* disp, float scale, uint16_t* out)
+{
+    const int P = h->p.W * h->p.H;
+    const int vec = (((uintptr_t)disp & 15u) == 0 && ((uintptr_t)out & 7u) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_disp16, dim3((unsigned)((P + DISP16_WG * DISP16_PER_LANE - 1) / (DISP16_WG * DISP16_PER_LANE))), dim3(DISP16_WG), 0, h->stream,
+                       disp, out, P, scale, vec);
+    return hipGetLastError();
 }
 
 size_t adc_outputs_scratch_bytes(int W, int H)

@@ -120,6 +120,16 @@ unsigned long long ADCensusStereo::CloudCount() const
     uint64_t n = 0;
     return impl_ && adc_get_cloud_count(impl_, &n) == 0 ? n : 0;
 }
+bool ADCensusStereo::MatchProducts(const uint8* l, const uint8* r, float32* d, const adc_products* products)
+{
+    if (!impl_ || !l || !r || !d) return false;
+    return adc_match_products(impl_, l, r, d, products) == 0;
+}
+bool ADCensusStereo::MatchAsyncProducts(const uint8* l, const uint8* r, float32* d, const adc_products* products)
+{
+    if (!impl_ || !l || !r || !d) return false;
+    return adc_match_async_products(impl_, l, r, d, products) == 0;
+}
 bool ADCensusStereo::Wait() { return impl_ && adc_wait(impl_) == 0; }
 bool ADCensusStereo::SetPaperModes(unsigned modes)
 {

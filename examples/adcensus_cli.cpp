@@ -370,6 +370,20 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_disp16 = false; // (--disp16 and its value likewise)
+    float disp16_scale = 0.f;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--disp16")) {
+            char tail = 0;
+            if (i + 1 >= argc || sscanf(argv[i + 1], "%f%c", &disp16_scale, &tail) != 1 || !std::isfinite(disp16_scale) || disp16_scale <= 0.f) {
+                printf("--disp16 needs SCALE (finite and > 0; 256 is KITTI's encoding)\n");
+                return -1;
+            }
+            with_disp16 = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     if (with_calib && with_gt) { printf("--calib and --gt are separate runs\n"); return -1; }
     if (with_calib && extras) { printf("--calib and --extras are separate runs\n"); return -1; }
     // file-format helpers that need no GPU (used by the CPU test tier):
@@ -471,8 +485,13 @@ int main(int argc, char** argv)
     std::vector<float32> depth(with_calib ? (size_t)w * h : 0);
     std::vector<adc_point> cloud(with_calib ? (size_t)w * h : 0);
     adc_outputs outputs = {&calib, depth.data(), cloud.data(), cloud.size(), nullptr, nullptr};
+    // --disp16: ONE Match through MatchProducts delivers the 16-bit map together with whatever the other options ask for
+    std::vector<uint16_t> disp16(with_disp16 ? (size_t)w * h : 0);
+    adc_products products = {extras ? provenance.data() : nullptr, extras ? confidence.data() : nullptr, {nullptr, nullptr, nullptr, 0, nullptr, nullptr},
+                             disp16.data(), disp16_scale, 0};
+    if (with_calib) products.out = outputs;
     t0 = std::chrono::steady_clock::now();
-    const bool ok = with_calib ? ad_census.MatchOut(left.data(), right.data(), disparity.data(), &outputs) : extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
+    const bool ok = with_disp16 ? ad_census.MatchProducts(left.data(), right.data(), disparity.data(), &products) : with_calib ? ad_census.MatchOut(left.data(), right.data(), disparity.data(), &outputs) : extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
                            : ad_census.Match(left.data(), right.data(), disparity.data());
     if (!ok) { printf("AD-Census matching failed: %s\n", ad_census.LastError()); return -2; }
     t1 = std::chrono::steady_clock::now();
@@ -556,6 +575,18 @@ int main(int argc, char** argv)
         }
         write_pfm(out + "-err.pfm", err.data(), w, h);
         if (!write_png(out + "-bad.png", rgb.data(), w, h, 3)) printf("cannot write %s-bad.png\n", out.c_str());
+    }
+    if (with_disp16) { // binary PGM, maxval 65535: two bytes per sample, most significant first
+        FILE* pgm = fopen((out + "-disp16.pgm").c_str(), "wb");
+        if (pgm) {
+            fprintf(pgm, "P5\n%d %d\n65535\n", w, h);
+            std::vector<uint8> row((size_t)w * 2);
+            for (int y = 0; y < h; y++) {
+                for (int x = 0; x < w; x++) { const uint16_t v = disp16[(size_t)y * w + x]; row[2 * x] = (uint8)(v >> 8); row[2 * x + 1] = (uint8)(v & 0xff); }
+                fwrite(row.data(), 1, row.size(), pgm);
+            }
+            fclose(pgm);
+        } else printf("cannot write %s-disp16.pgm\n", out.c_str());
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

@@ -13,7 +13,8 @@
  * MatchEx (per-pixel provenance and confidence maps next to the disparity), MatchOut (depth, point cloud and 8-bit image computed
  * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default),
  * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default),
- * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device).
+ * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device),
+ * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
 
@@ -21,6 +22,7 @@
 
 struct adc_handle;
 struct adc_outputs; // include/adcensus_c_api.h
+struct adc_products;
 struct adc_raw_format;
 struct adc_camera_model;
 struct adc_gt;
@@ -63,6 +65,15 @@ public:
     bool MatchOut(const uint8* img_left, const uint8* img_right, float32* disp_left, const adc_outputs* outputs);
     /** Valid pixels of the last MatchOut that asked for a cloud (whatever the capacity was). */
     unsigned long long CloudCount() const;
+    /** Match plus every optional product through ONE request (adc_match_products, include/adcensus_c_api.h: adc_products with host
+     *  pointers): provenance and confidence of MatchEx, depth / cloud / 8-bit image of MatchOut, and the map in 16-bit fixed point
+     *  (disp16, scale 256 = KITTI's encoding), all from the same Match.  A null request or one that asks for nothing is exactly
+     *  Match.  false where Match is false, and when the request is refused (what MatchEx and MatchOut refuse, a disp16_scale that is
+     *  not finite or <= 0, a Match pending). */
+    bool MatchProducts(const uint8* img_left, const uint8* img_right, float32* disp_left, const adc_products* products);
+    /** The same, only enqueued (adc_match_async_products): the images may be reused at once, Wait delivers the map and every
+     *  product; the product buffers belong to the library until then. */
+    bool MatchAsyncProducts(const uint8* img_left, const uint8* img_right, float32* disp_left, const adc_products* products);
     bool Wait();
     /** Opt-in paper features the reference declares / stores but does not implement (bit 0: 5x5 census, adcensus_types.h:39-42;
      *  bit 1: averaged instead of chained scanline paths; bit 2: right-image arms, cross_aggregator.h:91).  0 (default) = the

@@ -21,6 +21,9 @@
  *   adc_match_out /       the same Matches with outputs computed on the device from the final map: metric depth, a point
  *   adc_match_device_out  cloud in raster order, the min-max normalised 8-bit image; adc_reproject_device: the same from any map
  *   adc_match_async/wait  several objects in flight from one host thread
+ *   adc_match_products /  every optional product above from ONE Match through one request struct (adc_products), synchronous,
+ *   adc_match_async_products / adc_match_device_products / adc_farm_submit_products   asynchronous, device-resident and through the
+ *                         farm; plus a 16-bit fixed-point disparity map (adc_disp16_device: that kernel on any map)
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -121,7 +124,7 @@ int adc_match_device(adc_handle* h, const void* d_bgr_left, const void* d_bgr_ri
  * Either map pointer may be NULL; with both NULL the calls are exactly adc_match / adc_match_device.  Return codes are theirs,
  * plus 1 (with adc_last_error) when a map is requested on a handle with paper modes set.  adc_match_ex allocates device scratch
  * for the maps on the first call that needs it (freed by adc_destroy).  adc_match_device_ex writes the caller's device buffers
- * directly and, like adc_match_device, is completed by adc_wait.  adc_match_async and the farm deliver no maps.
+ * directly and, like adc_match_device, is completed by adc_wait.  adc_match_async_products and adc_farm_submit_products (below) deliver the maps on the asynchronous paths.
  * ------------------------------------------------------------------------------------------- */
 #define ADC_LR_CONSISTENT 0
 #define ADC_LR_MISMATCH 1
@@ -169,7 +172,8 @@ int adc_match_device_ex(adc_handle* h, const void* d_bgr_left, const void* d_bgr
  * adc_reproject_device  the same kernels on any device-resident float32 [H][W] map of the handle's geometry, without a Match
  *                       (d_bgr_left is needed for a cloud only); completed by adc_wait.  Refused while a Match with outputs is
  *                       pending.  A caller of adc_match_device_ex gets depth and points this way.
- * Every redo adc_wait can take rewrites the outputs from the map it delivers.  adc_match_async and the farm deliver none.
+ * Every redo adc_wait can take rewrites the outputs from the map it delivers.  adc_match_async_products and
+ * adc_farm_submit_products (below) deliver them on the asynchronous paths.
  * ------------------------------------------------------------------------------------------- */
 typedef struct adc_calib {
     float focal_px, baseline, cx, cy, doffs;
@@ -415,7 +419,8 @@ int adc_farm_set_input_format(adc_farm* f, int side, const adc_raw_format* raw);
  * Return codes: 0; 1 with adc_last_error and nothing enqueued or changed (NULL handle / map / left ground truth, an unknown format, a
  * bad scale, occ_thres or pitch, more than ADC_EVAL_MAX_THRESHOLDS thresholds, a threshold negative or not finite, a confidence map
  * without a provenance map, no ground truth set, a Match pending); 2 on a HIP failure (a failed set call leaves ground truth unset,
- * the handle stays usable).  There is no farm entry point: ground truth differs per pair.
+ * the handle stays usable).  The farm has no evaluation entry point: ground truth differs per pair (every other product goes
+ * through adc_farm_submit_products).
  * ------------------------------------------------------------------------------------------- */
 #define ADC_GT_U8 0
 #define ADC_GT_U16 1
@@ -464,6 +469,57 @@ int adc_evaluate_device(adc_handle* h, const void* d_disp, const void* d_provena
 int adc_evaluate(adc_handle* h, const float* disp, const uint8_t* provenance, const float* confidence, const adc_eval_params* params,
                  float* err, uint8_t* eval_class, adc_eval_report* out);
 int adc_get_eval_report(adc_handle* h, adc_eval_report* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Every optional product of a Match through ONE request, on every path: synchronous, asynchronous, device-resident, pair farm.
+ *
+ * adc_products  provenance / confidence as in adc_match_ex, an embedded adc_outputs (calib, depth, cloud, cloud_capacity,
+ *               cloud_count, disp8) with the meaning of adc_match_out, and
+ * disp16        uint16 [H][W], the delivered map in 16-bit fixed point (k_outputs.hip: k_disp16; tests/products_ref.py holds the
+ *               definition in numpy, all binary32): a = fabsf(d); a not finite (+inf, -inf, NaN) -> 0; otherwise p = a * disp16_scale
+ *               (one rounding), q = fminf(fmaxf(p, 1.0f), 65535.0f), pixel = (uint16_t)q (truncating).  0 means "invalid" and nothing
+ *               else: a valid disparity of exactly 0 becomes 1, products above 65535 saturate.  It is the inverse of the ADC_GT_U16
+ *               decode (g = v / scale, 0 unknown): a map written with scale 256 can be scored as KITTI-encoded ground truth, and
+ *               wherever 1 < q < 65535 it decodes back within 1 / scale.  2 bytes per pixel instead of 4 on the way to the host.
+ *
+ * Any product pointer may be NULL.  A NULL request, or one that asks for nothing, makes each call exactly its plain entry point
+ * (adc_match, adc_match_async, adc_match_device, adc_farm_submit).  The request struct and *calib are read before the call returns.
+ * All products describe the DELIVERED map: with the speckle filter on they come from the filtered map and ADC_PROV_SPECKLE is set,
+ * with rectification / an input format on the cloud colours come from the rectified left image, and every redo adc_wait can take
+ * rewrites them.
+ *
+ * adc_match_products         HOST pointers, synchronous.
+ * adc_match_async_products   HOST pointers, only enqueues; adc_wait completes it and delivers every product.  The images may be reused
+ *                            as soon as the call returns; the product buffers belong to the library until adc_wait returns.  Each
+ *                            product travels device -> pinned staging on the stream (allocated by the first call that needs it,
+ *                            freed by adc_destroy) and is copied to the caller by adc_wait; a destination inside an
+ *                            adc_host_register'ed range is written in place.  The cloud is copied by adc_wait once the count is
+ *                            known: min(count, capacity) points and nothing behind them; cloud_count is a host uint32 here.
+ * adc_match_device_products  DEVICE addresses, written directly; completed by adc_wait; the borrow rules of adc_match_device.
+ * adc_farm_submit_products   adc_farm_submit with a request: ordered delivery by adc_farm_wait, adc_farm_drain or the next submit on
+ *                            the pipeline, the same return codes (ADC_FARM_PREVIOUS_FAILED included).  With a cloud, cloud_count (a
+ *                            host uint32, written at delivery) is required: the farm has no per-ticket getter.
+ * adc_disp16_device          the disp16 kernel alone on any device-resident float32 [H][W] map of the handle's geometry; asynchronous
+ *                            on the handle's stream, completed by adc_wait (the counterpart of adc_reproject_device).
+ * Refused with 1 and adc_last_error, nothing enqueued, the handle stays usable: everything adc_match_ex and adc_match_out refuse
+ * (maps with paper modes set, depth without a calibration, a bad calibration, an unaligned device cloud address), a disp16 request
+ * whose disp16_scale is not finite or <= 0, an odd device address for disp16, a farm cloud without cloud_count, a products call
+ * while a Match is pending on the handle (adc_wait first).  2 on a HIP failure.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct adc_products {
+    uint8_t* provenance; /* uint8 [H][W] or NULL */
+    float* confidence;   /* float32 [H][W] or NULL */
+    adc_outputs out;     /* depth / cloud / disp8, as in adc_match_out */
+    uint16_t* disp16;    /* uint16 [H][W] or NULL */
+    float disp16_scale;  /* looked at only with disp16: finite and > 0 (256: KITTI's encoding) */
+    uint32_t reserved_;
+} adc_products;
+int adc_match_products(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, const adc_products* products);
+int adc_match_async_products(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, const adc_products* products);
+int adc_match_device_products(adc_handle* h, const void* d_bgr_left, const void* d_bgr_right, void* d_disp_left, const adc_products* products);
+int adc_farm_submit_products(adc_farm* f, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, const adc_products* products,
+                             uint64_t* ticket);
+int adc_disp16_device(adc_handle* h, const void* d_disp, float scale, void* d_disp16);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
