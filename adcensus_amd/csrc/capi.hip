@@ -1788,7 +1788,11 @@ const char* adc_stage_name(int s)
 }
 int adc_set_paper_modes(adc_handle* h, uint32_t modes)
 {
-    if (!h || (modes & ~(ADC_PAPER_CENSUS5X5 | ADC_PAPER_SO_SUM | ADC_PAPER_RIGHT_ARMS))) return 1;
+    if (!h) { g_last_error = "adc_set_paper_modes: null handle"; return 1; }
+    if (modes & ~(ADC_PAPER_CENSUS5X5 | ADC_PAPER_SO_SUM | ADC_PAPER_RIGHT_ARMS)) {
+        g_last_error = "adc_set_paper_modes: unknown mode bits " + std::to_string((unsigned)modes);
+        return 1;
+    }
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
     if ((modes & ADC_PAPER_RIGHT_ARMS) && !(h->arms_r && h->bgrx_r && h->armmax_r)) {

@@ -741,7 +741,13 @@ hipError_t adc_voting_finish(adc_handle* h, int* continued)
     hipError_t e;
     int32_t* st = h->pin_flags + 16;
     int guard = 0;
-    while (st[0] != IRV_DONE) {
+    // A chain whose write-back kernel (FINAL) was the LAST kernel of the budget has finished as well: the result is in disp_l and the
+    // state it published carries the statistics.  Continuing it would only run idle kernels -- and report *continued, upon which
+    // adc_wait redoes the stages behind the voting on a map the first run of those stages has already interpolated IN PLACE: the
+    // final map comes out the same, but the provenance kernel then finds every interpolated pixel finite and calls it voted.
+    const bool ended_on_final = st[0] == IRV_FINAL_WB;
+    if (ended_on_final) st[7] = h->irv_chain; // (the first kernel with nothing left to do would have been the next one)
+    while (st[0] != IRV_DONE && !ended_on_final) {
         *continued = 1;
         if ((e = irv_launch(h, h->irv_chain, 64)) != hipSuccess) return e;
         h->irv_chain += 64;
