@@ -584,18 +584,24 @@ class ADCensusStereo:
         return d
 
     # -- additive API --------------------------------------------------------------------------
-    def MatchEx(self, img_left, img_right, disp_left, provenance=None, confidence=None):
-        """Match plus the optional per-pixel maps (adc_match_ex): provenance uint8 [H][W] (code = lr | fill << 2, LR_* / FILL_*),
-        confidence float32 [H][W]; either may be None (both None: exactly Match).  False where Match is, and on a handle with paper
-        modes set when a map is requested."""
-        if not self._h:
-            return False
-        if img_left is None or img_right is None or disp_left is None:
-            return False
+    def _match_args(self, img_left, img_right, disp_left):
+        """what MatchEx / MatchOut / MatchProducts check first: None where Match returns False, else (left, right, pixels)"""
+        if not self._h or img_left is None or img_right is None or disp_left is None:
+            return None
         l, r = _img(img_left), _img(img_right)
         n = self.width * self.height
         assert (l.size, r.size) == self._rect.sizes(n * 3)
         assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        return l, r, n
+
+    def MatchEx(self, img_left, img_right, disp_left, provenance=None, confidence=None):
+        """Match plus the optional per-pixel maps (adc_match_ex): provenance uint8 [H][W] (code = lr | fill << 2, LR_* / FILL_*),
+        confidence float32 [H][W]; either may be None (both None: exactly Match).  False where Match is, and on a handle with paper
+        modes set when a map is requested."""
+        args = self._match_args(img_left, img_right, disp_left)
+        if args is None:
+            return False
+        l, r, n = args
         for a, dt in ((provenance, np.uint8), (confidence, np.float32)):
             assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
         return lib().adc_match_ex(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data,
@@ -618,14 +624,10 @@ class ADCensusStereo:
         """Match plus the outputs computed on the device from the final map (adc_match_out) into the caller's arrays: depth
         float32 [H][W] (needs calib), cloud a POINT_DTYPE array (its length is the capacity), disp8 uint8 [H][W]; any may be None
         (all None: exactly Match).  False where Match is, and when the request is refused; cloud_count() tells how many points are valid."""
-        if not self._h:
+        args = self._match_args(img_left, img_right, disp_left)
+        if args is None:
             return False
-        if img_left is None or img_right is None or disp_left is None:
-            return False
-        l, r = _img(img_left), _img(img_right)
-        n = self.width * self.height
-        assert (l.size, r.size) == self._rect.sizes(n * 3)
-        assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        l, r, n = args
         for a, dt in ((depth, np.float32), (disp8, np.uint8)):
             assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n)
         assert cloud is None or (cloud.dtype == POINT_DTYPE and cloud.flags["C_CONTIGUOUS"])
@@ -664,12 +666,10 @@ class ADCensusStereo:
     def MatchProducts(self, img_left, img_right, disp_left, products):
         """Match plus every product the request asks for (adc_match_products; a Products with HOST addresses, e.g. Products.from_arrays),
         synchronous.  None or an empty request: exactly Match.  False where Match is, and when the request is refused."""
-        if not self._h or img_left is None or img_right is None or disp_left is None:
+        args = self._match_args(img_left, img_right, disp_left)
+        if args is None:
             return False
-        l, r = _img(img_left), _img(img_right)
-        n = self.width * self.height
-        assert (l.size, r.size) == self._rect.sizes(n * 3)
-        assert disp_left.dtype == np.float32 and disp_left.flags["C_CONTIGUOUS"] and disp_left.size == n
+        l, r, n = args
         assert products is None or products.sizes_ok(n)
         return lib().adc_match_products(self._h, l.ctypes.data, r.ctypes.data, disp_left.ctypes.data, None if products is None else C.byref(products)) == 0
 

@@ -55,8 +55,8 @@ struct AdcParams {
     adc_option opt;
 };
 
-// One request for the outputs computed from the final map (adc_match_out / adc_match_device_out / adc_reproject_device,
-// k_outputs.hip), validated and resolved to device addresses
+// The outputs computed from the final map (k_outputs.hip), validated and resolved to device addresses: part of a Match's request,
+// or the whole request of adc_reproject_device
 struct AdcOutReq {
     int active;           // kept until adc_wait, so that its redos (which call enqueue_output again) rewrite the outputs
     int calibrated;       // calib holds the caller's calibration, fb = focal_px * baseline (one f32 multiply on the host)
@@ -69,23 +69,39 @@ struct AdcOutReq {
     uint8_t* disp8;
 };
 
-// The host side of a products Match (adc_match_products / adc_match_async_products / adc_farm_submit_products): where adc_wait
-// delivers each product.  The kernels write the handle's device scratch (xs_*, os_*); enqueue_output sends every map behind them to
-// its pinned staging block (or straight into a destination the caller has registered), adc_wait copies staging -> caller and, once
-// the count is known, the first min(count, capacity) points of the cloud.
-#define ADC_PROD_MAPS 5 // provenance, confidence, depth, disp8, disp16
-struct AdcProdMap {
+// The optional map products of a Match, in the order of every per-map table (AdcMatchReq::host, adc_handle::map_buf)
+enum { ADC_MAP_PROV, ADC_MAP_CONF, ADC_MAP_DEPTH, ADC_MAP_DISP8, ADC_MAP_DISP16, ADC_REQ_MAPS };
+struct AdcHostMap {
     void* dst;         // the caller's host buffer; NULL = not requested
-    const void* dev;   // the device scratch it comes from
     size_t bytes;
-    int direct;        // dst lies in a registered range: the stream writes it in place
+    int direct;        // 0 = via pinned staging + host copy in adc_wait, 1 = dst lies in a registered range: the stream writes it in place,
+                       // 2 = blocking copy by adc_wait from the device scratch (adc_match_ex, adc_match_out)
 };
-struct AdcProdReq {
-    int active;        // kept until adc_wait (its redos send the maps again), forgotten by abort_match
-    AdcProdMap map[ADC_PROD_MAPS];
-    adc_point* cloud;  // host
+// Everything the Match in flight was asked for; all zero = idle (match_req_clear).  Every entry point is a view of this one
+// request: the kernels write the device targets (the caller's device buffers, or for host callers the handle's map_buf scratch),
+// enqueue_output sends every host map behind them to its pinned staging block (or straight into a destination the caller has
+// registered), adc_wait copies staging -> caller (adc_match_ex, adc_match_out: device scratch -> caller, blocking) and, once the count
+// is known, the first min(count, capacity) points of the cloud.
+// Kept until adc_wait, so that its redos write and send everything again.
+struct AdcMatchReq {
+    float* map_host;      // the disparity map: a host destination ...
+    int map_host_direct;  // 0 = via pin_out + host copy, 1 = DMA into the caller's page-locked map, 2 = pageable copy by adc_wait (ADC_HOST_DIRECT)
+    void* map_dev;        // ... or the caller's device buffer (re-filled by the median fallback)
+    uint8_t* prov;        // device targets of the provenance / confidence / 16-bit maps; NULL: not requested
+    float* conf;
+    uint16_t* disp16;
+    float disp16_scale;
+    AdcOutReq out;        // depth / cloud / 8-bit image (out.active)
+    int host_delivery;    // a host caller asked for products: the table below says where adc_wait delivers them
+    AdcHostMap host[ADC_REQ_MAPS];
+    adc_point* cloud;     // host
     uint32_t capacity;
     uint32_t* cloud_count; // host word, written at delivery
+};
+// what a host caller's map product goes through, each allocated by the first call that needs it
+struct AdcMapBuf {
+    void* dev;         // device scratch the kernels write
+    void* pin;         // pinned staging of the asynchronous delivery (none while no destination needed it)
 };
 
 // One side of the optional rectification (k_rectify.hip): the declared geometry of the raw images, and what the set call made of
@@ -103,6 +119,9 @@ struct AdcRectSide {
 };
 
 #define ADC_PIN_ARM 64 // pin_flags[ADC_PIN_ARM + i] = armmax[i] of the last Match (one copy at the end of the heavy stream)
+#define ADC_PIN_MEDIAN 0   // error flag of the banded median's hand-off (k_refine.hip)
+#define ADC_PIN_CLOUD 8    // point count of the last cloud (k_outputs.hip): adc_get_cloud_count
+#define ADC_PIN_SPECKLE 9  // three stat words of the last speckle filter run (k_speckle.hip): adc_get_speckle_stats
 struct adc_handle {
     AdcParams p;
     int device;
@@ -227,24 +246,11 @@ struct adc_handle {
     // pinned staging for adc_match / adc_match_async
     uint8_t* pin_in;  // 2 * 3*W*H
     float* pin_out;   // W*H
-    float* async_dst;
-    int async_dst_direct; // 0 = via pin_out + host copy, 1 = DMA into the caller's page-locked map, 2 = pageable copy by adc_wait (ADC_HOST_DIRECT)
-    void* device_dst;  // adc_match_device: the caller's device buffer (re-filled by the median fallback)
-    uint8_t* x_prov;   // adc_match_ex / adc_match_device_ex: where this Match's provenance / confidence maps go (the caller's device
-    float* x_conf;     // buffers or the scratch below; NULL: not requested); kept until adc_wait, so that its redos write them again
-    uint8_t* xs_prov;  // device scratch of adc_match_ex (host callers), allocated on the first call that needs it
-    float* xs_conf;
-    AdcOutReq out;        // outputs requested with this Match (out.active) -- the caller's device buffers or the scratch below
+    AdcMatchReq req;      // what the Match in flight was asked for
+    AdcMapBuf map_buf[ADC_REQ_MAPS]; // scratch and staging of the host callers' map products
     uint32_t* out_words;  // device scratch of k_outputs.hip (min / max words, count, tile counts), allocated on first use
-    float* os_depth;      // device scratch of adc_match_out (host callers), allocated on the first call that needs it
-    void* os_cloud;
+    void* os_cloud;       // device scratch of the host callers' cloud; grows with the largest capacity asked for
     uint32_t os_cloud_cap; // points os_cloud holds
-    uint8_t* os_disp8;
-    uint16_t* x_disp16;   // adc_*_products: where this Match's 16-bit map goes (the caller's device buffer or the scratch below; NULL:
-    float x_disp16_scale; // not requested); kept until adc_wait, so that its redos write it again
-    uint16_t* os_disp16;  // device scratch of the host products calls, allocated on the first call that needs it
-    AdcProdReq prod;      // host delivery of the products Match in flight (prod.active)
-    void* ps_map[ADC_PROD_MAPS]; // pinned staging of the asynchronous host delivery, each allocated by the first call that needs it
     // optional speckle filter (k_speckle.hip; off = sp_max_size <= 0: nothing of it is enqueued)
     int32_t sp_max_size;  // handle state (adc_set_speckle_filter): every later Match filters its delivered map
     float sp_max_diff;
@@ -320,8 +326,8 @@ hipError_t adc_launch_wta_left(adc_handle* h);                  // vol_a -> disp
 hipError_t adc_paper_aggregate(adc_handle* h, int iterations);  // k_paper.hip: aggregation limited by both images' arms
 hipError_t adc_paper_accumulate(adc_handle* h, float* acc, const float* src, int first, int last);
 hipError_t adc_launch_lrcheck(adc_handle* h);
-hipError_t adc_launch_confidence(adc_handle* h);                // k_extras.hip: vol_a -> x_conf (heavy stream, behind the WTA)
-hipError_t adc_launch_provenance(adc_handle* h);                // label, disp_l -> x_prov, x_conf = 0 where filled (object stream)
+hipError_t adc_launch_confidence(adc_handle* h);                // k_extras.hip: vol_a -> req.conf (heavy stream, behind the WTA)
+hipError_t adc_launch_provenance(adc_handle* h);                // label, disp_l -> req.prov, req.conf = 0 where filled (object stream)
 size_t adc_outputs_scratch_bytes(int W, int H);                 // k_outputs.hip: bytes of out_words
 hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img); // disp -> depth, min / max words, tile counts
 hipError_t adc_launch_out_scan(adc_handle* h);                  // tile counts -> tile bases, count words

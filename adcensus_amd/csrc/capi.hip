@@ -331,12 +331,15 @@ void adc_destroy(adc_handle* h)
     void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
                     h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->xs_prov, h->xs_conf, h->out_words, h->os_depth, h->os_cloud, h->os_disp8, h->os_disp16, h->sp_parent, h->sp_map,
+                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->out_words, h->os_cloud, h->sp_parent, h->sp_map,
                     h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw,
                     h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->ev_pin) hipHostFree(h->ev_pin);
-    for (void* b : h->ps_map) if (b) hipHostFree(b);
+    for (const AdcMapBuf& m : h->map_buf) {
+        if (m.dev) hipFree(m.dev);
+        if (m.pin) hipHostFree(m.pin);
+    }
     if (h->pin_raw) hipHostFree(h->pin_raw);
     if (h->pin_in) hipHostFree(h->pin_in);
     if (h->pin_out) hipHostFree(h->pin_out);
@@ -354,7 +357,7 @@ void adc_destroy(adc_handle* h)
 static hipError_t run_refine_tail(adc_handle* h)
 {
     const adc_option& o = h->p.opt;
-    if (h->x_prov || h->x_conf) HIP_OK(adc_launch_provenance(h)); // (adc_match_ex: reads the voted map before interpolation fills it)
+    if (h->req.prov || h->req.conf) HIP_OK(adc_launch_provenance(h)); // (reads the voted map before interpolation fills it)
     if (o.do_filling && o.do_lr_check) HIP_OK(adc_launch_interpolation(h));
     if (o.do_discontinuity_adjustment) HIP_OK(adc_launch_discontinuity(h));
     HIP_OK(adc_launch_median(h));
@@ -458,7 +461,7 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     }
     MARK(4, h->heavy);
     HIP_OK(adc_launch_wta(h));                   // ComputeDisparity + ComputeDisparityRight, :108-109
-    if (h->x_conf) HIP_OK(adc_launch_confidence(h)); // (adc_match_ex: one more read of the optimised volume)
+    if (h->req.conf) HIP_OK(adc_launch_confidence(h)); // (one more read of the optimised volume)
     MARK(5, h->heavy);
     // maxima + violation flag of this pair, looked at by adc_wait (they seed the next Match's assumption)
     // ... together with its record densities, which seed the next Match's choice between dense and sparse small-ring launches
@@ -512,23 +515,23 @@ static void collect_timings(adc_handle* h)
     }
 }
 
-// depth / point cloud / 8-bit image of h->out from a device-resident map (k_outputs.hip), on the object stream; only what was
+// depth / point cloud / 8-bit image of h->req.out from a device-resident map (k_outputs.hip), on the object stream; only what was
 // asked for is launched
 static hipError_t enqueue_outputs(adc_handle* h, const float* disp, const uint8_t* img)
 {
-    const AdcOutReq& r = h->out;
+    const AdcOutReq& r = h->req.out;
     if (r.disp8) HIP_OK(hipMemsetAsync(h->out_words, 0, 2 * sizeof(uint32_t), h->stream)); // (the min / max words)
     HIP_OK(adc_launch_out_measure(h, disp, img));
     if (r.cloud) {
         HIP_OK(adc_launch_out_scan(h));
-        HIP_OK(hipMemcpyAsync(h->pin_flags + 8, h->out_words + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream)); // adc_get_cloud_count
+        HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_CLOUD, h->out_words + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream)); // adc_get_cloud_count
     }
     if (r.cloud || r.disp8) HIP_OK(adc_launch_out_emit(h, disp, img));
     return hipSuccess;
 }
 
 // The speckle filter (k_speckle.hip) on a device-resident map: four launches with geometry-only grids, then the three stat words
-// on their way to pin_flags[9..11] (adc_get_speckle_stats).  dst == src filters in place; max_size <= 0 only labels.
+// on their way to pin_flags[ADC_PIN_SPECKLE..] (adc_get_speckle_stats).  dst == src filters in place; max_size <= 0 only labels.
 static hipError_t enqueue_speckle(adc_handle* h, const float* src, float* dst, int32_t max_size, float max_diff, int32_t* labels, uint8_t* prov)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
@@ -536,7 +539,7 @@ static hipError_t enqueue_speckle(adc_handle* h, const float* src, float* dst, i
     HIP_OK(adc_launch_speckle_merge(h, src, max_diff));
     HIP_OK(adc_launch_speckle_flatten(h, labels));
     if (max_size > 0) HIP_OK(adc_launch_speckle_apply(h, src, dst, prov, max_size));
-    HIP_OK(hipMemcpyAsync(h->pin_flags + 9, h->sp_parent + 2 * P, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_SPECKLE, h->sp_parent + 2 * P, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     return hipSuccess;
 }
 
@@ -550,19 +553,20 @@ static hipError_t enqueue_output(adc_handle* h)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
     hipError_t e = hipSuccess;
-    if (h->sp_max_size > 0 && (e = enqueue_speckle(h, h->disp_l, h->sp_map, h->sp_max_size, h->sp_max_diff, nullptr, h->x_prov)) != hipSuccess) return e;
+    const AdcMatchReq& r = h->req;
+    if (h->sp_max_size > 0 && (e = enqueue_speckle(h, h->disp_l, h->sp_map, h->sp_max_size, h->sp_max_diff, nullptr, r.prov)) != hipSuccess) return e;
     const float* map = delivered_map(h);
-    if (h->async_dst && h->async_dst_direct == 1) e = ADC_HIP(hipMemcpyAsync(h->async_dst, map, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
-    else if (h->async_dst && h->async_dst_direct == 2) e = hipSuccess; // (pageable, ADC_HOST_DIRECT: copied by adc_wait after the stream has drained)
-    else if (h->async_dst) e = ADC_HIP(hipMemcpyAsync(h->pin_out, map, P * 4, hipMemcpyDeviceToHost, h->stream));
-    else if (h->device_dst) e = ADC_HIP(hipMemcpyAsync(h->device_dst, map, P * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (e == hipSuccess && h->out.active) e = enqueue_outputs(h, map, h->img_l);
-    if (e == hipSuccess && h->x_disp16) e = ADC_HIP(adc_launch_disp16(h, map, h->x_disp16_scale, h->x_disp16));
-    // a products Match of a host caller: every map product behind the kernel that wrote it (the provenance map behind the speckle
-    // filter's mark) -> its pinned staging, or straight into a destination the caller has registered
-    for (int i = 0; e == hipSuccess && h->prod.active && i < ADC_PROD_MAPS; i++) {
-        const AdcProdMap& m = h->prod.map[i];
-        if (m.dst) e = ADC_HIP(hipMemcpyAsync(m.direct ? m.dst : h->ps_map[i], m.dev, m.bytes, hipMemcpyDeviceToHost, h->stream));
+    if (r.map_host && r.map_host_direct == 1) e = ADC_HIP(hipMemcpyAsync(r.map_host, map, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
+    else if (r.map_host && r.map_host_direct == 2) e = hipSuccess; // (pageable, ADC_HOST_DIRECT: copied by adc_wait after the stream has drained)
+    else if (r.map_host) e = ADC_HIP(hipMemcpyAsync(h->pin_out, map, P * 4, hipMemcpyDeviceToHost, h->stream));
+    else if (r.map_dev) e = ADC_HIP(hipMemcpyAsync(r.map_dev, map, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (e == hipSuccess && r.out.active) e = enqueue_outputs(h, map, h->img_l);
+    if (e == hipSuccess && r.disp16) e = ADC_HIP(adc_launch_disp16(h, map, r.disp16_scale, r.disp16));
+    // a host caller's products: every map behind the kernel that wrote it (the provenance map behind the speckle filter's mark)
+    // -> its pinned staging, or straight into a destination the caller has registered (direct == 2: copied by adc_wait, like the map)
+    for (int i = 0; e == hipSuccess && r.host_delivery && i < ADC_REQ_MAPS; i++) {
+        const AdcHostMap& m = r.host[i];
+        if (m.dst && m.direct != 2) e = ADC_HIP(hipMemcpyAsync(m.direct ? m.dst : h->map_buf[i].pin, h->map_buf[i].dev, m.bytes, hipMemcpyDeviceToHost, h->stream));
     }
     return e;
 }
@@ -614,6 +618,8 @@ static hipError_t enqueue_rectify(adc_handle* h, const void* raw_l, const void* 
 // scanline stage never consumed (round-5 advisor finding), speculation flags of launches that never ran -- and the caller's
 // buffers are forgotten.  What the handle has LEARNED from earlier pairs (arm maxima, chain budget) stays: it is verified on the
 // device for every pair anyway.
+static void match_req_clear(adc_handle* h) { memset(&h->req, 0, sizeof(h->req)); }
+
 static void abort_match(adc_handle* h)
 {
     if (h->heavy) hipStreamSynchronize(h->heavy);
@@ -630,14 +636,9 @@ static void abort_match(adc_handle* h)
     h->wta_left_done = 0;
     h->timings_pending = false;
     h->force_median_fallback = 0;
-    h->async_dst = nullptr;
-    h->device_dst = nullptr;
-    h->x_prov = nullptr; h->x_conf = nullptr;
-    h->out.active = 0;
-    h->x_disp16 = nullptr;
-    h->prod.active = 0;
+    match_req_clear(h);
     h->ev_pending = 0;
-    if (h->pin_flags) { h->pin_flags[0] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[9] = h->pin_flags[10] = h->pin_flags[11] = 0; }
+    if (h->pin_flags) { h->pin_flags[ADC_PIN_MEDIAN] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[ADC_PIN_SPECKLE] = h->pin_flags[ADC_PIN_SPECKLE + 1] = h->pin_flags[ADC_PIN_SPECKLE + 2] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
 }
@@ -661,8 +662,8 @@ int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, voi
     h->img_r = const_cast<uint8_t*>(static_cast<const uint8_t*>(d_right));
     }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
-    h->device_dst = d_disp;
-    h->async_dst = nullptr;
+    h->req.map_dev = d_disp;
+    h->req.map_host = nullptr;
     if (enqueue_output(h) != hipSuccess) { set_error("adc_match_device: output copy", hipGetLastError()); abort_match(h); return 2; }
     return 0;
 }
@@ -717,9 +718,9 @@ static int match_async_impl(adc_handle* h, const uint8_t* left, const uint8_t* r
     }
     if (rect && enqueue_rectify(h, dst_l, dst_r) != hipSuccess) { abort_match(h); return 2; }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
-    h->async_dst = disp;
-    h->async_dst_direct = host_registered(disp, P * 4) ? 1 : (direct ? 2 : 0);
-    h->device_dst = nullptr;
+    h->req.map_host = disp;
+    h->req.map_host_direct = host_registered(disp, P * 4) ? 1 : (direct ? 2 : 0);
+    h->req.map_dev = nullptr;
     if (enqueue_output(h) != hipSuccess) { set_error("adc_match: output copy", hipGetLastError()); abort_match(h); return 2; }
     return 0;
 }
@@ -826,9 +827,9 @@ int adc_wait(adc_handle* h)
     if (e != hipSuccess) { set_error("adc_wait: region voting continuation", e); abort_match(h); return 2; }
     // (3) a median band gave up waiting for its upstream band: the map is incomplete -- redo the filter with the
     //     single-workgroup kernel (no inter-workgroup dependency) and deliver that result
-    if (h->pin_flags && (h->pin_flags[0] != 0 || h->force_median_fallback)) {
-        e = adc_median_fallback(h); // (looks at pin_flags[0]: 2 = a speculative seam differed -> chained form first)
-        h->pin_flags[0] = 0;
+    if (h->pin_flags && (h->pin_flags[ADC_PIN_MEDIAN] != 0 || h->force_median_fallback)) {
+        e = adc_median_fallback(h); // (looks at pin_flags[ADC_PIN_MEDIAN]: 2 = a speculative seam differed -> chained form first)
+        h->pin_flags[ADC_PIN_MEDIAN] = 0;
         if (e == hipSuccess) e = enqueue_output(h);
         if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
         h->median_fallbacks++;
@@ -837,30 +838,26 @@ int adc_wait(adc_handle* h)
     h->force_median_fallback = 0;
     if (h->med_spec_off > 0 && h->med_spec_last == 0) h->med_spec_off--;
     else if (h->med_seg_off > 0 && h->med_seg_last <= 1) h->med_seg_off--; // (whole rows again because a segment seam had failed)
-    if (h->async_dst) {
-        if (h->async_dst_direct == 2) {
-            if (ADC_HIP(hipMemcpy(h->async_dst, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
-        } else if (h->async_dst_direct == 0) {
-            memcpy(h->async_dst, h->pin_out, (size_t)h->p.W * h->p.H * 4);
-        }
-        h->async_dst = nullptr;
+    const AdcMatchReq r = h->req;
+    if (r.map_host && r.map_host_direct == 2) {
+        if (ADC_HIP(hipMemcpy(r.map_host, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
+    } else if (r.map_host && r.map_host_direct == 0) {
+        memcpy(r.map_host, h->pin_out, (size_t)h->p.W * h->p.H * 4);
     }
-    h->device_dst = nullptr;
-    if (h->prod.active) { // a products Match of a host caller: staging -> the caller's buffers, then the points that exist
-        const AdcProdReq r = h->prod;
-        for (int i = 0; i < ADC_PROD_MAPS; i++)
-            if (r.map[i].dst && !r.map[i].direct) memcpy(r.map[i].dst, h->ps_map[i], r.map[i].bytes);
-        if (r.cloud || r.cloud_count) {
-            const uint32_t count = (uint32_t)h->pin_flags[8];
+    if (r.host_delivery) { // a host caller's products: staging (or, direct == 2, the device scratch) -> the caller's buffers, then the points that exist
+        for (int i = 0; i < ADC_REQ_MAPS; i++) {
+            const AdcHostMap& m = r.host[i];
+            if (m.dst && m.direct == 0) memcpy(m.dst, h->map_buf[i].pin, m.bytes);
+            if (m.dst && m.direct == 2 && ADC_HIP(hipMemcpy(m.dst, h->map_buf[i].dev, m.bytes, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: product copy-out", hipGetLastError()); abort_match(h); return 2; }
+        }
+        if (r.cloud) {
+            const uint32_t count = (uint32_t)h->pin_flags[ADC_PIN_CLOUD];
             const size_t n = count < r.capacity ? count : r.capacity;
-            if (n && r.cloud && ADC_HIP(hipMemcpy(r.cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: cloud copy-out", hipGetLastError()); abort_match(h); return 2; }
+            if (n && ADC_HIP(hipMemcpy(r.cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: cloud copy-out", hipGetLastError()); abort_match(h); return 2; }
             if (r.cloud_count) *r.cloud_count = count;
         }
-        h->prod.active = 0;
     }
-    h->x_prov = nullptr; h->x_conf = nullptr;
-    h->x_disp16 = nullptr;
-    h->out.active = 0;
+    match_req_clear(h);
     if (h->ev_pending) { // an evaluation has completed: its report words have arrived in the pinned block (adc_get_eval_report)
         h->ev_report = h->ev_echo;
         memcpy(&h->ev_report, h->ev_pin, adc_eval_report_words() * sizeof(uint64_t));
@@ -885,9 +882,19 @@ int adc_match(adc_handle* h, const uint8_t* left, const uint8_t* right, float* d
     return adc_wait(h);
 }
 
-// ------------------------------------------------------------------------------ optional per-pixel maps (k_extras.hip)
-// The confidence kernel runs behind the WTA in run_heavy, the provenance kernel at the top of run_refine_tail: every redo of
-// adc_wait goes through one of the two, so the maps always describe the delivered disparity map.
+// ------------------------------------------------------------------------------ one request for every optional product
+// Every Match entry point is a view of one request (adc_products; the _ex and _out forms ask for a part of it): it is validated and
+// resolved into h->req, the existing stages and enqueue_output do the rest -- the confidence kernel runs behind the WTA in run_heavy,
+// the provenance kernel at the top of run_refine_tail, depth / cloud / 8-bit image / 16-bit map are computed from the delivered map in
+// enqueue_output.  Every redo of adc_wait goes through these, so every product always describes the delivered disparity map.
+static bool outputs_requested(const adc_outputs* o) { return o && (o->depth || o->cloud || o->disp8); }
+static bool products_requested(const adc_products* p) { return p && (p->provenance || p->confidence || outputs_requested(&p->out) || p->disp16); }
+static bool match_in_flight(const adc_handle* h)
+{
+    const AdcMatchReq& r = h->req;
+    return h->match_pending || r.map_host || r.map_dev || r.out.active || r.host_delivery || r.disp16;
+}
+
 static bool extras_allowed(adc_handle* h, const char* who)
 {
     if (!h->paper) return true;
@@ -895,53 +902,8 @@ static bool extras_allowed(adc_handle* h, const char* who)
     return false;
 }
 
-int adc_match_ex(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, uint8_t* prov, float* conf)
-{
-    if (!prov && !conf) return adc_match(h, left, right, disp);
-    if (!h || !left || !right || !disp) return 1;
-    if (!extras_allowed(h, "adc_match_ex")) return 1;
-    hipSetDevice(h->device);
-    const size_t P = (size_t)h->p.W * h->p.H;
-    if (prov && !h->xs_prov && ADC_HIP(hipMalloc(&h->xs_prov, P)) != hipSuccess) {
-        h->xs_prov = nullptr;
-        set_error("adc_match_ex: provenance scratch", hipGetLastError());
-        return 2;
-    }
-    if (conf && !h->xs_conf && ADC_HIP(hipMalloc(&h->xs_conf, P * 4)) != hipSuccess) {
-        h->xs_conf = nullptr;
-        set_error("adc_match_ex: confidence scratch", hipGetLastError());
-        return 2;
-    }
-    h->x_prov = prov ? h->xs_prov : nullptr;
-    h->x_conf = conf ? h->xs_conf : nullptr;
-    int rc = match_async_impl(h, left, right, disp, true);
-    if (rc == 0) rc = adc_wait(h);
-    h->x_prov = nullptr; h->x_conf = nullptr; // (adc_wait / abort_match have cleared them already)
-    if (rc != 0) return rc;
-    if (prov && ADC_HIP(hipMemcpy(prov, h->xs_prov, P, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_ex: provenance copy-out", hipGetLastError()); return 2; }
-    if (conf && ADC_HIP(hipMemcpy(conf, h->xs_conf, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_ex: confidence copy-out", hipGetLastError()); return 2; }
-    return 0;
-}
-
-int adc_match_device_ex(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, void* d_prov, void* d_conf)
-{
-    if (!d_prov && !d_conf) return adc_match_device(h, d_left, d_right, d_disp);
-    if (!h || !d_left || !d_right || !d_disp) return 1;
-    if (!extras_allowed(h, "adc_match_device_ex")) return 1;
-    h->x_prov = static_cast<uint8_t*>(d_prov);
-    h->x_conf = static_cast<float*>(d_conf);
-    const int rc = adc_match_device(h, d_left, d_right, d_disp);
-    if (rc != 0) { h->x_prov = nullptr; h->x_conf = nullptr; }
-    return rc;
-}
-
-// ------------------------------------------------------------------------------ outputs from the final map (k_outputs.hip)
-// Depth, point cloud and 8-bit image are functions of the delivered map only: enqueue_output computes them from disp_l behind the
-// copy of the map, so every redo of adc_wait (which ends in enqueue_output) rewrites them.
-static bool outputs_requested(const adc_outputs* o) { return o && (o->depth || o->cloud || o->disp8); }
-
-// validates a request and resolves it into h->out (not yet active); 0, or 1 (refused, adc_last_error) / 2 (scratch allocation)
-static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who, bool device_pointers)
+// validates the outputs of a request and resolves them into *out (not yet active); 0, or 1 (refused, adc_last_error) / 2 (scratch allocation)
+static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who, bool device_pointers, AdcOutReq* out)
 {
     AdcOutReq r;
     memset(&r, 0, sizeof(r));
@@ -971,195 +933,169 @@ static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who,
         set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
         return 2;
     }
-    h->out = r;
+    *out = r;
     return 0;
 }
 
-int adc_match_device_out(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_outputs* out)
+// a host caller's products: the device scratch of every requested map and (where the map is delivered through it) its pinned staging
+// block, allocated on first use, and a cloud scratch of the capacity asked for
+static hipError_t host_scratch(adc_handle* h, const AdcHostMap* host, bool cloud, uint32_t capacity)
 {
-    if (!outputs_requested(out)) return adc_match_device(h, d_left, d_right, d_disp);
+    hipError_t e = hipSuccess;
+    for (int i = 0; e == hipSuccess && i < ADC_REQ_MAPS; i++) {
+        AdcMapBuf& b = h->map_buf[i];
+        if (!host[i].dst) continue;
+        if (!b.dev && (e = ADC_HIP(hipMalloc(&b.dev, host[i].bytes))) != hipSuccess) b.dev = nullptr;
+        else if (host[i].direct == 0 && !b.pin && (e = ADC_HIP(hipHostMalloc(&b.pin, host[i].bytes, hipHostMallocDefault))) != hipSuccess) b.pin = nullptr;
+    }
+    if (e == hipSuccess && cloud && (!h->os_cloud || h->os_cloud_cap < capacity)) { // (grows with the largest capacity asked for; at least one point)
+        if (h->os_cloud) hipFree(h->os_cloud);
+        h->os_cloud_cap = capacity > 0 ? capacity : 1;
+        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
+    }
+    return e;
+}
+
+// Validates a request and resolves it into h->req, whole, for the Match that the caller enqueues next.  device_pointers: the request's
+// addresses are the device targets themselves; otherwise they are host destinations, the targets are the handle's scratch and
+// enqueue_output / adc_wait deliver.  older: the call comes from adc_match_ex / _out or their device forms, which do not refuse while
+// a Match is pending and whose host forms (all synchronous) keep their blocking copies behind adc_wait's synchronisation (direct = 2:
+// through the staging they were slower than before, profiles/match_request_timing.md).  0, or 1 (refused, adc_last_error) /
+// 2 (allocation); h->req is written on 0 only.
+static int match_req_resolve(adc_handle* h, const adc_products* p, const char* who, bool device_pointers, bool older)
+{
+    if (!older && match_in_flight(h)) { g_last_error = std::string(who) + ": a Match is pending (adc_wait first)"; return 1; }
+    if ((p->provenance || p->confidence) && !extras_allowed(h, who)) return 1;
+    if (p->disp16 && !(__builtin_isfinite(p->disp16_scale) && p->disp16_scale > 0.0f)) { g_last_error = std::string(who) + ": disp16_scale must be finite and > 0"; return 1; }
+    if (p->disp16 && device_pointers && ((uintptr_t)p->disp16 & 1u)) { g_last_error = std::string(who) + ": the device address of disp16 must be even"; return 1; }
+    AdcMatchReq r;
+    memset(&r, 0, sizeof(r));
+    if (outputs_requested(&p->out)) {
+        const int rc = outputs_prepare(h, &p->out, who, device_pointers, &r.out);
+        if (rc != 0) return rc;
+        r.out.active = 1;
+    }
+    void* target[ADC_REQ_MAPS] = {p->provenance, p->confidence, p->out.depth, p->out.disp8, p->disp16};
+    if (!device_pointers) {
+        const size_t P = (size_t)h->p.W * h->p.H;
+        const size_t bytes[ADC_REQ_MAPS] = {P, P * 4, P * 4, P, P * 2};
+        for (int i = 0; i < ADC_REQ_MAPS; i++)
+            if (target[i]) r.host[i] = AdcHostMap{target[i], bytes[i], host_registered(target[i], bytes[i]) ? 1 : (older ? 2 : 0)};
+        const hipError_t e = host_scratch(h, r.host, p->out.cloud != nullptr, r.out.capacity);
+        if (e != hipSuccess) { set_error((std::string(who) + ": scratch").c_str(), e); (void)hipGetLastError(); return 2; }
+        for (int i = 0; i < ADC_REQ_MAPS; i++)
+            if (target[i]) target[i] = h->map_buf[i].dev;
+        r.cloud = p->out.cloud;
+        r.capacity = r.out.capacity;
+        r.cloud_count = p->out.cloud ? p->out.cloud_count : nullptr;
+        r.out.cloud = p->out.cloud ? h->os_cloud : nullptr;
+        r.out.cloud_count = nullptr; // (the count reaches the host through pin_flags[ADC_PIN_CLOUD])
+        r.host_delivery = 1;
+    }
+    r.prov = static_cast<uint8_t*>(target[ADC_MAP_PROV]);
+    r.conf = static_cast<float*>(target[ADC_MAP_CONF]);
+    r.out.depth = static_cast<float*>(target[ADC_MAP_DEPTH]);
+    r.out.disp8 = static_cast<uint8_t*>(target[ADC_MAP_DISP8]);
+    r.disp16 = static_cast<uint16_t*>(target[ADC_MAP_DISP16]);
+    r.disp16_scale = p->disp16_scale;
+    h->req = r;
+    return 0;
+}
+
+// The host entry points: nothing requested = exactly adc_match / adc_match_async.  A call that is refused behind the resolver (1)
+// leaves the request as it found it -- a Match pending on the handle keeps its own; a HIP failure (2) has been through abort_match.
+static int match_host_req(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p, bool sync_call, const char* who, bool older)
+{
+    if (!products_requested(p)) {
+        const int rc = match_async_impl(h, left, right, disp, sync_call);
+        return rc == 0 && sync_call ? adc_wait(h) : rc;
+    }
+    if (!h || !left || !right || !disp) return 1;
+    hipSetDevice(h->device);
+    const AdcMatchReq before = h->req;
+    int rc = match_req_resolve(h, p, who, false, older);
+    if (rc != 0) return rc;
+    rc = match_async_impl(h, left, right, disp, sync_call);
+    if (rc == 1) h->req = before;
+    if (rc == 0 && sync_call) rc = adc_wait(h);
+    return rc;
+}
+// the device entry points: nothing requested = exactly adc_match_device
+static int match_device_req(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_products* p, const char* who, bool older)
+{
+    if (!products_requested(p)) return adc_match_device(h, d_left, d_right, d_disp);
     if (!h || !d_left || !d_right || !d_disp) return 1;
     hipSetDevice(h->device);
-    int rc = outputs_prepare(h, out, "adc_match_device_out", true);
+    const AdcMatchReq before = h->req;
+    int rc = match_req_resolve(h, p, who, true, older);
     if (rc != 0) return rc;
-    h->out.active = 1;
     rc = adc_match_device(h, d_left, d_right, d_disp);
-    if (rc != 0) h->out.active = 0;
+    if (rc == 1) h->req = before;
     return rc;
+}
+
+int adc_match_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
+{
+    return match_host_req(h, left, right, disp, p, true, "adc_match_products", false);
+}
+int adc_match_async_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
+{
+    return match_host_req(h, left, right, disp, p, false, "adc_match_async_products", false);
+}
+int adc_match_device_products(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_products* p)
+{
+    return match_device_req(h, d_left, d_right, d_disp, p, "adc_match_device_products", false);
+}
+
+// the two older generations ask for a part of the request (older = true)
+static adc_products products_of(void* prov, void* conf, const adc_outputs* out)
+{
+    adc_products p;
+    memset(&p, 0, sizeof(p));
+    p.provenance = static_cast<uint8_t*>(prov);
+    p.confidence = static_cast<float*>(conf);
+    if (out) p.out = *out;
+    return p;
+}
+int adc_match_ex(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, uint8_t* prov, float* conf)
+{
+    const adc_products p = products_of(prov, conf, nullptr);
+    return match_host_req(h, left, right, disp, &p, true, "adc_match_ex", true);
+}
+int adc_match_device_ex(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, void* d_prov, void* d_conf)
+{
+    const adc_products p = products_of(d_prov, d_conf, nullptr);
+    return match_device_req(h, d_left, d_right, d_disp, &p, "adc_match_device_ex", true);
+}
+int adc_match_out(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_outputs* out)
+{
+    const adc_products p = products_of(nullptr, nullptr, out);
+    return match_host_req(h, left, right, disp, &p, true, "adc_match_out", true);
+}
+int adc_match_device_out(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_outputs* out)
+{
+    const adc_products p = products_of(nullptr, nullptr, out);
+    return match_device_req(h, d_left, d_right, d_disp, &p, "adc_match_device_out", true);
 }
 
 int adc_reproject_device(adc_handle* h, const void* d_disp, const void* d_bgr_left, const adc_outputs* out)
 {
     if (!h || !d_disp || (out && out->cloud && !d_bgr_left)) return 1;
     if (!outputs_requested(out)) return 0;
-    if (h->out.active) { g_last_error = "adc_reproject_device: a Match with outputs is pending (adc_wait first)"; return 1; }
+    if (h->req.out.active) { g_last_error = "adc_reproject_device: a Match with outputs is pending (adc_wait first)"; return 1; }
     hipSetDevice(h->device);
-    const int rc = outputs_prepare(h, out, "adc_reproject_device", true);
+    const int rc = outputs_prepare(h, out, "adc_reproject_device", true, &h->req.out);
     if (rc != 0) return rc;
     // (out.active stays 0: nothing of a later adc_wait may run these again on the handle's own map)
     if (enqueue_outputs(h, static_cast<const float*>(d_disp), static_cast<const uint8_t*>(d_bgr_left)) != hipSuccess) { abort_match(h); return 2; }
     return 0;
 }
 
-int adc_match_out(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_outputs* out)
-{
-    if (!outputs_requested(out)) return adc_match(h, left, right, disp);
-    if (!h || !left || !right || !disp) return 1;
-    hipSetDevice(h->device);
-    int rc = outputs_prepare(h, out, "adc_match_out", false);
-    if (rc != 0) return rc;
-    const size_t P = (size_t)h->p.W * h->p.H;
-    const uint32_t cap = h->out.capacity;
-    hipError_t e = hipSuccess;
-    if (out->depth && !h->os_depth && (e = ADC_HIP(hipMalloc(&h->os_depth, P * 4))) != hipSuccess) h->os_depth = nullptr;
-    if (e == hipSuccess && out->disp8 && !h->os_disp8 && (e = ADC_HIP(hipMalloc(&h->os_disp8, P))) != hipSuccess) h->os_disp8 = nullptr;
-    if (e == hipSuccess && out->cloud && (!h->os_cloud || h->os_cloud_cap < cap)) { // (grows with the largest capacity asked for; at least one point)
-        if (h->os_cloud) hipFree(h->os_cloud);
-        h->os_cloud_cap = cap > 0 ? cap : 1;
-        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
-    }
-    if (e != hipSuccess) { set_error("adc_match_out: scratch", hipGetLastError()); return 2; }
-    h->out.depth = out->depth ? h->os_depth : nullptr;
-    h->out.disp8 = out->disp8 ? h->os_disp8 : nullptr;
-    h->out.cloud = out->cloud ? h->os_cloud : nullptr;
-    h->out.cloud_count = nullptr;
-    h->out.active = 1;
-    rc = match_async_impl(h, left, right, disp, true);
-    if (rc == 0) rc = adc_wait(h);
-    h->out.active = 0; // (adc_wait / abort_match have cleared it already)
-    if (rc != 0) return rc;
-    if (out->depth && ADC_HIP(hipMemcpy(out->depth, h->os_depth, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: depth copy-out", hipGetLastError()); return 2; }
-    if (out->disp8 && ADC_HIP(hipMemcpy(out->disp8, h->os_disp8, P, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: image copy-out", hipGetLastError()); return 2; }
-    if (out->cloud) {
-        const uint32_t count = (uint32_t)h->pin_flags[8];
-        const size_t n = count < cap ? count : cap;
-        if (n && ADC_HIP(hipMemcpy(out->cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_match_out: cloud copy-out", hipGetLastError()); return 2; }
-        if (out->cloud_count) *out->cloud_count = count;
-    }
-    return 0;
-}
-
 int adc_get_cloud_count(adc_handle* h, uint64_t* count)
 {
     if (!h || !count || !h->pin_flags) return 1;
-    *count = (uint32_t)h->pin_flags[8];
+    *count = (uint32_t)h->pin_flags[ADC_PIN_CLOUD];
     return 0;
-}
-
-// ------------------------------------------------------------------------------ every product through one request (adc_products)
-// One path for the four Match entry points: the request is validated and resolved into the per-Match state the kernels already look
-// at (x_prov / x_conf, out, x_disp16), the host callers additionally into prod (where adc_wait delivers).  Everything is enqueued by
-// the existing stages and by enqueue_output, so every redo of adc_wait rewrites every product from the map it delivers.
-static bool match_in_flight(const adc_handle* h);
-static bool products_requested(const adc_products* p) { return p && (p->provenance || p->confidence || outputs_requested(&p->out) || p->disp16); }
-
-static void products_forget(adc_handle* h)
-{
-    h->x_prov = nullptr; h->x_conf = nullptr;
-    h->out.active = 0;
-    h->x_disp16 = nullptr;
-    h->prod.active = 0;
-}
-
-// what all three forms refuse; 0, or 1 (adc_last_error) / 2 (scratch of the outputs).  On 0 h->out holds the resolved outputs (inactive).
-static int products_check(adc_handle* h, const adc_products* p, const char* who, bool device_pointers)
-{
-    if (match_in_flight(h)) { g_last_error = std::string(who) + ": a Match is pending (adc_wait first)"; return 1; }
-    if ((p->provenance || p->confidence) && !extras_allowed(h, who)) return 1;
-    if (p->disp16 && !(__builtin_isfinite(p->disp16_scale) && p->disp16_scale > 0.0f)) { g_last_error = std::string(who) + ": disp16_scale must be finite and > 0"; return 1; }
-    if (p->disp16 && device_pointers && ((uintptr_t)p->disp16 & 1u)) { g_last_error = std::string(who) + ": the device address of disp16 must be even"; return 1; }
-    if (outputs_requested(&p->out)) return outputs_prepare(h, &p->out, who, device_pointers);
-    memset(&h->out, 0, sizeof(h->out));
-    return 0;
-}
-
-int adc_match_device_products(adc_handle* h, const void* d_left, const void* d_right, void* d_disp, const adc_products* p)
-{
-    if (!products_requested(p)) return adc_match_device(h, d_left, d_right, d_disp);
-    if (!h || !d_left || !d_right || !d_disp) return 1;
-    hipSetDevice(h->device);
-    int rc = products_check(h, p, "adc_match_device_products", true);
-    if (rc != 0) return rc;
-    h->x_prov = p->provenance;
-    h->x_conf = p->confidence;
-    h->out.active = outputs_requested(&p->out) ? 1 : 0;
-    h->x_disp16 = p->disp16;
-    h->x_disp16_scale = p->disp16_scale;
-    rc = adc_match_device(h, d_left, d_right, d_disp);
-    if (rc != 0) products_forget(h);
-    return rc;
-}
-
-// first use of a product by a host caller: its device scratch and its pinned staging block
-static hipError_t products_map_buffers(adc_handle* h, int i, void** dev, size_t bytes, bool staged)
-{
-    if (!*dev) {
-        const hipError_t e = ADC_HIP(hipMalloc(dev, bytes));
-        if (e != hipSuccess) { *dev = nullptr; return e; }
-    }
-    if (staged && !h->ps_map[i]) {
-        const hipError_t e = ADC_HIP(hipHostMalloc(&h->ps_map[i], bytes, hipHostMallocDefault));
-        if (e != hipSuccess) { h->ps_map[i] = nullptr; return e; }
-    }
-    return hipSuccess;
-}
-
-static int match_products_impl(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p, bool sync_call, const char* who)
-{
-    if (!h || !left || !right || !disp) return 1;
-    hipSetDevice(h->device);
-    int rc = products_check(h, p, who, false);
-    if (rc != 0) return rc;
-    const size_t P = (size_t)h->p.W * h->p.H;
-    AdcProdReq r;
-    memset(&r, 0, sizeof(r));
-    void* host[ADC_PROD_MAPS] = {p->provenance, p->confidence, p->out.depth, p->out.disp8, p->disp16};
-    void** dev[ADC_PROD_MAPS] = {(void**)&h->xs_prov, (void**)&h->xs_conf, (void**)&h->os_depth, (void**)&h->os_disp8, (void**)&h->os_disp16};
-    const size_t bytes[ADC_PROD_MAPS] = {P, P * 4, P * 4, P, P * 2};
-    hipError_t e = hipSuccess;
-    for (int i = 0; e == hipSuccess && i < ADC_PROD_MAPS; i++) {
-        if (!host[i]) continue;
-        r.map[i].dst = host[i];
-        r.map[i].bytes = bytes[i];
-        r.map[i].direct = host_registered(host[i], bytes[i]) ? 1 : 0;
-        e = products_map_buffers(h, i, dev[i], bytes[i], !r.map[i].direct);
-        r.map[i].dev = *dev[i];
-    }
-    const uint32_t cap = h->out.capacity;
-    if (e == hipSuccess && p->out.cloud && (!h->os_cloud || h->os_cloud_cap < cap)) { // (grows with the largest capacity asked for; at least one point)
-        if (h->os_cloud) hipFree(h->os_cloud);
-        h->os_cloud_cap = cap > 0 ? cap : 1;
-        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
-    }
-    if (e != hipSuccess) { set_error((std::string(who) + ": scratch").c_str(), e); (void)hipGetLastError(); return 2; }
-    if (p->out.cloud) { r.cloud = p->out.cloud; r.capacity = cap; r.cloud_count = p->out.cloud_count; }
-    h->x_prov = p->provenance ? h->xs_prov : nullptr;
-    h->x_conf = p->confidence ? h->xs_conf : nullptr;
-    h->out.depth = p->out.depth ? h->os_depth : nullptr;
-    h->out.disp8 = p->out.disp8 ? h->os_disp8 : nullptr;
-    h->out.cloud = p->out.cloud ? h->os_cloud : nullptr;
-    h->out.cloud_count = nullptr;
-    h->out.active = outputs_requested(&p->out) ? 1 : 0;
-    h->x_disp16 = p->disp16 ? h->os_disp16 : nullptr;
-    h->x_disp16_scale = p->disp16_scale;
-    r.active = 1;
-    h->prod = r;
-    rc = match_async_impl(h, left, right, disp, sync_call);
-    if (rc != 0) products_forget(h);
-    return rc;
-}
-
-int adc_match_async_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
-{
-    if (!products_requested(p)) return adc_match_async(h, left, right, disp);
-    return match_products_impl(h, left, right, disp, p, false, "adc_match_async_products");
-}
-
-int adc_match_products(adc_handle* h, const uint8_t* left, const uint8_t* right, float* disp, const adc_products* p)
-{
-    if (!products_requested(p)) return adc_match(h, left, right, disp);
-    const int rc = match_products_impl(h, left, right, disp, p, true, "adc_match_products");
-    return rc != 0 ? rc : adc_wait(h);
 }
 
 int adc_disp16_device(adc_handle* h, const void* d_disp, float scale, void* d_disp16)
@@ -1201,8 +1137,6 @@ static int speckle_scratch(adc_handle* h, bool with_map, const char* who)
     return 0;
 }
 
-static bool match_in_flight(const adc_handle* h) { return h->match_pending || h->async_dst || h->device_dst || h->out.active || h->prod.active || h->x_disp16; }
-
 int adc_set_speckle_filter(adc_handle* h, int32_t max_size, float max_diff)
 {
     if (!h) return 1;
@@ -1234,9 +1168,9 @@ int adc_filter_speckles_device(adc_handle* h, void* d_disp_inout, int32_t max_si
 int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed_components, uint32_t* removed_pixels)
 {
     if (!h || !h->pin_flags) return 1;
-    if (components) *components = (uint32_t)h->pin_flags[9];
-    if (removed_components) *removed_components = (uint32_t)h->pin_flags[10];
-    if (removed_pixels) *removed_pixels = (uint32_t)h->pin_flags[11];
+    if (components) *components = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE];
+    if (removed_components) *removed_components = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE + 1];
+    if (removed_pixels) *removed_pixels = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE + 2];
     return 0;
 }
 
@@ -2027,9 +1961,9 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
             return 3;
         }
     }
-    if (stage == ADC_RUN_MEDIAN && h->pin_flags && h->pin_flags[0] != 0) { // what adc_wait does behind a Match
+    if (stage == ADC_RUN_MEDIAN && h->pin_flags && h->pin_flags[ADC_PIN_MEDIAN] != 0) { // what adc_wait does behind a Match
         e = adc_median_fallback(h);
-        h->pin_flags[0] = 0;
+        h->pin_flags[ADC_PIN_MEDIAN] = 0;
         h->median_fallbacks++;
         if (e != hipSuccess) { set_error("adc_debug_run: median fallback", e); return 2; }
     }
