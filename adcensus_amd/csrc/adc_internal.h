@@ -206,6 +206,7 @@ struct adc_handle {
     int in_redo;          // adc_wait is redoing a Match (no sparse launches there)
     int agg_sparse_last;  // the last aggregation run used sparse launches (pass timings are then not priced as read V + write V)
     int agg_sparse_launches; // sparse launches of this handle
+    int agg_gather_launches; // ... of which in the gather form (k_agg_gather: only the changed pixels are computed)
     int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     float* med_hand;      // banded median: per-band hand-off rows [bands][med_hpitch], indexed by wavefront level
     int med_hpitch;
@@ -308,6 +309,7 @@ hipError_t adc_launch_cost(adc_handle* h, float* vol_out);
 hipError_t adc_launch_cost_records(adc_handle* h);
 int adc_agg_small_L(const adc_handle* h);
 double adc_agg_sparse_density(void); // density of pass-changing records up to which a direction's small-ring launches run sparse
+double adc_agg_gather_density(void); // ... up to which the sparse launches run in their gather form
 hipError_t adc_launch_arms(adc_handle* h); // arms, support counts, colour-difference maps (= _left + _rest)
 hipError_t adc_launch_arms_left(adc_handle* h); // what needs only the left image: packed pixels, arms, maxima, support counts
 hipError_t adc_launch_sup_counts(adc_handle* h); // support counts + region boxes from the arms in HBM (debug surface)

@@ -1984,6 +1984,8 @@ int64_t adc_debug_counter(adc_handle* h, int which)
     case 13: return h->agg_so_fusions; // Matches whose last aggregation pass ran inside the first scanline pass
     case 16: return h->agg_sparse_launches; // small-ring aggregation launches that ran in their sparse form (+ k_agg_apply)
     case 17: return (int64_t)(adc_agg_sparse_density() * 1e6 + 0.5); // density threshold of the sparse form, parts per million of the pixels
+    case 20: return h->agg_gather_launches; // ... of which in the gather form (k_agg_gather + k_agg_apply)
+    case 21: return (int64_t)(adc_agg_gather_density() * 1e6 + 0.5); // density threshold of the gather form, parts per million of the pixels
     case 18: return h->rec_nz_known ? h->rec_nz_host[0] : -1; // pixels with a pass-changing horizontal record the handle last saw
     case 19: return h->rec_nz_known ? h->rec_nz_host[1] : -1; // ... vertical record
     case 14: return h->irv_xcd_mode;   // the voting chain sweeps band -> XCD (the mapping was probed on this device)

@@ -20,6 +20,7 @@
 #include <mutex>
 #include "k_aggregate_rr.h"
 #include "k_aggregate_rr2.h"
+#include "k_agg_gather.h"
 
 // ---------------------------------------------------------------------------------- marching ring
 // One 64-lane workgroup (= one wave) per line segment.
@@ -625,6 +626,63 @@ __global__ __launch_bounds__(256) void k_agg_apply(const float* __restrict__ fro
     }
 }
 
+// GATHER form of a sparse small-ring launch (runs in place of k_agg_march<.., SPARSE>, with k_agg_apply behind it as before): the
+// launch computes ONLY the pixels it stores.  Same walk as k_agg_apply -- a wave takes 64 consecutive records of the direction's
+// line-major record set, ballots the launch's predicate and loops over the set bits -- and for every changed pixel the arithmetic
+// of k_agg_gather.h on the input vectors of its span (a pair: of the spans of its span's pixels), which it reads from src (L2 serves
+// the re-reads of neighbouring changed pixels: no streaming hint).  A lane holds the two disparities it holds in the VPL = 2 march.
+// The records of a pixel's neighbours are wave-uniform: one load of the 64 records around it, picked with v_readlane (arms beyond
+// the window -- never with the small ring -- fall back to a load of their own).  No ring and no depth: the arithmetic holds for
+// any arm length, but the launch keeps the gate of the march it replaces -- in the short-arm plan the vertical pair launches are
+// the only kernels that verify the ASSUMED vertical depth (the fused-cost pass, the horizontal pair and k_scanline_seg_agg are all
+// horizontal), so it skips, and raises armmax[3], exactly when the march would.  Stores go to the OTHER volume: neighbours read src.
+template <bool VERT, bool DIVIDE, bool PAIR>
+__global__ __launch_bounds__(256) void k_agg_gather(const float* __restrict__ src, float* __restrict__ dst,
+                                                    const uint32_t* __restrict__ rec, int W, int H, int Dp,
+                                                    const int* __restrict__ armmax, int small_variant, int small_L)
+{
+    static_assert(!PAIR || DIVIDE, "a pair = dividing pass + the following non-dividing pass");
+    if (agg_gate_skip(armmax, small_variant, small_L, VERT)) return;
+    typedef AggT<2>::V V;
+    const int lane = threadIdx.x & 63;
+    const long long P = (long long)W * H;
+    // (the wave's number through readfirstlane: everything per pixel below is then scalar work -- indices, records, loop bounds)
+    const long long i0 = ((long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 64;
+    const long long i = i0 + lane; // record index: y * W + x, or x * H + y
+    const uint32_t mine = rec[i < P ? i : 0];
+    unsigned long long todo = __ballot(i < P && adc_rec_changes_pixel(mine, DIVIDE || PAIR));
+    const long long fstep = (VERT ? (long long)W : 1LL) * Dp; // floats between neighbouring elements of a line
+    while (todo) {
+        const int b = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        todo &= todo - 1;
+        const long long r = i0 + b;
+        const int N = VERT ? H : W;
+        const long long line = r / N;
+        const int s = (int)(r - line * N);
+        // (arms as k_build_arms makes them end at the line's ends; the clip changes no valid record and keeps every read of a
+        // damaged one inside the line)
+        auto clip = [&](uint32_t q, int pos) -> uint32_t {
+            const uint32_t lo = adc_imin((int)(q & 255u), pos), hi = adc_imin((int)((q >> 8) & 255u), N - 1 - pos);
+            return (q & 0xFFFF0000u) | (hi << 8) | lo;
+        };
+        const uint32_t rs = clip((uint32_t)__builtin_amdgcn_readlane((int)mine, b), s);
+        uint32_t win = 0; // lane l: record of the pixel l - 32 places along the line
+        if constexpr (PAIR) {
+            const long long wi = r - 32 + lane;
+            win = rec[wi < 0 ? 0 : (wi >= P ? P - 1 : wi)];
+        }
+        auto rec_at = [&](int t) -> uint32_t { // (s + t lies inside the line: t comes from the clipped span of s)
+            if (t >= -32 && t < 32) return clip((uint32_t)__builtin_amdgcn_readlane((int)win, t + 32), s + t);
+            return clip((uint32_t)__builtin_amdgcn_readfirstlane((int)rec[r + t]), s + t);
+        };
+        const long long pix = VERT ? (long long)s * W + line : r;
+        const float* ps = src + pix * Dp + lane * 2;
+        float* pd = dst + pix * Dp + lane * 2;
+        for (int c = 0; c < Dp; c += 128)
+            *reinterpret_cast<V*>(pd + c) = agg_gather_pixel<V, DIVIDE, PAIR>(ps + c, fstep, rs, rec_at);
+    }
+}
+
 // full ring in registers (2L+1 <= AGG_RING_REGS): the compiler keeps to v0..v55, ring 1 owns v56..v127, ring 2 (pairs)
 // v128..v199.  Body: k_aggregate_rr.h.
 template <bool VERT, bool DIVIDE>
@@ -766,10 +824,32 @@ static bool agg_sparse_wanted(const adc_handle* h, bool vert, bool pair)
     return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_sparse_density() * (double)h->p.W * (double)h->p.H;
 }
 
+// Density up to which a sparse launch runs in its GATHER form (k_agg_gather: computes only the pixels it stores, from the vectors of
+// their spans) instead of marching over the whole volume with the stores masked.  Rule: half of the measured break-even density
+// against the sparse march.  Measured (tools/gpu_sparse_sweep.py 5 gather, profiles/gather_agg_density_sweep.md: 1080p noise pairs
+// with planted copies): gather is faster at every density up to 0.30 and breaks even at 0.42, half of which (0.211) lies above the
+// whole range in which the sparse march runs -- so the threshold EQUALS AGG_SPARSE_MAX_DENSITY: every sparse launch gathers.
+// ADC_AGG_GATHER_DENSITY overrides the value, read per call: the sweep and the tests vary it.
+#define AGG_GATHER_MAX_DENSITY AGG_SPARSE_MAX_DENSITY
+double adc_agg_gather_density(void)
+{
+    const char* e = getenv("ADC_AGG_GATHER_DENSITY");
+    return e ? atof(e) : AGG_GATHER_MAX_DENSITY;
+}
+// Does a sparse launch of this direction (agg_sparse_wanted holds: never a first Match, a two-plan Match or a redo) gather?
+// Every form gives the same bits.  ADC_AGG_GATHER=0 switches the form off.
+static bool agg_gather_wanted(const adc_handle* h, bool vert)
+{
+    const char* e = getenv("ADC_AGG_GATHER"); // (read per call, like ADC_AGG_SPARSE)
+    if (e && atoi(e) == 0) return false;
+    return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_gather_density() * (double)h->p.W * (double)h->p.H;
+}
+
 // sparse: small-ring launch in its sparse form + k_agg_apply (the result is then in src, not in dst); which == 1 only
 template <bool VERT, bool DIVIDE, bool COSTIN = false, bool PAIR = false>
 static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int which = 0, bool sparse = false)
 {
+    const bool gather = sparse && agg_gather_wanted(h, VERT);
     const AdcParams& p = h->p;
     const int L = adc_imax(0, adc_imin(p.opt.cross_L1, 255)); // (a ring of 2 * 255 + 1 entries of 256 bytes fits the 160 KiB of LDS: every arm limit marches)
     const int N = VERT ? p.H : p.W;
@@ -815,6 +895,8 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
             h->agg_kernel = rr2 ? "k_agg_rr2 (register ring of VGPR pairs, 2 disparities per lane, one pass per launch)"
                           : regring ? (PAIR ? "k_agg_regring_pair (two register rings, dividing pass + next first pass per launch)"
                                             : "k_agg_regring (register ring, 1 disparity per lane, one pass per launch)")
+                          : (variant && gather) ? (PAIR ? "k_agg_gather<.., PAIR> + k_agg_apply (SPARSE launch, gather form: dividing pass + next first pass, only changed pixels computed)"
+                                                        : "k_agg_gather + k_agg_apply (SPARSE launch, gather form: one pass per launch, only changed pixels computed)")
                           : (variant && sparse) ? (PAIR ? "k_agg_march<.., PAIR, SPARSE> + k_agg_apply (LDS small rings: dividing pass + next first pass per launch, only changed pixels stored)"
                                                         : "k_agg_march<.., SMALL, SPARSE> + k_agg_apply (LDS small ring, one pass per launch, only changed pixels stored)")
                           : variant ? (PAIR ? "k_agg_march<.., PAIR> (LDS small rings: dividing pass + next first pass per launch)"
@@ -848,9 +930,14 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
         } else if (variant && vpl == 2) {
             if constexpr (!COSTIN) {
                 if (sparse) {
-                    hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2, true>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
                     const long long P = (long long)p.W * p.H;
+                    if (gather) {
+                        hipLaunchKernelGGL((k_agg_gather<VERT, DIVIDE, PAIR>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->heavy, src, dst,
+                                           VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, h->armmax, sv, sl);
+                        h->agg_gather_launches++;
+                    } else
+                        hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2, true>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
+                                           VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
                     hipLaunchKernelGGL((k_agg_apply<VERT>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->heavy, dst, const_cast<float*>(src),
                                        VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, (DIVIDE || PAIR) ? 1 : 0, h->armmax, sv, sl);
                     h->agg_sparse_launches++;

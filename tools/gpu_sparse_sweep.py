@@ -4,7 +4,11 @@ copies its left or its upper neighbour, each matched alternately with the dense 
 forced (ADC_AGG_SPARSE_DENSITY=1) on one handle; the time is the aggregation stage's (HIP events).  The planted copies sit on every
 third column / row only, so no arm outgrows the small ring.  Prints a markdown table; the committed threshold
 (AGG_SPARSE_MAX_DENSITY, k_aggregate.hip) is half of the density at which the two forms take the same time.
-    python tools/gpu_sparse_sweep.py [reps]"""
+    python tools/gpu_sparse_sweep.py [reps]
+With `gather` as second argument the same pairs are matched alternately with the sparse march (ADC_AGG_GATHER=0) and with the gather
+form of the sparse launches forced (ADC_AGG_GATHER_DENSITY=1), both with the sparse form forced: the table behind
+AGG_GATHER_MAX_DENSITY (profiles/gather_agg_density_sweep.md).
+    python tools/gpu_sparse_sweep.py [reps] gather"""
 import os
 import sys
 
@@ -31,30 +35,34 @@ def planted(W, H, p, seed=12345):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    gather = len(sys.argv) > 2 and sys.argv[2] == "gather"
+    switch, counter = ("ADC_AGG_GATHER", 20) if gather else ("ADC_AGG_SPARSE", 16)
+    a, b = ("march", "gather") if gather else ("dense", "sparse")
     W, H, D = 1920, 1080, 128
     opt = A.ADCensusOption()
     opt.max_disparity = D
     rows = []
-    print("| planted share p | density h | density v | dense ms (median, min) | sparse ms (median, min) | sparse - dense ms | sparse launches per Match |")
+    print("| planted share p | density h | density v | %s ms (median, min) | %s ms (median, min) | %s - %s ms | %s launches per Match |" % (a, b, b, a, b))
     print("|---|---|---|---|---|---|---|")
-    for p in (0.0, 0.03, 0.08, 0.15, 0.25, 0.4, 0.55, 0.7, 0.85, 1.0):
+    for p in ((0.0, 0.01, 0.03, 0.05, 0.08, 0.12, 0.15, 0.2, 0.25, 0.4, 0.55) if gather else (0.0, 0.03, 0.08, 0.15, 0.25, 0.4, 0.55, 0.7, 0.85, 1.0)):
         l, r = planted(W, H, p)
         st = A.ADCensusStereo(device=0)
         assert st.Initialize(W, H, opt)
         st.set_profiling(True)
-        os.environ["ADC_AGG_SPARSE"] = "0"
+        os.environ["ADC_AGG_SPARSE_DENSITY"] = os.environ["ADC_AGG_GATHER_DENSITY"] = "1.0"
+        os.environ["ADC_AGG_SPARSE"] = "1" if gather else "0"
+        os.environ["ADC_AGG_GATHER"] = "0"
         st.match(l, r)  # (first Match of a handle: full ring)
         st.match(l, r)
         t = {"0": [], "1": []}
         launches = 0
         for _ in range(reps):
             for mode in ("0", "1"):
-                os.environ["ADC_AGG_SPARSE"] = mode
-                os.environ["ADC_AGG_SPARSE_DENSITY"] = "1.0"
-                before = st.debug_counter(16)
+                os.environ[switch] = mode
+                before = st.debug_counter(counter)
                 st.match(l, r)
                 t[mode].append(st.stage_ms()["aggregate"])
-                ran = st.debug_counter(16) - before
+                ran = st.debug_counter(counter) - before
                 assert (ran > 0) == (mode == "1"), (mode, ran, st.aggregate_kernel())
                 launches = max(launches, ran)
         dh, dv = st.debug_counter(18) / float(W * H), st.debug_counter(19) / float(W * H)
