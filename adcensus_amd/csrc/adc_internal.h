@@ -207,6 +207,7 @@ struct adc_handle {
     int agg_sparse_last;  // the last aggregation run used sparse launches (pass timings are then not priced as read V + write V)
     int agg_sparse_launches; // sparse launches of this handle
     int agg_gather_launches; // ... of which in the gather form (k_agg_gather: only the changed pixels are computed)
+    int agg_flat_launches;   // first (fused-cost) launches that ran as the element-wise k_cost_agg_flat instead of the small-ring march
     int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     float* med_hand;      // banded median: per-band hand-off rows [bands][med_hpitch], indexed by wavefront level
     int med_hpitch;
@@ -307,9 +308,14 @@ struct adc_handle {
 hipError_t adc_launch_gray_census(adc_handle* h);
 hipError_t adc_launch_cost(adc_handle* h, float* vol_out);
 hipError_t adc_launch_cost_records(adc_handle* h);
+// first aggregation pass of the short-arm plan, element-wise (k_cost_agg_flat): writes the volume the small-ring fused-cost march would;
+// cap = the ring depth that march would have had, (small_variant, small_L) = its gate.  hipErrorInvalidValue: the geometry does not fit.
+bool adc_cost_agg_flat_fits(const adc_handle* h, int cap);
+hipError_t adc_launch_cost_agg_flat(adc_handle* h, float* dst, int cap, int small_variant, int small_L);
 int adc_agg_small_L(const adc_handle* h);
 double adc_agg_sparse_density(void); // density of pass-changing records up to which a direction's small-ring launches run sparse
 double adc_agg_gather_density(void); // ... up to which the sparse launches run in their gather form
+double adc_cost_flat_density(void);  // horizontal density up to which the first launch of the short-arm plan runs as k_cost_agg_flat
 hipError_t adc_launch_arms(adc_handle* h); // arms, support counts, colour-difference maps (= _left + _rest)
 hipError_t adc_launch_arms_left(adc_handle* h); // what needs only the left image: packed pixels, arms, maxima, support counts
 hipError_t adc_launch_sup_counts(adc_handle* h); // support counts + region boxes from the arms in HBM (debug surface)

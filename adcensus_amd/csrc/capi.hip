@@ -1986,6 +1986,13 @@ int64_t adc_debug_counter(adc_handle* h, int which)
     case 17: return (int64_t)(adc_agg_sparse_density() * 1e6 + 0.5); // density threshold of the sparse form, parts per million of the pixels
     case 20: return h->agg_gather_launches; // ... of which in the gather form (k_agg_gather + k_agg_apply)
     case 21: return (int64_t)(adc_agg_gather_density() * 1e6 + 0.5); // density threshold of the gather form, parts per million of the pixels
+    case 22: return h->agg_flat_launches; // first aggregation launches that ran as k_cost_agg_flat (element-wise) instead of the small-ring march
+    case 23: return (int64_t)(adc_cost_flat_density() * 1e6 + 0.5); // density threshold of the flat first launch, parts per million of the pixels
+    case 24: { // first aggregation launch of the last Match in nanoseconds, from the aggregation marks (profiling on, one plan enqueued); else -1
+        float ms = 0.f;
+        if (!h->profiling || h->agg_dual_last || h->agg_launches < 1 || hipEventElapsedTime(&ms, h->ev_agg[0], h->ev_agg[1]) != hipSuccess) return -1;
+        return (int64_t)((double)ms * 1e6 + 0.5);
+    }
     case 18: return h->rec_nz_known ? h->rec_nz_host[0] : -1; // pixels with a pass-changing horizontal record the handle last saw
     case 19: return h->rec_nz_known ? h->rec_nz_host[1] : -1; // ... vertical record
     case 14: return h->irv_xcd_mode;   // the voting chain sweeps band -> XCD (the mapping was probed on this device)

@@ -845,6 +845,27 @@ static bool agg_gather_wanted(const adc_handle* h, bool vert)
     return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_gather_density() * (double)h->p.W * (double)h->p.H;
 }
 
+// Density (horizontal pass-changing records of the previous Match) up to which the FIRST launch of the short-arm plan -- fused cost,
+// small ring -- runs as the element-wise k_cost_agg_flat (k_cost.hip) instead of k_agg_march<.., COSTIN>.  Rule: half of the measured
+// break-even density against the march, never above AGG_SPARSE_MAX_DENSITY (agg_sparse_wanted is part of the predicate).
+// ADC_COST_FLAT_DENSITY overrides the value, read per call: the sweep and the tests vary it.
+#define COST_FLAT_MAX_DENSITY AGG_SPARSE_MAX_DENSITY
+double adc_cost_flat_density(void)
+{
+    const char* e = getenv("ADC_COST_FLAT_DENSITY");
+    return e ? atof(e) : COST_FLAT_MAX_DENSITY;
+}
+// Does the first launch run flat?  Only where the horizontal small-ring launches run sparse (agg_sparse_wanted: never the first Match
+// of a handle, a two-plan Match or a redo; low density), with the host knowing or assuming the arms (which == 1).  Both forms give the
+// same bits and keep the same gate.  ADC_COST_FLAT=0 gives the march back.
+static bool cost_flat_wanted(const adc_handle* h, int which, int cap)
+{
+    const char* e = getenv("ADC_COST_FLAT"); // (read per call, like ADC_AGG_GATHER)
+    if (e && atoi(e) == 0) return false;
+    if (which != 1 || !agg_sparse_wanted(h, false, false) || !adc_cost_agg_flat_fits(h, cap)) return false;
+    return (double)h->rec_nz_host[0] <= adc_cost_flat_density() * (double)h->p.W * (double)h->p.H;
+}
+
 // sparse: small-ring launch in its sparse form + k_agg_apply (the result is then in src, not in dst); which == 1 only
 template <bool VERT, bool DIVIDE, bool COSTIN = false, bool PAIR = false>
 static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int which = 0, bool sparse = false)
@@ -946,6 +967,10 @@ static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int w
                     hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
                                        VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
             }
+        } else if (variant && COSTIN && cost_flat_wanted(h, which, Lv)) {
+            const hipError_t ef = adc_launch_cost_agg_flat(h, dst, Lv, sv, sl); // (one launch for one launch, same gate)
+            if (ef != hipSuccess) return ef;
+            h->agg_flat_launches++;
         } else if (variant)
             hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, COSTIN, PAIR>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
                                VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);

@@ -10,6 +10,9 @@
 // glibc expf on the host.
 #include "adc_internal.h"
 #include "adc_device_fn.h"
+#include "k_aggregate_rr.h"  // agg_gate_skip
+#include "k_aggregate_rr2.h" // AggCostIn
+#include "k_cost_flat.h"
 
 // ------------------------------------------------------------------------------------------- K1
 #define CT_W 32
@@ -207,6 +210,139 @@ hipError_t adc_launch_cost_records(adc_handle* h)
     hipLaunchKernelGGL(k_cost_records, dim3((h->rrec_pitch + 255) / 256, p.H), dim3(256), 0, h->heavy, h->img_l, h->img_r,
                        h->census_l, h->census_r, reinterpret_cast<uint4*>(h->cost_lrec), reinterpret_cast<uint4*>(h->cost_rrec),
                        p.W, p.H, h->rrec_pitch, h->rrec_padl);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------- first aggregation pass of the short-arm plan, element-wise
+// k_cost_agg_flat runs in place of k_agg_march<false, false, true, true, false, 1> (small ring, fused cost) and writes the same
+// volume: per element the ordered f32 sum from 0.0f over the pixel's own horizontal span of the matching costs (k_cost_flat.h).  On a
+// short-arm image that span is the pixel itself for ~99 % of the pixels, and the march pays its ring, its DPP window and its slot
+// bookkeeping for nothing; here a span is evaluated where it stands.
+//   * a workgroup of 4 waves owns CF_TX consecutive pixels of one row and stages, in LDS, the right records of every column its
+//     spans can reach (tile - dmin - Dp + 1 - cap .. tile + cap: the padded rows of k_cost_records need no bounds logic, indices
+//     beyond the pitch repeat a marker column) and the two tables;
+//   * a wave owns CF_PW of those pixels: lane l holds the left record and the arm record of column first - CF_HALO + l (one
+//     coalesced load per wave), and every pixel picks what its span needs with v_readlane -- wave-uniform, like the loop over the span;
+//   * a lane holds disparities 2 * lane and 2 * lane + 1 of each 128-float chunk (the layout of the VPL = 2 kernels): one 8-byte
+//     store per lane, 512 contiguous bytes per wave.
+// Keeps the gate of the march it replaces (agg_gate_skip with the same arguments): it skips, and raises the too-shallow flag, exactly
+// when that march would.  cap = the ring depth the march would have had; no valid record of an image that passes the gate has a
+// longer arm.  The arithmetic holds for any arm length (arms beyond CF_HALO cost a load of their own per span entry).
+#define CF_PW 32
+#define CF_HALO 16
+#define CF_TX (4 * CF_PW)
+#define CF_LDS_MAX (48 * 1024)
+typedef float cf_f2 __attribute__((ext_vector_type(2)));
+
+template <bool PAD> // PAD = false: D == Dp, no padding lanes
+__global__ __launch_bounds__(256) void k_cost_agg_flat(float* __restrict__ dst, const uint32_t* __restrict__ rec, int W, int H, int Dp,
+                                                       int cap, int tiles, const int* __restrict__ armmax, int small_variant,
+                                                       int small_L, AggCostIn ci)
+{
+    if (agg_gate_skip(armmax, small_variant, small_L, false)) return;
+    extern __shared__ __attribute__((aligned(16))) uint32_t cf_lds[];
+    const int n = CF_TX + Dp - 1 + 2 * cap; // staged right columns
+    float* lutA = reinterpret_cast<float*>(cf_lds);
+    float* lutC = lutA + 768;
+    uint32_t* sB = cf_lds + 768 + 64;
+    uint32_t* sC0 = sB + n;
+    uint32_t* sC1 = sC0 + n;
+    const int tid = threadIdx.x;
+    const int y = (int)blockIdx.x / tiles;
+    const int x0 = ((int)blockIdx.x - y * tiles) * CF_TX;
+    for (int i = tid; i < 766; i += 256) lutA[i] = ci.lut_ad[i];
+    if (tid < 64) lutC[tid] = ci.lut_census[tid];
+    // staged entry i = right column col_lo + i; disparity index d of pixel x + t is matched against column x + t - dmin - d
+    const int col_lo = x0 - cap - ci.dmin - (Dp - 1);
+    const uint4* rrow = ci.rrec + (size_t)y * ci.rpitch;
+    for (int i = tid; i < n; i += 256) {
+        int gi = ci.padl + col_lo + i;
+        gi = gi < 0 ? 0 : (gi >= ci.rpitch ? ci.rpitch - 1 : gi); // (both ends of a padded row are marker columns; no pixel of the image needs a clamped one)
+        const uint4 r = rrow[gi];
+        sB[i] = r.x;
+        sC0[i] = r.y;
+        sC1[i] = r.z;
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int xw = x0 + wave * CF_PW; // first pixel of this wave
+    if (xw >= W) return;
+    const int xl = adc_imax(0, adc_imin(W - 1, xw - CF_HALO + lane));
+    const uint4 lr = ci.lrec[(size_t)y * W + xl];
+    const uint32_t myrec = rec[(size_t)y * W + xl];
+    const int npx = adc_imin(CF_PW, W - xw);
+    // staged entry of (pixel, t = 0, chunk 0, first disparity of the lane) = (x - x0) + cap + (Dp - 1) - 2 * lane, in [cap + 1, n - 1 - cap];
+    // entry + t - c - k is what disparity c + 2 * lane + k of pixel x + t is matched against
+    const uint32_t* qB = sB + (xw - x0) + cap + (Dp - 1) - 2 * lane;
+    const uint32_t* qC0 = qB + n;
+    const uint32_t* qC1 = qC0 + n;
+    float* pd = dst + ((size_t)y * W + xw) * Dp + 2 * lane;
+    for (int p = 0; p < npx; p++, qB++, qC0++, qC1++, pd += Dp) {
+        const int li = CF_HALO + p; // the lane that holds column x
+        const uint32_t rq = (uint32_t)__builtin_amdgcn_readlane((int)myrec, li);
+        auto left_at = [&](int t) -> CfRec { // (x + t lies inside the row: t comes from the clipped span of x)
+            CfRec l;
+            if (li + t >= 0 && li + t < 64) {
+                l.b = (uint32_t)__builtin_amdgcn_readlane((int)lr.x, li + t);
+                l.c0 = (uint32_t)__builtin_amdgcn_readlane((int)lr.y, li + t);
+                l.c1 = (uint32_t)__builtin_amdgcn_readlane((int)lr.z, li + t);
+            } else { // arms beyond the wave's window -- never with the small ring -- fall back to a load of their own
+                const uint4 q = ci.lrec[(size_t)y * W + xw + p + t];
+                l.b = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x);
+                l.c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
+                l.c1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z);
+            }
+            return l;
+        };
+        int lo = 0, hi = 0;
+        const bool single = (rq & 0xFFFFu) == 0u; // arms 0 / 0 (the clip changes no zero): the straight-line form of cost_flat_span
+        if (!single) cost_flat_arms(rq, xw + p, W, cap, &lo, &hi);
+        for (int c = 0; c < Dp; c += 128) {
+            const bool pad[2] = {c + 2 * lane >= ci.D, c + 2 * lane + 1 >= ci.D};
+            auto right_at = [&](int t, int k) -> CfRec {
+                CfRec r;
+                r.b = qB[t - c - k];
+                r.c0 = qC0[t - c - k];
+                r.c1 = qC1[t - c - k];
+                return r;
+            };
+            float out[2];
+            if (single) cost_flat_span<2, PAD>(0, 0, left_at, right_at, lutA, lutC, pad, out);
+            else cost_flat_span<2, PAD>(lo, hi, left_at, right_at, lutA, lutC, pad, out);
+            cf_f2 v;
+            v.x = out[0];
+            v.y = out[1];
+            ADC_VOL_STORE(reinterpret_cast<cf_f2*>(pd + c), v);
+        }
+    }
+}
+
+static size_t cost_agg_flat_lds(const adc_handle* h, int cap)
+{
+    return (size_t)(768 + 64 + 3 * (CF_TX + h->p.Dp - 1 + 2 * cap)) * 4;
+}
+bool adc_cost_agg_flat_fits(const adc_handle* h, int cap)
+{
+    return h->p.Dp % 128 == 0 && cap >= 0 && cost_agg_flat_lds(h, cap) <= CF_LDS_MAX;
+}
+hipError_t adc_launch_cost_agg_flat(adc_handle* h, float* dst, int cap, int small_variant, int small_L)
+{
+    const AdcParams& p = h->p;
+    if (!adc_cost_agg_flat_fits(h, cap)) return hipErrorInvalidValue;
+    AggCostIn ci;
+    ci.rrec = reinterpret_cast<const uint4*>(h->cost_rrec);
+    ci.lrec = reinterpret_cast<const uint4*>(h->cost_lrec);
+    ci.lut_ad = h->lut_ad;
+    ci.lut_census = h->lut_census;
+    ci.rpitch = h->rrec_pitch; ci.padl = h->rrec_padl; ci.dmin = p.dmin; ci.D = p.D;
+    const int tiles = (p.W + CF_TX - 1) / CF_TX;
+    if (p.D == p.Dp)
+        hipLaunchKernelGGL(k_cost_agg_flat<false>, dim3((unsigned)tiles * p.H), dim3(256), cost_agg_flat_lds(h, cap), h->heavy, dst, h->rec_h,
+                           p.W, p.H, p.Dp, cap, tiles, h->armmax, small_variant, small_L, ci);
+    else
+        hipLaunchKernelGGL(k_cost_agg_flat<true>, dim3((unsigned)tiles * p.H), dim3(256), cost_agg_flat_lds(h, cap), h->heavy, dst, h->rec_h,
+                           p.W, p.H, p.Dp, cap, tiles, h->armmax, small_variant, small_L, ci);
     return hipGetLastError();
 }
 

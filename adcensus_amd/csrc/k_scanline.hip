@@ -344,12 +344,20 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
 #define SO_AGG_EVAL(EIDX, C)                                                                                   \
     do {                                                                                                       \
         const uint32_t rec_ = recp[(EIDX)];                                                                    \
-        const int top_ = SO_AGG_LA + (int)(rec_ & 255u), bot_ = SO_AGG_LA - (int)((rec_ >> 8) & 255u);         \
-        const float cnt_ = (float)(rec_ >> 16);                                                                \
-        _Pragma("unroll") for (int k_ = 0; k_ < VPL; k_++) {                                                   \
-            float acc_ = 0.0f;                                                                                 \
-            _Pragma("unroll") for (int t_ = 2 * SO_AGG_LA; t_ >= 0; t_--) acc_ += (t_ <= top_ && t_ >= bot_) ? agr[t_][k_] : 0.0f; \
-            (C)[k_] = acc_ / cnt_; /* cross_aggregator.cpp:389 (x / 1 == x) */                                  \
+        /* The record is wave-uniform (a scalar load), so the branch is a scalar one.  Arms 0 / 0 and divisor 1 (about   */ \
+        /* 99 % of the elements of a short-arm image): the element is ring position SO_AGG_LA itself.  Exact: every value */ \
+        /* here is a sum or a quotient of non-negative costs, so never -0; the skipped sum is 0.0f + x plus +0.0f for     */ \
+        /* each masked position, which is x, and x / 1 == x.                                                              */ \
+        if (!adc_rec_changes_pixel(rec_, true)) {                                                              \
+            _Pragma("unroll") for (int k_ = 0; k_ < VPL; k_++) (C)[k_] = agr[SO_AGG_LA][k_];                   \
+        } else {                                                                                               \
+            const int top_ = SO_AGG_LA + (int)(rec_ & 255u), bot_ = SO_AGG_LA - (int)((rec_ >> 8) & 255u);     \
+            const float cnt_ = (float)(rec_ >> 16);                                                            \
+            _Pragma("unroll") for (int k_ = 0; k_ < VPL; k_++) {                                               \
+                float acc_ = 0.0f;                                                                             \
+                _Pragma("unroll") for (int t_ = 2 * SO_AGG_LA; t_ >= 0; t_--) acc_ += (t_ <= top_ && t_ >= bot_) ? agr[t_][k_] : 0.0f; \
+                (C)[k_] = acc_ / cnt_; /* cross_aggregator.cpp:389 (x / 1 == x) */                              \
+            }                                                                                                  \
         }                                                                                                      \
     } while (0)
     float Lp[VPL]; // previous path element's costs; padding lanes (d >= D) hold the sentinel

@@ -8,7 +8,12 @@ third column / row only, so no arm outgrows the small ring.  Prints a markdown t
 With `gather` as second argument the same pairs are matched alternately with the sparse march (ADC_AGG_GATHER=0) and with the gather
 form of the sparse launches forced (ADC_AGG_GATHER_DENSITY=1), both with the sparse form forced: the table behind
 AGG_GATHER_MAX_DENSITY (profiles/gather_agg_density_sweep.md).
-    python tools/gpu_sparse_sweep.py [reps] gather"""
+    python tools/gpu_sparse_sweep.py [reps] gather
+With `flat` the same pairs are matched alternately with the small-ring march as first launch (ADC_COST_FLAT=0) and with the
+element-wise first launch forced (k_cost_agg_flat, ADC_COST_FLAT_DENSITY=1), sparse and gather forms forced for the other launches;
+the time is the FIRST launch's, from the aggregation marks (debug counter 24): the table behind COST_FLAT_MAX_DENSITY
+(profiles/flat_cost_density_sweep.md).
+    python tools/gpu_sparse_sweep.py [reps] flat"""
 import os
 import sys
 
@@ -35,9 +40,10 @@ def planted(W, H, p, seed=12345):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    gather = len(sys.argv) > 2 and sys.argv[2] == "gather"
-    switch, counter = ("ADC_AGG_GATHER", 20) if gather else ("ADC_AGG_SPARSE", 16)
-    a, b = ("march", "gather") if gather else ("dense", "sparse")
+    flat = len(sys.argv) > 2 and sys.argv[2] == "flat"
+    gather = flat or (len(sys.argv) > 2 and sys.argv[2] == "gather")  # (flat: the pairs and the forced forms of the gather sweep)
+    switch, counter = ("ADC_COST_FLAT", 22) if flat else ("ADC_AGG_GATHER", 20) if gather else ("ADC_AGG_SPARSE", 16)
+    a, b = ("march", "flat") if flat else ("march", "gather") if gather else ("dense", "sparse")
     W, H, D = 1920, 1080, 128
     opt = A.ADCensusOption()
     opt.max_disparity = D
@@ -51,7 +57,9 @@ def main():
         st.set_profiling(True)
         os.environ["ADC_AGG_SPARSE_DENSITY"] = os.environ["ADC_AGG_GATHER_DENSITY"] = "1.0"
         os.environ["ADC_AGG_SPARSE"] = "1" if gather else "0"
-        os.environ["ADC_AGG_GATHER"] = "0"
+        os.environ["ADC_AGG_GATHER"] = "1" if flat else "0"
+        os.environ["ADC_COST_FLAT_DENSITY"] = "1.0"
+        os.environ["ADC_COST_FLAT"] = "0"
         st.match(l, r)  # (first Match of a handle: full ring)
         st.match(l, r)
         t = {"0": [], "1": []}
@@ -61,7 +69,8 @@ def main():
                 os.environ[switch] = mode
                 before = st.debug_counter(counter)
                 st.match(l, r)
-                t[mode].append(st.stage_ms()["aggregate"])
+                t[mode].append(st.debug_counter(24) * 1e-6 if flat else st.stage_ms()["aggregate"])
+                assert t[mode][-1] > 0
                 ran = st.debug_counter(counter) - before
                 assert (ran > 0) == (mode == "1"), (mode, ran, st.aggregate_kernel())
                 launches = max(launches, ran)
