@@ -189,13 +189,10 @@ struct adc_handle {
     int agg_switches;     // how often consecutive Matches needed different plans
     int agg_dual_runs;    // Matches whose aggregation was enqueued as two plans
     int armmax_small[2];  // arm maxima of the last image that fitted the small rings (0 = none seen)
-    int agg_gate, agg_gate_thr; // set while a plan of a two-plan run is being enqueued: gate code (3 / 4) and packed depths
     int redo_partial;     // redos that restarted at the aggregation instead of the whole Match
     int match_pending;    // a Match was enqueued and adc_wait has not yet looked at its arm maxima / speculation flags
-    int fuse_cost;        // set by the pipeline: the first aggregation pass computes the matching cost itself
     int agg_first_fused;  // the last aggregation run did so (pass timings: the regular passes are 1..)
     int fuse_wta;         // set by the pipeline: the last scanline pass also writes the left-view disparity map
-    int fuse_agg_so;      // set by the pipeline: the last aggregation pass may move into the first scanline pass (short-arm plan)
     int so_agg_fused;     // adc_launch_aggregate did so: vol_a holds the volume BEFORE that pass (consumed by the scanline stage)
     int agg_so_fusions;   // Matches that ran that way
     // Sparse small-ring launches (k_aggregate.hip): chosen per direction from the density of pass-changing records the handle
@@ -322,7 +319,9 @@ hipError_t adc_launch_sup_counts(adc_handle* h); // support counts + region boxe
 hipError_t adc_launch_arms_rest(adc_handle* h); // what reads both images: colour-step maps (+ paper mode: right-image arms)
 hipError_t adc_launch_aggregate_tail(adc_handle* h); // the dividing H pass adc_launch_aggregate left to the scanline stage, as a launch of its own
 hipError_t adc_launch_records(adc_handle* h); // arms + counts -> packed aggregation records
-hipError_t adc_launch_aggregate(adc_handle* h, int iterations); // vol_a -> vol_a via vol_b
+// vol_a -> vol_a via vol_b; fuse_cost: the first pass computes the matching cost itself, fuse_agg_so: the last pass may move into the
+// first scanline pass (short-arm plan).  What it launches is planned by agg_plan.h from the handle's arm / density state, which it only reads.
+hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, bool fuse_agg_so);
 hipError_t adc_launch_so_classes(adc_handle* h, hipStream_t stream);
 size_t adc_so_cls_bytes(int W, int H);
 hipError_t adc_launch_scanline(adc_handle* h, int passes);      // vol_a -> vol_a via vol_b (passes=4)

@@ -442,12 +442,8 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     }
     HIP_OK(adc_launch_records(h));
     } // (!from_aggregation)
-    h->fuse_cost = fuse_cost_now ? 1 : 0;
-    h->fuse_agg_so = 1; // (the launcher decides: short-arm plan, arms <= 4, segmented row passes)
-    {
-        const hipError_t e_ = adc_launch_aggregate(h, 4); // aggregator_.Aggregate(4), :164
-        h->fuse_cost = 0;
-        h->fuse_agg_so = 0;
+    {   // aggregator_.Aggregate(4), :164; the last pass may move into the scanline stage (the launcher decides: short-arm plan, arms <= 4, segmented row passes)
+        const hipError_t e_ = adc_launch_aggregate(h, 4, fuse_cost_now, true);
         h->armmax_valid = 0;
         HIP_OK(e_);
     }
@@ -628,9 +624,8 @@ static void abort_match(adc_handle* h)
     h->match_pending = 0;
     h->irv_pending = 0;
     h->so_agg_fused = 0;
-    h->fuse_cost = 0; h->fuse_agg_so = 0; h->fuse_wta = 0;
+    h->fuse_wta = 0;
     h->armmax_valid = 0;
-    h->agg_gate = 0;
     h->in_redo = 0;
     h->rec_nz_known = 0;
     h->wta_left_done = 0;
@@ -1886,6 +1881,7 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
     if (!h) return 1;
     hipSetDevice(h->device);
     hipError_t e = hipSuccess;
+    bool fuse_cost = false; // (ADC_RUN_AGGREGATE)
     switch (stage) {
     case ADC_RUN_GRAY_CENSUS: e = adc_launch_gray_census(h); break;
     case ADC_RUN_COST: e = adc_launch_cost(h, h->vol_a); break;
@@ -1912,11 +1908,10 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         }
         if (e == hipSuccess && arg >= 100) {
             if (h->paper & ADC_PAPER_RIGHT_ARMS) e = adc_launch_cost(h, h->vol_a); // (no fused form in this mode: recompute the volume)
-            else { e = adc_launch_cost_records(h); h->fuse_cost = 1; }
+            else { e = adc_launch_cost_records(h); fuse_cost = true; }
             arg -= 100;
         }
-        if (e == hipSuccess) e = adc_launch_aggregate(h, arg > 0 ? arg : 4);
-        h->fuse_cost = 0;
+        if (e == hipSuccess) e = adc_launch_aggregate(h, arg > 0 ? arg : 4, fuse_cost, false);
         h->armmax_valid = 0;
         break;
     case ADC_RUN_SCANLINE: // arg = passes (default 4); arg >= 100: the production form of the last pass, which also

@@ -17,6 +17,7 @@
 //   * algorithmic bytes per pass: read V + write V (+4 B/pixel arms, +2 B/pixel counts), V = 4*W*H*Dp.
 #include "adc_internal.h"
 #include "adc_device_fn.h"
+#include "agg_plan.h"
 #include <mutex>
 #include "k_aggregate_rr.h"
 #include "k_aggregate_rr2.h"
@@ -728,370 +729,183 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(RR2_V0))) void k
     agg_rr2_body<false, false, true>(nullptr, dst, rec, W, H, Dp, L, chunk_len, nwaves, per_xcd, armmax, small_variant, small_L, ci);
 }
 
+// ------------------------------------------------------------------------------------------ host: plan (agg_plan.h), then launch
+static_assert(AGG_PLAN_RING_REGS == AGG_RING_REGS && AGG_PLAN_RR2_SLOTS == RR2_SLOTS, "agg_plan.h plans for the rings of these kernels");
+
 static int env_int(const char* name, int dflt)
 {
     const char* s = getenv(name);
     return s ? atoi(s) : dflt;
 }
+static double env_double(const char* name, double dflt)
+{
+    const char* s = getenv(name);
+    return s ? atof(s) : dflt;
+}
+// density thresholds (agg_plan.h) with their overrides, read per call: the sweeps and the tests vary them
+double adc_agg_sparse_density(void) { return env_double("ADC_AGG_SPARSE_DENSITY", AGG_SPARSE_MAX_DENSITY); }
+double adc_agg_gather_density(void) { return env_double("ADC_AGG_GATHER_DENSITY", AGG_GATHER_MAX_DENSITY); }
+double adc_cost_flat_density(void) { return env_double("ADC_COST_FLAT_DENSITY", COST_FLAT_MAX_DENSITY); }
+
+// The switches of the plan: the first group is latched by the first call of the process, the second read on every call.
+static AggKnobs agg_knobs()
+{
+    static const AggKnobs latched = [] {
+        AggKnobs k;
+        k.small_L = env_int("ADC_AGG_SMALL_L", 8);
+        k.vpl2 = env_int("ADC_AGG_VPL2", 1);
+        k.regring = env_int("ADC_AGG_REGRING", 1) != 0;
+        k.rr2 = env_int("ADC_AGG_RR2", 1) != 0;
+        k.pair = env_int("ADC_AGG_PAIR", 1) != 0;
+        k.pair_full = env_int("ADC_AGG_PAIR_FULL", 0);
+        return k;
+    }();
+    AggKnobs k = latched;
+    k.assume_margin = env_int("ADC_AGG_ASSUME_MARGIN", 1);
+    k.sparse = env_int("ADC_AGG_SPARSE", 1) != 0;
+    k.sparse_density = adc_agg_sparse_density();
+    k.gather = env_int("ADC_AGG_GATHER", 1) != 0;
+    k.gather_density = adc_agg_gather_density();
+    k.cost_flat = env_int("ADC_COST_FLAT", 1) != 0;
+    k.cost_flat_density = adc_cost_flat_density();
+    k.dual = env_int("ADC_AGG_DUAL", 1) != 0;
+    k.seg[0] = env_int("ADC_AGG_HSEG", 0);
+    k.seg[1] = env_int("ADC_AGG_VSEG", 0);
+    k.chunk[0] = env_int("ADC_AGG_HCHUNK", 0);
+    k.chunk[1] = env_int("ADC_AGG_VCHUNK", 0);
+    return k;
+}
+
+// what the handle knows, by value (the aggregation only READS the handle's arm and density state)
+static AggInputs agg_inputs(const adc_handle* h, const AggKnobs& kn, int iterations, bool fuse_cost, bool fuse_agg_so)
+{
+    AggInputs in = {};
+    in.W = h->p.W; in.H = h->p.H; in.Dp = h->p.Dp; in.cross_L1 = h->p.opt.cross_L1; in.iterations = iterations;
+    in.arms = (AggArms)h->armmax_valid;
+    for (int c = 0; c < 2; c++) { in.armmax[c] = h->armmax_host[c]; in.armmax_small[c] = h->armmax_small[c]; in.rec_nz[c] = h->rec_nz_host[c]; }
+    in.rec_nz_known = h->rec_nz_known != 0;
+    in.in_redo = h->in_redo != 0;
+    in.dual = h->agg_dual > 0;
+    in.fuse_cost = fuse_cost;
+    in.fuse_agg_so = fuse_agg_so;
+    in.so_can_fuse = adc_so_can_fuse_agg(h);
+    in.cost_flat_fits = adc_cost_agg_flat_fits(h, agg_assumed_depth(in, kn, false));
+    return in;
+}
 
 // arm length up to which the small-ring variant is used (ADC_AGG_SMALL_L, 0 disables it)
 int adc_agg_small_L(const adc_handle* h)
 {
-    static const int small_L_env = env_int("ADC_AGG_SMALL_L", 8);
-    const int L = adc_imax(0, adc_imin(h->p.opt.cross_L1, 255));
-    return adc_imin(small_L_env, L);
+    AggInputs in = {};
+    in.cross_L1 = h->p.opt.cross_L1;
+    return agg_small_L(in, agg_knobs());
 }
 
-// Picks the number of line segments: all waves of a "round" run concurrently (9 per CU), a pass costs
-// rounds x (segment length + halo) steps.
-static int pick_nseg(long long nlines, int N, int L, int slots)
+#define AGG_SEG_ARGS p.W, p.H, p.Dp, l.depth, l.seg_len, l.nseg, l.per_xcd, h->armmax, l.small_variant, l.small_L
+#define AGG_CHUNK_ARGS p.W, p.H, p.Dp, l.depth, l.chunk_len, l.nwaves, l.per_xcd, h->armmax, l.small_variant, l.small_L
+// One launch of a plan (+ k_agg_apply behind a sparse one: the result is then in src, not in dst).
+template <bool VERT, bool DIVIDE, bool COSTIN, bool PAIR>
+static hipError_t launch_form(adc_handle* h, const AggLaunch& l, const float* src, float* dst)
 {
-    int best = 1;
-    long long best_cost = -1;
-    for (int ns = 1; ns <= 16; ns++) {
-        const int seg = (N + ns - 1) / ns;
-        if (ns > 1 && seg < 2 * L) break;
-        const long long rounds = (nlines * ns + slots - 1) / slots;
-        const long long cost = rounds * (seg + (ns > 1 ? 2 * L : 0));
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ns; }
-    }
-    return best;
-}
-
-// Chunk length of the pair-register-ring kernels (a wave = chunk_len consecutive outputs of the line-major index space,
-// k_aggregate_rr2.h).  Candidates: whole-line segmentations N / k and equal shares of the whole pass per wave slot (1x, 2x, 3x
-// the slots); cost model = rounds x (steps + 2L halo entries + a fixed price per piece for its prologue / slow tail).
-static int pick_chunk(long long nlines, int N, int L, int slots)
-{
-    const long long total = nlines * N;
-    long long best_cost = -1;
-    int best = N;
-    auto consider = [&](long long c) {
-        if (c < 1) c = 1;
-        if (c < N && c < 4 * (long long)L) return; // halo-dominated
-        if (c > total) c = total;
-        const long long waves = (total + c - 1) / c;
-        const long long rounds = (waves + slots - 1) / slots;
-        const bool aligned = c >= N ? (c % N == 0) : (N % c == 0);
-        const long long pieces = aligned ? (c >= N ? c / N : 1) : (c >= N ? c / N + 2 : 2);
-        const long long halo = (c < N || !aligned) ? 2LL * L : 0;
-        const long long cost = rounds * (c + halo + 60 * pieces);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = (int)c; }
-    };
-    for (int k = 1; k <= 16; k++) consider((N + k - 1) / k);
-    for (int k = 1; k <= 3; k++) consider((total + (long long)slots * k - 1) / ((long long)slots * k));
-    return best;
-}
-
-// Ring depth of a small-ring launch along one direction when the host works with arm maxima (armmax_host): the longest arm,
-// plus one entry of margin when the maxima are ASSUMED from an earlier Match of the handle (armmax_valid == 2; the next image of a
-// similar stream may have a longest arm of 3 after 2, and a wrong depth costs a redo or the full-ring plan: ADC_AGG_ASSUME_MARGIN).
-static int agg_assumed_depth(const adc_handle* h, bool vert)
-{
-    const int assume_margin = env_int("ADC_AGG_ASSUME_MARGIN", 1); // (read per call: the tests vary it within one process)
-    const int Lknown = adc_imax(1, h->armmax_host[vert ? 1 : 0]) + (h->armmax_valid == 2 ? assume_margin : 0);
-    return adc_imin(adc_agg_small_L(h), Lknown);
-}
-
-// which: 0 = the host does not know the arms: launch the full-ring and the small-ring variant, the kernel decides;
-//        1 = small ring only, 2 = full ring only (the host has read armmax).  PAIR needs which == 1.
-// two disparities per lane with the small ring (ADC_AGG_VPL2: 1 = every small-ring launch, 2 = pass pairs only, 0 = off)
-static bool agg_small_vpl2(const adc_handle* h, bool pair)
-{
-    static const int vpl2_env = env_int("ADC_AGG_VPL2", 1);
-    return (vpl2_env == 1 || (vpl2_env == 2 && pair)) && h->p.Dp % 128 == 0;
-}
-
-// Largest fraction of pixels with a pass-changing record (per direction, of the previous Match) up to which the small-ring
-// launches of that direction run in their sparse form: half of the measured break-even density against the dense form (0.211
-// on 1080p noise pairs with planted copies: tools/gpu_sparse_sweep.py, profiles/sparse_agg_density_sweep.md;
-// ADC_AGG_SPARSE_DENSITY overrides the value, read per call: the sweep and the tests vary it).
-#define AGG_SPARSE_MAX_DENSITY 0.105
-double adc_agg_sparse_density(void)
-{
-    const char* e = getenv("ADC_AGG_SPARSE_DENSITY");
-    return e ? atof(e) : AGG_SPARSE_MAX_DENSITY;
-}
-// Does a small-ring launch of this direction run sparse?  Only in the plain short-arm plan of the pipeline (arms read back or
-// assumed, one plan enqueued, not a redo), with two disparities per lane, when the record density the handle last saw is low.
-// Both forms give the same bits for every image: a wrong guess costs time, never a redo.  ADC_AGG_SPARSE=0 switches it off.
-static bool agg_sparse_wanted(const adc_handle* h, bool vert, bool pair)
-{
-    const char* e = getenv("ADC_AGG_SPARSE"); // (read per call: the tests switch it within one process)
-    if (e && atoi(e) == 0) return false;
-    if (h->agg_gate || h->in_redo || !(h->armmax_valid == 1 || h->armmax_valid == 2) || !h->rec_nz_known) return false;
-    if (!agg_small_vpl2(h, pair)) return false;
-    return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_sparse_density() * (double)h->p.W * (double)h->p.H;
-}
-
-// Density up to which a sparse launch runs in its GATHER form (k_agg_gather: computes only the pixels it stores, from the vectors of
-// their spans) instead of marching over the whole volume with the stores masked.  Rule: half of the measured break-even density
-// against the sparse march.  Measured (tools/gpu_sparse_sweep.py 5 gather, profiles/gather_agg_density_sweep.md: 1080p noise pairs
-// with planted copies): gather is faster at every density up to 0.30 and breaks even at 0.42, half of which (0.211) lies above the
-// whole range in which the sparse march runs -- so the threshold EQUALS AGG_SPARSE_MAX_DENSITY: every sparse launch gathers.
-// ADC_AGG_GATHER_DENSITY overrides the value, read per call: the sweep and the tests vary it.
-#define AGG_GATHER_MAX_DENSITY AGG_SPARSE_MAX_DENSITY
-double adc_agg_gather_density(void)
-{
-    const char* e = getenv("ADC_AGG_GATHER_DENSITY");
-    return e ? atof(e) : AGG_GATHER_MAX_DENSITY;
-}
-// Does a sparse launch of this direction (agg_sparse_wanted holds: never a first Match, a two-plan Match or a redo) gather?
-// Every form gives the same bits.  ADC_AGG_GATHER=0 switches the form off.
-static bool agg_gather_wanted(const adc_handle* h, bool vert)
-{
-    const char* e = getenv("ADC_AGG_GATHER"); // (read per call, like ADC_AGG_SPARSE)
-    if (e && atoi(e) == 0) return false;
-    return (double)h->rec_nz_host[vert ? 1 : 0] <= adc_agg_gather_density() * (double)h->p.W * (double)h->p.H;
-}
-
-// Density (horizontal pass-changing records of the previous Match) up to which the FIRST launch of the short-arm plan -- fused cost,
-// small ring -- runs as the element-wise k_cost_agg_flat (k_cost.hip) instead of k_agg_march<.., COSTIN>.  Rule: half of the measured
-// break-even density against the march, never above AGG_SPARSE_MAX_DENSITY (agg_sparse_wanted is part of the predicate).
-// ADC_COST_FLAT_DENSITY overrides the value, read per call: the sweep and the tests vary it.
-#define COST_FLAT_MAX_DENSITY AGG_SPARSE_MAX_DENSITY
-double adc_cost_flat_density(void)
-{
-    const char* e = getenv("ADC_COST_FLAT_DENSITY");
-    return e ? atof(e) : COST_FLAT_MAX_DENSITY;
-}
-// Does the first launch run flat?  Only where the horizontal small-ring launches run sparse (agg_sparse_wanted: never the first Match
-// of a handle, a two-plan Match or a redo; low density), with the host knowing or assuming the arms (which == 1).  Both forms give the
-// same bits and keep the same gate.  ADC_COST_FLAT=0 gives the march back.
-static bool cost_flat_wanted(const adc_handle* h, int which, int cap)
-{
-    const char* e = getenv("ADC_COST_FLAT"); // (read per call, like ADC_AGG_GATHER)
-    if (e && atoi(e) == 0) return false;
-    if (which != 1 || !agg_sparse_wanted(h, false, false) || !adc_cost_agg_flat_fits(h, cap)) return false;
-    return (double)h->rec_nz_host[0] <= adc_cost_flat_density() * (double)h->p.W * (double)h->p.H;
-}
-
-// sparse: small-ring launch in its sparse form + k_agg_apply (the result is then in src, not in dst); which == 1 only
-template <bool VERT, bool DIVIDE, bool COSTIN = false, bool PAIR = false>
-static hipError_t launch_pass(adc_handle* h, const float* src, float* dst, int which = 0, bool sparse = false)
-{
-    const bool gather = sparse && agg_gather_wanted(h, VERT);
     const AdcParams& p = h->p;
-    const int L = adc_imax(0, adc_imin(p.opt.cross_L1, 255)); // (a ring of 2 * 255 + 1 entries of 256 bytes fits the 160 KiB of LDS: every arm limit marches)
-    const int N = VERT ? p.H : p.W;
-    const int small_L = adc_agg_small_L(h);
-    if (sparse && (COSTIN || which != 1 || !agg_small_vpl2(h, PAIR))) return hipErrorInvalidValue; // (agg_sparse_wanted)
-    for (int variant = 0; variant < 2; variant++) { // 0: full ring, 1: small ring (exits unless every arm <= small_L)
-        if (variant == 1 && (small_L <= 0 || small_L >= L)) break;
-        if ((which == 1 && variant == 0 && small_L > 0 && small_L < L) || (which == 2 && variant == 1)) continue;
-        // the ring only has to be as deep as the longest arm of this direction when the host knows it (which == 1)
-        const int Lv = variant ? ((which == 1 && h->armmax_valid) ? agg_assumed_depth(h, VERT) : small_L) : L;
-        // the fused-cost variant keeps the two cost tables (768 + 64 floats) behind the ring, the pair variant a second
-        // ring and a record ring
-        // full ring of a plain pass: in registers when it fits (ADC_AGG_REGRING=0: LDS ring)
-        static const bool regring_env = env_int("ADC_AGG_REGRING", 1) != 0;
-        const bool regring = variant == 0 && regring_env && Lv >= 1 && 2 * Lv + 1 <= AGG_RING_REGS;
-        // ... as VGPR pairs, two disparities per lane (k_aggregate_rr2.h; ADC_AGG_RR2=0: the one-float register ring)
-        static const bool rr2_env = env_int("ADC_AGG_RR2", 1) != 0;
-        const bool rr2 = regring && rr2_env && !PAIR && p.Dp % 128 == 0 && 2 * Lv + 1 <= RR2_SLOTS;
-        const int vpl = rr2 ? 2 : ((variant == 1 && !COSTIN && agg_small_vpl2(h, PAIR)) ? 2 : 1);
-        const long long nlines = (long long)(VERT ? p.W : p.H) * (p.Dp / (64 * vpl));
-        const size_t ring_bytes = regring ? 0 : (size_t)(2 * Lv + 1) * 64 * sizeof(float) * vpl;
-        const size_t ldsv = ring_bytes + (COSTIN ? (768 + 64) * sizeof(float) : 0) + ((PAIR && !regring) ? ring_bytes + (2 * Lv + 1) * 4 + 64 : 0);
-        // register rings: 128 VGPRs -> 4 waves per SIMD; a pair (two rings, 200 VGPRs) or a ring of pairs (240) -> 2
-        const int waves_per_cu = regring ? ((PAIR || rr2) ? 8 : 16) : adc_imax(1, adc_imin(32, (int)((160 * 1024) / ((ldsv + 511) / 512 * 512))));
-        int nseg = env_int(VERT ? "ADC_AGG_VSEG" : "ADC_AGG_HSEG", 0);
-        if (nseg < 1) nseg = pick_nseg(nlines, N, PAIR ? 2 * Lv : Lv, 256 * waves_per_cu);
-        int seg_len = (N + nseg - 1) / nseg;
-        if (seg_len < 1) seg_len = 1;
-        nseg = (N + seg_len - 1) / seg_len;
-        const long long waves = nlines * nseg;
-        const int per_xcd = (int)((waves + 7) / 8);
-        const bool both = which == 0 && small_L > 0 && small_L < L;
-        const bool verify = variant == 1 && which == 1 && h->armmax_valid == 2; // ring depth assumed from the previous Match
-        int sv = both ? variant : (verify ? 2 : -1), sl = both ? small_L : (verify ? Lv : 0x7fffffff);
-        if (h->agg_gate) { sv = h->agg_gate; sl = h->agg_gate_thr; } // one of two plans enqueued back to back (adc_launch_aggregate)
-        AggCostIn ci;
-        ci.rrec = reinterpret_cast<const uint4*>(h->cost_rrec);
-        ci.lrec = reinterpret_cast<const uint4*>(h->cost_lrec);
-        ci.lut_ad = h->lut_ad;
-        ci.lut_census = h->lut_census;
-        ci.rpitch = h->rrec_pitch; ci.padl = h->rrec_padl; ci.dmin = p.dmin; ci.D = p.D;
-        if (!COSTIN) // (which == 0, debug path: both variants are launched and the kernels decide; the label is then the last one)
-            h->agg_kernel = rr2 ? "k_agg_rr2 (register ring of VGPR pairs, 2 disparities per lane, one pass per launch)"
-                          : regring ? (PAIR ? "k_agg_regring_pair (two register rings, dividing pass + next first pass per launch)"
-                                            : "k_agg_regring (register ring, 1 disparity per lane, one pass per launch)")
-                          : (variant && gather) ? (PAIR ? "k_agg_gather<.., PAIR> + k_agg_apply (SPARSE launch, gather form: dividing pass + next first pass, only changed pixels computed)"
-                                                        : "k_agg_gather + k_agg_apply (SPARSE launch, gather form: one pass per launch, only changed pixels computed)")
-                          : (variant && sparse) ? (PAIR ? "k_agg_march<.., PAIR, SPARSE> + k_agg_apply (LDS small rings: dividing pass + next first pass per launch, only changed pixels stored)"
-                                                        : "k_agg_march<.., SMALL, SPARSE> + k_agg_apply (LDS small ring, one pass per launch, only changed pixels stored)")
-                          : variant ? (PAIR ? "k_agg_march<.., PAIR> (LDS small rings: dividing pass + next first pass per launch)"
-                                            : "k_agg_march<.., SMALL> (LDS small ring, one pass per launch)")
-                                    : "k_agg_march (LDS full ring, one pass per launch)";
-        if (rr2) {
-            int chunk_len = env_int(VERT ? "ADC_AGG_VCHUNK" : "ADC_AGG_HCHUNK", 0);
-            if (chunk_len < 1) chunk_len = pick_chunk(nlines, N, Lv, 256 * waves_per_cu);
-            const long long total = nlines * N;
-            const int nwaves = (int)((total + chunk_len - 1) / chunk_len);
-            const int pxc = (nwaves + 7) / 8;
-            if constexpr (COSTIN)
-                hipLaunchKernelGGL(k_agg_rr2_cost, dim3((unsigned)pxc * 8), dim3(64), ldsv, h->heavy, dst,
-                                   reinterpret_cast<const uint2*>(h->rec2_h), p.W, p.H, p.Dp, Lv, chunk_len, nwaves, pxc, h->armmax, sv, sl, ci);
-            else if constexpr (!PAIR)
-                hipLaunchKernelGGL((k_agg_rr2<VERT, DIVIDE>), dim3((unsigned)pxc * 8), dim3(64), 0, h->heavy, src, dst,
-                                   reinterpret_cast<const uint2*>(VERT ? h->rec2_v : h->rec2_h), p.W, p.H, p.Dp, Lv, chunk_len, nwaves,
-                                   pxc, h->armmax, sv, sl);
-        } else if (regring) {
-            if constexpr (COSTIN)
-                hipLaunchKernelGGL(k_agg_regring_cost, dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                                   VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
-            else if constexpr (PAIR)
-                hipLaunchKernelGGL((k_agg_regring_pair<VERT>), dim3((unsigned)per_xcd * 8), dim3(64), 0, h->heavy, src, dst,
-                                   reinterpret_cast<const uint2*>(VERT ? h->rec2_v : h->rec2_h), p.W, p.H, p.Dp, Lv, seg_len, nseg,
-                                   per_xcd, h->armmax, sv, sl, h->agg_sink);
-            else
-                hipLaunchKernelGGL((k_agg_regring<VERT, DIVIDE>), dim3((unsigned)per_xcd * 8), dim3(64), 0, h->heavy, src, dst,
-                                   reinterpret_cast<const uint2*>(VERT ? h->rec2_v : h->rec2_h), p.W, p.H, p.Dp, Lv, seg_len, nseg,
-                                   per_xcd, h->armmax, sv, sl, h->agg_sink);
-        } else if (variant && vpl == 2) {
-            if constexpr (!COSTIN) {
-                if (sparse) {
-                    const long long P = (long long)p.W * p.H;
-                    if (gather) {
-                        hipLaunchKernelGGL((k_agg_gather<VERT, DIVIDE, PAIR>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->heavy, src, dst,
-                                           VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, h->armmax, sv, sl);
-                        h->agg_gather_launches++;
-                    } else
-                        hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2, true>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                                           VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
-                    hipLaunchKernelGGL((k_agg_apply<VERT>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->heavy, dst, const_cast<float*>(src),
-                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, (DIVIDE || PAIR) ? 1 : 0, h->armmax, sv, sl);
-                    h->agg_sparse_launches++;
-                    h->agg_sparse_last = 1;
-                } else
-                    hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                                       VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
-            }
-        } else if (variant && COSTIN && cost_flat_wanted(h, which, Lv)) {
-            const hipError_t ef = adc_launch_cost_agg_flat(h, dst, Lv, sv, sl); // (one launch for one launch, same gate)
-            if (ef != hipSuccess) return ef;
-            h->agg_flat_launches++;
-        } else if (variant)
-            hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, COSTIN, PAIR>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                               VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
-        else
-            hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, false, COSTIN, PAIR>), dim3((unsigned)per_xcd * 8), dim3(64), ldsv, h->heavy, src, dst,
-                               VERT ? h->rec_v : h->rec_h, p.W, p.H, p.Dp, Lv, seg_len, nseg, per_xcd, h->armmax, sv, sl, ci);
+    const dim3 grid(l.grid), block(l.block);
+    const uint32_t* rec = VERT ? h->rec_v : h->rec_h;
+    const uint2* rec2 = reinterpret_cast<const uint2*>(VERT ? h->rec2_v : h->rec2_h);
+    AggCostIn ci;
+    ci.rrec = reinterpret_cast<const uint4*>(h->cost_rrec);
+    ci.lrec = reinterpret_cast<const uint4*>(h->cost_lrec);
+    ci.lut_ad = h->lut_ad;
+    ci.lut_census = h->lut_census;
+    ci.rpitch = h->rrec_pitch; ci.padl = h->rrec_padl; ci.dmin = p.dmin; ci.D = p.D;
+    switch (l.form) {
+    case AGG_RR2_COST:
+        if constexpr (COSTIN) hipLaunchKernelGGL(k_agg_rr2_cost, grid, block, l.lds, h->heavy, dst, rec2, AGG_CHUNK_ARGS, ci);
+        break;
+    case AGG_RR2:
+        if constexpr (!COSTIN && !PAIR) hipLaunchKernelGGL((k_agg_rr2<VERT, DIVIDE>), grid, block, l.lds, h->heavy, src, dst, rec2, AGG_CHUNK_ARGS);
+        break;
+    case AGG_REGRING_COST:
+        if constexpr (COSTIN) hipLaunchKernelGGL(k_agg_regring_cost, grid, block, l.lds, h->heavy, src, dst, rec, AGG_SEG_ARGS, ci);
+        break;
+    case AGG_REGRING_PAIR:
+        if constexpr (!COSTIN && PAIR) hipLaunchKernelGGL((k_agg_regring_pair<VERT>), grid, block, l.lds, h->heavy, src, dst, rec2, AGG_SEG_ARGS, h->agg_sink);
+        break;
+    case AGG_REGRING:
+        if constexpr (!COSTIN && !PAIR) hipLaunchKernelGGL((k_agg_regring<VERT, DIVIDE>), grid, block, l.lds, h->heavy, src, dst, rec2, AGG_SEG_ARGS, h->agg_sink);
+        break;
+    case AGG_GATHER:
+        if constexpr (!COSTIN)
+            hipLaunchKernelGGL((k_agg_gather<VERT, DIVIDE, PAIR>), grid, block, l.lds, h->heavy, src, dst, rec, p.W, p.H, p.Dp, h->armmax, l.small_variant, l.small_L);
+        break;
+    case AGG_MARCH_SPARSE:
+        if constexpr (!COSTIN) hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2, true>), grid, block, l.lds, h->heavy, src, dst, rec, AGG_SEG_ARGS, ci);
+        break;
+    case AGG_MARCH_SMALL2:
+        if constexpr (!COSTIN) hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, false, PAIR, 2>), grid, block, l.lds, h->heavy, src, dst, rec, AGG_SEG_ARGS, ci);
+        break;
+    case AGG_COST_FLAT: return adc_launch_cost_agg_flat(h, dst, l.depth, l.small_variant, l.small_L); // (one launch for one launch, same gate)
+    case AGG_MARCH_SMALL: hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, true, COSTIN, PAIR>), grid, block, l.lds, h->heavy, src, dst, rec, AGG_SEG_ARGS, ci); break;
+    case AGG_MARCH_FULL: hipLaunchKernelGGL((k_agg_march<VERT, DIVIDE, false, COSTIN, PAIR>), grid, block, l.lds, h->heavy, src, dst, rec, AGG_SEG_ARGS, ci); break;
+    default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
+    if constexpr (!COSTIN)
+        if (l.apply)
+            hipLaunchKernelGGL((k_agg_apply<VERT>), dim3((unsigned)(((long long)p.W * p.H + 255) / 256)), dim3(256), 0, h->heavy, dst, const_cast<float*>(src), rec,
+                               p.W, p.H, p.Dp, (DIVIDE || PAIR) ? 1 : 0, h->armmax, l.small_variant, l.small_L);
+    return hipSuccess;
+}
+#undef AGG_SEG_ARGS
+#undef AGG_CHUNK_ARGS
+
+// the pass kinds a plan holds: fused first pass | first passes H, V | dividing passes V, H, each single or as a pair
+static hipError_t launch_one(adc_handle* h, const AggLaunch& l, float* const vol[2])
+{
+    const float* src = vol[l.src];
+    float* dst = vol[l.dst];
+    switch ((l.vert ? 8 : 0) | (l.divide ? 4 : 0) | (l.costin ? 2 : 0) | (l.pair ? 1 : 0)) {
+    case 2: return launch_form<false, false, true, false>(h, l, src, dst);
+    case 0: return launch_form<false, false, false, false>(h, l, src, dst);
+    case 8: return launch_form<true, false, false, false>(h, l, src, dst);
+    case 12: return launch_form<true, true, false, false>(h, l, src, dst); // / sup_h
+    case 13: return launch_form<true, true, false, true>(h, l, src, dst);
+    case 4: return launch_form<false, true, false, false>(h, l, src, dst); // / sup_v
+    case 5: return launch_form<false, true, false, true>(h, l, src, dst);
+    default: return hipErrorInvalidValue;
+    }
 }
 
-// One plan of the aggregation: the launch sequence for the ring choice (which_h, which_v) the handle's state implies.
-//   dry            only count (no launch, no event, nothing of the handle changes)
-//   first_into_cur the first launch writes the volume it would have READ (only with the fused cost, which has no input volume):
-//                  flips which of the two volumes the plan ends in
-//   marks          record the profiling events / launch statistics of this plan
-struct AggSeq { int launches, passes; float* result; bool first_fused; };
-static hipError_t agg_sequence(adc_handle* h, int iterations, bool dry, bool first_into_cur, bool marks, AggSeq* out)
+// Walks a plan.  marks: record the profiling events (only the ones adc_wait reads: start of the first / first regular launch
+// step, end) and the launch statistics of this plan.
+static hipError_t agg_execute(adc_handle* h, const AggPlan& plan, float* const vol[2], bool marks)
 {
-    static const bool pair_env = env_int("ADC_AGG_PAIR", 1) != 0;
-    // pairs with the full ring: 0 (default) = never, 1 = when both rings fit into registers (k_agg_regring_pair), 2 = also
-    // as two 17 KiB LDS rings per wave.  Measured on MI355X (structured 1080p pair, rocprofv3): a register-ring pair
-    // launch takes 0.95-1.02 ms against 2 x 0.42 ms for two single passes -- 200 VGPRs leave 2 waves per SIMD, and this
-    // kernel family runs at ~8.7 cycles per instruction and wave whatever the occupancy, so halving the waves doubles
-    // the time per step while the saved HBM round trip (0.2 ms at the copy rate) does not pay for it; two LDS rings were
-    // 3x slower.  The single pass itself now runs at the device copy rate.
-    static const int pair_full = env_int("ADC_AGG_PAIR_FULL", 0);
-    static const bool regring_on = env_int("ADC_AGG_REGRING", 1) != 0;
+    const bool prof = marks && h->profiling;
+    const size_t n = plan.launch.size();
     hipError_t e = hipSuccess;
-    const int Lfull = adc_imax(0, adc_imin(h->p.opt.cross_L1, 255));
-    const bool regring_fits = regring_on && Lfull >= 1 && 2 * Lfull + 1 <= AGG_RING_REGS;
-    const bool lds_fits = (size_t)(2 * Lfull + 1) * 64 * sizeof(float) + (768 + 64) * sizeof(float) <= 150 * 1024;
-    const bool marching = true; // (every arm limit fits an LDS ring; round 6 dropped the one-thread-per-element fallback no geometry selected)
-    const bool prof = marks && !dry && h->profiling;
-    // armmax_host (valid when the pipeline / caller read the maximum arms back): pick the ring on the host
-    const int small_L = adc_agg_small_L(h);
-    const bool small_ok = small_L > 0 && small_L < Lfull;
-    int which_h = 0, which_v = 0; // 0 = let the kernels decide (two launches per pass)
-    if (h->armmax_valid == 3 && marching) { // nothing known about this image: the full ring is valid for every image
-        which_h = which_v = 2;
-    } else if (h->armmax_valid && marching) {
-        which_h = (small_ok && h->armmax_host[0] <= small_L) ? 1 : 2;
-        which_v = (small_ok && h->armmax_host[1] <= small_L) ? 1 : 2;
+    for (size_t i = 0; i < n && e == hipSuccess; i++) {
+        const AggLaunch& l = plan.launch[i];
+        const bool first = i == 0 || plan.launch[i - 1].step != l.step, last = i + 1 == n || plan.launch[i + 1].step != l.step;
+        if (prof && first && l.step < 2) hipEventRecord(h->ev_agg[l.step], h->heavy);
+        e = launch_one(h, l, vol);
+        if (l.label) h->agg_kernel = l.label; // (two launches per pass, debug surface: the label is then the last one)
+        if (e == hipSuccess && last) e = hipGetLastError();
     }
-    // Pass sequence (cross_aggregator.cpp:100-118): iteration k = [first direction][second direction, divided by the
-    // support count]; the direction order alternates, so the dividing pass of iteration k and the first pass of
-    // iteration k+1 run along the SAME direction and can share one launch (PAIR) when the small ring is in use.
-    float* cur = h->vol_a; // holds the input of the next launch
-    float* oth = h->vol_b;
-    bool horizontal_first = true; // cross_aggregator.cpp:100
-    int launch = 0;
-    int passes = 0; // algorithmic passes (cross_aggregator.cpp: 2 per iteration) covered by the launches so far
-    bool second_done = false; // the first pass of this iteration was already computed by the previous pair launch
-    bool first_fused = false;
-    for (int k = 0; k < iterations && e == hipSuccess; k++) {
-        const bool hf = horizontal_first;
-        if (!second_done) {
-            if (prof && launch < 2) hipEventRecord(h->ev_agg[launch], h->heavy); // (only the marks adc_wait reads: start of the first / first regular launch)
-            bool swap = true;
-            if (hf) {
-                // first pass of the pipeline: the matching cost is computed inside the pass (no input volume)
-                const bool fused = k == 0 && h->fuse_cost && lds_fits;
-                if (k == 0) first_fused = fused;
-                if (fused) {
-                    swap = !first_into_cur;
-                    if (!dry) e = launch_pass<false, false, true>(h, cur, swap ? oth : cur, which_h);
-                } else {
-                    const bool sp = which_h == 1 && agg_sparse_wanted(h, false, false);
-                    if (!dry) e = launch_pass<false, false>(h, cur, oth, which_h, sp);
-                    swap = !sp; // (a sparse launch leaves its result in the volume it read)
-                }
-            } else {
-                const bool sp = which_v == 1 && agg_sparse_wanted(h, true, false);
-                if (!dry) e = launch_pass<true, false>(h, cur, oth, which_v, sp);
-                swap = !sp;
-            }
-            if (swap) { float* t = cur; cur = oth; oth = t; }
-            launch++;
-            passes++;
-        }
-        second_done = false;
-        if (e != hipSuccess) break;
-        if (prof && launch < 2) hipEventRecord(h->ev_agg[launch], h->heavy); // (only the marks adc_wait reads: start of the first / first regular launch)
-        // second pass of the iteration (dividing): vertical after a horizontal first pass and vice versa
-        const int wsec = hf ? which_v : which_h;
-        // The LAST pass (horizontal, dividing) of a short-arm image moves into the first scanline pass (k_scanline_seg_agg:
-        // one launch and 2 V of traffic less): arms up to 4, assumed or known; the other horizontal passes verify the depth.
-        if (!hf && k + 1 == iterations && iterations == 4 && h->fuse_agg_so && !h->agg_gate && marching && which_h == 1 &&
-            (h->armmax_valid == 1 || h->armmax_valid == 2) && agg_assumed_depth(h, false) <= 4 && adc_so_can_fuse_agg(h)) {
-            if (!dry) { h->so_agg_fused = 1; h->agg_so_fusions++; }
-            break;
-        }
-        const bool pair = pair_env && marching && k + 1 < iterations &&
-                          (wsec == 1 || (wsec == 2 && (pair_full >= 2 || (pair_full == 1 && regring_fits))));
-        const bool sparse = wsec == 1 && agg_sparse_wanted(h, hf, pair); // (the second pass runs across the first: vertical after hf)
-        if (!dry) {
-            if (hf) {
-                if (pair) e = launch_pass<true, true, false, true>(h, cur, oth, wsec, sparse);
-                else e = launch_pass<true, true>(h, cur, oth, which_v, sparse); // / sup_h
-            } else {
-                if (pair) e = launch_pass<false, true, false, true>(h, cur, oth, wsec, sparse);
-                else e = launch_pass<false, true>(h, cur, oth, which_h, sparse); // / sup_v
-            }
-        }
-        if (!sparse) { float* t = cur; cur = oth; oth = t; } // (a sparse launch leaves its result in the volume it read)
-        launch++;
-        passes += pair ? 2 : 1;
-        second_done = pair;
-        horizontal_first = !horizontal_first;
+    if (prof) hipEventRecord(h->ev_agg[adc_imin(plan.steps, 8)], h->heavy);
+    if (marks) {
+        h->agg_first_fused = plan.first_fused ? 1 : 0;
+        h->agg_launches = adc_imin(plan.steps, 8);
+        h->agg_passes = plan.passes;
     }
-    if (prof) hipEventRecord(h->ev_agg[launch < 8 ? launch : 8], h->heavy);
-    if (marks && !dry) {
-        h->agg_first_fused = first_fused ? 1 : 0;
-        h->agg_launches = launch < 8 ? launch : 8;
-        h->agg_passes = passes;
-    }
-    if (out) { out->launches = launch; out->passes = passes; out->result = cur; out->first_fused = first_fused; }
+    h->agg_sparse_launches += plan.sparse;
+    h->agg_gather_launches += plan.gather;
+    h->agg_flat_launches += plan.flat;
+    if (plan.sparse) h->agg_sparse_last = 1;
     return e;
 }
 
 // vol_a -> (H,V | V,H alternating) -> vol_a.  Every iteration is two launches: a -> b -> a.
-hipError_t adc_launch_aggregate(adc_handle* h, int iterations)
+//   fuse_cost    the first pass computes the matching cost itself (k_agg_march<.., COSTIN>: vol_a holds nothing yet)
+//   fuse_agg_so  the last pass may move into the first scanline pass (so_agg_fused)
+hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, bool fuse_agg_so)
 {
     if ((h->paper & ADC_PAPER_RIGHT_ARMS) && h->arms_r) return adc_paper_aggregate(h, iterations); // opt-in paper mode (k_paper.hip)
     {   // allow > 64 KiB dynamic LDS for the ring (large cross_L1): a per-DEVICE function attribute -- set once for every
@@ -1115,50 +929,26 @@ hipError_t adc_launch_aggregate(adc_handle* h, int iterations)
     h->agg_dual_last = 0;
     h->agg_sparse_last = 0;
     h->so_agg_fused = 0; // (round-5 advisor finding: a Match that failed between this stage and the scanline stage must not leave it set)
+    const AggKnobs kn = agg_knobs();
+    const AggInputs in = agg_inputs(h, kn, iterations, fuse_cost, fuse_agg_so);
+    float* const vol[2] = {h->vol_a, h->vol_b};
     hipError_t e = hipSuccess;
-    AggSeq seq;
-    // Two plans (a stream that alternates between short-arm and long-arm images, h->agg_dual > 0; pipeline only: the arm maxima
-    // are not known on the host): plan S = small rings of the depth the last short-arm image needed (+ margin) with pass pairs,
-    // plan F = the full ring; every kernel of S runs iff both directions fit the assumed depths, every kernel of F iff not
-    // (agg_gate_skip).  Needs the fused cost: its first pass has no input volume, so plan F can start by writing vol_a
-    // instead of vol_b when that makes both plans END in the same volume (S: 5 launches, F: 8).
-    const bool dual_env = env_int("ADC_AGG_DUAL", 1) != 0; // (read per call: the tests switch it within one process)
-    const int small_L = adc_agg_small_L(h);
-    const int Lfull = adc_imax(0, adc_imin(h->p.opt.cross_L1, 255));
-    if (dual_env && h->agg_dual > 0 && h->armmax_valid >= 2 && h->fuse_cost && iterations >= 1 && small_L > 0 && small_L < Lfull) {
-        const int keep_host[2] = {h->armmax_host[0], h->armmax_host[1]}, keep_valid = h->armmax_valid;
-        h->armmax_host[0] = h->armmax_small[0] > 0 ? h->armmax_small[0] : small_L;
-        h->armmax_host[1] = h->armmax_small[1] > 0 ? h->armmax_small[1] : small_L;
-        h->armmax_valid = 2;
-        AggSeq s_dry, f_dry;
-        h->agg_gate = 3; // (also during the dry runs: a plan of a two-plan run never moves its last pass into the scanline stage)
-        e = agg_sequence(h, iterations, true, false, false, &s_dry);
-        h->armmax_valid = 3;
-        h->agg_gate = 4;
-        if (e == hipSuccess) e = agg_sequence(h, iterations, true, false, false, &f_dry);
-        h->agg_gate = 0;
-        const bool usable = e == hipSuccess && s_dry.first_fused && f_dry.first_fused;
-        if (usable) {
-            h->armmax_valid = 2;
-            h->agg_gate_thr = agg_assumed_depth(h, false) | (agg_assumed_depth(h, true) << 16);
-            h->agg_gate = 3;
-            e = agg_sequence(h, iterations, false, false, true, &seq);
-            h->armmax_valid = 3;
-            h->agg_gate = 4;
-            AggSeq f;
-            if (e == hipSuccess) e = agg_sequence(h, iterations, false, f_dry.result != s_dry.result, false, &f);
-            if (e == hipSuccess && f.result != seq.result) e = hipErrorUnknown; // (cannot happen: the flip above aligns them)
-            h->agg_gate = 0;
-            h->agg_dual_last = 1;
-            h->agg_dual_runs++;
-        }
-        h->armmax_host[0] = keep_host[0]; h->armmax_host[1] = keep_host[1]; h->armmax_valid = keep_valid;
-        if (!usable && e == hipSuccess) e = agg_sequence(h, iterations, false, false, true, &seq);
+    AggPlan plan;
+    if (agg_dual_wanted(in, kn)) { // two plans back to back (agg_plan.h): S with the marks, then F
+        AggPlan f;
+        agg_plan_dual(in, kn, &plan, &f);
+        if (f.result != plan.result) return hipErrorUnknown; // (agg_plan_dual aligns them)
+        e = agg_execute(h, plan, vol, true);
+        if (e == hipSuccess) e = agg_execute(h, f, vol, false);
+        h->agg_dual_last = 1;
+        h->agg_dual_runs++;
     } else {
-        e = agg_sequence(h, iterations, false, false, true, &seq);
+        plan = agg_plan(in, kn, AggGate{0, 0}, false);
+        e = agg_execute(h, plan, vol, true);
     }
+    if (plan.tail_moved) { h->so_agg_fused = 1; h->agg_so_fusions++; }
     // the result must be in vol_a (cost_aggr_): swap the two volume pointers if it ended up in the other one
-    if (e == hipSuccess && seq.result != h->vol_a) { h->vol_b = h->vol_a; h->vol_a = seq.result; }
+    if (e == hipSuccess && plan.result != 0) { h->vol_a = vol[1]; h->vol_b = vol[0]; }
     return e;
 }
 
@@ -1167,10 +957,12 @@ hipError_t adc_launch_aggregate(adc_handle* h, int iterations)
 // finding: that used to fail the Match).  Full ring: valid whatever the arms are.
 hipError_t adc_launch_aggregate_tail(adc_handle* h)
 {
-    const int keep = h->armmax_valid;
-    h->armmax_valid = 0;
-    const hipError_t e = launch_pass<false, true>(h, h->vol_a, h->vol_b, 2);
-    h->armmax_valid = keep;
-    if (e == hipSuccess) { float* t = h->vol_a; h->vol_a = h->vol_b; h->vol_b = t; }
+    const AggKnobs kn = agg_knobs();
+    AggPlan plan;
+    plan.launch.push_back(agg_plan_tail(agg_inputs(h, kn, 1, false, false), kn));
+    float* const vol[2] = {h->vol_a, h->vol_b};
+    const hipError_t e = agg_execute(h, plan, vol, false);
+    if (e == hipSuccess) { h->vol_a = vol[1]; h->vol_b = vol[0]; }
     return e;
 }
+

@@ -50,7 +50,7 @@ extern "C" int emul_rr_pass(const float* src_hwd, float* dst_hwd, const uint8_t*
             memcpy(&r.y, &y_, 4);
             rec[vert ? (size_t)x * H + y : p] = r;
         }
-    // launch geometry as launch_pass computes it
+    // launch geometry as agg_plan_launch (agg_plan.h) computes it
     int seg_len = (N + nseg - 1) / nseg;
     if (seg_len < 1) seg_len = 1;
     nseg = (N + seg_len - 1) / seg_len;
@@ -130,7 +130,7 @@ extern "C" int emul_rr2_pass(const float* src_hwd, float* dst_hwd, const uint8_t
         ci.rrec = rrec.data(); ci.lrec = lrec.data(); ci.lut_ad = nullptr; ci.lut_census = nullptr;
         ci.rpitch = pitch; ci.padl = padl; ci.dmin = dmin; ci.D = D;
     }
-    // launch geometry as launch_pass computes it: a wave = chunk_len outputs of the line-major index space
+    // launch geometry as agg_plan_launch (agg_plan.h) computes it: a wave = chunk_len outputs of the line-major index space
     const long long nlines = (long long)(vert ? W : H) * (Dp / 128);
     const long long total = nlines * N;
     if (chunk_len < 1) chunk_len = N;

@@ -92,7 +92,7 @@ def test_marching_ring_pass_pairs(emul, dumps, name, pf, hseg, vseg):
 
 
 RR_CASES = ["s2_96x64_d32", "q_20x40_d32", "q_9x20_d8", "q_1x40_d8", "q_40x1_d8", "q_3x3_d2", "cone_crop_d40", "q_257x131_d64"] + \
-    [n for n in OPT_ARMS if cases.make_case(n)[2].cross_L1 >= 1]  # (an arm limit of 0 never takes a register ring: launch_pass, Lv >= 1)
+    [n for n in OPT_ARMS if cases.make_case(n)[2].cross_L1 >= 1]  # (an arm limit of 0 never takes a register ring: agg_pick_form, depth >= 1)
 
 
 @pytest.mark.parametrize("name", RR_CASES)
