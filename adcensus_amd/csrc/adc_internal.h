@@ -150,6 +150,8 @@ struct adc_handle {
     int so_seg_off;  // > 0: row passes run whole (a seam failed: the redo and the next so_seg_off Matches of the handle)
     int so_nseg_last; // segments per row of the last scanline run (1 = whole rows)
     int so_seam_redos; // how often adc_wait had to redo a Match because a seam failed
+    int so_seg_probe;  // a seam of this handle failed and no segmented Match has held its seams since: when the segments come back they run
+                       // on their own first -- the last aggregation pass does not move into them (adc_so_can_fuse_agg) before they have held
     // volumes
     float *vol_a, *vol_b;
     // host-built tables: same libm as the CPU reference

@@ -766,7 +766,7 @@ int adc_wait(adc_handle* h)
             // on a stale volume -- a seam that failed THERE says nothing about this image and must not cost 64 Matches of whole
             // rows (which would also switch the fused tail pass off); the redo re-checks the seams on the real volume
             if (h->pin_flags[ADC_PIN_ARM + 3] != 0) { h->arm_redos++; h->arm_known = 0; }
-            else if (h->pin_flags[ADC_PIN_ARM + 2] != 0) { h->so_seam_redos++; h->so_seg_off = 64; }
+            else if (h->pin_flags[ADC_PIN_ARM + 2] != 0) { h->so_seam_redos++; h->so_seg_off = 64; h->so_seg_probe = 1; }
             if (h->so_seg_off < 1) h->so_seg_off = 1; // whole rows in every redo
             const bool partial = h->agg_first_fused != 0 && !(h->paper & ADC_PAPER_RIGHT_ARMS);
             if (partial) h->redo_partial++;
@@ -790,6 +790,8 @@ int adc_wait(adc_handle* h)
             h->rec_nz_known = 1;
         }
         if (h->match_pending && h->so_seg_off > 0) h->so_seg_off--; // (whole rows for a while after a failed seam)
+        // the segments are back and this Match's seams held (a redo runs whole rows: so_nseg_last is then 1): the tail may move again
+        if (h->match_pending && h->so_seg_probe && h->so_nseg_last > 1) h->so_seg_probe = 0;
         if (h->match_pending) { // (once per Match: a second adc_wait without a Match in between must not count again)
             // which plan did this image need?  Consecutive Matches that need different plans = a mixed stream: the next 64
             // Matches enqueue both plans and let the device choose (k_aggregate.hip) instead of assuming and redoing
@@ -831,8 +833,10 @@ int adc_wait(adc_handle* h)
         if (e != hipSuccess) { set_error("adc_wait: median fallback", e); abort_match(h); return 2; }
     }
     h->force_median_fallback = 0;
+    // the two holds of the median run side by side, each for its own 64 Matches (a handle that set both -- a segment seam AND a band
+    // seam differed in one Match -- would else go without column segments for 128)
     if (h->med_spec_off > 0 && h->med_spec_last == 0) h->med_spec_off--;
-    else if (h->med_seg_off > 0 && h->med_seg_last <= 1) h->med_seg_off--; // (whole rows again because a segment seam had failed)
+    if (h->med_seg_off > 0 && h->med_seg_last <= 1) h->med_seg_off--; // (whole rows again because a segment seam had failed)
     const AdcMatchReq r = h->req;
     if (r.map_host && r.map_host_direct == 2) {
         if (ADC_HIP(hipMemcpy(r.map_host, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
@@ -1952,6 +1956,7 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         if (hipMemcpy(&fails, h->armmax + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { set_error("adc_debug_run: seam flag", hipGetLastError()); return 2; }
         if (fails != 0) { // (as behind a Match: the handle's next scanline runs take whole rows, so a caller can write the volume again and rerun)
             h->so_seg_off = 64;
+            h->so_seg_probe = 1;
             g_last_error = "adc_debug_run(ADC_RUN_SCANLINE): a speculative row segment failed its seam check; rerun with ADC_SO_SEG=1";
             return 3;
         }

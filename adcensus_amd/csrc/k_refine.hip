@@ -1246,7 +1246,8 @@ hipError_t adc_launch_median(adc_handle* h)
         // (round 6: every band has its own chain, and the chains of the bands 1 .. spec are exact copies rooted in band 0 -- images of
         // 2 .. spec + 1 bands run the speculative form too, with nothing speculative about their rows: 1920 x 192 354 -> ~110 us)
         const int spec = h->med_spec_off == 0 ? spec_env : 0;
-        launch_median_banded(h, h->disp_l, h->disp_tmp, spec);
+        const hipError_t e = launch_median_banded(h, h->disp_l, h->disp_tmp, spec);
+        if (e != hipSuccess) return e; // (nothing was filtered: the buffers keep their roles)
         float* t = h->disp_l;
         h->disp_l = h->disp_tmp;
         h->disp_tmp = t;

@@ -946,6 +946,9 @@ bool adc_so_can_fuse_agg(const adc_handle* h)
 {
     static const bool env = [] { const char* e = getenv("ADC_FUSE_AGG_SO"); return e ? atoi(e) != 0 : true; }();
     if (!env || h->p.VPL != 2 || !so_use_dpp() || h->paper) return false;
+    // a handle whose seam failed tries its segments again after the hold (capi.hip: so_seg_off) WITHOUT the aggregation pass in
+    // them: that Match is the probe of the speculation that failed, and the tail moves again once a segmented Match has held its seams
+    if (h->so_seg_probe) return false;
     const int nseg = adc_so_segments(h, nullptr);
     return nseg > 1 && !so_uses_pin(h->p.H, nseg);
 }

@@ -3,11 +3,15 @@
 //   emul_agg_plan table FILE    plans every scenario line ("S name key=val ...") of the characterisation table and prints each plan as
 //                               the launches, events and end state it stands for, in the format of the table
 //   emul_agg_plan random SEED N draws N random inputs / knobs and checks the invariants of a plan; prints the violations
+//   emul_agg_plan one key=val.. plans ONE AggInputs (the keys of an S line; fits= states cost_flat_fits, env= the per-call switches) and prints
+//                               "sparse= gather= flat= tail_moved= first_fused= dual= forms=" with the form of every launch; "one -" reads one
+//                               such scenario per line of the standard input (tests/stream_model.py)
 #include "../../adcensus_amd/csrc/agg_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <iostream>
 #include <map>
 #include <random>
 #include <sstream>
@@ -215,10 +219,65 @@ static int run_random(unsigned seed, long n)
     return g_bad ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- one plan
+static const char* const form_name[AGG_FORM_COUNT] = {"march_full", "march_small", "march_small2", "march_sparse", "gather", "regring", "regring_pair",
+                                                      "regring_cost", "rr2", "rr2_cost", "cost_flat"};
+
+static int run_one(const std::string& line)
+{
+    std::stringstream ss(line);
+    std::string tok;
+    std::map<std::string, std::string> kv = {{"it", "4"}, {"fc", "1"}, {"fso", "1"}, {"env", "-"}, {"redo", "0"}, {"dual", "0"}, {"nzk", "0"}, {"nzh", "0"},
+                                             {"nzv", "0"}, {"sh", "0"}, {"sv", "0"}, {"ah", "0"}, {"av", "0"}, {"can", "0"}, {"fits", "0"}};
+    while (ss >> tok) {
+        const size_t eq = tok.find('=');
+        if (eq == std::string::npos) { fprintf(stderr, "not key=val: %s\n", tok.c_str()); return 2; }
+        kv[tok.substr(0, eq)] = tok.substr(eq + 1);
+    }
+    for (const char* need : {"W", "H", "Dp", "L1", "valid"})
+        if (!kv.count(need)) { fprintf(stderr, "missing %s=\n", need); return 2; }
+    auto I = [&](const char* k) { return atoi(kv[k].c_str()); };
+    AggKnobs kn;
+    apply_env(kv["env"], &kn);
+    AggInputs in = {};
+    in.W = I("W"); in.H = I("H"); in.Dp = I("Dp"); in.cross_L1 = I("L1"); in.iterations = I("it");
+    in.arms = (AggArms)I("valid");
+    in.armmax[0] = I("ah"); in.armmax[1] = I("av"); in.armmax_small[0] = I("sh"); in.armmax_small[1] = I("sv");
+    in.rec_nz_known = I("nzk") != 0; in.rec_nz[0] = atoll(kv["nzh"].c_str()); in.rec_nz[1] = atoll(kv["nzv"].c_str());
+    in.in_redo = I("redo") != 0; in.dual = I("dual") > 0; in.fuse_cost = I("fc") != 0; in.fuse_agg_so = I("fso") != 0;
+    in.so_can_fuse = I("can") != 0; in.cost_flat_fits = I("fits") != 0;
+    AggPlan plan, f;
+    const bool dual = agg_dual_wanted(in, kn);
+    if (dual) agg_plan_dual(in, kn, &plan, &f);
+    else plan = agg_plan(in, kn, AggGate{0, 0}, false);
+    printf("sparse=%d gather=%d flat=%d tail_moved=%d first_fused=%d dual=%d forms=", plan.sparse + f.sparse, plan.gather + f.gather, plan.flat + f.flat,
+           plan.tail_moved ? 1 : 0, plan.first_fused ? 1 : 0, dual ? 1 : 0);
+    bool sep = false;
+    for (const AggPlan* p : {&plan, &f})
+        for (const AggLaunch& l : p->launch) {
+            printf("%s%s%s:%d", sep ? "," : "", form_name[l.form], l.pair ? "+pair" : "", l.depth);
+            sep = true;
+        }
+    printf("\n");
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 3 && std::string(argv[1]) == "one" && std::string(argv[2]) == "-") {
+        std::string line;
+        int rc = 0;
+        while (rc == 0 && std::getline(std::cin, line))
+            if (!line.empty()) rc = run_one(line);
+        return rc;
+    }
+    if (argc >= 3 && std::string(argv[1]) == "one") {
+        std::string line;
+        for (int i = 2; i < argc; i++) line += std::string(argv[i]) + " ";
+        return run_one(line);
+    }
     if (argc == 3 && std::string(argv[1]) == "table") return run_table(argv[2]);
     if (argc == 4 && std::string(argv[1]) == "random") return run_random((unsigned)atol(argv[2]), atol(argv[3]));
-    fprintf(stderr, "usage: emul_agg_plan table FILE | random SEED N\n");
+    fprintf(stderr, "usage: emul_agg_plan table FILE | random SEED N | one key=val... | one -\n");
     return 2;
 }
