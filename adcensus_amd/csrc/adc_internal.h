@@ -171,7 +171,8 @@ struct adc_handle {
     int32_t* ray_tab;     // [max_search][16] packed ray offsets (dy<<16 | dx&0xffff), NULL when a step is too close to a .5 tie
     int ray_tab_rows;
     int32_t* ray_lin;     // [max_search + ADC_ITP_LPAD][16] linear ray offsets dy * itp_pitch + dx into the padded code map (same allocation as ray_tab)
-    int itp_pitch, itp_ms; // row pitch of the code map and the search range it is padded for (adc_device_fn.h)
+    int itp_pitch, itp_ms; // row pitch of the code map and the search range it is padded for (adc_device_fn.h); pitch 0: no table walk on this handle (itp_plan.h)
+    int itp_force_f64;     // debug surface: the next interpolation takes the f64 walk (adc_debug_run ADC_RUN_INTERPOLATION, arg 1)
     uint32_t* cost_rrec;  // [H][rrec_pitch] uint4 {bgrx, census lo, census hi, 0} of the RIGHT image, padded with out-of-image
                           // markers (bgrx = ~0) on both sides; cost_lrec [H][W] the same for the LEFT image (fused cost, k_aggregate.hip)
     uint32_t* cost_lrec;
@@ -359,7 +360,6 @@ size_t adc_eval_report_words(void);                             // k_eval.hip: u
 hipError_t adc_launch_eval_gt(adc_handle* h, int side, int format, int pitch, float scale); // ev_raw -> ev_g[side]
 hipError_t adc_launch_eval_occ(adc_handle* h, int mode, float occ_thres);                   // 1: ev_g[0], ev_g[1] -> ev_occ; 2: ev_g[0], mask in ev_raw -> ev_occ
 hipError_t adc_launch_eval_measure(adc_handle* h, const float* disp, const uint8_t* prov, const float* conf, const float* thresholds, float* err, uint8_t* cls);
-size_t adc_itp_cell_bytes(int W, int H, int ms);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

@@ -3,6 +3,7 @@
 // Host code only; kernels live in the k_*.hip files.
 #include "adc_internal.h"
 #include "adc_device_fn.h"
+#include "itp_plan.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -167,12 +168,13 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_OK(hipMalloc(&h->interp_list, 2 * P * 4)); // both target lists of the interpolation, P entries each
     HIP_OK(hipMalloc(&h->interp_counters, 64 * sizeof(int32_t)));
     {
-        const int da = p.dmax < 0 ? -p.dmax : p.dmax, di = p.dmin < 0 ? -p.dmin : p.dmin;
-        h->itp_ms = da > di ? da : di; // multistep_refiner.cpp:236
-        h->itp_pitch = adc_itp_code_pitch(p.W, h->itp_ms);
-        HIP_OK(hipMalloc(&h->itp_cells, adc_itp_cell_bytes(p.W, p.H, h->itp_ms)));
+        const long long ms = adc_itp_max_search(p.dmin, p.dmax); // multistep_refiner.cpp:236
+        const bool tab = adc_itp_table_walk_ok(p.W, p.H, ms);    // (itp_plan.h; without the table walk: the cell maps alone, no code maps)
+        h->itp_ms = ms > 0x7fffffff ? 0x7fffffff : (int)ms;
+        h->itp_pitch = tab ? adc_itp_code_pitch(p.W, h->itp_ms) : 0;
+        HIP_OK(hipMalloc(&h->itp_cells, adc_itp_alloc_bytes(p.W, p.H, ms)));
         // (everything outside the image never changes: the per-Match kernel only rewrites the image's own columns and rows)
-        HIP_OK(hipMemset(h->itp_cells, ADC_ITP_OUTSIDE, adc_itp_cell_bytes(p.W, p.H, h->itp_ms)));
+        HIP_OK(hipMemset(h->itp_cells, ADC_ITP_OUTSIDE, adc_itp_alloc_bytes(p.W, p.H, ms)));
     }
     h->st16_pitch = (p.W + 7) & ~7;
     HIP_OK(hipMalloc(&h->st16, ((size_t)h->st16_pitch * p.H + 64) * sizeof(uint16_t))); // (an uncached allocation -- visible across XCDs inside a kernel -- measured equal)
@@ -232,12 +234,12 @@ static hipError_t upload_tables(adc_handle* h)
     HIP_OK(hipMemcpy(h->ray_sincos, sc, sizeof(sc), hipMemcpyHostToDevice));
     {   // integer ray offsets: lround(y + m*sin) == y + lround(m*sin) for every integer 0 <= y < 2^20 as long as m*sin is
         // not within 1e-9 of a .5 tie (the addition's rounding error is < 2^-32); one unsafe entry disables the table
-        const int da = o.max_disparity < 0 ? -o.max_disparity : o.max_disparity, di = o.min_disparity < 0 ? -o.min_disparity : o.min_disparity;
-        const int ms = da > di ? da : di; // multistep_refiner.cpp:236
+        const long long ms_ll = adc_itp_max_search(o.min_disparity, o.max_disparity); // multistep_refiner.cpp:236
         h->ray_tab = nullptr;
         h->ray_lin = nullptr;
         h->ray_tab_rows = 0;
-        if (ms >= 1 && ms <= 30000 && h->p.W < (1 << 20) && h->p.H < (1 << 20)) {
+        if (adc_itp_table_walk_ok(h->p.W, h->p.H, ms_ll)) { // (itp_plan.h: no table where the table walk can never run)
+            const int ms = (int)ms_ll;
             // packed offsets [ms][16], then the linear offsets into the padded code map [ms + ADC_ITP_LPAD][16] (adc_device_fn.h)
             std::vector<int32_t> tab((size_t)ms * 16 + (size_t)(ms + ADC_ITP_LPAD) * 16, 0);
             int32_t* lin = tab.data() + (size_t)ms * 16;
@@ -1935,7 +1937,11 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e == hipSuccess) { int cont = 0; e = adc_voting_finish(h, &cont); }
         break;
-    case ADC_RUN_INTERPOLATION: e = adc_launch_interpolation(h); break;
+    case ADC_RUN_INTERPOLATION: // arg 1: the f64 walk (k_interpolate_rays) also where the handle would take the table walk (itp_plan.h)
+        h->itp_force_f64 = arg == 1 ? 1 : 0;
+        e = adc_launch_interpolation(h);
+        h->itp_force_f64 = 0;
+        break;
     case ADC_RUN_DISCONTINUITY: e = adc_launch_discontinuity(h); break;
     case ADC_RUN_MEDIAN: // arg 100: test hook -- arm the fallback path of the NEXT adc_wait (as if a band had timed out)
         if (arg == 100) { h->force_median_fallback = 1; return 0; }

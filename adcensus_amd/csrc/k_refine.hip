@@ -17,6 +17,7 @@
 #include "adc_internal.h"
 #include <mutex>
 #include "adc_device_fn.h"
+#include "itp_plan.h"
 
 #include <vector>
 #include <stdio.h>
@@ -264,10 +265,9 @@ __device__ __forceinline__ int packed_l1(uint32_t a, uint32_t b) // adc_color_di
 #define ITP_CELL ADC_ITP_CELL
 // cell / row / distance maps (one byte per cell each), then -- 16-byte aligned -- the padded code map of the walk
 // (per pass: cell / row / distance maps; behind both sets -- 16-byte aligned -- the two padded code maps of the walk)
-static size_t itp_cell_stride(int W, int H) { return 3 * (size_t)((W + ITP_CELL - 1) / ITP_CELL) * ((H + ITP_CELL - 1) / ITP_CELL); }
-static size_t itp_code_offset(int W, int H) { return (2 * itp_cell_stride(W, H) + 15) & ~(size_t)15; }
-static size_t itp_code_stride(int W, int H, int ms) { return ((size_t)adc_itp_code_pitch(W, ms) * adc_itp_code_rows(H, ms) + 64 + 15) & ~(size_t)15; }
-size_t adc_itp_cell_bytes(int W, int H, int ms) { return itp_code_offset(W, H) + 2 * itp_code_stride(W, H, ms) + 64; }
+static size_t itp_cell_stride(int W, int H) { return adc_itp_cell_stride(W, H); } // (itp_plan.h: the layout and the byte counts)
+static size_t itp_code_offset(int W, int H) { return adc_itp_code_offset(W, H); }
+static size_t itp_code_stride(int W, int H, int ms) { return adc_itp_code_stride(W, H, ms); }
 // Validity of both interpolation passes in one set of launches (round 6): the second pass sees the first pass's fills, and EVERY target
 // of the first pass is filled (a pixel no ray finds a value for gets 0.0f: multistep_refiner.cpp:246,270-272) -- so the second pass's
 // validity = valid pixels + invalid pixels of the mismatch list, known before the first pass runs.  Map 1 of every kernel (blockIdx.y)
@@ -530,8 +530,9 @@ hipError_t adc_launch_interpolation(adc_handle* h)
     const int P = p.W * p.H;
     const int dmaxa = p.dmax < 0 ? -p.dmax : p.dmax, dmina = p.dmin < 0 ? -p.dmin : p.dmin;
     const int max_search = dmaxa > dmina ? dmaxa : dmina; // multistep_refiner.cpp:236
-    if (h->ray_tab && max_search == h->ray_tab_rows && max_search == h->itp_ms && (size_t)h->itp_ms * (size_t)h->itp_pitch < ((size_t)1 << 24) && // (linear offsets exact in float: see the kernel)
-        (size_t)h->itp_pitch * (size_t)adc_itp_code_rows(p.H, h->itp_ms) < ((size_t)1 << 31)) { // (32-bit positions in the padded map)
+    // (h->ray_tab: upload_tables built the ray table -- the predicate of itp_plan.h held and no entry sat on a rounding tie;
+    // h->itp_force_f64: debug switch, adc_debug_run(ADC_RUN_INTERPOLATION, 1))
+    if (h->ray_tab && !h->itp_force_f64 && max_search == h->ray_tab_rows && max_search == h->itp_ms && adc_itp_table_walk_ok(p.W, p.H, h->itp_ms)) {
         // Round 6: ONE list pass, ONE set of map launches for both passes, fills written IN PLACE.  The reference computes the fill
         // values of a whole list from the UNCHANGED map and writes them back afterwards (fill_disps, multistep_refiner.cpp:246-303); a
         // walk here never reads the map at a pixel its own pass writes: it tests the CODE map (a snapshot) and fetches map values only at
@@ -563,7 +564,7 @@ hipError_t adc_launch_interpolation(adc_handle* h)
         }
         return hipGetLastError();
     }
-    for (int k = 0; k < 2; k++) { // (a ray step too close to a rounding tie for the integer tables: the f64 walk, list by list)
+    for (int k = 0; k < 2; k++) { // (no table walk on this handle -- itp_plan.h, or a ray step too close to a rounding tie: the f64 walk, list by list)
         const int which = k == 0 ? ADC_LABEL_MISMATCH : ADC_LABEL_OCCLUSION;
         hipError_t e;
         if ((e = hipMemsetAsync(h->interp_counters, 0, 8 * sizeof(int32_t), h->stream)) != hipSuccess) return e;

@@ -623,7 +623,9 @@ enum {
  * ring / pass pairs; ADC_RUN_SCANLINE: number of chained passes 1..4, 0 -> 4, +100 = the
  * production form whose last pass also writes DISP_LEFT (the fused left-view winner-takes-all);
  * ADC_RUN_MEDIAN: 100 = do not run, arm the fallback path of the next adc_wait (single-workgroup kernel); 101 = the same as if
- * a seam of the speculative bands had differed (the chained form of the banded kernel is redone); else ignored). */
+ * a seam of the speculative bands had differed (the chained form of the banded kernel is redone);
+ * ADC_RUN_INTERPOLATION: 1 = this run takes the double-precision ray walk also where the handle would walk the integer ray table
+ * (the walk of handles whose search range or padded width rules the table out); else ignored). */
 int adc_debug_run(adc_handle* h, int stage, int arg);
 /* Test-only event counters of the handle: which = 0 -> number of times adc_wait had to redo the median filter with the
  * single-workgroup kernel (hand-off time-out of the banded kernel); 1 -> continuations of the voting chain (launch budget

@@ -748,3 +748,45 @@ void adc_oracle_median3_inplace(float* disp, int32_t width, int32_t height)
 {
     port_median3_inplace(disp, width, height);
 }
+
+/* The refinement entered at stage `first` (oracle_abi.h): the port_* stages above on a context filled from the arguments; the
+ * lists rebuilt from the labels in raster order, which is the order port_outlier emits them in. */
+int adc_oracle_refine_from(int32_t width, int32_t height, const adc_option* opt, int32_t first, int32_t last,
+                           const uint8_t* bgr_left, const float* cost, const uint8_t* arms, float* disp_left,
+                           const float* disp_right, uint8_t* label)
+{
+    if (!opt || width <= 0 || height <= 0 || opt->max_disparity - opt->min_disparity <= 0) return 1;
+    if (first < ADC_ORACLE_STAGE_LR || last > ADC_ORACLE_STAGE_MEDIAN || first > last) return 3;
+#define RUNS(s) (first <= (s) && (s) <= last)
+    if (!disp_left || (RUNS(ADC_ORACLE_STAGE_LR) && !disp_right) || (RUNS(ADC_ORACLE_STAGE_VOTING) && !arms) ||
+        (RUNS(ADC_ORACLE_STAGE_INTERP) && !bgr_left) || (RUNS(ADC_ORACLE_STAGE_DDA) && !cost) || (first > ADC_ORACLE_STAGE_LR && !label))
+        return 2;
+    const size_t P = (size_t)width * height;
+    port_ctx c;
+    memset(&c, 0, sizeof(c));
+    c.w = width; c.h = height; c.opt = *opt;
+    c.dmin = opt->min_disparity; c.dmax = opt->max_disparity; c.D = c.dmax - c.dmin;
+    c.left = bgr_left;
+    c.cost_aggr = (float*)cost;    /* read only (port_dda) */
+    c.arms = (uint8_t*)arms;       /* read only (port_region_voting) */
+    c.disp_l = disp_left;
+    c.disp_r = (float*)disp_right; /* read only (port_outlier) */
+    c.label = calloc(P, 1); c.mis = calloc(P, 4); c.occ = calloc(P, 4);
+    if (first == ADC_ORACLE_STAGE_LR) {
+        port_outlier(&c);
+        if (label) memcpy(label, c.label, P);
+    } else {
+        for (size_t p = 0; p < P; p++) {
+            if (disp_left[p] != INVALID_FLOAT) continue;
+            if (label[p] == 1) c.mis[c.n_mis++] = (int32_t)p;
+            else if (label[p] == 2) c.occ[c.n_occ++] = (int32_t)p;
+        }
+    }
+    if (RUNS(ADC_ORACLE_STAGE_VOTING)) port_region_voting(&c);
+    if (RUNS(ADC_ORACLE_STAGE_INTERP)) port_interpolation(&c);
+    if (RUNS(ADC_ORACLE_STAGE_DDA)) port_dda(&c);
+    if (RUNS(ADC_ORACLE_STAGE_MEDIAN)) port_median3_inplace(disp_left, width, height);
+#undef RUNS
+    free(c.label); free(c.mis); free(c.occ);
+    return 0;
+}

@@ -61,6 +61,17 @@ int adc_oracle_match(int32_t width, int32_t height, const adc_option* opt,
 /* in-place-semantics 3x3 median (adcensus_util.cpp:55-81 called with in==out). */
 void adc_oracle_median3_inplace(float* disp, int32_t width, int32_t height);
 
+/* Entry in the middle of the refinement (multistep_refiner.cpp:60-87) with inputs of the caller's choosing: runs the stages
+ * first..last (ADC_ORACLE_STAGE_*), in place on disp_left.  The option's do_* switches are not consulted: the range names the
+ * stages.  cost [H][W][D], arms [H][W][4] and disp_right [H][W] may be NULL only when no stage of the range reads them (LR: disp_right,
+ * VOTING: arms, DDA: cost).  first == LR: label (nullable) is WRITTEN as adc_oracle_run dumps it.  first > LR: the mismatch and occlusion
+ * lists are rebuilt from label (required) in raster order, as OutlierDetection emits them -- 1 mismatch, 2 occlusion, only pixels
+ * whose disparity is still +inf.  Returns 0 ok, 1 bad size / range, 2 a missing input, 3 a bad stage range. */
+enum { ADC_ORACLE_STAGE_LR = 0, ADC_ORACLE_STAGE_VOTING = 1, ADC_ORACLE_STAGE_INTERP = 2, ADC_ORACLE_STAGE_DDA = 3, ADC_ORACLE_STAGE_MEDIAN = 4 };
+int adc_oracle_refine_from(int32_t width, int32_t height, const adc_option* opt, int32_t first, int32_t last,
+                           const uint8_t* bgr_left, const float* cost, const uint8_t* arms, float* disp_left,
+                           const float* disp_right, uint8_t* label);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,8 @@ _DUMP_FIELDS = [
     ("disp_final", np.float32, ()),
 ]
 DUMP_NAMES = [f[0] for f in _DUMP_FIELDS]
+# stages of Oracle.refine_from (oracle_abi.h: ADC_ORACLE_STAGE_*)
+LR, VOTING, INTERP, DDA, MEDIAN = range(5)
 
 
 class _Dump(C.Structure):
@@ -81,6 +83,7 @@ class Oracle:
         self.lib.adc_oracle_median3_inplace.restype = None
         self.lib.adc_oracle_median3_inplace.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         self.kind = self.lib.adc_oracle_kind().decode()
+        self.has_refine_from = hasattr(self.lib, "adc_oracle_refine_from")  # (False: a checker built before the entry point existed)
         try:
             self.lib.adc_oracle_build_info.restype = C.c_char_p
             self.build_info = self.lib.adc_oracle_build_info().decode()
@@ -138,6 +141,41 @@ class Oracle:
             raise RuntimeError("oracle match failed (rc=%d)" % rc)
         return disp, secs.value
 
+    def refine_from(self, first, last, disp_left, opt=None, left=None, cost=None, arms=None, disp_right=None, label=None):
+        """The refinement entered at stage `first`, run up to `last` (LR .. MEDIAN, oracle_abi.h: adc_oracle_refine_from) on a copy
+        of disp_left [H][W] f32.  left [H][W][3] u8, cost [H][W][D] f32, arms [H][W][4] u8, disp_right [H][W] f32 are needed by
+        the stages that read them (INTERP, DDA, VOTING, LR); label [H][W] u8 is the input of every entry behind LR.
+        Returns (disparity map, label): the label map is the LR check's output for first == LR, else the one passed in."""
+        if not self.has_refine_from:
+            raise RuntimeError("%s was built before adc_oracle_refine_from existed (run `make -C oracle`)" % self.path)
+        opt = opt or Option()
+        disp = np.array(disp_left, dtype=np.float32, order="C", copy=True)
+        assert disp.ndim == 2
+        h, w = disp.shape
+        d = opt.max_disparity - opt.min_disparity
+
+        def arg(a, dt, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert a.shape == shape, (a.shape, shape)
+            return a
+
+        left, cost, arms = arg(left, np.uint8, (h, w, 3)), arg(cost, np.float32, (h, w, d)), arg(arms, np.uint8, (h, w, 4))
+        disp_right = arg(disp_right, np.float32, (h, w))
+        lab = np.zeros((h, w), np.uint8) if label is None else np.array(label, dtype=np.uint8, order="C", copy=True)
+        assert lab.shape == (h, w)
+        if first > LR and label is None:
+            raise ValueError("refine_from: an entry behind the LR check needs the label map")
+        fn = self.lib.adc_oracle_refine_from
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int32, C.c_int32, C.POINTER(Option), C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        rc = fn(w, h, C.byref(opt), int(first), int(last), ptr(left), ptr(cost), ptr(arms), disp.ctypes.data, ptr(disp_right), lab.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("adc_oracle_refine_from failed (rc=%d: 1 size/range, 2 missing input, 3 stage range)" % rc)
+        return disp, lab
+
     def median3_inplace(self, disp):
         disp = np.array(disp, dtype=np.float32, order="C", copy=True)
         self.lib.adc_oracle_median3_inplace(disp.ctypes.data, disp.shape[1], disp.shape[0])
@@ -152,6 +190,23 @@ def have_port():
     return os.path.exists(PORT_SO)
 
 
+def exports(path, symbol=b"adc_oracle_refine_from"):
+    """the file holds the symbol's name (read as bytes: a library is not loaded to find out that it is too old to be loaded)"""
+    with open(path, "rb") as f:
+        return symbol in f.read()
+
+
+def _rebuild_if_older_than_the_abi(path, target):
+    """A library built before oracle_abi.h gained adc_oracle_refine_from -- kept from an earlier build of the tree -- is built again
+    where that is possible: the port always (-B: make compares time stamps, and a kept library may carry a later one than the
+    sources), the reference where its sources are (`make ref` says so and keeps the file otherwise).  Never raises: what is
+    there afterwards is loaded, and Oracle.has_refine_from says what it can do."""
+    if exports(path):
+        return
+    import subprocess
+    subprocess.run(["make", "-B", "-C", _HERE, target], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+
+
 def load(kind="auto"):
     """kind: 'reference', 'port' or 'auto' (reference if its .so exists, else port)."""
     if kind == "auto":
@@ -159,4 +214,15 @@ def load(kind="auto"):
     path = REF_SO if kind == "reference" else PORT_SO
     if not os.path.exists(path):
         raise FileNotFoundError("%s oracle not built: %s (run `make -C oracle`)" % (kind, path))
+    _rebuild_if_older_than_the_abi(path, "ref" if kind == "reference" else "port")
     return Oracle(path)
+
+
+def stage_entry_oracle(ref_oracle, port_oracle):
+    """The checker of the tests that enter the refinement in the middle (Oracle.refine_from): the reference build where there is one
+    that has the entry point, else the port (tests/test_refine_oracle.py pins the port to the reference through refine_from wherever
+    such a reference build exists).  A reference library from before the entry point, on a machine without the reference's
+    sources to build it again, still serves every whole-pipeline test."""
+    if ref_oracle is not None and ref_oracle.has_refine_from:
+        return ref_oracle
+    return port_oracle

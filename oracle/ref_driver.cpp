@@ -161,4 +161,46 @@ void adc_oracle_median3_inplace(float* disp, int32_t width, int32_t height)
     adcensus_util::MedianFilter(disp, disp, width, height, 3);
 }
 
+// The reference's own MultiStepRefiner entered at stage `first` (oracle_abi.h): SetData / SetParam as ADCensusStereo::MultiStepRefine
+// calls them (ADCensusStereo.cpp:177-186), the two pixel lists filled the way OutlierDetection leaves them (multistep_refiner.cpp:109-147).
+int adc_oracle_refine_from(int32_t width, int32_t height, const adc_option* opt, int32_t first, int32_t last,
+                           const uint8_t* bgr_left, const float* cost, const uint8_t* arms, float* disp_left,
+                           const float* disp_right, uint8_t* label)
+{
+    if (!opt || width <= 0 || height <= 0 || opt->max_disparity - opt->min_disparity <= 0) return 1;
+    if (first < ADC_ORACLE_STAGE_LR || last > ADC_ORACLE_STAGE_MEDIAN || first > last) return 3;
+    const auto runs = [&](int s) { return first <= s && s <= last; };
+    if (!disp_left || (runs(ADC_ORACLE_STAGE_LR) && !disp_right) || (runs(ADC_ORACLE_STAGE_VOTING) && !arms) ||
+        (runs(ADC_ORACLE_STAGE_INTERP) && !bgr_left) || (runs(ADC_ORACLE_STAGE_DDA) && !cost) || (first > ADC_ORACLE_STAGE_LR && !label))
+        return 2;
+    const ADCensusOption ro = to_ref_option(opt);
+    MultiStepRefiner rf;
+    if (!rf.Initialize(width, height)) return 1;
+    rf.SetData(bgr_left, const_cast<float*>(cost), reinterpret_cast<const CrossArm*>(arms), disp_left, const_cast<float*>(disp_right));
+    rf.SetParam(ro.min_disparity, ro.max_disparity, ro.irv_ts, ro.irv_th, ro.lrcheck_thres, runs(ADC_ORACLE_STAGE_LR),
+                runs(ADC_ORACLE_STAGE_VOTING), runs(ADC_ORACLE_STAGE_INTERP), runs(ADC_ORACLE_STAGE_DDA));
+    const size_t P = size_t(width) * size_t(height);
+    if (first == ADC_ORACLE_STAGE_LR) {
+        rf.OutlierDetection();
+        if (label) {
+            memset(label, 0, P);
+            for (auto& p : rf.mismatches_) label[size_t(p.second) * width + p.first] = 1;
+            for (auto& p : rf.occlusions_) label[size_t(p.second) * width + p.first] = 2;
+        }
+    } else {
+        for (int32_t y = 0; y < height; y++)
+            for (int32_t x = 0; x < width; x++) {
+                const size_t p = size_t(y) * width + x;
+                if (disp_left[p] != Invalid_Float) continue;
+                if (label[p] == 1) rf.mismatches_.emplace_back(x, y);
+                else if (label[p] == 2) rf.occlusions_.emplace_back(x, y);
+            }
+    }
+    if (rf.do_region_voting_) rf.IterativeRegionVoting();
+    if (rf.do_interpolating_) rf.ProperInterpolation();
+    if (rf.do_discontinuity_adjustment_) rf.DepthDiscontinuityAdjustment();
+    if (runs(ADC_ORACLE_STAGE_MEDIAN)) adcensus_util::MedianFilter(disp_left, disp_left, width, height, 3);
+    return 0;
+}
+
 } // extern "C"

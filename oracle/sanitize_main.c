@@ -4,7 +4,8 @@
  * sanitizer report = clean on this input (min_disparity = 0; the reference's documented out-of-bounds read for
  * min_disparity > 0, ADCensusStereo.cpp:296-300, is not provoked).
  * Arguments: option overrides as field=value (lambda_ad, lambda_census, cross_L1, cross_L2, cross_t1, cross_t2, so_p1, so_p2, so_tso,
- * irv_ts, irv_th, lrcheck_thres), e.g. `sanitize_port so_p1=-1 so_p2=-3`; an unknown field or a malformed value is exit code 4. */
+ * irv_ts, irv_th, lrcheck_thres), e.g. `sanitize_port so_p1=-1 so_p2=-3`; an unknown field or a malformed value is exit code 4.
+ * Or `refine FILE`: one constructed refinement input through adc_oracle_refine_from (refine_mode below). */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,8 +28,53 @@ static int override(adc_option* o, const char* arg)
     return 0;
 }
 
+/* `refine FILE`: one constructed refinement input (tests/refine_patterns.py) through adc_oracle_refine_from.  FILE = int32 {w, h, first,
+ * last, has_left, has_cost, has_arms, has_right, has_label}, the adc_option, then the arrays that are there, in this order: left u8
+ * [H][W][3], cost f32 [H][W][D], arms u8 [H][W][4], disp f32 [H][W], right f32 [H][W], label u8 [H][W].  Prints the sum of the
+ * result's 32-bit patterns; exit code 5 = unreadable file, 2 = refine_from refused the input. */
+static void* read_array(FILE* f, int present, size_t bytes, int* ok)
+{
+    if (!present) return NULL;
+    void* p = malloc(bytes ? bytes : 1);
+    if (!p || fread(p, 1, bytes, f) != bytes) *ok = 0;
+    return p;
+}
+
+static int refine_mode(const char* path)
+{
+    FILE* f = fopen(path, "rb");
+    int32_t hd[9];
+    adc_option opt;
+    if (!f || fread(hd, sizeof(hd), 1, f) != 1 || fread(&opt, sizeof(opt), 1, f) != 1 || hd[0] <= 0 || hd[1] <= 0 ||
+        opt.max_disparity <= opt.min_disparity) {
+        printf("unreadable pattern file: %s\n", path);
+        if (f) fclose(f);
+        return 5;
+    }
+    const size_t P = (size_t)hd[0] * (size_t)hd[1], D = (size_t)(opt.max_disparity - opt.min_disparity);
+    int ok = 1;
+    uint8_t* left = read_array(f, hd[4], P * 3, &ok);
+    float* cost = read_array(f, hd[5], P * D * 4, &ok);
+    uint8_t* arms = read_array(f, hd[6], P * 4, &ok);
+    float* disp = read_array(f, 1, P * 4, &ok);
+    float* right = read_array(f, hd[7], P * 4, &ok);
+    uint8_t* label = read_array(f, hd[8], P, &ok);
+    fclose(f);
+    int rc = 5;
+    if (ok) {
+        rc = adc_oracle_refine_from(hd[0], hd[1], &opt, hd[2], hd[3], left, cost, arms, disp, right, label) != 0 ? 2 : 0;
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < P; i++) { uint32_t u; memcpy(&u, disp + i, 4); sum += u; }
+        if (rc == 0) printf("%s oracle under the sanitizers: refine_from ok, sum %llu\n", adc_oracle_kind(), sum);
+        else printf("adc_oracle_refine_from refused the input\n");
+    } else printf("unreadable pattern file: %s\n", path);
+    free(left); free(cost); free(arms); free(disp); free(right); free(label);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 3 && !strcmp(argv[1], "refine")) return refine_mode(argv[2]);
     const int W = 96, H = 64, D = 24;
     uint8_t* l = (uint8_t*)malloc((size_t)W * H * 3);
     uint8_t* r = (uint8_t*)malloc((size_t)W * H * 3);

@@ -106,6 +106,31 @@ def test_full_size_aggregation_paths_agree(hip):
         st.Release()
 
 
+def test_interpolation_table_walk_at_full_depth(hip, ref_oracle, port_oracle):
+    """The interpolation stage alone (no Match) on the largest handle the table walk takes at the search range 2047: 4094 x 2048,
+    range [2045, 2047), pitch 8196 -- 2047 * 8196 = 2^24 - 4.  One target in row 0 and one valid pixel at step 2046 of the rays 7, 8
+    and 9: the hit's linear offset plus the left padding, about 16.77e6, is the largest value whose row the kernel ever recovers
+    with its float reciprocal; a quotient off by one puts the hit a whole image row away."""
+    from oracle.pyoracle import INTERP
+    from tests import refine_patterns as rp
+    oracle = pyoracle.stage_entry_oracle(ref_oracle, port_oracle)  # (a reference build that has refine_from, else the port)
+    pats = [rp.edge_2p24_full(s) for s in (7, 8, 9)]
+    w, h, dmin, dmax, _ = pats[0].geometry
+    st = hip.ADCensusStereo(device=0)
+    assert st.Initialize(w, h, cases.to_product_option(pats[0].opt)), hip.last_error()
+    try:
+        st.debug_set_images(pats[0].img, pats[0].img)
+        for p in pats:
+            want, _ = oracle.refine_from(INTERP, INTERP, p.disp, p.opt, left=p.img, label=p.label)
+            assert want[p.info["target"]] == p.disp[p.info["planted"]]  # (the reference's walk does find it: step 2046 < 2047)
+            st.debug_write(hip.BUF_DISP_LEFT, p.disp)
+            st.debug_write(hip.BUF_OUTLIER_LABEL, p.label)
+            st.debug_run(hip.RUN_INTERPOLATION)
+            assert _same(st.debug_read(hip.BUF_DISP_LEFT), want), p
+    finally:
+        st.Release()
+
+
 def test_full_size_stage_isolation_structured(hip, oracle):
     """Every stage in ISOLATION at 1920x1080, D=128 on a structured pair (seed 779: long arms -> the pair-register-ring
     aggregation with balanced chunks, ~350 voting kernels, 17 median bands): the reference's dump of stage k-1 in, HIP stage k,
