@@ -19,6 +19,7 @@
 #include <stddef.h>
 
 #include "../../include/adcensus_c_api.h"
+#include "learn_plan.h"
 
 #define ADC_WAVE 64
 
@@ -147,11 +148,25 @@ struct adc_handle {
     uint8_t *cdiff_lh, *cdiff_lv, *cdiff_rh, *cdiff_rv;
     uint8_t* so_cls; // path-ordered left-image colour-step words (d1) of the 4 scanline pass types (k_scanline.hip)
     float* so_seam;  // seam slots of the row passes cut into verified segments: [2 passes][H][ADC_SO_MAX_SEG - 1][Dp] (k_scanline.hip)
-    int so_seg_off;  // > 0: row passes run whole (a seam failed: the redo and the next so_seg_off Matches of the handle)
-    int so_nseg_last; // segments per row of the last scanline run (1 = whole rows)
-    int so_seam_redos; // how often adc_wait had to redo a Match because a seam failed
-    int so_seg_probe;  // a seam of this handle failed and no segmented Match has held its seams since: when the segments come back they run
-                       // on their own first -- the last aggregation pass does not move into them (adc_so_can_fuse_agg) before they have held
+    // What the handle has learned from its earlier Matches, and the counters of the rules that move it (learn_plan.h: the only
+    // file that assigns a member of `learned`, but for adc_create and the two budget hooks of adc_debug_run)
+    AdcLearned learned;
+    AdcLearnStats lstats;
+    // Per-Match flags: what the Match in flight (or the stage run last) did, read by the stages behind it and by adc_wait, which
+    // builds its AdcMatchReport from them and pin_flags; abort_match puts them back to idle
+    int match_pending;    // a Match was enqueued and adc_wait has not yet looked at its arm maxima / speculation flags
+    int in_redo;          // adc_wait is redoing a Match (no sparse launches there)
+    int armmax_valid;     // AggArms of the aggregation being enqueued: 0 unknown (debug surface: two launches per pass, the kernels
+                          // decide), 1 exact (read back), 2 assumed from the previous Match (the small-ring kernels verify on the device
+                          // and raise armmax[3]; adc_wait then redoes the Match), 3 unknown in the pipeline: full ring (always valid)
+    int irv_pending;      // a voting chain was enqueued and its final state has not been looked at yet
+    int irv_chain;        // kernels of the chain enqueued so far (continuation starts here)
+    int so_nseg_last;     // segments per row of the last scanline run (1 = whole rows)
+    int med_spec_last;    // the last banded median launch used speculative bands
+    int med_seg_last;     // ... and this many column segments per band link
+    int so_agg_fused;     // adc_launch_aggregate left its last pass to the scanline stage: vol_a holds the volume BEFORE that pass
+    int fuse_wta;         // set by the pipeline: the last scanline pass also writes the left-view disparity map
+    int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     // volumes
     float *vol_a, *vol_b;
     // host-built tables: same libm as the CPU reference
@@ -177,48 +192,24 @@ struct adc_handle {
                           // markers (bgrx = ~0) on both sides; cost_lrec [H][W] the same for the LEFT image (fused cost, k_aggregate.hip)
     uint32_t* cost_lrec;
     int rrec_pitch, rrec_padl;
-    int armmax_host[2];   // maximum horizontal / vertical arm of the current pair, read back by the pipeline
-    int armmax_valid;     // 0 unknown (debug surface: two launches per pass, the kernels decide), 1 exact (read back),
-                          // 2 assumed from the previous Match of this handle (the small-ring kernels verify on the device and
-                          // raise armmax[3]; adc_wait then redoes the Match), 3 unknown in the pipeline: full ring (always valid)
-    int arm_known;        // armmax_host holds the maxima of the previous Match
-    int arm_redos;        // how often the assumption was wrong
     // Streams that alternate between short-arm and long-arm images: instead of assuming ONE ring depth and redoing the
     // Match when it is wrong, the aggregation is enqueued as TWO plans (assumed small rings + pass pairs | full ring) and the
     // kernels decide on the device which plan works (agg_gate_skip, k_aggregate_rr.h).
-    int agg_dual;         // > 0: enqueue both plans (set to 64 whenever consecutive Matches needed different plans, counts down)
     int agg_dual_last;    // the last aggregation run enqueued both plans (per-launch timings are then not separable)
-    int agg_last_plan;    // plan the previous Match's image needed: 0 none yet, 1 small rings, 2 full ring
-    int agg_switches;     // how often consecutive Matches needed different plans
-    int agg_dual_runs;    // Matches whose aggregation was enqueued as two plans
-    int armmax_small[2];  // arm maxima of the last image that fitted the small rings (0 = none seen)
-    int redo_partial;     // redos that restarted at the aggregation instead of the whole Match
-    int match_pending;    // a Match was enqueued and adc_wait has not yet looked at its arm maxima / speculation flags
     int agg_first_fused;  // the last aggregation run did so (pass timings: the regular passes are 1..)
-    int fuse_wta;         // set by the pipeline: the last scanline pass also writes the left-view disparity map
-    int so_agg_fused;     // adc_launch_aggregate did so: vol_a holds the volume BEFORE that pass (consumed by the scanline stage)
-    int agg_so_fusions;   // Matches that ran that way
+    int agg_dual_runs;    // Matches whose aggregation was enqueued as two plans
+    int agg_so_fusions;   // Matches whose last aggregation pass ran inside the first scanline pass
     // Sparse small-ring launches (k_aggregate.hip): chosen per direction from the density of pass-changing records the handle
     // last saw (k_make_records counts them behind the arm maxima; they reach the host like the maxima do)
     int32_t* pin_nz;      // the sharded density words of the last Match inside pin_flags (pin_flags + ADC_PIN_ARM + ADC_NZ_BASE; ADC_NZ_*: adc_device_fn.h)
-    long long rec_nz_host[2]; // pixels with a pass-changing horizontal / vertical record, previous Match (or read back: debug surface)
-    int rec_nz_known;     // rec_nz_host is valid
-    int in_redo;          // adc_wait is redoing a Match (no sparse launches there)
     int agg_sparse_last;  // the last aggregation run used sparse launches (pass timings are then not priced as read V + write V)
     int agg_sparse_launches; // sparse launches of this handle
     int agg_gather_launches; // ... of which in the gather form (k_agg_gather: only the changed pixels are computed)
     int agg_flat_launches;   // first (fused-cost) launches that ran as the element-wise k_cost_agg_flat instead of the small-ring march
-    int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     float* med_hand;      // banded median: per-band hand-off rows [bands][med_hpitch], indexed by wavefront level
     int med_hpitch;
     float* med_sink;      // banded median: 16-byte store sink per lane of every wave (bands + speculative copies)
-    int med_spec_off;     // > 0: the banded median runs in its chained form (a speculative seam failed; counts down per Match)
-    int med_spec_last;    // the last banded launch used speculative bands
-    int med_seg_last;     // ... and this many column segments per band link
-    int med_seg_off;      // > 0: whole rows (a seam failed while column segments were on; counts down per Match)
-    int med_spec_fails;   // how often adc_wait had to redo the median because a speculative seam differed
     int force_median_fallback; // test hook (ADC_DEBUG_FORCE_MEDIAN_FALLBACK via adc_debug_run): adc_wait takes the fallback path
-    int median_fallbacks;      // how often adc_wait had to redo the median
     int32_t* pin_flags;   // pinned host word: error flag of the banded median's hand-off (read back after every Match)
     int bgrx_valid;       // bgrx_l holds the packed left image of the current pair (written by the arms stage)
     uint32_t* bgrx_l;     // left image packed B | G<<8 | R<<16 per pixel (interpolation gathers)
@@ -227,12 +218,6 @@ struct adc_handle {
     float* disp_vote;    // the map the voting chain works on (copy of the LR-checked map, copied back when the chain ends)
     int irv_xcd_mode;    // 1: the chain's work list uses the band -> XCD sweep layout (the device's workgroup -> XCD mapping was probed)
     int irv_grid;        // workgroups of the voting chain (adc_irv_grid, fixed per handle: the work-list layout depends on it)
-    int irv_budget;      // kernels the next Match enqueues for the voting chain (adapted from the last Matches)
-    int irv_used_hist[8]; // kernels the last 8 Matches needed
-    unsigned irv_used_pos;
-    int irv_chain;       // kernels of the chain enqueued so far (continuation starts here)
-    int irv_pending;     // a chain was enqueued and its final state has not been looked at yet
-    int irv_overflows;   // how often adc_wait had to continue the chain (budget too small)
     float *tail_disp_l, *tail_disp_tmp; // buffer roles at the start of the stages behind the voting (for a redo)
     void* irv_cold;                  // device block of the chain's rarely used kernel arguments (64 bytes)
     unsigned char irv_cold_host[64]; // the block as it was last sent (k_voting.hip: IrvCold; staged through pin_flags[32..63])
@@ -300,7 +285,6 @@ struct adc_handle {
     bool timings_pending;
     // region voting statistics of the last run
     int64_t vote_rounds, vote_evals;
-    // which volume holds the latest result (always vol_a at stage boundaries)
 };
 
 // ------------------------------------------------------------------ kernel launchers (one per stage)

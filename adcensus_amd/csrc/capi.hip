@@ -184,7 +184,7 @@ static hipError_t alloc_all(adc_handle* h)
     // voting chain budget of the FIRST Match of a handle (later ones adapt: kernels used + 40 % + 2): a natural 1080p image needs
     // ~50-75 kernels (round 5: all passes iterate at once; ~350 before); kernels past the end of the chain are no-ops of ~4 us, an
     // exhausted budget costs a synchronous continuation
-    h->irv_budget = 256;
+    h->learned.irv_budget = LEARN_IRV_FIRST;
     // change-tile map of the voting rounds: one BYTE per 8x8 tile, rows padded to a multiple of 4 (+16: a 16-byte load
     // may start at the last dword of a row)
     h->chg_pitch = (((p.W + 7) / 8 + 3) & ~3) + 16;
@@ -415,7 +415,7 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
         MARK(1, h->heavy);
         MARK(2, h->heavy);
         HIP_OK(hipMemsetAsync(h->armmax + 2, 0, 2 * sizeof(int), h->heavy)); // failed seams, "assumed ring too shallow" flag
-        h->armmax_valid = 3; // the full ring: valid for every image
+        h->armmax_valid = LEARN_ARMS_FULL; // valid for every image
     } else {
     HIP_OK(adc_launch_gray_census(h));           // ComputeCost, ADCensusStereo.cpp:84
     // ADC_FUSE_COST (default on): the cost volume is never written -- the first aggregation pass computes each cost
@@ -435,11 +435,10 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
         if (host_arms && h->pin_flags) {
             HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_ARM, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
             HIP_OK(hipStreamSynchronize(h->heavy));
-            h->armmax_host[0] = h->pin_flags[ADC_PIN_ARM + 0];
-            h->armmax_host[1] = h->pin_flags[ADC_PIN_ARM + 1];
+            learn_take_arms(&h->learned, h->pin_flags + ADC_PIN_ARM);
             h->armmax_valid = 1;
         } else {
-            h->armmax_valid = h->arm_known ? 2 : 3;
+            h->armmax_valid = learn_arm_assumption(h->learned);
         }
     }
     HIP_OK(adc_launch_records(h));
@@ -629,7 +628,7 @@ static void abort_match(adc_handle* h)
     h->fuse_wta = 0;
     h->armmax_valid = 0;
     h->in_redo = 0;
-    h->rec_nz_known = 0;
+    learn_forget_densities(&h->learned);
     h->wta_left_done = 0;
     h->timings_pending = false;
     h->force_median_fallback = 0;
@@ -748,62 +747,50 @@ int adc_host_unregister(void* ptr)
     return hipHostUnregister(ptr) == hipSuccess ? 0 : 2;
 }
 
+// pixels with a pass-changing horizontal / vertical record: the shard sums of the density words in pin_nz
+static void rec_nz_sums(const adc_handle* h, long long nz[2])
+{
+    for (int c = 0; c < 2; c++) {
+        nz[c] = 0;
+        for (int s = 0; s < ADC_NZ_SHARDS; s++) nz[c] += h->pin_nz[(c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE];
+    }
+}
+// what the device said about the Match just drained (pin_flags: one copy at the end of the heavy stream) and which forms it ran
+static AdcMatchReport match_report(const adc_handle* h)
+{
+    const int32_t* a = h->pin_flags + ADC_PIN_ARM;
+    AdcMatchReport r = {};
+    r.armmax[0] = a[0]; r.armmax[1] = a[1]; r.seam_fails = a[2]; r.ring_shallow = a[3];
+    r.rec_nz_valid = h->pin_nz != nullptr;
+    if (r.rec_nz_valid) rec_nz_sums(h, r.rec_nz);
+    r.so_nseg_last = h->so_nseg_last; r.med_spec_last = h->med_spec_last; r.med_seg_last = h->med_seg_last;
+    r.agg_first_fused = h->agg_first_fused != 0;
+    r.paper_right_arms = (h->paper & ADC_PAPER_RIGHT_ARMS) != 0;
+    return r;
+}
+
 int adc_wait(adc_handle* h)
 {
     if (!h) return 1;
     hipSetDevice(h->device);
     if (ADC_HIP(hipStreamSynchronize(h->stream)) != hipSuccess) { set_error("adc_wait", hipGetLastError()); abort_match(h); return 2; }
-    // (1) the aggregation assumed the arm maxima of the previous Match; a longer arm raised the flag and the pass was
-    //     skipped: redo with the full ring (valid for every image).
-    // (1b) a row of the scanline passes was cut into segments and a segment's warm-up did not reach the state of the full
-    //     pass (pin_flags[ADC_PIN_ARM + 2] = seams that failed): redo with whole rows, and keep them for the next Matches.
-    //     Both redos restart at the aggregation when its first pass computes the matching cost itself (the default): the
-    //     pixel records, arms and aggregation records of this pair are still in HBM; otherwise the whole Match runs again
-    //     (the inputs are still there).  EVERY redo runs whole scanline rows: its volume differs from the first run's when the
-    //     aggregation was skipped, so a seam could fail there that did not fail before (round-4 advisor finding) -- and the
-    //     seam count is looked at again behind the redo.
+    // (1) an assumed aggregation ring was too shallow, or a scanline row segment failed its seam: learn_redo says whether the Match
+    //     runs again and from where (the aggregation on, or as a whole: the inputs are still there); the flags are read again behind it
     if (h->pin_flags) {
-        for (int attempt = 0; attempt < 2 && (h->pin_flags[ADC_PIN_ARM + 3] != 0 || h->pin_flags[ADC_PIN_ARM + 2] != 0); attempt++) {
-            // (round-5 advisor finding) a too-shallow ring skipped aggregation passes: the row passes and their seam check then ran
-            // on a stale volume -- a seam that failed THERE says nothing about this image and must not cost 64 Matches of whole
-            // rows (which would also switch the fused tail pass off); the redo re-checks the seams on the real volume
-            if (h->pin_flags[ADC_PIN_ARM + 3] != 0) { h->arm_redos++; h->arm_known = 0; }
-            else if (h->pin_flags[ADC_PIN_ARM + 2] != 0) { h->so_seam_redos++; h->so_seg_off = 64; h->so_seg_probe = 1; }
-            if (h->so_seg_off < 1) h->so_seg_off = 1; // whole rows in every redo
-            const bool partial = h->agg_first_fused != 0 && !(h->paper & ADC_PAPER_RIGHT_ARMS);
-            if (partial) h->redo_partial++;
+        AdcMatchReport rep = match_report(h);
+        for (int attempt = 0; attempt < LEARN_MAX_REDOS; attempt++) {
+            const AdcRedo redo = learn_redo(&h->learned, &h->lstats, rep);
+            if (redo == ADC_REDO_NONE) break;
             h->in_redo = 1;
-            hipError_t e = run_pipeline(h, partial);
+            hipError_t e = run_pipeline(h, redo == ADC_REDO_FROM_AGGREGATION);
             h->in_redo = 0;
             if (e == hipSuccess) e = enqueue_output(h);
             if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
             if (e != hipSuccess) { set_error("adc_wait: redo (full aggregation ring / whole scanline rows)", e); abort_match(h); return 2; }
+            rep = match_report(h);
         }
-        if (h->pin_flags[ADC_PIN_ARM + 3] != 0 || h->pin_flags[ADC_PIN_ARM + 2] != 0) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
-        h->armmax_host[0] = h->pin_flags[ADC_PIN_ARM + 0];
-        h->armmax_host[1] = h->pin_flags[ADC_PIN_ARM + 1];
-        h->arm_known = 1;
-        if (h->pin_nz && h->match_pending) {
-            for (int c = 0; c < 2; c++) {
-                long long n = 0;
-                for (int s = 0; s < ADC_NZ_SHARDS; s++) n += h->pin_nz[(c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE];
-                h->rec_nz_host[c] = n;
-            }
-            h->rec_nz_known = 1;
-        }
-        if (h->match_pending && h->so_seg_off > 0) h->so_seg_off--; // (whole rows for a while after a failed seam)
-        // the segments are back and this Match's seams held (a redo runs whole rows: so_nseg_last is then 1): the tail may move again
-        if (h->match_pending && h->so_seg_probe && h->so_nseg_last > 1) h->so_seg_probe = 0;
-        if (h->match_pending) { // (once per Match: a second adc_wait without a Match in between must not count again)
-            // which plan did this image need?  Consecutive Matches that need different plans = a mixed stream: the next 64
-            // Matches enqueue both plans and let the device choose (k_aggregate.hip) instead of assuming and redoing
-            const int small_L = adc_agg_small_L(h);
-            const int plan = (h->pin_flags[ADC_PIN_ARM + 0] <= small_L && h->pin_flags[ADC_PIN_ARM + 1] <= small_L) ? 1 : 2;
-            if (plan == 1) { h->armmax_small[0] = h->pin_flags[ADC_PIN_ARM + 0] > 0 ? h->pin_flags[ADC_PIN_ARM + 0] : 1; h->armmax_small[1] = h->pin_flags[ADC_PIN_ARM + 1] > 0 ? h->pin_flags[ADC_PIN_ARM + 1] : 1; }
-            if (h->agg_last_plan != 0 && plan != h->agg_last_plan) { h->agg_switches++; h->agg_dual = 64; }
-            else if (h->agg_dual > 0) h->agg_dual--;
-            h->agg_last_plan = plan;
-        }
+        if (learn_redo_wanted(rep)) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
+        learn_commit(&h->learned, &h->lstats, rep, h->match_pending != 0, h->match_pending ? adc_agg_small_L(h) : 0);
         h->match_pending = 0;
     }
     // (2) the voting chain ran out of its launch budget before it converged: continue it, redo the stages behind it
@@ -831,14 +818,10 @@ int adc_wait(adc_handle* h)
         h->pin_flags[ADC_PIN_MEDIAN] = 0;
         if (e == hipSuccess) e = enqueue_output(h);
         if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
-        h->median_fallbacks++;
         if (e != hipSuccess) { set_error("adc_wait: median fallback", e); abort_match(h); return 2; }
     }
     h->force_median_fallback = 0;
-    // the two holds of the median run side by side, each for its own 64 Matches (a handle that set both -- a segment seam AND a band
-    // seam differed in one Match -- would else go without column segments for 128)
-    if (h->med_spec_off > 0 && h->med_spec_last == 0) h->med_spec_off--;
-    if (h->med_seg_off > 0 && h->med_seg_last <= 1) h->med_seg_off--; // (whole rows again because a segment seam had failed)
+    learn_median_commit(&h->learned, h->med_spec_last, h->med_seg_last);
     const AdcMatchReq r = h->req;
     if (r.map_host && r.map_host_direct == 2) {
         if (ADC_HIP(hipMemcpy(r.map_host, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
@@ -1898,17 +1881,17 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         // arg >= 200: additionally read the maximum arms back (needs ADC_RUN_ARMS before) so that the launcher picks
         // the ring depth on the host and fuses same-direction pass pairs -- the production pipeline's path
         if (e == hipSuccess && arg >= 200) {
-            e = hipMemcpy(h->armmax_host, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost);
+            int am[2] = {0, 0};
+            e = hipMemcpy(am, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) learn_take_arms(&h->learned, am);
             h->armmax_valid = e == hipSuccess ? 1 : 0;
             // ... and the record densities of THIS image (the pipeline assumes the previous Match's)
             if (e == hipSuccess && h->pin_nz) e = hipMemcpyAsync(h->pin_nz, h->armmax + ADC_NZ_BASE, 2 * ADC_NZ_SHARDS * ADC_NZ_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, h->heavy);
             if (e == hipSuccess && h->pin_nz) e = hipStreamSynchronize(h->heavy);
             if (e == hipSuccess && h->pin_nz) {
-                for (int c = 0; c < 2; c++) {
-                    h->rec_nz_host[c] = 0;
-                    for (int s = 0; s < ADC_NZ_SHARDS; s++) h->rec_nz_host[c] += h->pin_nz[(c * ADC_NZ_SHARDS + s) * ADC_NZ_STRIDE];
-                }
-                h->rec_nz_known = 1;
+                long long nz[2];
+                rec_nz_sums(h, nz);
+                learn_take_densities(&h->learned, nz);
             }
             arg -= 200;
         }
@@ -1930,8 +1913,8 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
     case ADC_RUN_WTA: e = adc_launch_wta(h); break;
     case ADC_RUN_LRCHECK: e = adc_launch_lrcheck(h); break;
     case ADC_RUN_REGION_VOTING: // arg > 0: launch budget (kernels) of this run, e.g. 4 to force the continuation path
-        if (arg < 0) { h->irv_budget = -arg; return 0; } // test hook: only set the budget of the NEXT Match's chain (continuation inside adc_wait)
-        if (arg > 0) h->irv_budget = arg;
+        if (arg < 0) { h->learned.irv_budget = -arg; return 0; } // test hook: only set the budget of the NEXT Match's chain (continuation inside adc_wait)
+        if (arg > 0) h->learned.irv_budget = arg;
         e = adc_launch_sup_counts(h); // (the region boxes of the votes come out of the arms stage; here the arms may have been written by the test)
         if (e == hipSuccess) e = adc_run_region_voting(h);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1961,8 +1944,7 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         int fails = 0;
         if (hipMemcpy(&fails, h->armmax + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { set_error("adc_debug_run: seam flag", hipGetLastError()); return 2; }
         if (fails != 0) { // (as behind a Match: the handle's next scanline runs take whole rows, so a caller can write the volume again and rerun)
-            h->so_seg_off = 64;
-            h->so_seg_probe = 1;
+            learn_so_seam_failed(&h->learned);
             g_last_error = "adc_debug_run(ADC_RUN_SCANLINE): a speculative row segment failed its seam check; rerun with ADC_SO_SEG=1";
             return 3;
         }
@@ -1970,7 +1952,6 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
     if (stage == ADC_RUN_MEDIAN && h->pin_flags && h->pin_flags[ADC_PIN_MEDIAN] != 0) { // what adc_wait does behind a Match
         e = adc_median_fallback(h);
         h->pin_flags[ADC_PIN_MEDIAN] = 0;
-        h->median_fallbacks++;
         if (e != hipSuccess) { set_error("adc_debug_run: median fallback", e); return 2; }
     }
     return 0;
@@ -1980,13 +1961,13 @@ int64_t adc_debug_counter(adc_handle* h, int which)
 {
     if (!h) return -1;
     switch (which) {
-    case 0: return h->median_fallbacks;
-    case 1: return h->irv_overflows;
-    case 2: return h->arm_redos;
-    case 9: return h->agg_switches;   // consecutive Matches that needed different aggregation plans
+    case 0: return h->lstats.median_fallbacks;
+    case 1: return h->lstats.irv_overflows;
+    case 2: return h->lstats.arm_redos;
+    case 9: return h->lstats.agg_switches;   // consecutive Matches that needed different aggregation plans
     case 10: return h->agg_dual_runs; // Matches whose aggregation was enqueued as two plans (the device chose)
-    case 11: return h->redo_partial;  // redos that restarted at the aggregation (not the whole Match)
-    case 12: return h->agg_dual;      // > 0: the next Match enqueues both plans
+    case 11: return h->lstats.redo_partial;  // redos that restarted at the aggregation (not the whole Match)
+    case 12: return h->learned.agg_dual;      // > 0: the next Match enqueues both plans
     case 13: return h->agg_so_fusions; // Matches whose last aggregation pass ran inside the first scanline pass
     case 16: return h->agg_sparse_launches; // small-ring aggregation launches that ran in their sparse form (+ k_agg_apply)
     case 17: return (int64_t)(adc_agg_sparse_density() * 1e6 + 0.5); // density threshold of the sparse form, parts per million of the pixels
@@ -1999,14 +1980,14 @@ int64_t adc_debug_counter(adc_handle* h, int which)
         if (!h->profiling || h->agg_dual_last || h->agg_launches < 1 || hipEventElapsedTime(&ms, h->ev_agg[0], h->ev_agg[1]) != hipSuccess) return -1;
         return (int64_t)((double)ms * 1e6 + 0.5);
     }
-    case 18: return h->rec_nz_known ? h->rec_nz_host[0] : -1; // pixels with a pass-changing horizontal record the handle last saw
-    case 19: return h->rec_nz_known ? h->rec_nz_host[1] : -1; // ... vertical record
+    case 18: return h->learned.rec_nz_known ? h->learned.rec_nz[0] : -1; // pixels with a pass-changing horizontal record the handle last saw
+    case 19: return h->learned.rec_nz_known ? h->learned.rec_nz[1] : -1; // ... vertical record
     case 14: return h->irv_xcd_mode;   // the voting chain sweeps band -> XCD (the mapping was probed on this device)
     case 15: return h->med_seg_last;   // column segments per band link of the last banded median launch (1: whole rows)
-    case 3: return h->irv_budget;
-    case 7: return h->med_spec_fails;
+    case 3: return h->learned.irv_budget;
+    case 7: return h->lstats.med_spec_fails;
     case 8: return h->med_spec_last;
-    case 4: return h->so_seam_redos;
+    case 4: return h->lstats.so_seam_redos;
     case 5: return h->so_nseg_last; // segments per row of the last scanline run
     case 6: { // seams that failed in the last scanline run (debug surface: nothing redoes it there)
         int v = -1;

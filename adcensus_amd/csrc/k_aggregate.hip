@@ -776,16 +776,18 @@ static AggKnobs agg_knobs()
     return k;
 }
 
+static_assert(AGG_ARMS_ASSUMED == LEARN_ARMS_ASSUMED && AGG_ARMS_FULL == LEARN_ARMS_FULL, "learn_plan.h names AggArms values");
 // what the handle knows, by value (the aggregation only READS the handle's arm and density state)
 static AggInputs agg_inputs(const adc_handle* h, const AggKnobs& kn, int iterations, bool fuse_cost, bool fuse_agg_so)
 {
     AggInputs in = {};
     in.W = h->p.W; in.H = h->p.H; in.Dp = h->p.Dp; in.cross_L1 = h->p.opt.cross_L1; in.iterations = iterations;
     in.arms = (AggArms)h->armmax_valid;
-    for (int c = 0; c < 2; c++) { in.armmax[c] = h->armmax_host[c]; in.armmax_small[c] = h->armmax_small[c]; in.rec_nz[c] = h->rec_nz_host[c]; }
-    in.rec_nz_known = h->rec_nz_known != 0;
+    const AdcLearned& L = h->learned;
+    for (int c = 0; c < 2; c++) { in.armmax[c] = L.armmax_host[c]; in.armmax_small[c] = L.armmax_small[c]; in.rec_nz[c] = L.rec_nz[c]; }
+    in.rec_nz_known = L.rec_nz_known != 0;
     in.in_redo = h->in_redo != 0;
-    in.dual = h->agg_dual > 0;
+    in.dual = L.agg_dual > 0;
     in.fuse_cost = fuse_cost;
     in.fuse_agg_so = fuse_agg_so;
     in.so_can_fuse = adc_so_can_fuse_agg(h);

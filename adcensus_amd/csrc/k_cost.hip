@@ -232,6 +232,7 @@ hipError_t adc_launch_cost_records(adc_handle* h)
 #define CF_HALO 16
 #define CF_TX (4 * CF_PW)
 #define CF_LDS_MAX (48 * 1024)
+static_assert(CF_TX == LEARN_CF_TX && CF_LDS_MAX == LEARN_CF_LDS_MAX, "learn_plan.h states the LDS footprint of k_cost_agg_flat");
 typedef float cf_f2 __attribute__((ext_vector_type(2)));
 
 template <bool PAD> // PAD = false: D == Dp, no padding lanes
@@ -320,11 +321,11 @@ __global__ __launch_bounds__(256) void k_cost_agg_flat(float* __restrict__ dst, 
 
 static size_t cost_agg_flat_lds(const adc_handle* h, int cap)
 {
-    return (size_t)(768 + 64 + 3 * (CF_TX + h->p.Dp - 1 + 2 * cap)) * 4;
+    return learn_cost_flat_lds(h->p.Dp, cap);
 }
 bool adc_cost_agg_flat_fits(const adc_handle* h, int cap)
 {
-    return h->p.Dp % 128 == 0 && cap >= 0 && cost_agg_flat_lds(h, cap) <= CF_LDS_MAX;
+    return learn_cost_flat_fits(h->p.Dp, cap);
 }
 hipError_t adc_launch_cost_agg_flat(adc_handle* h, float* dst, int cap, int small_variant, int small_L)
 {

@@ -1208,7 +1208,7 @@ static hipError_t launch_median_banded(adc_handle* h, const float* in, float* ou
     if ((in != h->disp_l && in != h->disp_tmp) || (out != h->disp_l && out != h->disp_tmp) || in == out) return hipErrorInvalidValue;
     const int nbands = (p.H + MEDB_ROWS - 1) / MEDB_ROWS;
     const int ncopies = spec ? medb_chain_off(nbands, spec) : 0; // a chain of min(b, spec) copies per target band b = 1 .. nbands - 1
-    const int nseg = h->med_seg_off > 0 ? 1 : median_segments(p.W, spec), nlinks = nbands + ncopies;
+    const int nseg = learn_median_whole_rows(h->learned) ? 1 : median_segments(p.W, spec), nlinks = nbands + ncopies;
     if ((size_t)nlinks * nseg + 1 > adc_median_hand_rows(p.H)) return hipErrorInvalidValue;
     // error word + store sinks live in vote_counters[160..]: prog[260] error word, prog[262..267] sinks of idle lanes;
     // the hand-off rows are reset to the "not written yet" sentinel (all ones) before every launch
@@ -1246,7 +1246,7 @@ hipError_t adc_launch_median(adc_handle* h)
         static const int spec_env = [] { const char* e = getenv("ADC_MEDIAN_SPEC"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 4 ? 4 : v); }();
         // (round 6: every band has its own chain, and the chains of the bands 1 .. spec are exact copies rooted in band 0 -- images of
         // 2 .. spec + 1 bands run the speculative form too, with nothing speculative about their rows: 1920 x 192 354 -> ~110 us)
-        const int spec = h->med_spec_off == 0 ? spec_env : 0;
+        const int spec = learn_median_speculates(h->learned) ? spec_env : 0;
         const hipError_t e = launch_median_banded(h, h->disp_l, h->disp_tmp, spec);
         if (e != hipSuccess) return e; // (nothing was filtered: the buffers keep their roles)
         float* t = h->disp_l;
@@ -1265,30 +1265,18 @@ hipError_t adc_launch_median(adc_handle* h)
 // The banded filter reported a hand-off time-out (a band gave up waiting for its upstream band; cannot happen while all
 // bands are co-resident, but the spin is bounded on principle): redo the filter with the single-workgroup wavefront
 // kernel, which has no inter-workgroup dependency.  The unfiltered input is still intact in disp_tmp (the filter writes
-// to the other buffer).  Called by adc_wait after the stream has drained.
+// to the other buffer).  Called by adc_wait (and adc_debug_run) after the stream has drained, with pin_flags allocated.
 hipError_t adc_median_fallback(adc_handle* h)
 {
-    hipError_t e;
-    if (h->med_spec_last && h->pin_flags && (h->pin_flags[0] == 2 || h->force_median_fallback == 2) && h->force_median_fallback != 1) {
-        // a speculative seam differed.  With column segments on, the speculative bands alone (whole rows: round 4's form, which has run
-        // on every pair since) come first -- segments stay off for the next 64 Matches of the handle; if that fails too, or no segments
-        // were on, the chained form of the banded kernel, which needs no assumption (and may itself report a time-out, then the
-        // single-workgroup kernel below runs), and whole chained bands for the next 64 Matches.
-        h->med_spec_fails++;
-        if (h->med_seg_last > 1 && h->force_median_fallback != 2) {
-            h->med_seg_off = 64;
-            e = launch_median_banded(h, h->disp_tmp, h->disp_l, h->med_spec_last); // (med_seg_off: whole rows)
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) return e;
-            if (h->pin_flags[0] == 0) return hipSuccess;
-        }
-        h->med_spec_off = 64;
-        e = launch_median_banded(h, h->disp_tmp, h->disp_l, 0);
+    // the ladder (learn_median_next): the speculative bands on whole rows where column segments were on, then the chained form of the
+    // banded kernel, which needs no assumption (and may itself report a time-out), then the single-workgroup kernel
+    AdcMedianForm form = ADC_MED_AS_ENQUEUED;
+    for (;;) {
+        form = learn_median_next(&h->learned, &h->lstats, form, h->pin_flags[ADC_PIN_MEDIAN], h->med_spec_last, h->med_seg_last, h->force_median_fallback);
+        if (form == ADC_MED_DONE) return hipSuccess;
+        hipError_t e = form == ADC_MED_SINGLE_WG ? launch_median_wavefront(h, h->disp_tmp, h->disp_l)
+                                                 : launch_median_banded(h, h->disp_tmp, h->disp_l, form == ADC_MED_BANDS_WHOLE_ROWS ? h->med_spec_last : 0);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) return e;
-        if (h->pin_flags[0] == 0) return hipSuccess;
     }
-    e = launch_median_wavefront(h, h->disp_tmp, h->disp_l);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(h->stream);
 }

@@ -914,20 +914,18 @@ static bool so_use_dpp()
 // Number of verified segments a row pass of this handle is cut into (1 = whole rows).  Automatic choice: enough chains for
 // two to three waves on every SIMD of the chip (1080 rows -> 3 x 1080, 375 rows -> 5 x 375); ADC_SO_SEG = 0 / 1 switches the segments
 // off, N >= 2 forces N; ADC_SO_WARM = warm-up steps (multiple of 16; the tests use short ones to provoke seam failures).
+static const AdcSoEnv& so_env()
+{
+    static const AdcSoEnv v = [] {
+        const char *s = getenv("ADC_SO_SEG"), *w = getenv("ADC_SO_WARM"), *f = getenv("ADC_SO_FAST");
+        return AdcSoEnv{s ? atoi(s) : -1, w ? atoi(w) : ADC_SO_WARM, f ? (atoi(f) != 0 ? 1 : 0) : -1};
+    }();
+    return v;
+}
 int adc_so_segments(const adc_handle* h, int* warm_out)
 {
-    static const int seg_env = [] { const char* e = getenv("ADC_SO_SEG"); return e ? atoi(e) : -1; }();
-    static const int warm_env = [] { const char* e = getenv("ADC_SO_WARM"); return e ? atoi(e) : ADC_SO_WARM; }();
-    const AdcParams& p = h->p;
-    if (warm_out) *warm_out = warm_env;
-    if (p.VPL > 2 || h->so_seg_off || !h->so_seam || seg_env == 0 || seg_env == 1) return 1;
-    int n = seg_env >= 2 ? seg_env : (2048 + p.H / 2) / p.H;
-    // (round 6, same box, interleaved -- profiles/r6_ab_scanline_segments.txt: at 1080 rows three segments per row instead of two, 3240
-    // chains for 1024 SIMDs: scanline stage of the noise pair 1.990 / 1.981 -> 1.937 ms, structured 1.888 / 1.879 -> 1.873; four: 1.965)
-    if (seg_env < 2 && n == 2 && 3 * p.H <= 4096) n = 3;
-    if (n > ADC_SO_MAX_SEG) n = ADC_SO_MAX_SEG;
-    while (n >= 2 && !adc_so_seg_ok(p.W, n, warm_env)) n--;
-    return n >= 2 ? n : 1;
+    if (warm_out) *warm_out = so_env().warm;
+    return learn_so_segments(h->p.W, h->p.H, h->p.VPL, h->so_seam != nullptr, h->learned, so_env());
 }
 size_t adc_so_seam_bytes(int W, int H, int Dp) { (void)W; return (size_t)2 * H * (ADC_SO_MAX_SEG - 1) * Dp * sizeof(float); }
 
@@ -935,22 +933,13 @@ size_t adc_so_seam_bytes(int W, int H, int Dp) { (void)W; return (size_t)2 * H *
 // of whole interior chunks (KITTI-size row passes: 375 paths, scanline stage 0.873 -> 0.675 ms, same-box A/B); where
 // every SIMD has a wave or two the pass is bound by its memory streams and runs k_scanline.  ADC_SO_FAST=0 / 1 forces
 // k_scanline / k_scanline_pin everywhere.
-static bool so_uses_pin(int npaths, int nseg)
-{
-    static const int so_fast_env = [] { const char* e = getenv("ADC_SO_FAST"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    return so_fast_env >= 0 ? so_fast_env != 0 : npaths * nseg < 1024;
-}
+static bool so_uses_pin(int npaths, int nseg) { return learn_so_uses_pin(npaths, nseg, so_env().fast); }
 // Can the L->R row pass of the next scanline run take over the last aggregation pass (k_scanline_seg_agg)?  Needs the segment
 // form of the compiler-allocated family with two disparities per lane.  (adc_launch_aggregate asks before it drops that pass.)
 bool adc_so_can_fuse_agg(const adc_handle* h)
 {
     static const bool env = [] { const char* e = getenv("ADC_FUSE_AGG_SO"); return e ? atoi(e) != 0 : true; }();
-    if (!env || h->p.VPL != 2 || !so_use_dpp() || h->paper) return false;
-    // a handle whose seam failed tries its segments again after the hold (capi.hip: so_seg_off) WITHOUT the aggregation pass in
-    // them: that Match is the probe of the speculation that failed, and the tail moves again once a segmented Match has held its seams
-    if (h->so_seg_probe) return false;
-    const int nseg = adc_so_segments(h, nullptr);
-    return nseg > 1 && !so_uses_pin(h->p.H, nseg);
+    return learn_so_can_fuse_agg(h->p.W, h->p.H, h->p.VPL, h->so_seam != nullptr, h->learned, so_env(), env, so_use_dpp(), h->paper);
 }
 
 template <int VPL>

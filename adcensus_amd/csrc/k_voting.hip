@@ -720,9 +720,9 @@ hipError_t adc_run_region_voting(adc_handle* h)
     const AdcParams& p = h->p;
     hipError_t e;
     if ((e = hipMemsetAsync(h->vote_counters, 0, IRV_CTRL_INTS * sizeof(int32_t), h->stream)) != hipSuccess) return e;
-    if (h->irv_budget < 4) h->irv_budget = 4;
-    if ((e = irv_launch(h, 0, h->irv_budget)) != hipSuccess) return e;
-    h->irv_chain = h->irv_budget;
+    const int budget = learn_voting_budget(&h->learned);
+    if ((e = irv_launch(h, 0, budget)) != hipSuccess) return e;
+    h->irv_chain = budget;
     // the state the last kernel published (slot chain & 1), read by adc_wait / adc_voting_finish
     if (h->pin_flags)
         e = hipMemcpyAsync(h->pin_flags + 16, h->vote_counters + 16 * (h->irv_chain & 1), 8 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
@@ -757,24 +757,9 @@ hipError_t adc_voting_finish(adc_handle* h, int* continued)
     }
     h->vote_rounds = st[5];
     h->vote_evals = st[6];
-    if (*continued) h->irv_overflows++; // (the FINAL kernel of the continued chain has written the result into disp_l)
-    // budget of the next Match: the kernels this one actually needed (st[7] = index of the first kernel that found
-    // nothing left to do) + 40 % (at least 2) + 2
-    const int used = st[7] + 1;
+    // budget of the next Match (learn_voting_commit): from the kernels this one actually needed, st[7] = index of the first kernel
+    // that found nothing left to do (the FINAL kernel of a continued chain has written the result into disp_l)
     static const int fixed = [] { const char* ev = getenv("ADC_IRV_BUDGET"); return ev ? atoi(ev) : 0; }();
-    // (the longest chain of the last 8 Matches of the handle: the pairs of a stream differ -- at the KITTI size 3 of 23 distinct
-    // structured pairs overran a budget taken from their predecessor alone; a surplus kernel is a 2.5 us no-op, an overrun a
-    // synchronous continuation)
-    h->irv_used_hist[h->irv_used_pos++ & 7] = used;
-    int longest = 0;
-    for (int i = 0; i < 8; i++) longest = adc_imax(longest, h->irv_used_hist[i]);
-    // (round 5: the chain of a natural 1080p image is 50-75 kernels instead of ~350 and varies more from pair to pair, relatively:
-    // a quarter of margin instead of an eighth -- 10 surplus kernels cost 0.05 ms, a continuation a synchronisation and the tail stages)
-    // a short chain (an image with next to no listed pixel: 6 kernels) gets 4 surplus kernels, a long one 40 %
-    // (measured on 24 distinct structured pairs: with a quarter of margin 1-2 of ~28 Matches still overran -- the chains of a stream
-    // vary 48-75 kernels --, and a continuation costs ~1.5 ms where 6 more surplus kernels cost 0.03 ms: 40 %)
-    // (an EMPTY work list -- BEGIN, then DONE: no round whose count could vary -- needs no margin beyond the floor of 4 kernels:
-    // two surplus kernels less per Match of a noise-like stream, 10 us)
-    h->irv_budget = fixed > 0 ? fixed : (longest <= 2 ? 4 : adc_imin(1 << 16, longest + adc_imax(2 * longest / 5, 2) + 2));
+    learn_voting_commit(&h->learned, &h->lstats, st[7] + 1, *continued != 0, fixed);
     return hipSuccess;
 }

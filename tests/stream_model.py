@@ -1,10 +1,13 @@
-"""A model of the host rules that decide what a Match launches from what its handle has learned: a plain restatement of adc_wait's
-state update and of the `armmax_valid` choice of run_heavy (adcensus_amd/csrc/capi.hip), of adc_so_segments / adc_so_can_fuse_agg
-(k_scanline.hip) and of adc_cost_agg_flat_fits (k_cost.hip).  The plan itself comes from the product's own header through
-tests/emul/emul_agg_plan.cpp ("one").  The model is fed the oracle's facts about every image of a stream (tests/streams.py:
+"""A model of the host rules that decide what a Match launches from what its handle has learned: a plain, independent restatement of
+adcensus_amd/csrc/learn_plan.h -- the commit behind a Match, the arm assumption of the next one, the scanline segments, whether the
+tail may move, whether the flat first launch fits.  It is the check, not the thing checked: tests/test_stream_model.py compares it with
+the header on the CPU (tests/emul/emul_learn.cpp), tests/test_gpu_streams.py with the device.  Only the named constants (hold lengths,
+warm-up, segment limit, the two knob defaults) come from the product, through `emul_learn consts`.  The plan itself comes from the
+product's own header through tests/emul/emul_agg_plan.cpp ("one").  The model is fed the oracle's facts about every image of a stream (tests/streams.py:
 arm maxima and record densities) and predicts, per Match, the deltas of debug counters 2, 10, 11, 16, 20, 22 and whether the last
 aggregation pass may move into the scanline stage (counter 13).  It reads nothing back from the product except the density thresholds
 (counters 17, 21, 23)."""
+import functools
 import os
 import re
 import subprocess
@@ -13,10 +16,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "adcensus_amd", "csrc")
 
 AGG_ARMS_ASSUMED, AGG_ARMS_FULL = 2, 3
-SMALL_L_KNOB = 8       # ADC_AGG_SMALL_L (k_aggregate.hip: agg_knobs)
-ASSUME_MARGIN = 1      # ADC_AGG_ASSUME_MARGIN
-SO_WARM, SO_MAX_SEG = 64, 8  # adc_device_fn.h: ADC_SO_WARM, ADC_SO_MAX_SEG
 CF_TX, CF_LDS_MAX = 128, 48 * 1024  # k_cost.hip
+# SMALL_L_KNOB, ASSUME_MARGIN (defaults of ADC_AGG_SMALL_L / ADC_AGG_ASSUME_MARGIN), SO_WARM, SO_MAX_SEG (adc_device_fn.h): from the
+# product, the first time one is asked for
+_FROM_CONSTS = {"SMALL_L_KNOB": "small_L", "ASSUME_MARGIN": "assume_margin", "SO_WARM": "so_warm", "SO_MAX_SEG": "so_max_seg"}
+
+
+def __getattr__(name):
+    if name in _FROM_CONSTS:
+        return consts()[_FROM_CONSTS[name]]
+    raise AttributeError(name)
 
 
 def _src(name):
@@ -24,14 +33,17 @@ def _src(name):
         return f.read()
 
 
+@functools.lru_cache(maxsize=None)
+def consts():
+    """`emul_learn consts`: the named constants of learn_plan.h, adc_device_fn.h and the knob defaults of agg_plan.h"""
+    out = subprocess.check_output([build_emul("emul_learn"), "consts"], text=True)
+    return {k: int(v) for k, v in (t.split("=", 1) for t in out.split())}
+
+
 def holds():
-    """The lengths of the four "hold for N Matches" counters, read from the code that sets them."""
-    capi, refine = _src("capi.hip"), _src("k_refine.hip")
-    wait = capi[capi.index("int adc_wait(adc_handle* h)"):]
-    out = {"agg_dual": re.search(r"h->agg_dual = (\d+);", wait), "so_seg_off": re.search(r"h->so_seg_off = (\d+);", wait),
-           "med_seg_off": re.search(r"h->med_seg_off = (\d+);", refine), "med_spec_off": re.search(r"h->med_spec_off = (\d+);", refine)}
-    assert all(out.values()), out
-    return {k: int(m.group(1)) for k, m in out.items()}
+    """The lengths of the four "hold for N Matches" counters, from the code that sets them (by the field each one sets)."""
+    c = consts()
+    return {"agg_dual": c["plan_switch"], "so_seg_off": c["so_seam"], "med_seg_off": c["med_column"], "med_spec_off": c["med_band"]}
 
 
 def default_thresholds_ppm():
@@ -41,10 +53,12 @@ def default_thresholds_ppm():
     return {"sparse": ppm, "gather": ppm, "flat": ppm}  # (AGG_GATHER_MAX_DENSITY and COST_FLAT_MAX_DENSITY are defined as the first)
 
 
-def build_emul():
+def build_emul(name="emul_agg_plan"):
     out_dir = os.path.join(ROOT, "tests", "emul", "_build")
-    exe = os.path.join(out_dir, "emul_agg_plan")
-    deps = [os.path.join(ROOT, "tests", "emul", "emul_agg_plan.cpp"), os.path.join(CSRC, "agg_plan.h")]
+    exe = os.path.join(out_dir, name)
+    deps = [os.path.join(ROOT, "tests", "emul", name + ".cpp"), os.path.join(CSRC, "agg_plan.h")]
+    if name == "emul_learn":
+        deps += [os.path.join(CSRC, "learn_plan.h"), os.path.join(CSRC, "adc_device_fn.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(out_dir, exist_ok=True)
         tmp = "%s.%d" % (exe, os.getpid())  # (built aside and renamed: another process may be running the old one)
@@ -80,31 +94,32 @@ def so_seg_start(plen, nseg, warm, s):
 
 
 def so_seg_ok(plen, nseg, warm):
-    if nseg < 2 or nseg > SO_MAX_SEG or warm < 16 or (warm & 15):
+    if nseg < 2 or nseg > consts()["so_max_seg"] or warm < 16 or (warm & 15):
         return False
     return all(so_seg_start(plen, nseg, warm, s) - so_seg_start(plen, nseg, warm, s - 1) >= 32 + (warm + 1 if s == 1 else 0)
                for s in range(1, nseg + 1))
 
 
-def so_segments(w, h, vpl, so_seg_off, seg_env=-1, warm=SO_WARM):
+def so_segments(w, h, vpl, so_seg_off, seg_env=-1, warm=None):
     """adc_so_segments; seg_env / warm: ADC_SO_SEG / ADC_SO_WARM (unset: -1 and the production warm-up)"""
+    warm = consts()["so_warm"] if warm is None else warm
     if vpl > 2 or so_seg_off or seg_env in (0, 1):
         return 1
     n = seg_env if seg_env >= 2 else (2048 + h // 2) // h
     if seg_env < 2 and n == 2 and 3 * h <= 4096:
         n = 3
-    n = min(n, SO_MAX_SEG)
+    n = min(n, consts()["so_max_seg"])
     while n >= 2 and not so_seg_ok(w, n, warm):
         n -= 1
     return n if n >= 2 else 1
 
 
-def so_can_fuse(w, h, vpl, so_seg_off, so_fast, so_seg_probe=0):
+def so_can_fuse(w, h, vpl, so_seg_off, so_fast, so_seg_probe=0, seg_env=-1):
     """adc_so_can_fuse_agg; so_fast: None (ADC_SO_FAST unset: the pinned family below 1024 chains) or 0 / 1; so_seg_probe: a seam of
     the handle failed and no segmented Match has held since (no seam fails in the model's streams: the handles there never set it)"""
     if vpl != 2 or so_seg_probe:
         return False
-    nseg = so_segments(w, h, vpl, so_seg_off)
+    nseg = so_segments(w, h, vpl, so_seg_off, seg_env)
     pin = (so_fast != 0) if so_fast is not None else h * nseg < 1024
     return nseg > 1 and not pin
 
@@ -125,7 +140,7 @@ class HandleModel:
         self.thr = thresholds_ppm or default_thresholds_ppm()
         self.hold = hold if hold is not None else holds()["agg_dual"]
         self.full_L = max(0, min(cross_L1, 255))
-        self.small_L = min(SMALL_L_KNOB, self.full_L)
+        self.small_L = min(consts()["small_L"], self.full_L)
         self.small_ok = 0 < self.small_L < self.full_L
         self.arm_known = 0
         self.armmax_host = [0, 0]
@@ -137,11 +152,11 @@ class HandleModel:
         self.so_seg_off = 0
 
     def _depth(self, c):  # agg_assumed_depth with ASSUMED arms
-        return min(self.small_L, max(1, self.armmax_host[c]) + ASSUME_MARGIN)
+        return min(self.small_L, max(1, self.armmax_host[c]) + consts()["assume_margin"])
 
     def scenario(self):
         valid = AGG_ARMS_ASSUMED if self.arm_known else AGG_ARMS_FULL  # run_heavy: armmax_valid
-        cap = min(self.small_L, max(1, self.armmax_host[0]) + (ASSUME_MARGIN if valid == AGG_ARMS_ASSUMED else 0))
+        cap = min(self.small_L, max(1, self.armmax_host[0]) + (consts()["assume_margin"] if valid == AGG_ARMS_ASSUMED else 0))
         env = "ADC_AGG_SPARSE_DENSITY=%de-6,ADC_AGG_GATHER_DENSITY=%de-6,ADC_COST_FLAT_DENSITY=%de-6" % (
             self.thr["sparse"], self.thr["gather"], self.thr["flat"])
         return {"W": self.w, "H": self.h, "Dp": self.dp, "L1": self.L1, "it": 4, "valid": valid, "ah": self.armmax_host[0],

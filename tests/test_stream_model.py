@@ -77,6 +77,24 @@ def test_restated_handle_facts():
     assert not M.so_can_fuse(160, 48, 2, 0, None) and M.so_can_fuse(160, 48, 2, 0, 0) and not M.so_can_fuse(160, 48, 2, 1, 0)
     assert not M.so_can_fuse(160, 48, 1, 0, 0) and not M.so_can_fuse(321, 37, 4, 0, 0) and not M.so_can_fuse(160, 48, 2, 0, 0, so_seg_probe=1)
     assert M.cost_flat_fits(128, 8) and M.cost_flat_fits(256, 8) and not M.cost_flat_fits(64, 2)
+    # ... and against the header (learn_plan.h through `emul_learn grid`): every geometry of the streams and the full sizes, widths
+    # 64 .. 2048 in coarse steps plus the widths around which each segment count starts to fit
+    limits = [next(w for w in range(64, 2049) if M.so_seg_ok(w, n, M.SO_WARM)) for n in range(2, M.SO_MAX_SEG + 1)]
+    widths = sorted(set(range(64, 2049, 62)) | {w + d for w in limits for d in (-1, 0, 1)} | {g[0] for g in streams.GEOMETRIES.values()})
+    heights = sorted({g[1] for g in streams.GEOMETRIES.values()} | {375, 1080})
+    grid = [(w, h, vpl, off, probe, seg, fast, 64 * vpl * (1 + w % 2), w % 37)
+            for w in widths for h in heights for vpl in (1, 2, 4) for off in (0, 1) for seg in (-1, 0, 1, 2, 5, 8)
+            for fast, probe in ((-1, 0), (0, 0), (0, 1), (1, 0))]
+    assert min(limits) > 64 and max(limits) < 2048 and len(grid) > 20000
+    out = subprocess.run([M.build_emul("emul_learn"), "grid"], input="".join("%d %d %d %d %d %d %d %d %d\n" % g for g in grid),
+                         capture_output=True, text=True, check=True).stdout.split("\n")
+    seen = collections.Counter()
+    for (w, h, vpl, off, probe, seg, fast, dp, cap), line in zip(grid, out):
+        want = (M.so_segments(w, h, vpl, off, seg_env=seg), int(M.so_can_fuse(w, h, vpl, off, None if fast < 0 else fast, probe, seg_env=seg)),
+                int(M.cost_flat_fits(dp, cap)))
+        assert tuple(int(t) for t in line.split()) == want, (w, h, vpl, off, probe, seg, fast, dp, cap, line, want)
+        seen[want] += 1
+    assert {k[0] for k in seen} == set(range(1, M.SO_MAX_SEG + 1)) and {k[1] for k in seen} == {0, 1} and {k[2] for k in seen} == {0, 1}
 
 
 @pytest.mark.parametrize("geometry,option_set", streams.COMBOS)
@@ -127,3 +145,53 @@ def test_coverage_floors(exe, tables, so_fast):
             assert total[kind] == 0  # (rows of these sizes run the pinned family, which cannot take the pass over)
             continue
         assert total[kind] >= FLOOR, (kind, dict(total))
+
+
+def _model_rows(exe, geometry, option_set, so_fast, keys, tab):
+    """HandleModel over one stream: per Match the scenario it enqueues, which gate redoes it, and the state behind it.  The state does
+    not depend on the plan, so the scenarios are collected first and planned in one call (by the caller)."""
+    mk = lambda: M.HandleModel(exe, *streams.GEOMETRIES[geometry], cross_L1=streams.OPTION_SETS[option_set].get("cross_L1", 34), so_fast=so_fast)
+    m, scen = mk(), []
+    none = {"dual": 1, "first_fused": 0, "sparse": 0, "gather": 0, "flat": 0, "tail_moved": 0, "forms": []}
+    for k in keys:
+        scen.append(m.scenario())
+        m.apply(none, tab[k])
+
+    def rows(plans):
+        m, out = mk(), []
+        for k, sc, plan in zip(keys, scen, plans):
+            assert m.scenario() == sc
+            p = m.apply(plan, tab[k])
+            out.append({"arms": sc["valid"], "can": sc["can"], "fits": sc["fits"], "dual": plan["dual"], "redos": p["redo"], "redo_h": int(p["redo_h"]),
+                        "redo_v": int(p["redo_v"]), "partial": p["d11"], "so_seg_off": m.so_seg_off, "agg_dual": m.agg_dual, "sh": m.armmax_small[0],
+                        "sv": m.armmax_small[1], "ah": m.armmax_host[0], "av": m.armmax_host[1], "nzh": m.rec_nz[0], "nzv": m.rec_nz[1]})
+        return out
+    return m, scen, rows
+
+
+@pytest.mark.parametrize("so_fast", [None, 0])
+def test_model_agrees_with_the_header(exe, tables, so_fast):
+    """Every committed stream's oracle facts through learn_plan.h (`emul_learn stream`: redo decision, commit, plan inputs, with the ring
+    word taken from the gates of the launches agg_plan.h plans) and through HandleModel: the two agree on every Match -- redone or not
+    and by which gate, the assumption, so_seg_off, agg_dual, armmax_small, the can / fits inputs of the plan."""
+    jobs, text, scenarios = [], [], []
+    for geometry, option_set in streams.COMBOS:
+        tab = tables(geometry, option_set)
+        w, h, dmin, dmax = streams.GEOMETRIES[geometry]
+        for name, order in streams.stream_orders(geometry).items():
+            keys = streams.expand(geometry, order)
+            m, scen, rows = _model_rows(exe, geometry, option_set, so_fast, keys, tab)
+            jobs.append(((geometry, option_set, name), keys, len(scenarios), rows))
+            scenarios += scen
+            text.append("G W=%d H=%d VPL=%d L1=%d so_fast=%d density_ppm=%d" % (w, h, m.vpl, m.L1, -1 if so_fast is None else so_fast, m.thr["sparse"]))
+            text += ["M ah=%d av=%d nzh=%d nzv=%d" % (*tab[k]["armmax"], *tab[k]["nz"]) for k in keys]
+    plans = M.plan_many(exe, scenarios)
+    out = subprocess.run([M.build_emul("emul_learn"), "stream"], input="\n".join(text) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(scenarios)
+    redone = collections.Counter()
+    for where, keys, at, rows in jobs:
+        for i, want in enumerate(rows(plans[at:at + len(keys)])):
+            got = {k: int(v) for k, v in (t.split("=", 1) for t in out[at + i].split() if "=" in t) if k in want}
+            assert got == want, (where, i, keys[i], got, want)
+            redone[(want["redo_h"], want["redo_v"])] += 1
+    assert min(redone[(0, 0)], redone[(1, 0)], redone[(0, 1)], redone[(1, 1)]) >= FLOOR, redone
