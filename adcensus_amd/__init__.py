@@ -48,6 +48,9 @@ GT_U8, GT_U16, GT_F32 = 0, 1, 2  # adc_gt.format (ADC_GT_*)
 GT_DTYPES = {GT_U8: np.uint8, GT_U16: np.uint16, GT_F32: np.float32}
 EVAL_MAX_THRESHOLDS, EVAL_ERR_BINS, EVAL_CONF_BINS = 4, 256, 256
 EVAL_KNOWN, EVAL_VALID, EVAL_BAD, EVAL_OCCLUDED = 1, 2, 4, 8  # bits of the class map (ADC_EVAL_*)
+REG_FROM_DISPARITY, REG_FROM_DEPTH = 0, 1  # input kind of a registration (ADC_REG_FROM_*)
+REG_NO_SPLAT, REG_PRETEST = 1, 2  # flags of register_depth (ADC_REG_NO_SPLAT, ADC_REG_PRETEST)
+REG_MAX_SPLAT = 8
 
 
 class ADCensusOption(C.Structure):
@@ -209,6 +212,29 @@ class EvalReport(C.Structure):
         return np.frombuffer(bytes(self), np.uint64, EvalReport.thresholds.offset // 8).copy()
 
 
+class RegTarget(C.Structure):
+    """adc_reg_target: the camera depth is registered into -- size, intrinsics, Brown-Conrady distortion, R (row-major, left-rectified
+    -> target coordinates) and t (unit of the calibration's baseline).  Defaults: R = I, everything else 0."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float), ("R", C.c_float * 9),
+                ("t", C.c_float * 3)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.R[0] = self.R[4] = self.R[8] = 1.0
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            if k in ("R", "t"):
+                v = (C.c_float * (9 if k == "R" else 3))(*[float(x) for x in np.asarray(v, np.float32).ravel()])
+            setattr(self, k, v)
+
+
+class RegReport(C.Structure):
+    """adc_reg_report: source pixels with a valid Z, those with a non-empty footprint, target pixels filled."""
+    _fields_ = [("src_valid", C.c_uint32), ("src_projected", C.c_uint32), ("dst_filled", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 POINT_DTYPE = np.dtype({"names": ["x", "y", "z", "r", "g", "b", "pad"], "formats": ["<f4", "<f4", "<f4", "u1", "u1", "u1", "u1"],
                         "offsets": [0, 4, 8, 12, 13, 14, 15], "itemsize": 16})
 
@@ -307,6 +333,17 @@ def lib():
         L.adc_evaluate.argtypes = [vp, vp, vp, vp, C.POINTER(EvalParams), vp, vp, C.POINTER(EvalReport)]
         L.adc_get_eval_report.argtypes = [vp, C.POINTER(EvalReport)]
         for name in ("adc_set_ground_truth", "adc_clear_ground_truth", "adc_evaluate_device", "adc_evaluate", "adc_get_eval_report"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_set_register_target"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_set_register_target.argtypes = [vp, C.POINTER(RegTarget)]
+        L.adc_clear_register_target.argtypes = [vp]
+        L.adc_register_depth_device.argtypes = [vp, vp, C.c_int, C.POINTER(Calib), C.c_uint32, vp, vp]
+        L.adc_align_color_device.argtypes = [vp, vp, C.c_int, C.POINTER(Calib), vp, vp, vp]
+        L.adc_register_depth.argtypes = [vp, vp, C.c_int, C.POINTER(Calib), C.c_uint32, vp, vp, C.POINTER(RegReport)]
+        L.adc_align_color.argtypes = [vp, vp, C.c_int, C.POINTER(Calib), vp, vp, vp]
+        L.adc_get_register_report.argtypes = [vp, C.POINTER(RegReport)]
+        for name in ("adc_set_register_target", "adc_clear_register_target", "adc_register_depth_device", "adc_align_color_device",
+                     "adc_register_depth", "adc_align_color", "adc_get_register_report"):
             getattr(L, name).restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
@@ -888,6 +925,70 @@ class ADCensusStereo:
         rep = EvalReport()
         if lib().adc_get_eval_report(self._h, C.byref(rep)) != 0:
             raise RuntimeError("adc_get_eval_report failed: " + last_error())
+        return rep
+
+    # -- registration of depth into a second camera (adc_set_register_target / adc_register_depth* / adc_align_color*) ------------
+    def set_register_target(self, target):
+        """Sets the camera every later register_depth / align_color of this object projects into (a RegTarget); the first call
+        allocates the z-buffer.  Raises when refused or on a HIP failure."""
+        if lib().adc_set_register_target(self._h, None if target is None else C.byref(target)) != 0:
+            raise RuntimeError("adc_set_register_target failed: " + last_error())
+        self._reg_size = (int(target.height), int(target.width))
+
+    def clear_register_target(self):
+        if lib().adc_clear_register_target(self._h) != 0:
+            raise RuntimeError("adc_clear_register_target failed: " + last_error())
+        self._reg_size = None
+
+    def register_depth_device(self, d_map, calib, kind=REG_FROM_DISPARITY, flags=0, d_depth=None, d_index=None):
+        """Registers a device-resident float32 [H][W] disparity or depth map into the target camera (adc_register_depth_device; ints:
+        device addresses, depth float32 / index int32 [Ht][Wt] or None); asynchronous, call wait(), then register_report().  False
+        when refused (no target, a Match pending, a bad calibration, kind or flag, no output) or on a HIP failure."""
+        c = _calib(calib)
+        return lib().adc_register_depth_device(self._h, d_map, int(kind), None if c is None else C.byref(c), int(flags), d_depth, d_index) == 0
+
+    def register_depth(self, map_, calib, kind=REG_FROM_DISPARITY, flags=0, depth=True, index=True):
+        """Host convenience (adc_register_depth): returns (depth float32 [Ht][Wt] or None, index int32 [Ht][Wt] or None, RegReport).
+        Raises on failure."""
+        m = np.ascontiguousarray(map_, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        shp = getattr(self, "_reg_size", None) or (0, 0)
+        d = np.empty(shp, np.float32) if depth else None
+        i = np.empty(shp, np.int32) if index else None
+        c = _calib(calib)
+        rep = RegReport()
+        if lib().adc_register_depth(self._h, m.ctypes.data, int(kind), None if c is None else C.byref(c), int(flags), None if d is None else d.ctypes.data,
+                                    None if i is None else i.ctypes.data, C.byref(rep)) != 0:
+            raise RuntimeError("adc_register_depth failed: " + last_error())
+        return d, i, rep
+
+    def align_color_device(self, d_map, calib, d_target_bgr, d_bgr_out, d_valid=None, kind=REG_FROM_DISPARITY):
+        """Colour aligned to depth (adc_align_color_device): every source pixel takes the target image's colour at its projection;
+        d_bgr_out uint8 [H][W][3] is what reproject_device takes as d_left.  Asynchronous, call wait().  False when refused or on a
+        HIP failure."""
+        c = _calib(calib)
+        return lib().adc_align_color_device(self._h, d_map, int(kind), None if c is None else C.byref(c), d_target_bgr, d_bgr_out, d_valid) == 0
+
+    def align_color(self, map_, calib, target_bgr, kind=REG_FROM_DISPARITY, valid=True):
+        """Host convenience (adc_align_color): returns (bgr uint8 [H][W][3], valid uint8 [H][W] or None).  Raises on failure."""
+        m = np.ascontiguousarray(map_, dtype=np.float32)
+        t = np.ascontiguousarray(target_bgr, dtype=np.uint8)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        shp = getattr(self, "_reg_size", None)
+        assert shp is None or t.shape == shp + (3,), (t.shape, shp)
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        v = np.empty((self.height, self.width), np.uint8) if valid else None
+        c = _calib(calib)
+        if lib().adc_align_color(self._h, m.ctypes.data, int(kind), None if c is None else C.byref(c), t.ctypes.data, out.ctypes.data,
+                                 None if v is None else v.ctypes.data) != 0:
+            raise RuntimeError("adc_align_color failed: " + last_error())
+        return out, v
+
+    def register_report(self):
+        """The RegReport of the last registration wait() has completed (adc_get_register_report)."""
+        rep = RegReport()
+        if lib().adc_get_register_report(self._h, C.byref(rep)) != 0:
+            raise RuntimeError("adc_get_register_report failed: " + last_error())
         return rep
 
     def match_device(self, d_left, d_right, d_disp):

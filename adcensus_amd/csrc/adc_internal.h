@@ -267,6 +267,26 @@ struct adc_handle {
     float* evs_conf;
     float* evs_err;
     uint8_t* evs_cls;
+    // optional registration of depth into a second camera (k_register.hip; nothing of it exists before the first adc_set_register_target)
+    int reg_set;              // a target is set (adc_clear_register_target / a failed set call: 0)
+    adc_reg_target reg_target;
+    int reg_cus;              // CUs of the device: the counting kernels' grids are a fixed multiple of it
+    uint64_t* reg_zbuf;       // one 64-bit key per target pixel, all ones = empty
+    size_t reg_zbuf_cap;      // target pixels reg_zbuf holds
+    uint32_t* reg_rep;        // the report words the kernels add to (adc_reg_report)
+    uint32_t* reg_pin;        // pinned: read-back of the report words, enqueued behind the kernels
+    int reg_pending;          // a registration was enqueued; adc_wait moves reg_pin into reg_report
+    adc_reg_report reg_report; // adc_get_register_report
+    int reg_report_valid;
+    float* regs_map;          // device scratch of adc_register_depth / adc_align_color (host callers), each allocated on the first call
+    uint8_t* regs_out;        // that needs it; the three target-sized ones grow with the largest target used
+    uint8_t* regs_valid;
+    float* regs_depth;
+    size_t regs_depth_cap;    // target pixels each holds
+    int32_t* regs_index;
+    size_t regs_index_cap;
+    uint8_t* regs_tbgr;
+    size_t regs_tbgr_cap;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -344,6 +364,9 @@ size_t adc_eval_report_words(void);                             // k_eval.hip: u
 hipError_t adc_launch_eval_gt(adc_handle* h, int side, int format, int pitch, float scale); // ev_raw -> ev_g[side]
 hipError_t adc_launch_eval_occ(adc_handle* h, int mode, float occ_thres);                   // 1: ev_g[0], ev_g[1] -> ev_occ; 2: ev_g[0], mask in ev_raw -> ev_occ
 hipError_t adc_launch_eval_measure(adc_handle* h, const float* disp, const uint8_t* prov, const float* conf, const float* thresholds, float* err, uint8_t* cls);
+hipError_t adc_launch_reg_scatter(adc_handle* h, const float* map, int kind, const adc_calib* calib, uint32_t flags); // k_register.hip: map -> keys in reg_zbuf, src counts
+hipError_t adc_launch_reg_resolve(adc_handle* h, float* depth, int32_t* index);                                       // reg_zbuf -> depth, index, dst_filled
+hipError_t adc_launch_reg_align(adc_handle* h, const float* map, int kind, const adc_calib* calib, const uint8_t* tbgr, uint8_t* out, uint8_t* valid);
 #define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

@@ -335,9 +335,11 @@ void adc_destroy(adc_handle* h)
                     h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
                     h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->out_words, h->os_cloud, h->sp_parent, h->sp_map,
                     h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw,
-                    h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls};
+                    h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls,
+                    h->reg_zbuf, h->reg_rep, h->regs_map, h->regs_out, h->regs_valid, h->regs_depth, h->regs_index, h->regs_tbgr};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->ev_pin) hipHostFree(h->ev_pin);
+    if (h->reg_pin) hipHostFree(h->reg_pin);
     for (const AdcMapBuf& m : h->map_buf) {
         if (m.dev) hipFree(m.dev);
         if (m.pin) hipHostFree(m.pin);
@@ -634,6 +636,7 @@ static void abort_match(adc_handle* h)
     h->force_median_fallback = 0;
     match_req_clear(h);
     h->ev_pending = 0;
+    h->reg_pending = 0;
     if (h->pin_flags) { h->pin_flags[ADC_PIN_MEDIAN] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[ADC_PIN_SPECKLE] = h->pin_flags[ADC_PIN_SPECKLE + 1] = h->pin_flags[ADC_PIN_SPECKLE + 2] = 0; }
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
@@ -847,6 +850,11 @@ int adc_wait(adc_handle* h)
         memcpy(&h->ev_report, h->ev_pin, adc_eval_report_words() * sizeof(uint64_t));
         h->ev_report_valid = 1;
         h->ev_pending = 0;
+    }
+    if (h->reg_pending) { // a registration has completed: its report words have arrived in the pinned block (adc_get_register_report)
+        memcpy(&h->reg_report, h->reg_pin, sizeof(h->reg_report));
+        h->reg_report_valid = 1;
+        h->reg_pending = 0;
     }
     // adc_match_device BORROWED the caller's device images until here: nothing of the handle may point at them any
     // more (a later debug stage would otherwise read memory the caller has reused or freed)
@@ -1541,6 +1549,194 @@ int adc_get_eval_report(adc_handle* h, adc_eval_report* out)
     if (!h || !out) { g_last_error = "adc_get_eval_report: null argument"; return 1; }
     if (!h->ev_report_valid) { g_last_error = "adc_get_eval_report: no evaluation has completed on this handle"; return 1; }
     *out = h->ev_report;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ registration into a second camera (k_register.hip)
+// Handle state (the target) plus entry points in the style of the evaluation: the device forms enqueue on the object stream and are
+// completed by adc_wait, which moves the pinned report words into reg_report.
+static const char* reg_target_why(const adc_reg_target* t)
+{
+    if (t->width < 1 || t->width > 32767 || t->height < 1 || t->height > 32767) return "the target's width and height must lie in [1, 32767]";
+    const float f[] = {t->fx, t->fy, t->cx, t->cy, t->k1, t->k2, t->p1, t->p2, t->k3, t->R[0], t->R[1], t->R[2], t->R[3], t->R[4],
+                       t->R[5], t->R[6], t->R[7], t->R[8], t->t[0], t->t[1], t->t[2]};
+    for (float v : f) if (!__builtin_isfinite(v)) return "the target has a non-finite field";
+    if (t->fx == 0.0f || t->fy == 0.0f) return "the target's fx and fy must not be 0";
+    return nullptr;
+}
+
+static hipError_t reg_grow(void** buf, size_t* cap, size_t need, size_t elem)
+{
+    if (*cap >= need) return hipSuccess;
+    if (*buf) hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    HIP_OK(hipMalloc(buf, need * elem));
+    *cap = need;
+    return hipSuccess;
+}
+
+static hipError_t reg_buffers(adc_handle* h, size_t Pt)
+{
+    if (!h->reg_cus) {
+        int cus = 0;
+        HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        h->reg_cus = cus > 0 ? cus : 1;
+    }
+    if (!h->reg_rep) HIP_OK(hipMalloc(&h->reg_rep, sizeof(adc_reg_report)));
+    if (!h->reg_pin) HIP_OK(hipHostMalloc(&h->reg_pin, sizeof(adc_reg_report), hipHostMallocDefault));
+    return reg_grow(reinterpret_cast<void**>(&h->reg_zbuf), &h->reg_zbuf_cap, Pt, sizeof(uint64_t));
+}
+
+int adc_set_register_target(adc_handle* h, const adc_reg_target* target)
+{
+    if (!h) { g_last_error = "adc_set_register_target: null handle"; return 1; }
+    if (!target) { g_last_error = "adc_set_register_target: null target"; return 1; }
+    const char* why = reg_target_why(target);
+    if (!why && match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string("adc_set_register_target: ") + why; return 1; }
+    hipSetDevice(h->device);
+    // (an earlier registration may still read the z-buffer that is about to be regrown)
+    hipError_t e = ADC_HIP(hipStreamSynchronize(h->stream));
+    if (e != hipSuccess) set_error("hipStreamSynchronize(h->stream)", e);
+    h->reg_set = 0; // (a failure below leaves the target unset)
+    if (e == hipSuccess) e = reg_buffers(h, (size_t)target->width * (size_t)target->height);
+    if (e != hipSuccess) {
+        const std::string keep = "adc_set_register_target: " + g_last_error;
+        abort_match(h); // (drains the stream; no Match was pending)
+        g_last_error = keep;
+        return 2;
+    }
+    h->reg_target = *target;
+    h->reg_set = 1;
+    return 0;
+}
+
+int adc_clear_register_target(adc_handle* h)
+{
+    if (!h) { g_last_error = "adc_clear_register_target: null handle"; return 1; }
+    if (match_in_flight(h)) { g_last_error = "adc_clear_register_target: a Match is pending (adc_wait first)"; return 1; }
+    h->reg_set = 0;
+    return 0;
+}
+
+// validates the part every registration request shares; 0, or 1 with adc_last_error
+// (extra: what the entry point itself found wrong with its other arguments, reported behind the shared ones and in front of the handle's state)
+static int reg_check(adc_handle* h, const void* map, int input_kind, const adc_calib* calib, const char* extra, const char* who)
+{
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (!calib) why = "null calibration";
+    else if (input_kind != ADC_REG_FROM_DISPARITY && input_kind != ADC_REG_FROM_DEPTH) why = "unknown input kind";
+    else if (!(__builtin_isfinite(calib->focal_px) && __builtin_isfinite(calib->baseline) && __builtin_isfinite(calib->cx) && __builtin_isfinite(calib->cy) &&
+               __builtin_isfinite(calib->doffs)))
+        why = "the calibration has a non-finite field";
+    else if (!(calib->focal_px > 0.0f)) why = "the calibration's focal_px must be positive";
+    else if (extra) why = extra;
+    else if (!h->reg_set) why = "no target set (adc_set_register_target)";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static const char* reg_request_why(uint32_t flags, bool any_output)
+{
+    if (flags & ~(ADC_REG_NO_SPLAT | ADC_REG_PRETEST)) return "unknown flag";
+    return any_output ? nullptr : "no output requested";
+}
+
+static hipError_t enqueue_registration(adc_handle* h, const float* map, int kind, const adc_calib* calib, uint32_t flags, float* depth, int32_t* index)
+{
+    const size_t Pt = (size_t)h->reg_target.width * (size_t)h->reg_target.height;
+    HIP_OK(hipMemsetAsync(h->reg_zbuf, 0xff, Pt * sizeof(uint64_t), h->stream));
+    HIP_OK(hipMemsetAsync(h->reg_rep, 0, sizeof(adc_reg_report), h->stream));
+    HIP_OK(adc_launch_reg_scatter(h, map, kind, calib, flags));
+    HIP_OK(adc_launch_reg_resolve(h, depth, index));
+    HIP_OK(hipMemcpyAsync(h->reg_pin, h->reg_rep, sizeof(adc_reg_report), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+static int reg_failed(adc_handle* h, const char* who)
+{
+    const std::string keep = std::string(who) + ": " + g_last_error;
+    abort_match(h);
+    g_last_error = keep;
+    return 2;
+}
+
+int adc_register_depth_device(adc_handle* h, const void* d_map, int input_kind, const adc_calib* calib, uint32_t flags, void* d_depth, void* d_index)
+{
+    const char* who = "adc_register_depth_device";
+    if (reg_check(h, d_map, input_kind, calib, reg_request_why(flags, d_depth || d_index), who) != 0) return 1;
+    hipSetDevice(h->device);
+    if (enqueue_registration(h, static_cast<const float*>(d_map), input_kind, calib, flags, static_cast<float*>(d_depth), static_cast<int32_t*>(d_index)) != hipSuccess)
+        return reg_failed(h, who);
+    h->reg_pending = 1;
+    return 0;
+}
+
+int adc_align_color_device(adc_handle* h, const void* d_map, int input_kind, const adc_calib* calib, const void* d_target_bgr, void* d_bgr_out, void* d_valid)
+{
+    const char* who = "adc_align_color_device";
+    if (reg_check(h, d_map, input_kind, calib, !d_target_bgr ? "null target image" : (!d_bgr_out ? "no output requested" : nullptr), who) != 0) return 1;
+    hipSetDevice(h->device);
+    const hipError_t e = ADC_HIP(adc_launch_reg_align(h, static_cast<const float*>(d_map), input_kind, calib, static_cast<const uint8_t*>(d_target_bgr),
+                                                      static_cast<uint8_t*>(d_bgr_out), static_cast<uint8_t*>(d_valid)));
+    if (e != hipSuccess) { set_error("adc_launch_reg_align", e); return reg_failed(h, who); }
+    return 0;
+}
+
+int adc_register_depth(adc_handle* h, const float* map, int input_kind, const adc_calib* calib, uint32_t flags, float* depth, int32_t* index, adc_reg_report* report)
+{
+    const char* who = "adc_register_depth";
+    if (reg_check(h, map, input_kind, calib, reg_request_why(flags, depth || index), who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H, Pt = (size_t)h->reg_target.width * (size_t)h->reg_target.height;
+    hipError_t e = hipSuccess;
+    if (!h->regs_map && (e = ADC_HIP(hipMalloc(&h->regs_map, P * 4))) != hipSuccess) h->regs_map = nullptr;
+    if (e != hipSuccess) set_error("hipMalloc(&h->regs_map)", e);
+    if (e == hipSuccess && depth) e = reg_grow(reinterpret_cast<void**>(&h->regs_depth), &h->regs_depth_cap, Pt, 4);
+    if (e == hipSuccess && index) e = reg_grow(reinterpret_cast<void**>(&h->regs_index), &h->regs_index_cap, Pt, 4);
+    if (e != hipSuccess) { g_last_error = std::string(who) + ": scratch: " + g_last_error; (void)hipGetLastError(); return 2; }
+    if ((e = ADC_HIP(hipMemcpy(h->regs_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_register_depth: upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_register_depth_device(h, h->regs_map, input_kind, calib, flags, depth ? h->regs_depth : nullptr, index ? h->regs_index : nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (depth && (e = ADC_HIP(hipMemcpy(depth, h->regs_depth, Pt * 4, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_register_depth: depth copy-out", e); return 2; }
+    if (index && (e = ADC_HIP(hipMemcpy(index, h->regs_index, Pt * 4, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_register_depth: index copy-out", e); return 2; }
+    if (report) *report = h->reg_report;
+    return 0;
+}
+
+int adc_align_color(adc_handle* h, const float* map, int input_kind, const adc_calib* calib, const uint8_t* target_bgr, uint8_t* bgr_out, uint8_t* valid)
+{
+    const char* who = "adc_align_color";
+    if (reg_check(h, map, input_kind, calib, !target_bgr ? "null target image" : (!bgr_out ? "no output requested" : nullptr), who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H, Pt = (size_t)h->reg_target.width * (size_t)h->reg_target.height;
+    hipError_t e = hipSuccess;
+    if (!h->regs_map && (e = ADC_HIP(hipMalloc(&h->regs_map, P * 4))) != hipSuccess) h->regs_map = nullptr;
+    if (e == hipSuccess && !h->regs_out && (e = ADC_HIP(hipMalloc(&h->regs_out, P * 3))) != hipSuccess) h->regs_out = nullptr;
+    if (e == hipSuccess && valid && !h->regs_valid && (e = ADC_HIP(hipMalloc(&h->regs_valid, P))) != hipSuccess) h->regs_valid = nullptr;
+    if (e != hipSuccess) set_error("hipMalloc", e);
+    if (e == hipSuccess) e = reg_grow(reinterpret_cast<void**>(&h->regs_tbgr), &h->regs_tbgr_cap, Pt, 3);
+    if (e != hipSuccess) { g_last_error = std::string(who) + ": scratch: " + g_last_error; (void)hipGetLastError(); return 2; }
+    e = ADC_HIP(hipMemcpy(h->regs_map, map, P * 4, hipMemcpyHostToDevice));
+    if (e == hipSuccess) e = ADC_HIP(hipMemcpy(h->regs_tbgr, target_bgr, Pt * 3, hipMemcpyHostToDevice));
+    if (e != hipSuccess) { set_error("adc_align_color: upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_align_color_device(h, h->regs_map, input_kind, calib, h->regs_tbgr, h->regs_out, valid ? h->regs_valid : nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if ((e = ADC_HIP(hipMemcpy(bgr_out, h->regs_out, P * 3, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_align_color: image copy-out", e); return 2; }
+    if (valid && (e = ADC_HIP(hipMemcpy(valid, h->regs_valid, P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_align_color: valid map copy-out", e); return 2; }
+    return 0;
+}
+
+int adc_get_register_report(adc_handle* h, adc_reg_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_register_report: null argument"; return 1; }
+    if (!h->reg_report_valid) { g_last_error = "adc_get_register_report: no registration has completed on this handle"; return 1; }
+    *out = h->reg_report;
     return 0;
 }
 

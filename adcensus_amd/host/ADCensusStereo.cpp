@@ -252,4 +252,15 @@ bool ADCensusStereo::Evaluate(const float32* disp, const uint8* provenance, cons
     return impl_ && adc_evaluate(impl_, disp, provenance, confidence, params, err, eval_class, report) == 0;
 }
 bool ADCensusStereo::EvalReport(adc_eval_report* report) const { return impl_ && adc_get_eval_report(impl_, report) == 0; }
+bool ADCensusStereo::SetRegisterTarget(const adc_reg_target* target) { return impl_ && adc_set_register_target(impl_, target) == 0; }
+bool ADCensusStereo::ClearRegisterTarget() { return impl_ && adc_clear_register_target(impl_) == 0; }
+bool ADCensusStereo::RegisterDepth(const float32* map, int input_kind, const adc_calib* calib, unsigned flags, float32* depth, sint32* index,
+                                   adc_reg_report* report)
+{
+    return impl_ && adc_register_depth(impl_, map, input_kind, calib, flags, depth, index, report) == 0;
+}
+bool ADCensusStereo::AlignColor(const float32* map, int input_kind, const adc_calib* calib, const uint8* target_bgr, uint8* bgr_out, uint8* valid)
+{
+    return impl_ && adc_align_color(impl_, map, input_kind, calib, target_bgr, bgr_out, valid) == 0;
+}
 const char* ADCensusStereo::LastError() const { return adc_last_error(); }

@@ -31,6 +31,12 @@
 // --rectify the frames are already rectified and are only converted on the device (ADCensusStereo::SetInputFormat); with --rectify
 // FMT,W,H,PITCH are the raw geometry of both cameras (the camera files' width and height must agree, their pitch and format are
 // superseded).  A malformed flag is refused while the arguments are parsed.  The run also writes <out>-rect-left.png / -right.png.
+// --register TARGET.txt[,COLOR.png] (anywhere after the program name; needs --calib) registers the depth of the run into a second
+// camera on the device (ADCensusStereo::SetRegisterTarget / RegisterDepth).  TARGET.txt holds the numbers of adc_reg_target in
+// declaration order, separated by white space: width height fx fy cx cy k1 k2 p1 p2 k3 R[0..8] t[0..2]; a malformed flag or file is
+// refused while the arguments are parsed.  The run also writes <out>-reg.pfm (the registered depth, +inf where nothing landed); with a
+// colour image of the target's size also <out>-aligned.png (the colour image aligned to the left view, ADCensusStereo::AlignColor),
+// and the points of <out>-cloud.ply take their colours from it.
 // --gt LEFT[,RIGHT],SCALE [--bad T0[,T1..]] (anywhere after the program name) scores the map against ground truth on the device
 // (ADCensusStereo::SetGroundTruth / Evaluate): LEFT / RIGHT are the left- / right-view disparities as 8-bit gray PNG (0 = unknown) or
 // PFM, disparity = value / SCALE (Middlebury: 4 for Cone, 2 for Cloth3 / Wood2, 1 for PFM); with RIGHT the non-occluded mask comes
@@ -245,6 +251,33 @@ static void print_eval_row(const char* name, uint64_t pixels, uint64_t invalid, 
     printf("\n");
 }
 
+// the file of --register; false (with the reason in `why`) unless it holds exactly the numbers of adc_reg_target, all usable
+static bool parse_register_file(const std::string& path, adc_reg_target& out, std::string& why)
+{
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) { why = "cannot read " + path; return false; }
+    double v[23];
+    int n = 0;
+    while (n < 23 && fscanf(f, "%lf", &v[n]) == 1) n++;
+    char tail[2];
+    const bool more = fscanf(f, "%1s", tail) == 1;
+    fclose(f);
+    if (n != 23 || more) { why = path + ": it holds width height fx fy cx cy k1 k2 p1 p2 k3, nine numbers of R and three of t, nothing else"; return false; }
+    for (int i = 0; i < 23; i++)
+        if (!std::isfinite(v[i]) || !std::isfinite((float)v[i])) { why = path + ": a value is not finite"; return false; }
+    if (v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]) || v[0] < 1 || v[0] > 32767 || v[1] < 1 || v[1] > 32767) {
+        why = path + ": width and height must be whole numbers in [1, 32767]";
+        return false;
+    }
+    if ((float)v[2] == 0.f || (float)v[3] == 0.f) { why = path + ": fx and fy must not be 0"; return false; }
+    out.width = (int32_t)v[0]; out.height = (int32_t)v[1];
+    out.fx = (float)v[2]; out.fy = (float)v[3]; out.cx = (float)v[4]; out.cy = (float)v[5];
+    out.k1 = (float)v[6]; out.k2 = (float)v[7]; out.p1 = (float)v[8]; out.p2 = (float)v[9]; out.k3 = (float)v[10];
+    for (int i = 0; i < 9; i++) out.R[i] = (float)v[11 + i];
+    for (int i = 0; i < 3; i++) out.t[i] = (float)v[20 + i];
+    return true;
+}
+
 static void write_pfm(const std::string& path, const float32* px, int w, int h)
 {
     FILE* f = fopen(path.c_str(), "wb");
@@ -384,6 +417,28 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_register = false; // (--register and its value likewise; the target file is read and checked here, the colour image behind the pair)
+    adc_reg_target reg_target;
+    std::string reg_color;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--register")) {
+            std::string why = "it needs TARGET.txt[,COLOR.png]";
+            bool ok = i + 1 < argc;
+            if (ok) {
+                const std::string v(argv[i + 1]);
+                const size_t comma = v.find(',');
+                const std::string file = v.substr(0, comma);
+                if (comma != std::string::npos) reg_color = v.substr(comma + 1);
+                ok = !file.empty() && (comma == std::string::npos || (!reg_color.empty() && reg_color.find(',') == std::string::npos));
+                ok = ok && parse_register_file(file, reg_target, why);
+            }
+            if (!ok) { printf("--register refused: %s\n", why.c_str()); return -1; }
+            with_register = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_register && !with_calib) { printf("--register refused: it needs --calib\n"); return -1; }
     if (with_calib && with_gt) { printf("--calib and --gt are separate runs\n"); return -1; }
     if (with_calib && extras) { printf("--calib and --extras are separate runs\n"); return -1; }
     // file-format helpers that need no GPU (used by the CPU test tier):
@@ -439,6 +494,14 @@ int main(int argc, char** argv)
         std::string why;
         if (!load_gt(gt_path[0], gt_scale, w, h, gt_img[0], why) || (!gt_path[1].empty() && !load_gt(gt_path[1], gt_scale, w, h, gt_img[1], why))) {
             printf("--gt refused: %s\n", why.c_str());
+            return -1;
+        }
+    }
+    std::vector<uint8> reg_bgr; // (the colour image of --register: B, G, R of the target camera)
+    if (with_register && !reg_color.empty()) {
+        int cw = 0, chh = 0;
+        if (!load_image(reg_color.c_str(), reg_bgr, cw, chh) || cw != reg_target.width || chh != reg_target.height) {
+            printf("--register refused: %s is not a readable image of the target's size\n", reg_color.c_str());
             return -1;
         }
     }
@@ -587,6 +650,36 @@ int main(int argc, char** argv)
             }
             fclose(pgm);
         } else printf("cannot write %s-disp16.pgm\n", out.c_str());
+    }
+    if (with_register) { // depth into the target camera; with a colour image the image aligned to the left view, which then colours the cloud
+        const size_t pt = (size_t)reg_target.width * reg_target.height;
+        std::vector<float32> reg_depth(pt);
+        adc_reg_report rep;
+        if (!ad_census.SetRegisterTarget(&reg_target) ||
+            !ad_census.RegisterDepth(disparity.data(), ADC_REG_FROM_DISPARITY, &calib, 0, reg_depth.data(), nullptr, &rep)) {
+            printf("registration refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        printf("\nRegistered into %d x %d: %u valid source pixels, %u projected, %u target pixels filled\n", reg_target.width, reg_target.height, rep.src_valid,
+               rep.src_projected, rep.dst_filled);
+        write_pfm(out + "-reg.pfm", reg_depth.data(), reg_target.width, reg_target.height);
+        if (!reg_bgr.empty()) {
+            std::vector<uint8> aligned((size_t)w * h * 3), rgb((size_t)w * h * 3);
+            if (!ad_census.AlignColor(disparity.data(), ADC_REG_FROM_DISPARITY, &calib, reg_bgr.data(), aligned.data(), nullptr)) {
+                printf("registration refused: %s\n", ad_census.LastError());
+                return -2;
+            }
+            for (size_t i = 0; i < (size_t)w * h; i++) { rgb[3 * i] = aligned[3 * i + 2]; rgb[3 * i + 1] = aligned[3 * i + 1]; rgb[3 * i + 2] = aligned[3 * i]; }
+            if (!write_png(out + "-aligned.png", rgb.data(), w, h, 3)) printf("cannot write %s-aligned.png\n", out.c_str());
+            // the cloud holds the valid pixels (a = |d| finite, a + doffs > 0) in raster order: the k-th of them is the k-th point
+            size_t k = 0;
+            for (size_t i = 0; i < (size_t)w * h && k < cloud.size(); i++) {
+                const float32 a = fabsf(disparity[i]);
+                if (!(std::isfinite(a) && a + calib.doffs > 0.0f)) continue;
+                cloud[k].r = aligned[3 * i + 2]; cloud[k].g = aligned[3 * i + 1]; cloud[k].b = aligned[3 * i];
+                k++;
+            }
+        }
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

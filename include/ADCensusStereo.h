@@ -14,6 +14,7 @@
  * on the device from the final map), SetSpeckleFilter (optional removal of small disparity islands on the device, off by default),
  * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default),
  * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device),
+ * SetRegisterTarget / ClearRegisterTarget / RegisterDepth / AlignColor (optional registration of depth into a second camera on the device),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -28,6 +29,9 @@ struct adc_camera_model;
 struct adc_gt;
 struct adc_eval_params;
 struct adc_eval_report;
+struct adc_calib;
+struct adc_reg_target;
+struct adc_reg_report;
 
 class ADCensusStereo {
 public:
@@ -116,6 +120,20 @@ public:
                   uint8* eval_class, adc_eval_report* report);
     /** The report of the last evaluation completed on this object. */
     bool EvalReport(adc_eval_report* report) const;
+    /** Optional registration of depth into a second camera on the device ("align depth to colour"; adc_set_register_target /
+     *  adc_register_depth / adc_align_color, include/adcensus_c_api.h holds the definition).  The target -- size, intrinsics, distortion,
+     *  R and t from the left rectified camera -- is state of the matcher object underneath: needs Initialize, and Initialize / Reset
+     *  drop it.  false: a refused target (a size outside [1, 32767], a non-finite field, fx or fy == 0), a Match pending, a HIP failure. */
+    bool SetRegisterTarget(const adc_reg_target* target);
+    bool ClearRegisterTarget();
+    /** Registers a float32 [H][W] host map (input_kind ADC_REG_FROM_DISPARITY or ADC_REG_FROM_DEPTH, calib the rectified left camera)
+     *  into the target: depth float32 [Ht][Wt] (+inf where nothing landed) and index int32 [Ht][Wt] (source raster index, -1), either
+     *  may be null, not both; flags: ADC_REG_NO_SPLAT.  report may be null. */
+    bool RegisterDepth(const float32* map, int input_kind, const adc_calib* calib, unsigned flags, float32* depth, sint32* index,
+                       adc_reg_report* report);
+    /** The other direction: bgr_out uint8 [H][W][3] takes, per source pixel, the colour of target_bgr uint8 [Ht][Wt][3] at the pixel's
+     *  projection (0 and valid = 0 where there is none); valid uint8 [H][W] may be null. */
+    bool AlignColor(const float32* map, int input_kind, const adc_calib* calib, const uint8* target_bgr, uint8* bgr_out, uint8* valid);
     const char* LastError() const;
 
 private:

@@ -24,6 +24,8 @@
  *   adc_match_products /  every optional product above from ONE Match through one request struct (adc_products), synchronous,
  *   adc_match_async_products / adc_match_device_products / adc_farm_submit_products   asynchronous, device-resident and through the
  *                         farm; plus a 16-bit fixed-point disparity map (adc_disp16_device: that kernel on any map)
+ *   adc_set_register_target / adc_register_depth_device / adc_align_color_device   depth registered into a second camera on the
+ *                         device (z-buffered scatter), and that camera's colours gathered into the left view
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -520,6 +522,92 @@ int adc_match_device_products(adc_handle* h, const void* d_bgr_left, const void*
 int adc_farm_submit_products(adc_farm* f, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left, const adc_products* products,
                              uint64_t* ticket);
 int adc_disp16_device(adc_handle* h, const void* d_disp, float scale, void* d_disp16);
+
+/* -------------------------------------------------------------------------------------------
+ * Registration of depth into a second camera on the device ("align depth to colour"; k_register.hip, the arithmetic is
+ * adcensus_amd/csrc/reg_project.h, tests/register_ref.py holds the same definition in numpy and the kernels match it bit for bit).
+ * All arithmetic is IEEE binary32, one rounding per operation, nothing fused, divisions correctly rounded, in the order written.
+ *
+ * Source: a device-resident float32 [H][W] map of the handle's geometry and an adc_calib of the rectified LEFT camera;
+ * fb = focal_px * baseline (one multiply on the host).
+ *   ADC_REG_FROM_DISPARITY  a = fabsf(d), s = a + doffs, valid <=> a finite and s > 0, Z = fb / s (the rule of adc_outputs.depth)
+ *   ADC_REG_FROM_DEPTH      Z = v, valid <=> v finite and v > 0
+ * Target camera (adc_reg_target): width, height in [1, 32767]; fx, fy, cx, cy; Brown-Conrady k1, k2, p1, p2, k3; R row-major maps
+ * left-rectified coordinates to target coordinates; t in the unit of baseline.
+ * Projection of a source point (xs, ys, Z):
+ *   X = ((xs - cx) * Z) / focal_px, Y = ((ys - cy) * Z) / focal_px
+ *   Xt = ((R0*X + R1*Y) + R2*Z) + t0, Yt = ((R3*X + R4*Y) + R5*Z) + t1, Zt = ((R6*X + R7*Y) + R8*Z) + t2
+ *   in front <=> Zt finite and Zt > 0;  x = Xt / Zt, y = Yt / Zt
+ *   x2 = x*x, y2 = y*y, r2 = x2 + y2, xy = x*y; rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ *   xd = (x rad + (2 p1) xy) + p2 (r2 + 2 x2); yd = (y rad + p1 (r2 + 2 y2)) + (2 p2) xy   (as in adc_set_rectify_model)
+ *   u = fx xd + cx_t, v = fy yd + cy_t;  in range <=> fabsf(u) < 32768 and fabsf(v) < 32768 (NaN fails)
+ * Footprint of a source pixel (x, y) with valid Z: three projections, all with the pixel's own Z -- the centre (float(x), float(y))
+ * giving Zc = Zt and (uc, vc), corner A (float(x) - 0.5, float(y) - 0.5), corner B (float(x) + 0.5, float(y) + 0.5).  The pixel is
+ * dropped unless all three are in front and in range.  With splat (the default): j0 = (int)ceilf(fminf(uA, uB)),
+ * j1 = (int)ceilf(fmaxf(uA, uB)) - 1 (the target centres in [lo, hi)), i0 / i1 the same from v; without (ADC_REG_NO_SPLAT):
+ * j0 = j1 = (int)floorf(uc + 0.5f), rows likewise.  Then in integers: j0 = max(j0, 0), j1 = min(j1, width - 1),
+ * j1 = min(j1, j0 + ADC_REG_MAX_SPLAT - 1), rows likewise; an empty footprint writes nothing.  No float reaches an address.
+ * Z-buffer: every target pixel of the footprint receives the key ((uint64)bits(Zc) << 32) | (uint32)(y * W + x) and keeps the MINIMUM
+ * key (one 64-bit unsigned atomic minimum): for positive floats the bit order is the value order, so the nearest surface wins and among
+ * equal Zc the lowest raster index; the result does not depend on the order of arrival.
+ * Because the corners use the pixel's own Z, the footprints of a smooth slanted surface tile the target only approximately: small
+ * cracks (target pixels no footprint covers) are part of the definition, not an error.
+ * Outputs, device addresses, each may be NULL (not both):
+ *   depth  float32 [Ht][Wt]: Zc of the winner, +inf where nothing landed
+ *   index  int32 [Ht][Wt]: the winner's source raster index y * W + x, -1 where nothing landed (gather anything else through it)
+ *   adc_reg_report: src_valid = source pixels with a valid Z, src_projected = those with a non-empty footprint, dst_filled = target
+ *   pixels that received a key; read back through a pinned block behind the kernels, available after adc_wait
+ * With R = I, t = 0, the source's intrinsics, no distortion and ADC_REG_FROM_DEPTH, depth equals the input bit for bit at every valid
+ * pixel and index is the raster index.
+ *
+ * The other direction (colour aligned to depth): for every source pixel the centre projection only, j = (int)floorf(uc + 0.5f),
+ * i = (int)floorf(vc + 0.5f); if Z is valid, the projection in front and in range and (i, j) inside the target:
+ * out[y][x] = target_bgr[i][j] (3 bytes) and valid[y][x] = 1, otherwise the three bytes are 0 and valid is 0.  target_bgr is a tightly
+ * packed uint8 [Ht][Wt][3], out uint8 [H][W][3] -- exactly what adc_reproject_device takes as d_bgr_left -- valid uint8 [H][W] or NULL.
+ *
+ * adc_set_register_target    validates and stores the target; the first call allocates the z-buffer (8 * Wt * Ht bytes) and the report
+ *                            words, a larger target regrows the z-buffer (adc_create allocates none of them, adc_destroy frees them).
+ *                            Synchronous.
+ * adc_clear_register_target  back to "no target" (the buffers stay until adc_destroy).
+ * adc_register_depth_device  asynchronous on the handle's stream, completed by adc_wait.  flags: ADC_REG_NO_SPLAT;
+ *                            ADC_REG_PRETEST (measurement only: look at the z-buffer word with a plain load first and skip an atomic
+ *                            that cannot win, instead of issuing every atomic -- the same result bit for bit).
+ * adc_align_color_device     asynchronous, completed by adc_wait.
+ * adc_register_depth /       the same with HOST pointers, synchronous; device scratch is allocated on the first call that needs it
+ * adc_align_color            (freed by adc_destroy); report may be NULL.
+ * adc_get_register_report    the report of the last registration that adc_wait (or adc_register_depth) has completed.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued or changed (a NULL handle, map or calib, an unknown input kind or flag, a
+ * calibration adc_match_out would refuse, a target with a non-finite field or fx or fy == 0, a size outside [1, 32767], no target
+ * set, no output requested, a Match pending -- adc_wait first, for the reason given at adc_evaluate_device); 2 on a HIP failure (the
+ * handle stays usable, a failed set call leaves the target unset).  The registered map is not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_REG_FROM_DISPARITY 0
+#define ADC_REG_FROM_DEPTH 1
+#define ADC_REG_NO_SPLAT 1u
+#define ADC_REG_PRETEST 2u
+#define ADC_REG_MAX_SPLAT 8
+typedef struct adc_reg_target {
+    int32_t width, height;
+    float fx, fy, cx, cy;
+    float k1, k2, p1, p2, k3;
+    float R[9];
+    float t[3];
+} adc_reg_target;
+typedef struct adc_reg_report {
+    uint32_t src_valid, src_projected, dst_filled;
+    uint32_t reserved_;
+} adc_reg_report;
+int adc_set_register_target(adc_handle* h, const adc_reg_target* target);
+int adc_clear_register_target(adc_handle* h);
+int adc_register_depth_device(adc_handle* h, const void* d_map, int input_kind, const adc_calib* calib, uint32_t flags, void* d_depth,
+                              void* d_index);
+int adc_align_color_device(adc_handle* h, const void* d_map, int input_kind, const adc_calib* calib, const void* d_target_bgr,
+                           void* d_bgr_out, void* d_valid);
+int adc_register_depth(adc_handle* h, const float* map, int input_kind, const adc_calib* calib, uint32_t flags, float* depth,
+                       int32_t* index, adc_reg_report* report);
+int adc_align_color(adc_handle* h, const float* map, int input_kind, const adc_calib* calib, const uint8_t* target_bgr, uint8_t* bgr_out,
+                    uint8_t* valid);
+int adc_get_register_report(adc_handle* h, adc_reg_report* out);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
