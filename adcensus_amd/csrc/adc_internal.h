@@ -1,6 +1,15 @@
 // adc_internal.h -- private state of an adc_handle and the kernel-launch entry points.
 //
-// HBM layout (all buffers allocated once in adc_create, 288 GB HBM3E is plentiful):
+// Memory.  Every device and pinned buffer of a handle is one of the pointer fields below, allocated through dev_mem.h, the only owner:
+// capi.hip calls it (no k_*.hip file allocates or frees handle state), the handle's registry `mem` knows which fields own memory, and
+// adc_destroy releases exactly that registry.  adc_create allocates what every Match needs (alloc_all: images, per-pixel maps, volumes,
+// tables, refinement state, pin_in / pin_out / pin_flags; upload_tables: ray_tab).  Everything optional is allocated by the first call
+// that needs it and kept until adc_destroy: out_words, map_buf[], os_cloud (products); sp_* (speckle filter); rect[], pin_raw
+// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
+// os_cloud, the raw buffers, ev_raw, reg_zbuf and the target-sized regs_* grow with the largest size asked for; their capacities count
+// elements of the field's own type.
+//
+// HBM layout of the buffers of adc_create (288 GB HBM3E is plentiful):
 //   img_l / img_r      u8  [H][W][3]  BGR, as handed over by the caller
 //   gray_l / gray_r    u8  [H][W]
 //   census_l/census_r  u64 [H][W]
@@ -20,6 +29,7 @@
 
 #include "../../include/adcensus_c_api.h"
 #include "learn_plan.h"
+#include "dev_mem.h"
 
 #define ADC_WAVE 64
 
@@ -126,6 +136,7 @@ struct AdcRectSide {
 struct adc_handle {
     AdcParams p;
     int device;
+    DevMemOwner mem;    // which of the pointer fields below own device / pinned memory (dev_mem.h)
     hipStream_t stream; // per-object stream: uploads, refinement (latency-bound kernels), downloads
     hipStream_t heavy;  // bandwidth lane: cost/arms/aggregate/scanline/WTA kernels.  Shared by all objects of a
                         // device (FIFO), so the streaming kernels of different pairs never fight for HBM while
@@ -237,7 +248,7 @@ struct adc_handle {
     AdcMapBuf map_buf[ADC_REQ_MAPS]; // scratch and staging of the host callers' map products
     uint32_t* out_words;  // device scratch of k_outputs.hip (min / max words, count, tile counts), allocated on first use
     void* os_cloud;       // device scratch of the host callers' cloud; grows with the largest capacity asked for
-    uint32_t os_cloud_cap; // points os_cloud holds
+    size_t os_cloud_cap;  // points os_cloud holds
     // optional speckle filter (k_speckle.hip; off = sp_max_size <= 0: nothing of it is enqueued)
     int32_t sp_max_size;  // handle state (adc_set_speckle_filter): every later Match filters its delivered map
     float sp_max_diff;

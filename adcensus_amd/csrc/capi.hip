@@ -23,6 +23,11 @@ static std::atomic<long> g_fi_fail_at{[] { const char* e = getenv("ADC_TEST_FAIL
 extern "C" int adc_test_fault_now(void) { const long n = ++g_fi_calls; return n == g_fi_fail_at.load(); }
 extern "C" void adc_test_fail_at(long n) { g_fi_calls = 0; g_fi_fail_at = n; } // the n-th call from now on fails (0: none)
 extern "C" long adc_test_hip_calls(void) { return g_fi_calls.load(); }
+static std::atomic<long> g_fi_live{0};
+extern "C" long adc_test_live_buffers(void) { return g_fi_live.load(); } // allocations of HipMem not yet freed, all handles of the process
+#define ADC_LIVE(d) (g_fi_live += (d))
+#else
+#define ADC_LIVE(d) ((void)0)
 #endif
 
 // Host ranges the CALLER has page-locked for the library (adc_host_register): images / maps inside such a range are
@@ -45,14 +50,32 @@ static void set_error(const char* what, hipError_t e)
 {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
 }
-#define HIP_OK(call)                          \
-    do {                                      \
-        hipError_t e__ = ADC_HIP(call);       \
-        if (e__ != hipSuccess) {              \
-            set_error(#call, e__);            \
-            return e__;                       \
-        }                                     \
-    } while (0)
+static hipError_t hip_checked(const char* what, hipError_t e) { if (e != hipSuccess) set_error(what, e); return e; }
+// HIP_TRY: return the error of a call that has made its own hooked HIP calls and left its own message (not counted again);
+// HIP_OK: one hooked HIP call, its text is the message
+#define HIP_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return e__; } while (0)
+#define HIP_OK(call) HIP_TRY(hip_checked(#call, ADC_HIP(call)))
+
+// A handle's device and pinned memory: dev_mem.h owns it, these are the four HIP calls it makes.  One hooked call per allocation;
+// frees are not hooked.  No other function of this file allocates or frees handle state.
+struct HipMem {
+    static int alloc_device(void** p, size_t bytes) { const hipError_t e = ADC_HIP(hipMalloc(p, bytes)); if (e == hipSuccess) ADC_LIVE(1); return e; }
+    static int alloc_pinned(void** p, size_t bytes) { const hipError_t e = ADC_HIP(hipHostMalloc(p, bytes, hipHostMallocDefault)); if (e == hipSuccess) ADC_LIVE(1); return e; }
+    static void free_device(void* p) { hipFree(p); ADC_LIVE(-1); }
+    static void free_pinned(void* p) { hipHostFree(p); ADC_LIVE(-1); }
+};
+static hipError_t mem_result(int rc, const char* field)
+{
+    if (rc != DEV_MEM_FULL) return hip_checked(field, (hipError_t)rc);
+    g_last_error = std::string(field) + ": the handle's buffer registry is full (DEV_MEM_SLOTS)";
+    return hipErrorOutOfMemory;
+}
+// (`h` is the handle in scope; on failure the field is null, a grown field's capacity 0, and adc_last_error names the field)
+#define MEM_ONCE(field, bytes) mem_result(dev_mem_once<HipMem>(&h->mem, &(field), (bytes)), #field)
+#define MEM_ONCE_PINNED(field, bytes) mem_result(dev_mem_once_pinned<HipMem>(&h->mem, &(field), (bytes)), #field)
+#define MEM_GROW(field, cap, need, elem) mem_result(dev_mem_grow<HipMem>(&h->mem, &(field), &(cap), (need), (elem)), #field)
+#define MEM_GROW_PINNED(field, cap, need, elem) mem_result(dev_mem_grow_pinned<HipMem>(&h->mem, &(field), &(cap), (need), (elem)), #field)
+static int scratch_failed(const char* who) { g_last_error = std::string(who) + ": scratch: " + g_last_error; (void)hipGetLastError(); return 2; } // (first use)
 
 // The guide's yardstick (MI355X_MICROARCH.md: "float4 copy"): a grid-stride copy kernel, 16 bytes per lane, four loads in
 // flight per lane; best time over a few grid sizes and plain / non-temporal accesses (tools/ubench/copy_ceiling.hip sweeps more
@@ -111,76 +134,76 @@ static hipError_t alloc_all(adc_handle* h)
     const AdcParams& p = h->p;
     const size_t P = (size_t)p.W * p.H;
     const size_t VB = P * p.Dp * sizeof(float);
-    HIP_OK(hipMalloc(&h->img_l_own, P * 3));
-    HIP_OK(hipMalloc(&h->img_r_own, P * 3));
+    HIP_TRY(MEM_ONCE(h->img_l_own, P * 3));
+    HIP_TRY(MEM_ONCE(h->img_r_own, P * 3));
     h->img_l = h->img_l_own;
     h->img_r = h->img_r_own;
-    HIP_OK(hipMalloc(&h->gray_l, P));
-    HIP_OK(hipMalloc(&h->bgrx_l, P * 4));
+    HIP_TRY(MEM_ONCE(h->gray_l, P));
+    HIP_TRY(MEM_ONCE(h->bgrx_l, P * 4));
     // sized from the PADDED range: the fused-cost pass also marches over padding chunks / lanes (d >= D), whose
     // right-image column x - d lies up to dmin + Dp - 1 columns to the left of the row
     h->rrec_padl = (p.dmin + p.Dp - 1 > 0 ? p.dmin + p.Dp - 1 : 0) + 1;
     h->rrec_pitch = h->rrec_padl + p.W + (p.dmin < 0 ? -p.dmin : 0) + 1;
-    HIP_OK(hipMalloc(&h->cost_rrec, (size_t)p.H * h->rrec_pitch * 16));
-    HIP_OK(hipMalloc(&h->cost_lrec, P * 16));
+    HIP_TRY(MEM_ONCE(h->cost_rrec, (size_t)p.H * h->rrec_pitch * 16));
+    HIP_TRY(MEM_ONCE(h->cost_lrec, P * 16));
     h->med_hpitch = ((p.W + 2 * p.H + 64 + 15) / 16) * 16;
-    HIP_OK(hipMalloc(&h->med_hand, adc_median_hand_rows(p.H) * h->med_hpitch * sizeof(float))); // (bands + chains of <= 4 speculative copies per band, per column segment)
-    HIP_OK(hipMalloc(&h->med_sink, adc_median_hand_rows(p.H) * 64 * 16 + (size_t)((p.H + 63) / 64) * ADC_MEDB_MAX_SEG * 64 * 8 + 64)); // store sinks, then the segments' seam columns
-    HIP_OK(hipMalloc(&h->gray_r, P));
-    HIP_OK(hipMalloc(&h->census_l, P * 8));
-    HIP_OK(hipMalloc(&h->census_r, P * 8));
-    HIP_OK(hipMalloc(&h->arms, P * 4));
-    HIP_OK(hipMalloc(&h->sup_h, P * 2));
-    HIP_OK(hipMalloc(&h->sup_v, P * 2));
-    HIP_OK(hipMalloc(&h->armmax, ADC_ARMMAX_WORDS * sizeof(int)));
-    HIP_OK(hipMalloc(&h->rec_h, P * 4));
-    HIP_OK(hipMalloc(&h->rec_v, P * 4));
-    HIP_OK(hipMalloc(&h->rec2_h, P * 8));
-    HIP_OK(hipMalloc(&h->rec2_v, P * 8));
-    HIP_OK(hipMalloc(&h->agg_sink, 1024 * 64 * sizeof(float)));
+    HIP_TRY(MEM_ONCE(h->med_hand, adc_median_hand_rows(p.H) * h->med_hpitch * sizeof(float))); // (bands + chains of <= 4 speculative copies per band, per column segment)
+    HIP_TRY(MEM_ONCE(h->med_sink, adc_median_hand_rows(p.H) * 64 * 16 + (size_t)((p.H + 63) / 64) * ADC_MEDB_MAX_SEG * 64 * 8 + 64)); // store sinks, then the segments' seam columns
+    HIP_TRY(MEM_ONCE(h->gray_r, P));
+    HIP_TRY(MEM_ONCE(h->census_l, P * 8));
+    HIP_TRY(MEM_ONCE(h->census_r, P * 8));
+    HIP_TRY(MEM_ONCE(h->arms, P * 4));
+    HIP_TRY(MEM_ONCE(h->sup_h, P * 2));
+    HIP_TRY(MEM_ONCE(h->sup_v, P * 2));
+    HIP_TRY(MEM_ONCE(h->armmax, ADC_ARMMAX_WORDS * sizeof(int)));
+    HIP_TRY(MEM_ONCE(h->rec_h, P * 4));
+    HIP_TRY(MEM_ONCE(h->rec_v, P * 4));
+    HIP_TRY(MEM_ONCE(h->rec2_h, P * 8));
+    HIP_TRY(MEM_ONCE(h->rec2_v, P * 8));
+    HIP_TRY(MEM_ONCE(h->agg_sink, 1024 * 64 * sizeof(float)));
     // + slack: the scanline kernels fetch up to VPL (<= 32) bytes starting at a column <= W-1 (+1 on R->L passes)
-    HIP_OK(hipMalloc(&h->cdiff_lh, P + 64));
-    HIP_OK(hipMalloc(&h->cdiff_lv, P + 64));
-    HIP_OK(hipMalloc(&h->cdiff_rh, P + 64));
-    HIP_OK(hipMalloc(&h->cdiff_rv, P + 64));
-    HIP_OK(hipMalloc(&h->so_cls, adc_so_cls_bytes(p.W, p.H)));
-    if (p.VPL <= 2) HIP_OK(hipMalloc(&h->so_seam, adc_so_seam_bytes(p.W, p.H, p.Dp))); // (verified segments of the scanline row passes)
-    HIP_OK(hipMalloc(&h->vol_a, VB));
-    HIP_OK(hipMalloc(&h->vol_b, VB));
-    HIP_OK(hipMalloc(&h->lut_ad, 768 * sizeof(float)));
-    HIP_OK(hipMalloc(&h->lut_census, 64 * sizeof(float)));
-    HIP_OK(hipMalloc(&h->ray_sincos, 32 * sizeof(double)));
+    HIP_TRY(MEM_ONCE(h->cdiff_lh, P + 64));
+    HIP_TRY(MEM_ONCE(h->cdiff_lv, P + 64));
+    HIP_TRY(MEM_ONCE(h->cdiff_rh, P + 64));
+    HIP_TRY(MEM_ONCE(h->cdiff_rv, P + 64));
+    HIP_TRY(MEM_ONCE(h->so_cls, adc_so_cls_bytes(p.W, p.H)));
+    if (p.VPL <= 2) HIP_TRY(MEM_ONCE(h->so_seam, adc_so_seam_bytes(p.W, p.H, p.Dp))); // (verified segments of the scanline row passes)
+    HIP_TRY(MEM_ONCE(h->vol_a, VB));
+    HIP_TRY(MEM_ONCE(h->vol_b, VB));
+    HIP_TRY(MEM_ONCE(h->lut_ad, 768 * sizeof(float)));
+    HIP_TRY(MEM_ONCE(h->lut_census, 64 * sizeof(float)));
+    HIP_TRY(MEM_ONCE(h->ray_sincos, 32 * sizeof(double)));
     // (+ 1 KiB: the banded median prefetches a few columns past the last row's end without clamping, k_refine.hip)
-    HIP_OK(hipMalloc(&h->disp_l, P * 4 + 1024));
-    HIP_OK(hipMalloc(&h->disp_r, P * 4));
-    HIP_OK(hipMalloc(&h->disp_tmp, P * 4 + 1024));
+    HIP_TRY(MEM_ONCE(h->disp_l, P * 4 + 1024));
+    HIP_TRY(MEM_ONCE(h->disp_r, P * 4));
+    HIP_TRY(MEM_ONCE(h->disp_tmp, P * 4 + 1024));
     HIP_OK(hipMemset(h->disp_l + P, 0, 1024));
     HIP_OK(hipMemset(h->disp_tmp + P, 0, 1024));
-    HIP_OK(hipMalloc(&h->label, P));
-    HIP_OK(hipMalloc(&h->elig, P + 64)); // (LR check: invalid mask, 1 byte per pixel; then the voting chain's bitmap of listed pixels, whole 64-bit words)
-    HIP_OK(hipMalloc(&h->irv_bbox, P * 4));
+    HIP_TRY(MEM_ONCE(h->label, P));
+    HIP_TRY(MEM_ONCE(h->elig, P + 64)); // (LR check: invalid mask, 1 byte per pixel; then the voting chain's bitmap of listed pixels, whole 64-bit words)
+    HIP_TRY(MEM_ONCE(h->irv_bbox, P * 4));
     h->irv_grid = adc_irv_grid(P);
     h->irv_xcd_mode = adc_irv_probe_xcd_mode(h->device);
-    HIP_OK(hipMalloc(&h->vote_list, adc_irv_list_entries(p.W, p.H, p.D, h->irv_grid) * 16)); // int4 per entry, one segment per workgroup (irv_plan.h)
+    HIP_TRY(MEM_ONCE(h->vote_list, adc_irv_list_entries(p.W, p.H, p.D, h->irv_grid) * 16)); // int4 per entry, one segment per workgroup (irv_plan.h)
     HIP_OK(hipMemset(h->vote_list, 0xFF, adc_irv_list_entries(p.W, p.H, p.D, h->irv_grid) * 16)); // every slot = IRV_LIST_END
-    HIP_OK(hipMalloc(&h->vote_evals_arr, adc_irv_waves(h->irv_grid) * sizeof(int32_t)));
+    HIP_TRY(MEM_ONCE(h->vote_evals_arr, adc_irv_waves(h->irv_grid) * sizeof(int32_t)));
     HIP_OK(hipMemset(h->vote_evals_arr, 0, adc_irv_waves(h->irv_grid) * sizeof(int32_t)));
-    HIP_OK(hipMalloc(&h->interp_list, 2 * P * 4)); // both target lists of the interpolation, P entries each
-    HIP_OK(hipMalloc(&h->interp_counters, 64 * sizeof(int32_t)));
+    HIP_TRY(MEM_ONCE(h->interp_list, 2 * P * 4)); // both target lists of the interpolation, P entries each
+    HIP_TRY(MEM_ONCE(h->interp_counters, 64 * sizeof(int32_t)));
     {
         const long long ms = adc_itp_max_search(p.dmin, p.dmax); // multistep_refiner.cpp:236
         const bool tab = adc_itp_table_walk_ok(p.W, p.H, ms);    // (itp_plan.h; without the table walk: the cell maps alone, no code maps)
         h->itp_ms = ms > 0x7fffffff ? 0x7fffffff : (int)ms;
         h->itp_pitch = tab ? adc_itp_code_pitch(p.W, h->itp_ms) : 0;
-        HIP_OK(hipMalloc(&h->itp_cells, adc_itp_alloc_bytes(p.W, p.H, ms)));
+        HIP_TRY(MEM_ONCE(h->itp_cells, adc_itp_alloc_bytes(p.W, p.H, ms)));
         // (everything outside the image never changes: the per-Match kernel only rewrites the image's own columns and rows)
         HIP_OK(hipMemset(h->itp_cells, ADC_ITP_OUTSIDE, adc_itp_alloc_bytes(p.W, p.H, ms)));
     }
     h->st16_pitch = (p.W + 7) & ~7;
-    HIP_OK(hipMalloc(&h->st16, ((size_t)h->st16_pitch * p.H + 64) * sizeof(uint16_t))); // (an uncached allocation -- visible across XCDs inside a kernel -- measured equal)
+    HIP_TRY(MEM_ONCE(h->st16, ((size_t)h->st16_pitch * p.H + 64) * sizeof(uint16_t))); // (an uncached allocation -- visible across XCDs inside a kernel -- measured equal)
     HIP_OK(hipMemset(h->st16, 0xFF, ((size_t)h->st16_pitch * p.H + 64) * sizeof(uint16_t))); // padding columns: invalid bin
-    HIP_OK(hipMalloc(&h->disp_vote, P * 4));
-    HIP_OK(hipMalloc(&h->vote_counters, 512 * sizeof(int32_t)));
+    HIP_TRY(MEM_ONCE(h->disp_vote, P * 4));
+    HIP_TRY(MEM_ONCE(h->vote_counters, 512 * sizeof(int32_t)));
     // voting chain budget of the FIRST Match of a handle (later ones adapt: kernels used + 40 % + 2): a natural 1080p image needs
     // ~50-75 kernels (round 5: all passes iterate at once; ~350 before); kernels past the end of the chain are no-ops of ~4 us, an
     // exhausted budget costs a synchronous continuation
@@ -189,15 +212,15 @@ static hipError_t alloc_all(adc_handle* h)
     // may start at the last dword of a row)
     h->chg_pitch = (((p.W + 7) / 8 + 3) & ~3) + 16;
     const size_t tiles = (size_t)h->chg_pitch * ((p.H + 7) / 8) + 64;
-    HIP_OK(hipMalloc(&h->chg_a, 2 * tiles)); // two planes (round parity)
-    HIP_OK(hipMalloc(&h->irv_cold, 64));
-    HIP_OK(hipMalloc(&h->irv_px, adc_irv_px_words(p.W, p.H) * sizeof(uint32_t)));
+    HIP_TRY(MEM_ONCE(h->chg_a, 2 * tiles)); // two planes (round parity)
+    HIP_TRY(MEM_ONCE(h->irv_cold, 64));
+    HIP_TRY(MEM_ONCE(h->irv_px, adc_irv_px_words(p.W, p.H) * sizeof(uint32_t)));
     HIP_OK(hipMemset(h->irv_px, 0, adc_irv_px_words(p.W, p.H) * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&h->edge, P));
-    HIP_OK(hipHostMalloc(&h->pin_in, P * 6, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc(&h->pin_out, P * 4, hipHostMallocDefault));
+    HIP_TRY(MEM_ONCE(h->edge, P));
+    HIP_TRY(MEM_ONCE_PINNED(h->pin_in, P * 6));
+    HIP_TRY(MEM_ONCE_PINNED(h->pin_out, P * 4));
     // (one block: the 64 flag words, then the mirror of the device's armmax words -- maxima, speculation flags, record densities)
-    HIP_OK(hipHostMalloc(&h->pin_flags, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(MEM_ONCE_PINNED(h->pin_flags, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t)));
     h->pin_nz = h->pin_flags + ADC_PIN_ARM + ADC_NZ_BASE; // record densities (k_make_records)
     memset(h->pin_flags, 0, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t)); // [0] median error, [ADC_PIN_ARM..] mirror of the armmax words (maxima, failed seams, violation flag, record densities), [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
     HIP_OK(hipMemset(h->label, 0, P));
@@ -255,7 +278,7 @@ static hipError_t upload_tables(adc_handle* h)
                     if (dy < 0 || dy >= ms || dx <= -ms || dx >= ms) safe = false; // (the padding of the code map assumes it; always true)
                 }
             if (safe) {
-                HIP_OK(hipMalloc(&h->ray_tab, tab.size() * sizeof(int32_t)));
+                HIP_TRY(MEM_ONCE(h->ray_tab, tab.size() * sizeof(int32_t)));
                 HIP_OK(hipMemcpy(h->ray_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
                 h->ray_tab_rows = ms;
                 h->ray_lin = h->ray_tab + (size_t)ms * 16;
@@ -330,24 +353,7 @@ void adc_destroy(adc_handle* h)
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->heavy) hipStreamSynchronize(h->heavy);
-    void* bufs[] = {h->img_l_own, h->img_r_own, h->gray_l, h->gray_r, h->census_l, h->census_r, h->arms, h->sup_h, h->sup_v,
-                    h->armmax, h->rec_h, h->rec_v, h->rec2_h, h->rec2_v, h->agg_sink, h->so_cls, h->so_seam, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, h->vol_a, h->vol_b, h->lut_ad, h->lut_census,
-                    h->ray_sincos, h->ray_tab, h->bgrx_l, h->cost_rrec, h->cost_lrec, h->med_hand, h->med_sink, h->disp_l, h->disp_r, h->disp_tmp, h->label, h->elig, h->irv_bbox, h->vote_list, h->vote_evals_arr, h->interp_list, h->interp_counters, h->itp_cells, h->st16, h->disp_vote, h->vote_counters,
-                    h->chg_a, h->irv_px, h->irv_cold, h->edge, h->arms_r, h->bgrx_r, h->armmax_r, h->vol_c, h->out_words, h->os_cloud, h->sp_parent, h->sp_map,
-                    h->rect[0].rec, h->rect[0].mx, h->rect[0].my, h->rect[0].valid, h->rect[0].raw, h->rect[1].rec, h->rect[1].mx, h->rect[1].my, h->rect[1].valid, h->rect[1].raw,
-                    h->ev_g[0], h->ev_g[1], h->ev_occ, h->ev_raw, h->ev_rep, h->evs_disp, h->evs_prov, h->evs_conf, h->evs_err, h->evs_cls,
-                    h->reg_zbuf, h->reg_rep, h->regs_map, h->regs_out, h->regs_valid, h->regs_depth, h->regs_index, h->regs_tbgr};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (h->ev_pin) hipHostFree(h->ev_pin);
-    if (h->reg_pin) hipHostFree(h->reg_pin);
-    for (const AdcMapBuf& m : h->map_buf) {
-        if (m.dev) hipFree(m.dev);
-        if (m.pin) hipHostFree(m.pin);
-    }
-    if (h->pin_raw) hipHostFree(h->pin_raw);
-    if (h->pin_in) hipHostFree(h->pin_in);
-    if (h->pin_out) hipHostFree(h->pin_out);
-    if (h->pin_flags) hipHostFree(h->pin_flags);
+    dev_mem_release_all<HipMem>(&h->mem);
     for (int i = 0; i <= ADC_STAGE_COUNT; i++) if (h->ev[i]) hipEventDestroy(h->ev[i]);
     for (int i = 0; i < 9; i++) if (h->ev_agg[i]) hipEventDestroy(h->ev_agg[i]);
     if (h->ev_in) hipEventDestroy(h->ev_in);
@@ -641,6 +647,14 @@ static void abort_match(adc_handle* h)
     if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
     h->bgrx_valid = 0;
 }
+// the failure epilogue of a call outside a Match: adc_last_error gains the entry point's name, the streams are drained; code 2
+static int fail_call(adc_handle* h, const char* who)
+{
+    const std::string keep = std::string(who) + ": " + g_last_error;
+    abort_match(h);
+    g_last_error = keep;
+    return 2;
+}
 
 int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, void* d_disp)
 {
@@ -920,11 +934,7 @@ static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who,
     r.capacity = (uint32_t)(o->cloud_capacity < P ? o->cloud_capacity : P); // (there are at most W * H points)
     r.cloud_count = o->cloud ? o->cloud_count : nullptr;
     r.disp8 = o->disp8;
-    if (!h->out_words && ADC_HIP(hipMalloc(&h->out_words, adc_outputs_scratch_bytes(h->p.W, h->p.H))) != hipSuccess) {
-        h->out_words = nullptr;
-        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
-        return 2;
-    }
+    if (MEM_ONCE(h->out_words, adc_outputs_scratch_bytes(h->p.W, h->p.H)) != hipSuccess) return scratch_failed(who);
     *out = r;
     return 0;
 }
@@ -933,19 +943,14 @@ static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who,
 // block, allocated on first use, and a cloud scratch of the capacity asked for
 static hipError_t host_scratch(adc_handle* h, const AdcHostMap* host, bool cloud, uint32_t capacity)
 {
-    hipError_t e = hipSuccess;
-    for (int i = 0; e == hipSuccess && i < ADC_REQ_MAPS; i++) {
+    for (int i = 0; i < ADC_REQ_MAPS; i++) {
         AdcMapBuf& b = h->map_buf[i];
         if (!host[i].dst) continue;
-        if (!b.dev && (e = ADC_HIP(hipMalloc(&b.dev, host[i].bytes))) != hipSuccess) b.dev = nullptr;
-        else if (host[i].direct == 0 && !b.pin && (e = ADC_HIP(hipHostMalloc(&b.pin, host[i].bytes, hipHostMallocDefault))) != hipSuccess) b.pin = nullptr;
+        HIP_TRY(MEM_ONCE(b.dev, host[i].bytes));
+        if (host[i].direct == 0) HIP_TRY(MEM_ONCE_PINNED(b.pin, host[i].bytes));
     }
-    if (e == hipSuccess && cloud && (!h->os_cloud || h->os_cloud_cap < capacity)) { // (grows with the largest capacity asked for; at least one point)
-        if (h->os_cloud) hipFree(h->os_cloud);
-        h->os_cloud_cap = capacity > 0 ? capacity : 1;
-        if ((e = ADC_HIP(hipMalloc(&h->os_cloud, (size_t)h->os_cloud_cap * sizeof(adc_point)))) != hipSuccess) { h->os_cloud = nullptr; h->os_cloud_cap = 0; }
-    }
-    return e;
+    if (cloud) HIP_TRY(MEM_GROW(h->os_cloud, h->os_cloud_cap, capacity > 0 ? capacity : 1, sizeof(adc_point))); // (at least one point)
+    return hipSuccess;
 }
 
 // Validates a request and resolves it into h->req, whole, for the Match that the caller enqueues next.  device_pointers: the request's
@@ -973,8 +978,7 @@ static int match_req_resolve(adc_handle* h, const adc_products* p, const char* w
         const size_t bytes[ADC_REQ_MAPS] = {P, P * 4, P * 4, P, P * 2};
         for (int i = 0; i < ADC_REQ_MAPS; i++)
             if (target[i]) r.host[i] = AdcHostMap{target[i], bytes[i], host_registered(target[i], bytes[i]) ? 1 : (older ? 2 : 0)};
-        const hipError_t e = host_scratch(h, r.host, p->out.cloud != nullptr, r.out.capacity);
-        if (e != hipSuccess) { set_error((std::string(who) + ": scratch").c_str(), e); (void)hipGetLastError(); return 2; }
+        if (host_scratch(h, r.host, p->out.cloud != nullptr, r.out.capacity) != hipSuccess) return scratch_failed(who);
         for (int i = 0; i < ADC_REQ_MAPS; i++)
             if (target[i]) target[i] = h->map_buf[i].dev;
         r.cloud = p->out.cloud;
@@ -1115,17 +1119,8 @@ static bool speckle_args_ok(float max_diff, const char* who)
 // first use: parent / size / stat words, and (for the Matches) the filtered map
 static int speckle_scratch(adc_handle* h, bool with_map, const char* who)
 {
-    const size_t P = (size_t)h->p.W * h->p.H;
-    if (!h->sp_parent && ADC_HIP(hipMalloc(&h->sp_parent, adc_speckle_scratch_words(h->p.W, h->p.H) * sizeof(int32_t))) != hipSuccess) {
-        h->sp_parent = nullptr;
-        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
-        return 2;
-    }
-    if (with_map && !h->sp_map && ADC_HIP(hipMalloc(&h->sp_map, P * 4)) != hipSuccess) {
-        h->sp_map = nullptr;
-        set_error((std::string(who) + ": scratch").c_str(), hipGetLastError());
-        return 2;
-    }
+    if (MEM_ONCE(h->sp_parent, adc_speckle_scratch_words(h->p.W, h->p.H) * sizeof(int32_t)) != hipSuccess) return scratch_failed(who);
+    if (with_map && MEM_ONCE(h->sp_map, (size_t)h->p.W * h->p.H * 4) != hipSuccess) return scratch_failed(who);
     return 0;
 }
 
@@ -1213,27 +1208,16 @@ static hipError_t rect_buffers(adc_handle* h, int side, const adc_raw_format* f,
     const size_t P = (size_t)h->p.W * h->p.H;
     for (int s = 0; maps && s < 2; s++) { // (conversion only: no records, no maps, no valid map)
         AdcRectSide& r = h->rect[s];
-        if (!r.rec) HIP_OK(hipMalloc(&r.rec, P * 8));
-        if (!r.mx) HIP_OK(hipMalloc(&r.mx, P * 4));
-        if (!r.my) HIP_OK(hipMalloc(&r.my, P * 4));
-        if (!r.valid) HIP_OK(hipMalloc(&r.valid, P));
+        HIP_TRY(MEM_ONCE(r.rec, P * 8));
+        HIP_TRY(MEM_ONCE(r.mx, P * 4));
+        HIP_TRY(MEM_ONCE(r.my, P * 4));
+        HIP_TRY(MEM_ONCE(r.valid, P));
     }
     AdcRectSide& r = h->rect[side];
     const size_t n = raw_bytes(*f);
-    if (r.raw_cap < n) {
-        if (r.raw) hipFree(r.raw);
-        r.raw = nullptr; r.raw_cap = 0;
-        HIP_OK(hipMalloc(&r.raw, n));
-        r.raw_cap = n;
-    }
+    HIP_TRY(MEM_GROW(r.raw, r.raw_cap, n, 1));
     const size_t other = h->rect[side ^ 1].set ? raw_bytes(h->rect[side ^ 1].fmt) : n; // (sized for two raw images)
-    if (h->pin_raw_cap < n + other) {
-        if (h->pin_raw) hipHostFree(h->pin_raw);
-        h->pin_raw = nullptr; h->pin_raw_cap = 0;
-        HIP_OK(hipHostMalloc(&h->pin_raw, n + other, hipHostMallocDefault));
-        h->pin_raw_cap = n + other;
-    }
-    return hipSuccess;
+    return MEM_GROW_PINNED(h->pin_raw, h->pin_raw_cap, n + other, 1);
 }
 
 static hipError_t rect_install(adc_handle* h, int side, const adc_raw_format* f, const float* map_x, const float* map_y, const adc_camera_model* model)
@@ -1257,12 +1241,7 @@ static int rect_set(adc_handle* h, int side, const adc_raw_format* f, const floa
 {
     hipSetDevice(h->device);
     h->rect[side].set = 0; // (a failure below leaves this side unset: its records may be half written)
-    if (rect_install(h, side, f, map_x, map_y, model) != hipSuccess) {
-        const std::string keep = std::string(who) + ": " + g_last_error;
-        abort_match(h); // (drains the stream; no Match was pending)
-        g_last_error = keep;
-        return 2;
-    }
+    if (rect_install(h, side, f, map_x, map_y, model) != hipSuccess) return fail_call(h, who);
     h->rect[side].set = 1;
     return 0;
 }
@@ -1295,12 +1274,7 @@ int adc_set_input_format(adc_handle* h, int side, const adc_raw_format* raw)
     }
     hipSetDevice(h->device);
     h->rect[side].set = 0;
-    if (rect_buffers(h, side, raw, false) != hipSuccess) { // raw buffer and raw staging of the host entry points
-        const std::string keep = "adc_set_input_format: " + g_last_error;
-        abort_match(h);
-        g_last_error = keep;
-        return 2;
-    }
+    if (rect_buffers(h, side, raw, false) != hipSuccess) return fail_call(h, "adc_set_input_format"); // raw buffer and raw staging of the host entry points
     h->rect[side].fmt = *raw;
     h->rect[side].set = 2;
     return 0;
@@ -1372,17 +1346,11 @@ static hipError_t gt_buffers(adc_handle* h, size_t raw_bytes)
         HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
         h->ev_cus = cus > 0 ? cus : 1;
     }
-    for (int s = 0; s < 2; s++) if (!h->ev_g[s]) HIP_OK(hipMalloc(&h->ev_g[s], P * 4));
-    if (!h->ev_occ) HIP_OK(hipMalloc(&h->ev_occ, P));
-    if (!h->ev_rep) HIP_OK(hipMalloc(&h->ev_rep, adc_eval_report_words() * sizeof(uint64_t)));
-    if (!h->ev_pin) HIP_OK(hipHostMalloc(&h->ev_pin, adc_eval_report_words() * sizeof(uint64_t), hipHostMallocDefault));
-    if (h->ev_raw_cap < raw_bytes) {
-        if (h->ev_raw) hipFree(h->ev_raw);
-        h->ev_raw = nullptr; h->ev_raw_cap = 0;
-        HIP_OK(hipMalloc(&h->ev_raw, raw_bytes));
-        h->ev_raw_cap = raw_bytes;
-    }
-    return hipSuccess;
+    for (int s = 0; s < 2; s++) HIP_TRY(MEM_ONCE(h->ev_g[s], P * 4));
+    HIP_TRY(MEM_ONCE(h->ev_occ, P));
+    HIP_TRY(MEM_ONCE(h->ev_rep, adc_eval_report_words() * sizeof(uint64_t)));
+    HIP_TRY(MEM_ONCE_PINNED(h->ev_pin, adc_eval_report_words() * sizeof(uint64_t)));
+    return MEM_GROW(h->ev_raw, h->ev_raw_cap, raw_bytes, 1);
 }
 
 static hipError_t gt_install(adc_handle* h, const adc_gt* left, int pitch_l, const adc_gt* right, int pitch_r, const uint8_t* nonocc, float occ_thres)
@@ -1428,12 +1396,7 @@ int adc_set_ground_truth(adc_handle* h, const adc_gt* left, const adc_gt* right,
     if (why) { g_last_error = std::string("adc_set_ground_truth: ") + why; return 1; }
     hipSetDevice(h->device);
     h->ev_set = 0; // (a failure below leaves ground truth unset: the maps may be half written)
-    if (gt_install(h, left, pitch_l, right, pitch_r, nonocc, occ_thres) != hipSuccess) {
-        const std::string keep = "adc_set_ground_truth: " + g_last_error;
-        abort_match(h); // (drains the stream; no Match was pending)
-        g_last_error = keep;
-        return 2;
-    }
+    if (gt_install(h, left, pitch_l, right, pitch_r, nonocc, occ_thres) != hipSuccess) return fail_call(h, "adc_set_ground_truth");
     h->ev_has_right = right ? 1 : 0;
     h->ev_has_mask = (!right && nonocc) ? 1 : 0;
     h->ev_occ_thres = occ_thres;
@@ -1488,12 +1451,8 @@ static int evaluate_device_impl(adc_handle* h, const void* d_disp, const void* d
 {
     hipSetDevice(h->device);
     if (enqueue_evaluation(h, static_cast<const float*>(d_disp), static_cast<const uint8_t*>(d_prov), static_cast<const float*>(d_conf), t,
-                           static_cast<float*>(d_err), static_cast<uint8_t*>(d_class)) != hipSuccess) {
-        const std::string keep = std::string(who) + ": " + g_last_error;
-        abort_match(h);
-        g_last_error = keep;
-        return 2;
-    }
+                           static_cast<float*>(d_err), static_cast<uint8_t*>(d_class)) != hipSuccess)
+        return fail_call(h, who);
     memset(&h->ev_echo, 0, sizeof(h->ev_echo));
     for (int k = 0; k < n; k++) h->ev_echo.thresholds[k] = t[k];
     h->ev_echo.n_thresholds = n;
@@ -1523,13 +1482,12 @@ int adc_evaluate(adc_handle* h, const float* disp, const uint8_t* provenance, co
     if (eval_check(h, disp, provenance, confidence, params, t, &n, "adc_evaluate") != 0) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
-    hipError_t e = hipSuccess;
-    if (!h->evs_disp && (e = ADC_HIP(hipMalloc(&h->evs_disp, P * 4))) != hipSuccess) h->evs_disp = nullptr;
-    if (e == hipSuccess && provenance && !h->evs_prov && (e = ADC_HIP(hipMalloc(&h->evs_prov, P))) != hipSuccess) h->evs_prov = nullptr;
-    if (e == hipSuccess && confidence && !h->evs_conf && (e = ADC_HIP(hipMalloc(&h->evs_conf, P * 4))) != hipSuccess) h->evs_conf = nullptr;
-    if (e == hipSuccess && err && !h->evs_err && (e = ADC_HIP(hipMalloc(&h->evs_err, P * 4))) != hipSuccess) h->evs_err = nullptr;
-    if (e == hipSuccess && eval_class && !h->evs_cls && (e = ADC_HIP(hipMalloc(&h->evs_cls, P))) != hipSuccess) h->evs_cls = nullptr;
-    if (e != hipSuccess) { set_error("adc_evaluate: scratch", e); (void)hipGetLastError(); return 2; }
+    hipError_t e = MEM_ONCE(h->evs_disp, P * 4);
+    if (e == hipSuccess && provenance) e = MEM_ONCE(h->evs_prov, P);
+    if (e == hipSuccess && confidence) e = MEM_ONCE(h->evs_conf, P * 4);
+    if (e == hipSuccess && err) e = MEM_ONCE(h->evs_err, P * 4);
+    if (e == hipSuccess && eval_class) e = MEM_ONCE(h->evs_cls, P);
+    if (e != hipSuccess) return scratch_failed("adc_evaluate");
     e = ADC_HIP(hipMemcpy(h->evs_disp, disp, P * 4, hipMemcpyHostToDevice));
     if (e == hipSuccess && provenance) e = ADC_HIP(hipMemcpy(h->evs_prov, provenance, P, hipMemcpyHostToDevice));
     if (e == hipSuccess && confidence) e = ADC_HIP(hipMemcpy(h->evs_conf, confidence, P * 4, hipMemcpyHostToDevice));
@@ -1565,16 +1523,6 @@ static const char* reg_target_why(const adc_reg_target* t)
     return nullptr;
 }
 
-static hipError_t reg_grow(void** buf, size_t* cap, size_t need, size_t elem)
-{
-    if (*cap >= need) return hipSuccess;
-    if (*buf) hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    HIP_OK(hipMalloc(buf, need * elem));
-    *cap = need;
-    return hipSuccess;
-}
-
 static hipError_t reg_buffers(adc_handle* h, size_t Pt)
 {
     if (!h->reg_cus) {
@@ -1582,9 +1530,9 @@ static hipError_t reg_buffers(adc_handle* h, size_t Pt)
         HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
         h->reg_cus = cus > 0 ? cus : 1;
     }
-    if (!h->reg_rep) HIP_OK(hipMalloc(&h->reg_rep, sizeof(adc_reg_report)));
-    if (!h->reg_pin) HIP_OK(hipHostMalloc(&h->reg_pin, sizeof(adc_reg_report), hipHostMallocDefault));
-    return reg_grow(reinterpret_cast<void**>(&h->reg_zbuf), &h->reg_zbuf_cap, Pt, sizeof(uint64_t));
+    HIP_TRY(MEM_ONCE(h->reg_rep, sizeof(adc_reg_report)));
+    HIP_TRY(MEM_ONCE_PINNED(h->reg_pin, sizeof(adc_reg_report)));
+    return MEM_GROW(h->reg_zbuf, h->reg_zbuf_cap, Pt, sizeof(uint64_t));
 }
 
 int adc_set_register_target(adc_handle* h, const adc_reg_target* target)
@@ -1600,12 +1548,7 @@ int adc_set_register_target(adc_handle* h, const adc_reg_target* target)
     if (e != hipSuccess) set_error("hipStreamSynchronize(h->stream)", e);
     h->reg_set = 0; // (a failure below leaves the target unset)
     if (e == hipSuccess) e = reg_buffers(h, (size_t)target->width * (size_t)target->height);
-    if (e != hipSuccess) {
-        const std::string keep = "adc_set_register_target: " + g_last_error;
-        abort_match(h); // (drains the stream; no Match was pending)
-        g_last_error = keep;
-        return 2;
-    }
+    if (e != hipSuccess) return fail_call(h, "adc_set_register_target");
     h->reg_target = *target;
     h->reg_set = 1;
     return 0;
@@ -1656,21 +1599,13 @@ static hipError_t enqueue_registration(adc_handle* h, const float* map, int kind
     return hipSuccess;
 }
 
-static int reg_failed(adc_handle* h, const char* who)
-{
-    const std::string keep = std::string(who) + ": " + g_last_error;
-    abort_match(h);
-    g_last_error = keep;
-    return 2;
-}
-
 int adc_register_depth_device(adc_handle* h, const void* d_map, int input_kind, const adc_calib* calib, uint32_t flags, void* d_depth, void* d_index)
 {
     const char* who = "adc_register_depth_device";
     if (reg_check(h, d_map, input_kind, calib, reg_request_why(flags, d_depth || d_index), who) != 0) return 1;
     hipSetDevice(h->device);
     if (enqueue_registration(h, static_cast<const float*>(d_map), input_kind, calib, flags, static_cast<float*>(d_depth), static_cast<int32_t*>(d_index)) != hipSuccess)
-        return reg_failed(h, who);
+        return fail_call(h, who);
     h->reg_pending = 1;
     return 0;
 }
@@ -1682,7 +1617,7 @@ int adc_align_color_device(adc_handle* h, const void* d_map, int input_kind, con
     hipSetDevice(h->device);
     const hipError_t e = ADC_HIP(adc_launch_reg_align(h, static_cast<const float*>(d_map), input_kind, calib, static_cast<const uint8_t*>(d_target_bgr),
                                                       static_cast<uint8_t*>(d_bgr_out), static_cast<uint8_t*>(d_valid)));
-    if (e != hipSuccess) { set_error("adc_launch_reg_align", e); return reg_failed(h, who); }
+    if (e != hipSuccess) { set_error("adc_launch_reg_align", e); return fail_call(h, who); }
     return 0;
 }
 
@@ -1692,12 +1627,10 @@ int adc_register_depth(adc_handle* h, const float* map, int input_kind, const ad
     if (reg_check(h, map, input_kind, calib, reg_request_why(flags, depth || index), who) != 0) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H, Pt = (size_t)h->reg_target.width * (size_t)h->reg_target.height;
-    hipError_t e = hipSuccess;
-    if (!h->regs_map && (e = ADC_HIP(hipMalloc(&h->regs_map, P * 4))) != hipSuccess) h->regs_map = nullptr;
-    if (e != hipSuccess) set_error("hipMalloc(&h->regs_map)", e);
-    if (e == hipSuccess && depth) e = reg_grow(reinterpret_cast<void**>(&h->regs_depth), &h->regs_depth_cap, Pt, 4);
-    if (e == hipSuccess && index) e = reg_grow(reinterpret_cast<void**>(&h->regs_index), &h->regs_index_cap, Pt, 4);
-    if (e != hipSuccess) { g_last_error = std::string(who) + ": scratch: " + g_last_error; (void)hipGetLastError(); return 2; }
+    hipError_t e = MEM_ONCE(h->regs_map, P * 4);
+    if (e == hipSuccess && depth) e = MEM_GROW(h->regs_depth, h->regs_depth_cap, Pt, 4);
+    if (e == hipSuccess && index) e = MEM_GROW(h->regs_index, h->regs_index_cap, Pt, 4);
+    if (e != hipSuccess) return scratch_failed(who);
     if ((e = ADC_HIP(hipMemcpy(h->regs_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_register_depth: upload", e); (void)hipGetLastError(); return 2; }
     int rc = adc_register_depth_device(h, h->regs_map, input_kind, calib, flags, depth ? h->regs_depth : nullptr, index ? h->regs_index : nullptr);
     if (rc == 0) rc = adc_wait(h);
@@ -1714,13 +1647,11 @@ int adc_align_color(adc_handle* h, const float* map, int input_kind, const adc_c
     if (reg_check(h, map, input_kind, calib, !target_bgr ? "null target image" : (!bgr_out ? "no output requested" : nullptr), who) != 0) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H, Pt = (size_t)h->reg_target.width * (size_t)h->reg_target.height;
-    hipError_t e = hipSuccess;
-    if (!h->regs_map && (e = ADC_HIP(hipMalloc(&h->regs_map, P * 4))) != hipSuccess) h->regs_map = nullptr;
-    if (e == hipSuccess && !h->regs_out && (e = ADC_HIP(hipMalloc(&h->regs_out, P * 3))) != hipSuccess) h->regs_out = nullptr;
-    if (e == hipSuccess && valid && !h->regs_valid && (e = ADC_HIP(hipMalloc(&h->regs_valid, P))) != hipSuccess) h->regs_valid = nullptr;
-    if (e != hipSuccess) set_error("hipMalloc", e);
-    if (e == hipSuccess) e = reg_grow(reinterpret_cast<void**>(&h->regs_tbgr), &h->regs_tbgr_cap, Pt, 3);
-    if (e != hipSuccess) { g_last_error = std::string(who) + ": scratch: " + g_last_error; (void)hipGetLastError(); return 2; }
+    hipError_t e = MEM_ONCE(h->regs_map, P * 4);
+    if (e == hipSuccess) e = MEM_ONCE(h->regs_out, P * 3);
+    if (e == hipSuccess && valid) e = MEM_ONCE(h->regs_valid, P);
+    if (e == hipSuccess) e = MEM_GROW(h->regs_tbgr, h->regs_tbgr_cap, Pt, 3);
+    if (e != hipSuccess) return scratch_failed(who);
     e = ADC_HIP(hipMemcpy(h->regs_map, map, P * 4, hipMemcpyHostToDevice));
     if (e == hipSuccess) e = ADC_HIP(hipMemcpy(h->regs_tbgr, target_bgr, Pt * 3, hipMemcpyHostToDevice));
     if (e != hipSuccess) { set_error("adc_align_color: upload", e); (void)hipGetLastError(); return 2; }
@@ -1911,19 +1842,15 @@ int adc_set_paper_modes(adc_handle* h, uint32_t modes)
     const size_t P = (size_t)h->p.W * h->p.H;
     if ((modes & ADC_PAPER_RIGHT_ARMS) && !(h->arms_r && h->bgrx_r && h->armmax_r)) {
         // all three or none: a partial set left behind by a failed call must not pass for "allocated" in the next one
-        if ((!h->arms_r && hipMalloc(&h->arms_r, P * 4) != hipSuccess) || (!h->bgrx_r && hipMalloc(&h->bgrx_r, P * 4) != hipSuccess) ||
-            (!h->armmax_r && hipMalloc(&h->armmax_r, 4 * sizeof(int)) != hipSuccess)) {
-            if (h->arms_r) hipFree(h->arms_r);
-            if (h->bgrx_r) hipFree(h->bgrx_r);
-            if (h->armmax_r) hipFree(h->armmax_r);
-            h->arms_r = nullptr; h->bgrx_r = nullptr; h->armmax_r = nullptr;
-            g_last_error = "adc_set_paper_modes: allocation failed";
+        if (MEM_ONCE(h->arms_r, P * 4) != hipSuccess || MEM_ONCE(h->bgrx_r, P * 4) != hipSuccess || MEM_ONCE(h->armmax_r, 4 * sizeof(int)) != hipSuccess) {
+            dev_mem_release<HipMem>(&h->mem, &h->arms_r);
+            dev_mem_release<HipMem>(&h->mem, &h->bgrx_r);
+            dev_mem_release<HipMem>(&h->mem, &h->armmax_r);
+            g_last_error = "adc_set_paper_modes: allocation failed: " + g_last_error;
             return 2;
         }
     }
-    if ((modes & ADC_PAPER_SO_SUM) && !h->vol_c) {
-        if (hipMalloc(&h->vol_c, P * h->p.Dp * sizeof(float)) != hipSuccess) { g_last_error = "adc_set_paper_modes: allocation failed"; return 2; }
-    }
+    if ((modes & ADC_PAPER_SO_SUM) && MEM_ONCE(h->vol_c, P * h->p.Dp * sizeof(float)) != hipSuccess) { g_last_error = "adc_set_paper_modes: allocation failed: " + g_last_error; return 2; }
     h->paper = modes;
     return 0;
 }
