@@ -1,4 +1,5 @@
-// adc_internal.h -- private state of an adc_handle and the kernel-launch entry points.
+// adc_internal.h -- private state of an adc_handle and the kernel-launch entry points.  Which kind of state lives where (parameters,
+// resources, set-call configuration, learned, in flight, observations of the last run): DESIGN.md, "Kinds of handle state".
 //
 // Memory.  Every device and pinned buffer of a handle is one of the pointer fields below, allocated through dev_mem.h, the only owner:
 // capi.hip calls it (no k_*.hip file allocates or frees handle state), the handle's registry `mem` knows which fields own memory, and
@@ -26,9 +27,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "../../include/adcensus_c_api.h"
 #include "learn_plan.h"
+#include "agg_plan.h" // AggArms
 #include "dev_mem.h"
 
 #define ADC_WAVE 64
@@ -114,6 +117,22 @@ struct AdcMapBuf {
     void* dev;         // device scratch the kernels write
     void* pin;         // pinned staging of the asynchronous delivery (none while no destination needed it)
 };
+// Everything IN FLIGHT on a handle: what the next adc_wait has to settle, or the next stage of the same Match consumes.  All zero =
+// idle: a successful adc_wait leaves every byte zero, a failed call gets there by the ONE reset of abort_match (a memset of the struct:
+// a member added here cannot be forgotten on the failure path).  Each member is written by whom its comment names first and
+// consumed (put back to 0) by whom it names behind "->".
+struct AdcInFlight {
+    int match_pending;    // run_heavy: a Match was enqueued -> adc_wait, once it has looked at its arm maxima / speculation flags
+    int irv_pending;      // adc_run_region_voting: a chain was enqueued -> adc_voting_finish (adc_wait), which looks at its final state
+    int so_agg_fused;     // adc_launch_aggregate left its last pass to the scanline stage: vol_a holds the volume BEFORE that pass -> run_so
+    int wta_left_done;    // run_so: the last scanline pass also wrote the left-view map -> adc_launch_wta, which then only runs the right view
+    bool timings_pending; // run_pipeline: profiling marks were recorded -> collect_timings (adc_wait)
+    int force_median_fallback; // test hook (adc_debug_run ADC_RUN_MEDIAN 100 / 101): the next adc_wait takes the fallback path -> adc_wait
+    int ev_pending;       // adc_evaluate_device: an evaluation was enqueued -> adc_wait moves ev_pin and ev_echo into ev_report
+    int reg_pending;      // adc_register_depth_device: a registration was enqueued -> adc_wait moves reg_pin into reg_report
+    AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
+};
+static_assert(std::is_trivially_copyable<AdcInFlight>::value, "AdcInFlight is reset with memset");
 
 // One side of the optional rectification (k_rectify.hip): the declared geometry of the raw images, and what the set call made of
 // the maps.  The [H][W] buffers are allocated by the first set call of a handle (both sides at once), the raw buffer grows with the
@@ -147,6 +166,7 @@ struct adc_handle {
     // images + per-pixel maps
     uint8_t *img_l, *img_r;         // the pair being matched: the handle's own buffers, or the caller's (adc_match_device)
     uint8_t *img_l_own, *img_r_own;
+    int bgrx_valid;                 // cache tag of the pair: bgrx_l holds its packed left image (written by the arms stage); capi.hip: images_own
     uint8_t *gray_l, *gray_r;
     uint64_t *census_l, *census_r;
     uint8_t* arms;
@@ -163,21 +183,11 @@ struct adc_handle {
     // file that assigns a member of `learned`, but for adc_create and the two budget hooks of adc_debug_run)
     AdcLearned learned;
     AdcLearnStats lstats;
-    // Per-Match flags: what the Match in flight (or the stage run last) did, read by the stages behind it and by adc_wait, which
-    // builds its AdcMatchReport from them and pin_flags; abort_match puts them back to idle
-    int match_pending;    // a Match was enqueued and adc_wait has not yet looked at its arm maxima / speculation flags
-    int in_redo;          // adc_wait is redoing a Match (no sparse launches there)
-    int armmax_valid;     // AggArms of the aggregation being enqueued: 0 unknown (debug surface: two launches per pass, the kernels
-                          // decide), 1 exact (read back), 2 assumed from the previous Match (the small-ring kernels verify on the device
-                          // and raise armmax[3]; adc_wait then redoes the Match), 3 unknown in the pipeline: full ring (always valid)
-    int irv_pending;      // a voting chain was enqueued and its final state has not been looked at yet
+    AdcInFlight fly;      // what is in flight; all zero = idle.  Below: what the stage run last did (adc_wait's AdcMatchReport, with pin_flags)
     int irv_chain;        // kernels of the chain enqueued so far (continuation starts here)
     int so_nseg_last;     // segments per row of the last scanline run (1 = whole rows)
     int med_spec_last;    // the last banded median launch used speculative bands
     int med_seg_last;     // ... and this many column segments per band link
-    int so_agg_fused;     // adc_launch_aggregate left its last pass to the scanline stage: vol_a holds the volume BEFORE that pass
-    int fuse_wta;         // set by the pipeline: the last scanline pass also writes the left-view disparity map
-    int wta_left_done;    // the scanline stage did so: adc_launch_wta only runs the right view
     // volumes
     float *vol_a, *vol_b;
     // host-built tables: same libm as the CPU reference
@@ -198,7 +208,6 @@ struct adc_handle {
     int ray_tab_rows;
     int32_t* ray_lin;     // [max_search + ADC_ITP_LPAD][16] linear ray offsets dy * itp_pitch + dx into the padded code map (same allocation as ray_tab)
     int itp_pitch, itp_ms; // row pitch of the code map and the search range it is padded for (adc_device_fn.h); pitch 0: no table walk on this handle (itp_plan.h)
-    int itp_force_f64;     // debug surface: the next interpolation takes the f64 walk (adc_debug_run ADC_RUN_INTERPOLATION, arg 1)
     uint32_t* cost_rrec;  // [H][rrec_pitch] uint4 {bgrx, census lo, census hi, 0} of the RIGHT image, padded with out-of-image
                           // markers (bgrx = ~0) on both sides; cost_lrec [H][W] the same for the LEFT image (fused cost, k_aggregate.hip)
     uint32_t* cost_lrec;
@@ -220,9 +229,7 @@ struct adc_handle {
     float* med_hand;      // banded median: per-band hand-off rows [bands][med_hpitch], indexed by wavefront level
     int med_hpitch;
     float* med_sink;      // banded median: 16-byte store sink per lane of every wave (bands + speculative copies)
-    int force_median_fallback; // test hook (ADC_DEBUG_FORCE_MEDIAN_FALLBACK via adc_debug_run): adc_wait takes the fallback path
     int32_t* pin_flags;   // pinned host word: error flag of the banded median's hand-off (read back after every Match)
-    int bgrx_valid;       // bgrx_l holds the packed left image of the current pair (written by the arms stage)
     uint32_t* bgrx_l;     // left image packed B | G<<8 | R<<16 per pixel (interpolation gathers)
     uint16_t* st16;      // region voting: 16-bit state map [H][st16_pitch] {bin:11 | iteration of the fill:3 | list:2} (irv_plan.h)
     int st16_pitch;      // row pitch of st16 in elements (multiple of 8: rows start 16-byte aligned)
@@ -244,7 +251,6 @@ struct adc_handle {
     // pinned staging for adc_match / adc_match_async
     uint8_t* pin_in;  // 2 * 3*W*H
     float* pin_out;   // W*H
-    AdcMatchReq req;      // what the Match in flight was asked for
     AdcMapBuf map_buf[ADC_REQ_MAPS]; // scratch and staging of the host callers' map products
     uint32_t* out_words;  // device scratch of k_outputs.hip (min / max words, count, tile counts), allocated on first use
     void* os_cloud;       // device scratch of the host callers' cloud; grows with the largest capacity asked for
@@ -269,7 +275,6 @@ struct adc_handle {
     size_t ev_raw_cap;
     uint64_t* ev_rep;         // the report words the measure kernel adds to (adc_eval_report without its echo)
     uint64_t* ev_pin;         // pinned: read-back of the report words, enqueued behind the kernel
-    int ev_pending;           // an evaluation was enqueued; adc_wait moves ev_pin and ev_echo into ev_report
     adc_eval_report ev_echo;  // the echo fields of the evaluation enqueued last
     adc_eval_report ev_report; // adc_get_eval_report
     int ev_report_valid;
@@ -286,7 +291,6 @@ struct adc_handle {
     size_t reg_zbuf_cap;      // target pixels reg_zbuf holds
     uint32_t* reg_rep;        // the report words the kernels add to (adc_reg_report)
     uint32_t* reg_pin;        // pinned: read-back of the report words, enqueued behind the kernels
-    int reg_pending;          // a registration was enqueued; adc_wait moves reg_pin into reg_report
     adc_reg_report reg_report; // adc_get_register_report
     int reg_report_valid;
     float* regs_map;          // device scratch of adc_register_depth / adc_align_color (host callers), each allocated on the first call
@@ -313,7 +317,6 @@ struct adc_handle {
     uint32_t* bgrx_r;
     int* armmax_r;
     float* vol_c;         // third volume: accumulator of the averaged scanline paths (ADC_PAPER_SO_SUM)
-    bool timings_pending;
     // region voting statistics of the last run
     int64_t vote_rounds, vote_evals;
 };
@@ -338,11 +341,12 @@ hipError_t adc_launch_arms_rest(adc_handle* h); // what reads both images: colou
 hipError_t adc_launch_aggregate_tail(adc_handle* h); // the dividing H pass adc_launch_aggregate left to the scanline stage, as a launch of its own
 hipError_t adc_launch_records(adc_handle* h); // arms + counts -> packed aggregation records
 // vol_a -> vol_a via vol_b; fuse_cost: the first pass computes the matching cost itself, fuse_agg_so: the last pass may move into the
-// first scanline pass (short-arm plan).  What it launches is planned by agg_plan.h from the handle's arm / density state, which it only reads.
-hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, bool fuse_agg_so);
+// first scanline pass (short-arm plan); arms: what the caller knows about this image's arm maxima, redo: adc_wait is redoing the Match
+// (no sparse launches).  What it launches is planned by agg_plan.h from these and the handle's learned arm / density state, which it only reads.
+hipError_t adc_launch_aggregate(adc_handle* h, int iterations, AggArms arms, bool redo, bool fuse_cost, bool fuse_agg_so);
 hipError_t adc_launch_so_classes(adc_handle* h, hipStream_t stream);
 size_t adc_so_cls_bytes(int W, int H);
-hipError_t adc_launch_scanline(adc_handle* h, int passes);      // vol_a -> vol_a via vol_b (passes=4)
+hipError_t adc_launch_scanline(adc_handle* h, int passes, bool fuse_wta); // vol_a -> vol_a via vol_b (passes=4); fuse_wta: the last pass also writes disp_l
 int adc_so_segments(const adc_handle* h, int* warm_out);        // verified segments per row of the next scanline run
 bool adc_so_can_fuse_agg(const adc_handle* h);                  // the next scanline run can take over the last aggregation pass
 size_t adc_so_seam_bytes(int W, int H, int Dp);
@@ -387,7 +391,7 @@ size_t adc_irv_px_words(int W, int H);          // dwords of the per-pixel chang
 size_t adc_irv_list_entries(int W, int H, int D, int grid);     // capacity of the voting work list (one segment per workgroup)
 hipError_t adc_run_region_voting(adc_handle* h); // enqueue only (device-driven chain with a launch budget)
 hipError_t adc_voting_finish(adc_handle* h, int* continued); // after a sync: continue the chain if the budget was too small
-hipError_t adc_launch_interpolation(adc_handle* h);
+hipError_t adc_launch_interpolation(adc_handle* h, bool force_f64); // force_f64 (debug surface): the f64 walk also where the table walk would run
 hipError_t adc_launch_discontinuity(adc_handle* h);
 hipError_t adc_launch_median(adc_handle* h);
 hipError_t adc_median_fallback(adc_handle* h); // after a hand-off time-out of the banded filter (adc_wait)

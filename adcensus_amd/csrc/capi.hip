@@ -26,6 +26,12 @@ extern "C" long adc_test_hip_calls(void) { return g_fi_calls.load(); }
 static std::atomic<long> g_fi_live{0};
 extern "C" long adc_test_live_buffers(void) { return g_fi_live.load(); } // allocations of HipMem not yet freed, all handles of the process
 #define ADC_LIVE(d) (g_fi_live += (d))
+extern "C" int adc_test_inflight(adc_handle* h) // 0 = idle; bit 0: some byte of h->fly is nonzero, bit 1: the image pointers are borrowed
+{
+    int r = (h->img_l != h->img_l_own || h->img_r != h->img_r_own) ? 2 : 0;
+    for (size_t i = 0; i < sizeof(h->fly); i++) r |= reinterpret_cast<const unsigned char*>(&h->fly)[i] ? 1 : 0;
+    return r;
+}
 #else
 #define ADC_LIVE(d) ((void)0)
 #endif
@@ -367,8 +373,8 @@ void adc_destroy(adc_handle* h)
 static hipError_t run_refine_tail(adc_handle* h)
 {
     const adc_option& o = h->p.opt;
-    if (h->req.prov || h->req.conf) HIP_OK(adc_launch_provenance(h)); // (reads the voted map before interpolation fills it)
-    if (o.do_filling && o.do_lr_check) HIP_OK(adc_launch_interpolation(h));
+    if (h->fly.req.prov || h->fly.req.conf) HIP_OK(adc_launch_provenance(h)); // (reads the voted map before interpolation fills it)
+    if (o.do_filling && o.do_lr_check) HIP_OK(adc_launch_interpolation(h, false));
     if (o.do_discontinuity_adjustment) HIP_OK(adc_launch_discontinuity(h));
     HIP_OK(adc_launch_median(h));
     return hipSuccess;
@@ -381,7 +387,7 @@ static hipError_t run_refine(adc_handle* h)
     const size_t P = (size_t)h->p.W * h->p.H;
     if (o.do_lr_check) HIP_OK(adc_launch_lrcheck(h));
     else HIP_OK(hipMemsetAsync(h->label, 0, P, h->stream));
-    h->irv_pending = 0;
+    h->fly.irv_pending = 0;
     if (o.do_filling && o.do_lr_check) HIP_OK(adc_run_region_voting(h));
     h->tail_disp_l = h->disp_l;
     h->tail_disp_tmp = h->disp_tmp;
@@ -404,11 +410,13 @@ static bool heavy_exclusive()
     return v;
 }
 
-// from_aggregation: a redo by adc_wait that keeps what the stages in front of the aggregation produced (gray / census, the pixel
+// redo (of adc_wait) == ADC_REDO_FROM_AGGREGATION: a redo that keeps what the stages in front of the aggregation produced (gray / census, the pixel
 // records of the fused cost, arms, support counts, aggregation records: none of them is touched by the later stages) and
 // restarts at the first aggregation pass -- possible whenever that pass computes the matching cost itself (no input volume).
-static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
+static hipError_t run_heavy(adc_handle* h, AdcRedo redo)
 {
+    const bool from_aggregation = redo == ADC_REDO_FROM_AGGREGATION;
+    AggArms arms = AGG_ARMS_FULL; // (a redo from the aggregation: valid for every image)
     const bool prof = h->profiling == 1; // (level 2: only the marks around the aggregation launches, k_aggregate.hip)
 #define MARK(i, s) do { if (prof) HIP_OK(hipEventRecord(h->ev[i], s)); } while (0)
     if (h->heavy != h->stream) {
@@ -418,12 +426,11 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     MARK(0, h->heavy);
     static const bool fuse_cost = [] { const char* e = getenv("ADC_FUSE_COST"); return e ? atoi(e) != 0 : true; }();
     const bool fuse_cost_now = fuse_cost && !(h->paper & ADC_PAPER_RIGHT_ARMS); // (paper mode: plain kernels on a stored cost volume)
-    h->match_pending = 1; // (adc_wait looks at this Match's arm maxima / speculation flags exactly once)
+    h->fly.match_pending = 1; // (adc_wait looks at this Match's arm maxima / speculation flags exactly once)
     if (from_aggregation) {
         MARK(1, h->heavy);
         MARK(2, h->heavy);
         HIP_OK(hipMemsetAsync(h->armmax + 2, 0, 2 * sizeof(int), h->heavy)); // failed seams, "assumed ring too shallow" flag
-        h->armmax_valid = LEARN_ARMS_FULL; // valid for every image
     } else {
     HIP_OK(adc_launch_gray_census(h));           // ComputeCost, ADCensusStereo.cpp:84
     // ADC_FUSE_COST (default on): the cost volume is never written -- the first aggregation pass computes each cost
@@ -444,29 +451,26 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
             HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_ARM, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost, h->heavy));
             HIP_OK(hipStreamSynchronize(h->heavy));
             learn_take_arms(&h->learned, h->pin_flags + ADC_PIN_ARM);
-            h->armmax_valid = 1;
+            arms = AGG_ARMS_EXACT;
         } else {
-            h->armmax_valid = learn_arm_assumption(h->learned);
+            arms = (AggArms)learn_arm_assumption(h->learned);
         }
     }
     HIP_OK(adc_launch_records(h));
     } // (!from_aggregation)
     {   // aggregator_.Aggregate(4), :164; the last pass may move into the scanline stage (the launcher decides: short-arm plan, arms <= 4, segmented row passes)
-        const hipError_t e_ = adc_launch_aggregate(h, 4, fuse_cost_now, true);
-        h->armmax_valid = 0;
-        HIP_OK(e_);
+        const hipError_t e_ = adc_launch_aggregate(h, 4, arms, redo != ADC_REDO_NONE, fuse_cost_now, true);
+        HIP_OK(e_); // (hooked behind the launcher, like the scanline stage: an injected failure finds the stage enqueued)
     }
     MARK(3, h->heavy);
     static const bool fuse_wta = [] { const char* e = getenv("ADC_FUSE_WTA"); return e ? atoi(e) != 0 : true; }();
-    h->fuse_wta = fuse_wta ? 1 : 0;
-    {
-        const hipError_t e_ = adc_launch_scanline(h, 4); // ScanlineOptimize, :100 (+ left-view ComputeDisparity, :108)
-        h->fuse_wta = 0;
+    {   // ScanlineOptimize, :100 (+ left-view ComputeDisparity, :108)
+        const hipError_t e_ = adc_launch_scanline(h, 4, fuse_wta);
         HIP_OK(e_);
     }
     MARK(4, h->heavy);
     HIP_OK(adc_launch_wta(h));                   // ComputeDisparity + ComputeDisparityRight, :108-109
-    if (h->req.conf) HIP_OK(adc_launch_confidence(h)); // (one more read of the optimised volume)
+    if (h->fly.req.conf) HIP_OK(adc_launch_confidence(h)); // (one more read of the optimised volume)
     MARK(5, h->heavy);
     // maxima + violation flag of this pair, looked at by adc_wait (they seed the next Match's assumption)
     // ... together with its record densities, which seed the next Match's choice between dense and sparse small-ring launches
@@ -478,26 +482,26 @@ static hipError_t run_heavy(adc_handle* h, bool from_aggregation = false)
     return hipSuccess;
 }
 
-static hipError_t run_pipeline(adc_handle* h, bool from_aggregation = false)
+static hipError_t run_pipeline(adc_handle* h, AdcRedo redo = ADC_REDO_NONE)
 {
     if (heavy_exclusive()) {
         // the uploads of this pair (already queued on the object's stream) run before the lock is taken
         std::lock_guard<std::mutex> lk(heavy_lock(h->device));
-        HIP_OK(run_heavy(h, from_aggregation));
+        HIP_OK(run_heavy(h, redo));
         HIP_OK(hipEventSynchronize(h->ev_heavy_done)); // hold the lane until the streaming phase has drained
     } else {
-        HIP_OK(run_heavy(h, from_aggregation));
+        HIP_OK(run_heavy(h, redo));
     }
     HIP_OK(run_refine(h));                       // MultiStepRefine, :117 (object stream)
     if (h->profiling == 1) HIP_OK(hipEventRecord(h->ev[6], h->stream));
-    h->timings_pending = h->profiling != 0;
+    h->fly.timings_pending = h->profiling != 0;
     return hipSuccess;
 }
 
 static void collect_timings(adc_handle* h)
 {
-    if (!h->timings_pending) return;
-    h->timings_pending = false;
+    if (!h->fly.timings_pending) return;
+    h->fly.timings_pending = false;
     for (int i = 0; i < ADC_STAGE_COUNT; i++) {
         float ms = 0.f;
         if (h->profiling != 1 || hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]) != hipSuccess) ms = -1.f; // (level 2: no stage marks were recorded)
@@ -520,11 +524,11 @@ static void collect_timings(adc_handle* h)
     }
 }
 
-// depth / point cloud / 8-bit image of h->req.out from a device-resident map (k_outputs.hip), on the object stream; only what was
+// depth / point cloud / 8-bit image of h->fly.req.out from a device-resident map (k_outputs.hip), on the object stream; only what was
 // asked for is launched
 static hipError_t enqueue_outputs(adc_handle* h, const float* disp, const uint8_t* img)
 {
-    const AdcOutReq& r = h->req.out;
+    const AdcOutReq& r = h->fly.req.out;
     if (r.disp8) HIP_OK(hipMemsetAsync(h->out_words, 0, 2 * sizeof(uint32_t), h->stream)); // (the min / max words)
     HIP_OK(adc_launch_out_measure(h, disp, img));
     if (r.cloud) {
@@ -558,7 +562,7 @@ static hipError_t enqueue_output(adc_handle* h)
 {
     const size_t P = (size_t)h->p.W * h->p.H;
     hipError_t e = hipSuccess;
-    const AdcMatchReq& r = h->req;
+    const AdcMatchReq& r = h->fly.req;
     if (h->sp_max_size > 0 && (e = enqueue_speckle(h, h->disp_l, h->sp_map, h->sp_max_size, h->sp_max_diff, nullptr, r.prov)) != hipSuccess) return e;
     const float* map = delivered_map(h);
     if (r.map_host && r.map_host_direct == 1) e = ADC_HIP(hipMemcpyAsync(r.map_host, map, P * 4, hipMemcpyDeviceToHost, h->stream)); // page-locked by the caller
@@ -618,35 +622,31 @@ static hipError_t enqueue_rectify(adc_handle* h, const void* raw_l, const void* 
 }
 
 // A HIP call of a Match failed half-way (the reference's contract: Match returns false and the object stays usable,
-// ADCensusStereo.cpp:71-76).  Whatever was already enqueued is drained, every per-Match flag of the handle goes back to its idle
-// value -- a later Match must not find a half-described predecessor: a pending voting chain, a dropped aggregation pass the
-// scanline stage never consumed (round-5 advisor finding), speculation flags of launches that never ran -- and the caller's
-// buffers are forgotten.  What the handle has LEARNED from earlier pairs (arm maxima, chain budget) stays: it is verified on the
-// device for every pair anyway.
-static void match_req_clear(adc_handle* h) { memset(&h->req, 0, sizeof(h->req)); }
+// ADCensusStereo.cpp:71-76).  Whatever was already enqueued is drained and everything in flight goes back to idle in ONE reset of
+// h->fly -- a later Match cannot find a half-described predecessor (a pending voting chain, a dropped aggregation pass the scanline
+// stage never consumed, a request with the caller's buffers): a flag that lives in AdcInFlight cannot be forgotten here.  What the
+// handle has LEARNED from earlier pairs (arm maxima, chain budget) stays: it is verified on the device for every pair anyway.
+static void match_req_clear(adc_handle* h) { memset(&h->fly.req, 0, sizeof(h->fly.req)); }
+static void inflight_reset(adc_handle* h) { memset(&h->fly, 0, sizeof(h->fly)); }
+// the handle looks at its own image buffers again; the packed left image is stale when they had been borrowed (or the caller says so)
+static void images_own(adc_handle* h, bool repack)
+{
+    if (repack || h->img_l != h->img_l_own || h->img_r != h->img_r_own) h->bgrx_valid = 0;
+    h->img_l = h->img_l_own; h->img_r = h->img_r_own;
+}
 
 static void abort_match(adc_handle* h)
 {
     if (h->heavy) hipStreamSynchronize(h->heavy);
     if (h->stream) hipStreamSynchronize(h->stream);
     (void)hipGetLastError();
-    h->match_pending = 0;
-    h->irv_pending = 0;
-    h->so_agg_fused = 0;
-    h->fuse_wta = 0;
-    h->armmax_valid = 0;
-    h->in_redo = 0;
+    inflight_reset(h);
     learn_forget_densities(&h->learned);
-    h->wta_left_done = 0;
-    h->timings_pending = false;
-    h->force_median_fallback = 0;
-    match_req_clear(h);
-    h->ev_pending = 0;
-    h->reg_pending = 0;
     if (h->pin_flags) { h->pin_flags[ADC_PIN_MEDIAN] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[ADC_PIN_SPECKLE] = h->pin_flags[ADC_PIN_SPECKLE + 1] = h->pin_flags[ADC_PIN_SPECKLE + 2] = 0; }
-    if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) { h->img_l = h->img_l_own; h->img_r = h->img_r_own; }
-    h->bgrx_valid = 0;
+    images_own(h, true);
 }
+// the failure epilogue of the Match path: the message, everything in flight back to idle; code 2
+static int fail_match(adc_handle* h, const char* what, hipError_t e) { set_error(what, e); abort_match(h); return 2; }
 // the failure epilogue of a call outside a Match: adc_last_error gains the entry point's name, the streams are drained; code 2
 static int fail_call(adc_handle* h, const char* who)
 {
@@ -665,8 +665,7 @@ int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, voi
     if (rectify_state(h) > 0) {
         // rectification on: the caller's RAW images are read by the remap only (borrowed until adc_wait all the same), the Match
         // runs on the handle's own buffers
-        h->img_l = h->img_l_own;
-        h->img_r = h->img_r_own;
+        images_own(h, false);
         if (enqueue_rectify(h, d_left, d_right) != hipSuccess) { abort_match(h); return 2; }
     } else {
     // the caller's device images are BORROWED until adc_wait returns (like the reference borrows the host pointers for the
@@ -675,9 +674,9 @@ int adc_match_device(adc_handle* h, const void* d_left, const void* d_right, voi
     h->img_r = const_cast<uint8_t*>(static_cast<const uint8_t*>(d_right));
     }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
-    h->req.map_dev = d_disp;
-    h->req.map_host = nullptr;
-    if (enqueue_output(h) != hipSuccess) { set_error("adc_match_device: output copy", hipGetLastError()); abort_match(h); return 2; }
+    h->fly.req.map_dev = d_disp;
+    h->fly.req.map_host = nullptr;
+    if (enqueue_output(h) != hipSuccess) return fail_match(h, "adc_match_device: output copy", hipGetLastError());
     return 0;
 }
 
@@ -687,8 +686,7 @@ static int match_async_impl(adc_handle* h, const uint8_t* left, const uint8_t* r
     if (rectify_refused(h, "adc_match")) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
-    h->img_l = h->img_l_own;
-    h->img_r = h->img_r_own;
+    images_own(h, false);
     // rectification on: what is uploaded are the two RAW images (height * pitch_bytes each) into the raw buffers, through the raw
     // staging; the remap then writes the own buffers.  Off: nl == nr == 3 * P into the image buffers, as ever
     const bool rect = rectify_state(h) > 0;
@@ -715,26 +713,18 @@ static int match_async_impl(adc_handle* h, const uint8_t* left, const uint8_t* r
         lsrc = pin;
     }
     // (reg_in / direct: DMA from the caller's memory -- page-locked by the caller: asynchronous; pageable: the runtime stages)
-    if (ADC_HIP(hipMemcpyAsync(dst_l, lsrc, nl, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
-        set_error("adc_match: upload of the left image", hipGetLastError());
-        abort_match(h);
-        return 2;
-    }
+    if (ADC_HIP(hipMemcpyAsync(dst_l, lsrc, nl, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail_match(h, "adc_match: upload of the left image", hipGetLastError());
     if (!(reg_in || direct)) {
         memcpy(pin + nl, right, nr);
         rsrc = pin + nl;
     }
-    if (ADC_HIP(hipMemcpyAsync(dst_r, rsrc, nr, hipMemcpyHostToDevice, h->stream)) != hipSuccess) {
-        set_error("adc_match: upload of the right image", hipGetLastError());
-        abort_match(h);
-        return 2;
-    }
+    if (ADC_HIP(hipMemcpyAsync(dst_r, rsrc, nr, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail_match(h, "adc_match: upload of the right image", hipGetLastError());
     if (rect && enqueue_rectify(h, dst_l, dst_r) != hipSuccess) { abort_match(h); return 2; }
     if (run_pipeline(h) != hipSuccess) { abort_match(h); return 2; }
-    h->req.map_host = disp;
-    h->req.map_host_direct = host_registered(disp, P * 4) ? 1 : (direct ? 2 : 0);
-    h->req.map_dev = nullptr;
-    if (enqueue_output(h) != hipSuccess) { set_error("adc_match: output copy", hipGetLastError()); abort_match(h); return 2; }
+    h->fly.req.map_host = disp;
+    h->fly.req.map_host_direct = host_registered(disp, P * 4) ? 1 : (direct ? 2 : 0);
+    h->fly.req.map_dev = nullptr;
+    if (enqueue_output(h) != hipSuccess) return fail_match(h, "adc_match: output copy", hipGetLastError());
     return 0;
 }
 
@@ -786,97 +776,109 @@ static AdcMatchReport match_report(const adc_handle* h)
     return r;
 }
 
-int adc_wait(adc_handle* h)
+// deliver again: everything enqueue_output sends, then the wait for it
+static hipError_t redeliver(adc_handle* h) { const hipError_t e = enqueue_output(h); return e != hipSuccess ? e : ADC_HIP(hipStreamSynchronize(h->stream)); }
+
+// The steps of adc_wait, in its order:
+// (1) an assumed aggregation ring was too shallow, or a scanline row segment failed its seam: learn_redo says whether the Match
+//     runs again and from where (the aggregation on, or as a whole: the inputs are still there); the flags are read again behind it
+static int wait_settle_speculation(adc_handle* h)
 {
-    if (!h) return 1;
-    hipSetDevice(h->device);
-    if (ADC_HIP(hipStreamSynchronize(h->stream)) != hipSuccess) { set_error("adc_wait", hipGetLastError()); abort_match(h); return 2; }
-    // (1) an assumed aggregation ring was too shallow, or a scanline row segment failed its seam: learn_redo says whether the Match
-    //     runs again and from where (the aggregation on, or as a whole: the inputs are still there); the flags are read again behind it
-    if (h->pin_flags) {
-        AdcMatchReport rep = match_report(h);
-        for (int attempt = 0; attempt < LEARN_MAX_REDOS; attempt++) {
-            const AdcRedo redo = learn_redo(&h->learned, &h->lstats, rep);
-            if (redo == ADC_REDO_NONE) break;
-            h->in_redo = 1;
-            hipError_t e = run_pipeline(h, redo == ADC_REDO_FROM_AGGREGATION);
-            h->in_redo = 0;
-            if (e == hipSuccess) e = enqueue_output(h);
-            if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
-            if (e != hipSuccess) { set_error("adc_wait: redo (full aggregation ring / whole scanline rows)", e); abort_match(h); return 2; }
-            rep = match_report(h);
-        }
-        if (learn_redo_wanted(rep)) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
-        learn_commit(&h->learned, &h->lstats, rep, h->match_pending != 0, h->match_pending ? adc_agg_small_L(h) : 0);
-        h->match_pending = 0;
+    if (!h->pin_flags) return 0;
+    AdcMatchReport rep = match_report(h);
+    for (int attempt = 0; attempt < LEARN_MAX_REDOS; attempt++) {
+        const AdcRedo redo = learn_redo(&h->learned, &h->lstats, rep);
+        if (redo == ADC_REDO_NONE) break;
+        hipError_t e = run_pipeline(h, redo);
+        if (e == hipSuccess) e = redeliver(h);
+        if (e != hipSuccess) return fail_match(h, "adc_wait: redo (full aggregation ring / whole scanline rows)", e);
+        rep = match_report(h);
     }
-    // (2) the voting chain ran out of its launch budget before it converged: continue it, redo the stages behind it
+    if (learn_redo_wanted(rep)) { g_last_error = "adc_wait: redo did not clear the speculation flags"; abort_match(h); return 2; }
+    learn_commit(&h->learned, &h->lstats, rep, h->fly.match_pending != 0, h->fly.match_pending ? adc_agg_small_L(h) : 0);
+    h->fly.match_pending = 0;
+    return 0;
+}
+// (2) the voting chain ran out of its launch budget before it converged: continue it, redo the stages behind it
+static hipError_t wait_continue_voting(adc_handle* h)
+{
+    if (!h->fly.irv_pending) return hipSuccess;
+    // the continuation delivers into the buffer that was disp_l when the chain was enqueued (the stages behind the voting have swapped the roles since)
+    float *now_l = h->disp_l, *now_tmp = h->disp_tmp;
+    h->disp_l = h->tail_disp_l;
+    h->disp_tmp = h->tail_disp_tmp;
     int continued = 0;
-    hipError_t e = hipSuccess;
-    if (h->irv_pending) {
-        // the continuation delivers into the buffer that was disp_l when the chain was enqueued (the stages behind the
-        // voting have swapped the roles since)
-        float *now_l = h->disp_l, *now_tmp = h->disp_tmp;
-        h->disp_l = h->tail_disp_l;
-        h->disp_tmp = h->tail_disp_tmp;
-        e = adc_voting_finish(h, &continued);
-        if (!continued) { h->disp_l = now_l; h->disp_tmp = now_tmp; }
-    }
-    if (e == hipSuccess && continued) {
-        e = run_refine_tail(h);
-        if (e == hipSuccess) e = enqueue_output(h);
-        if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
-    }
-    if (e != hipSuccess) { set_error("adc_wait: region voting continuation", e); abort_match(h); return 2; }
-    // (3) a median band gave up waiting for its upstream band: the map is incomplete -- redo the filter with the
-    //     single-workgroup kernel (no inter-workgroup dependency) and deliver that result
-    if (h->pin_flags && (h->pin_flags[ADC_PIN_MEDIAN] != 0 || h->force_median_fallback)) {
-        e = adc_median_fallback(h); // (looks at pin_flags[ADC_PIN_MEDIAN]: 2 = a speculative seam differed -> chained form first)
+    hipError_t e = adc_voting_finish(h, &continued);
+    if (!continued) { h->disp_l = now_l; h->disp_tmp = now_tmp; }
+    if (e == hipSuccess && continued) e = run_refine_tail(h);
+    if (e == hipSuccess && continued) e = redeliver(h);
+    return e;
+}
+// (3) a median band gave up waiting for its upstream band: the map is incomplete -- redo the filter with the
+//     single-workgroup kernel (no inter-workgroup dependency) and deliver that result
+static hipError_t wait_median_fallback(adc_handle* h)
+{
+    if (h->pin_flags && (h->pin_flags[ADC_PIN_MEDIAN] != 0 || h->fly.force_median_fallback)) {
+        hipError_t e = adc_median_fallback(h); // (looks at pin_flags[ADC_PIN_MEDIAN]: 2 = a speculative seam differed -> chained form first)
         h->pin_flags[ADC_PIN_MEDIAN] = 0;
-        if (e == hipSuccess) e = enqueue_output(h);
-        if (e == hipSuccess) e = ADC_HIP(hipStreamSynchronize(h->stream));
-        if (e != hipSuccess) { set_error("adc_wait: median fallback", e); abort_match(h); return 2; }
+        if (e == hipSuccess) e = redeliver(h);
+        if (e != hipSuccess) return e;
     }
-    h->force_median_fallback = 0;
+    h->fly.force_median_fallback = 0;
     learn_median_commit(&h->learned, h->med_spec_last, h->med_seg_last);
-    const AdcMatchReq r = h->req;
-    if (r.map_host && r.map_host_direct == 2) {
-        if (ADC_HIP(hipMemcpy(r.map_host, delivered_map(h), (size_t)h->p.W * h->p.H * 4, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: copy-out", hipGetLastError()); abort_match(h); return 2; }
-    } else if (r.map_host && r.map_host_direct == 0) {
-        memcpy(r.map_host, h->pin_out, (size_t)h->p.W * h->p.H * 4);
-    }
-    if (r.host_delivery) { // a host caller's products: staging (or, direct == 2, the device scratch) -> the caller's buffers, then the points that exist
+    return hipSuccess;
+}
+// (4) a host caller's map and products: staging (or, direct == 2, the device scratch) -> the caller's buffers, then the points that exist
+static int wait_deliver(adc_handle* h)
+{
+    const AdcMatchReq r = h->fly.req;
+    const size_t map_bytes = (size_t)h->p.W * h->p.H * 4;
+    if (r.map_host && r.map_host_direct == 2 && ADC_HIP(hipMemcpy(r.map_host, delivered_map(h), map_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail_match(h, "adc_wait: copy-out", hipGetLastError());
+    if (r.map_host && r.map_host_direct == 0) memcpy(r.map_host, h->pin_out, map_bytes);
+    if (r.host_delivery) {
         for (int i = 0; i < ADC_REQ_MAPS; i++) {
             const AdcHostMap& m = r.host[i];
             if (m.dst && m.direct == 0) memcpy(m.dst, h->map_buf[i].pin, m.bytes);
-            if (m.dst && m.direct == 2 && ADC_HIP(hipMemcpy(m.dst, h->map_buf[i].dev, m.bytes, hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: product copy-out", hipGetLastError()); abort_match(h); return 2; }
+            if (m.dst && m.direct == 2 && ADC_HIP(hipMemcpy(m.dst, h->map_buf[i].dev, m.bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail_match(h, "adc_wait: product copy-out", hipGetLastError());
         }
         if (r.cloud) {
             const uint32_t count = (uint32_t)h->pin_flags[ADC_PIN_CLOUD];
             const size_t n = count < r.capacity ? count : r.capacity;
-            if (n && ADC_HIP(hipMemcpy(r.cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) { set_error("adc_wait: cloud copy-out", hipGetLastError()); abort_match(h); return 2; }
+            if (n && ADC_HIP(hipMemcpy(r.cloud, h->os_cloud, n * sizeof(adc_point), hipMemcpyDeviceToHost)) != hipSuccess) return fail_match(h, "adc_wait: cloud copy-out", hipGetLastError());
             if (r.cloud_count) *r.cloud_count = count;
         }
     }
     match_req_clear(h);
-    if (h->ev_pending) { // an evaluation has completed: its report words have arrived in the pinned block (adc_get_eval_report)
+    return 0;
+}
+// (5) an evaluation / a registration has completed: its report words have arrived in the pinned block (adc_get_eval_report, adc_get_register_report)
+static void wait_take_reports(adc_handle* h)
+{
+    if (h->fly.ev_pending) {
         h->ev_report = h->ev_echo;
         memcpy(&h->ev_report, h->ev_pin, adc_eval_report_words() * sizeof(uint64_t));
         h->ev_report_valid = 1;
-        h->ev_pending = 0;
+        h->fly.ev_pending = 0;
     }
-    if (h->reg_pending) { // a registration has completed: its report words have arrived in the pinned block (adc_get_register_report)
+    if (h->fly.reg_pending) {
         memcpy(&h->reg_report, h->reg_pin, sizeof(h->reg_report));
         h->reg_report_valid = 1;
-        h->reg_pending = 0;
+        h->fly.reg_pending = 0;
     }
-    // adc_match_device BORROWED the caller's device images until here: nothing of the handle may point at them any
-    // more (a later debug stage would otherwise read memory the caller has reused or freed)
-    if (h->img_l != h->img_l_own || h->img_r != h->img_r_own) {
-        h->img_l = h->img_l_own;
-        h->img_r = h->img_r_own;
-        h->bgrx_valid = 0;
-    }
+}
+
+int adc_wait(adc_handle* h)
+{
+    if (!h) return 1;
+    hipSetDevice(h->device);
+    if (ADC_HIP(hipStreamSynchronize(h->stream)) != hipSuccess) return fail_match(h, "adc_wait", hipGetLastError());
+    if (wait_settle_speculation(h) != 0) return 2;
+    hipError_t e = wait_continue_voting(h);
+    if (e != hipSuccess) return fail_match(h, "adc_wait: region voting continuation", e);
+    if ((e = wait_median_fallback(h)) != hipSuccess) return fail_match(h, "adc_wait: median fallback", e);
+    if (wait_deliver(h) != 0) return 2;
+    wait_take_reports(h);
+    images_own(h, false); // adc_match_device BORROWED the caller's images until here (a later debug stage would read memory the caller has reused or freed)
     collect_timings(h);
     return 0;
 }
@@ -890,15 +892,15 @@ int adc_match(adc_handle* h, const uint8_t* left, const uint8_t* right, float* d
 
 // ------------------------------------------------------------------------------ one request for every optional product
 // Every Match entry point is a view of one request (adc_products; the _ex and _out forms ask for a part of it): it is validated and
-// resolved into h->req, the existing stages and enqueue_output do the rest -- the confidence kernel runs behind the WTA in run_heavy,
+// resolved into h->fly.req, the existing stages and enqueue_output do the rest -- the confidence kernel runs behind the WTA in run_heavy,
 // the provenance kernel at the top of run_refine_tail, depth / cloud / 8-bit image / 16-bit map are computed from the delivered map in
 // enqueue_output.  Every redo of adc_wait goes through these, so every product always describes the delivered disparity map.
 static bool outputs_requested(const adc_outputs* o) { return o && (o->depth || o->cloud || o->disp8); }
 static bool products_requested(const adc_products* p) { return p && (p->provenance || p->confidence || outputs_requested(&p->out) || p->disp16); }
 static bool match_in_flight(const adc_handle* h)
 {
-    const AdcMatchReq& r = h->req;
-    return h->match_pending || r.map_host || r.map_dev || r.out.active || r.host_delivery || r.disp16;
+    const AdcMatchReq& r = h->fly.req;
+    return h->fly.match_pending || r.map_host || r.map_dev || r.out.active || r.host_delivery || r.disp16;
 }
 
 static bool extras_allowed(adc_handle* h, const char* who)
@@ -953,12 +955,12 @@ static hipError_t host_scratch(adc_handle* h, const AdcHostMap* host, bool cloud
     return hipSuccess;
 }
 
-// Validates a request and resolves it into h->req, whole, for the Match that the caller enqueues next.  device_pointers: the request's
+// Validates a request and resolves it into h->fly.req, whole, for the Match that the caller enqueues next.  device_pointers: the request's
 // addresses are the device targets themselves; otherwise they are host destinations, the targets are the handle's scratch and
 // enqueue_output / adc_wait deliver.  older: the call comes from adc_match_ex / _out or their device forms, which do not refuse while
 // a Match is pending and whose host forms (all synchronous) keep their blocking copies behind adc_wait's synchronisation (direct = 2:
 // through the staging they were slower than before, profiles/match_request_timing.md).  0, or 1 (refused, adc_last_error) /
-// 2 (allocation); h->req is written on 0 only.
+// 2 (allocation); h->fly.req is written on 0 only.
 static int match_req_resolve(adc_handle* h, const adc_products* p, const char* who, bool device_pointers, bool older)
 {
     if (!older && match_in_flight(h)) { g_last_error = std::string(who) + ": a Match is pending (adc_wait first)"; return 1; }
@@ -994,7 +996,7 @@ static int match_req_resolve(adc_handle* h, const adc_products* p, const char* w
     r.out.disp8 = static_cast<uint8_t*>(target[ADC_MAP_DISP8]);
     r.disp16 = static_cast<uint16_t*>(target[ADC_MAP_DISP16]);
     r.disp16_scale = p->disp16_scale;
-    h->req = r;
+    h->fly.req = r;
     return 0;
 }
 
@@ -1008,11 +1010,11 @@ static int match_host_req(adc_handle* h, const uint8_t* left, const uint8_t* rig
     }
     if (!h || !left || !right || !disp) return 1;
     hipSetDevice(h->device);
-    const AdcMatchReq before = h->req;
+    const AdcMatchReq before = h->fly.req;
     int rc = match_req_resolve(h, p, who, false, older);
     if (rc != 0) return rc;
     rc = match_async_impl(h, left, right, disp, sync_call);
-    if (rc == 1) h->req = before;
+    if (rc == 1) h->fly.req = before;
     if (rc == 0 && sync_call) rc = adc_wait(h);
     return rc;
 }
@@ -1022,11 +1024,11 @@ static int match_device_req(adc_handle* h, const void* d_left, const void* d_rig
     if (!products_requested(p)) return adc_match_device(h, d_left, d_right, d_disp);
     if (!h || !d_left || !d_right || !d_disp) return 1;
     hipSetDevice(h->device);
-    const AdcMatchReq before = h->req;
+    const AdcMatchReq before = h->fly.req;
     int rc = match_req_resolve(h, p, who, true, older);
     if (rc != 0) return rc;
     rc = adc_match_device(h, d_left, d_right, d_disp);
-    if (rc == 1) h->req = before;
+    if (rc == 1) h->fly.req = before;
     return rc;
 }
 
@@ -1078,9 +1080,9 @@ int adc_reproject_device(adc_handle* h, const void* d_disp, const void* d_bgr_le
 {
     if (!h || !d_disp || (out && out->cloud && !d_bgr_left)) return 1;
     if (!outputs_requested(out)) return 0;
-    if (h->req.out.active) { g_last_error = "adc_reproject_device: a Match with outputs is pending (adc_wait first)"; return 1; }
+    if (h->fly.req.out.active) { g_last_error = "adc_reproject_device: a Match with outputs is pending (adc_wait first)"; return 1; }
     hipSetDevice(h->device);
-    const int rc = outputs_prepare(h, out, "adc_reproject_device", true, &h->req.out);
+    const int rc = outputs_prepare(h, out, "adc_reproject_device", true, &h->fly.req.out);
     if (rc != 0) return rc;
     // (out.active stays 0: nothing of a later adc_wait may run these again on the handle's own map)
     if (enqueue_outputs(h, static_cast<const float*>(d_disp), static_cast<const uint8_t*>(d_bgr_left)) != hipSuccess) { abort_match(h); return 2; }
@@ -1102,7 +1104,7 @@ int adc_disp16_device(adc_handle* h, const void* d_disp, float scale, void* d_di
     if ((uintptr_t)d_disp16 & 1u) { g_last_error = "adc_disp16_device: the device address of disp16 must be even"; return 1; }
     hipSetDevice(h->device);
     const hipError_t e = ADC_HIP(adc_launch_disp16(h, static_cast<const float*>(d_disp), scale, static_cast<uint16_t*>(d_disp16)));
-    if (e != hipSuccess) { set_error("adc_disp16_device", e); abort_match(h); return 2; }
+    if (e != hipSuccess) return fail_match(h, "adc_disp16_device", e);
     return 0;
 }
 
@@ -1312,7 +1314,7 @@ int adc_rectify_device(adc_handle* h, int side, const void* d_raw, void* d_bgr_o
     if (raw_address_refused(h, side, d_raw, "adc_rectify_device")) return 1;
     hipSetDevice(h->device);
     const hipError_t e = ADC_HIP(launch_rect_side(h, side, static_cast<const uint8_t*>(d_raw), static_cast<uint8_t*>(d_bgr_out)));
-    if (e != hipSuccess) { set_error("adc_rectify_device", e); abort_match(h); return 2; }
+    if (e != hipSuccess) return fail_match(h, "adc_rectify_device", e);
     return 0;
 }
 
@@ -1461,7 +1463,7 @@ static int evaluate_device_impl(adc_handle* h, const void* d_disp, const void* d
     h->ev_echo.has_nonocc_mask = (uint8_t)h->ev_has_mask;
     h->ev_echo.has_provenance = d_prov ? 1 : 0;
     h->ev_echo.has_confidence = d_conf ? 1 : 0;
-    h->ev_pending = 1;
+    h->fly.ev_pending = 1;
     return 0;
 }
 
@@ -1606,7 +1608,7 @@ int adc_register_depth_device(adc_handle* h, const void* d_map, int input_kind, 
     hipSetDevice(h->device);
     if (enqueue_registration(h, static_cast<const float*>(d_map), input_kind, calib, flags, static_cast<float*>(d_depth), static_cast<int32_t*>(d_index)) != hipSuccess)
         return fail_call(h, who);
-    h->reg_pending = 1;
+    h->fly.reg_pending = 1;
     return 0;
 }
 
@@ -1980,11 +1982,9 @@ int adc_debug_set_images(adc_handle* h, const uint8_t* left, const uint8_t* righ
     if (!h || !left || !right) return 1;
     hipSetDevice(h->device);
     const size_t P = (size_t)h->p.W * h->p.H;
-    h->img_l = h->img_l_own;
-    h->img_r = h->img_r_own;
+    images_own(h, true); // (the packed left image is stale from here on, also behind a copy that fails half-way)
     if (hipMemcpy(h->img_l, left, P * 3, hipMemcpyHostToDevice) != hipSuccess) return 2;
     if (hipMemcpy(h->img_r, right, P * 3, hipMemcpyHostToDevice) != hipSuccess) return 2;
-    h->bgrx_valid = 0;
     return 0;
 }
 
@@ -1993,7 +1993,7 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
     if (!h) return 1;
     hipSetDevice(h->device);
     hipError_t e = hipSuccess;
-    bool fuse_cost = false; // (ADC_RUN_AGGREGATE)
+    bool fuse_cost = false; AggArms arms = AGG_ARMS_UNKNOWN; // (ADC_RUN_AGGREGATE; unknown arms: two launches per pass, the kernels decide)
     switch (stage) {
     case ADC_RUN_GRAY_CENSUS: e = adc_launch_gray_census(h); break;
     case ADC_RUN_COST: e = adc_launch_cost(h, h->vol_a); break;
@@ -2007,7 +2007,7 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
             int am[2] = {0, 0};
             e = hipMemcpy(am, h->armmax, 2 * sizeof(int), hipMemcpyDeviceToHost);
             if (e == hipSuccess) learn_take_arms(&h->learned, am);
-            h->armmax_valid = e == hipSuccess ? 1 : 0;
+            if (e == hipSuccess) arms = AGG_ARMS_EXACT;
             // ... and the record densities of THIS image (the pipeline assumes the previous Match's)
             if (e == hipSuccess && h->pin_nz) e = hipMemcpyAsync(h->pin_nz, h->armmax + ADC_NZ_BASE, 2 * ADC_NZ_SHARDS * ADC_NZ_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, h->heavy);
             if (e == hipSuccess && h->pin_nz) e = hipStreamSynchronize(h->heavy);
@@ -2023,15 +2023,12 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
             else { e = adc_launch_cost_records(h); fuse_cost = true; }
             arg -= 100;
         }
-        if (e == hipSuccess) e = adc_launch_aggregate(h, arg > 0 ? arg : 4, fuse_cost, false);
-        h->armmax_valid = 0;
+        if (e == hipSuccess) e = adc_launch_aggregate(h, arg > 0 ? arg : 4, arms, false, fuse_cost, false);
         break;
     case ADC_RUN_SCANLINE: // arg = passes (default 4); arg >= 100: the production form of the last pass, which also
                            // writes the left-view disparity map (ADC_BUF_DISP_LEFT) -- ADC_RUN_WTA then only adds the right view
-        h->fuse_wta = arg >= 100 ? 1 : 0;
-        h->wta_left_done = 0;
-        e = adc_launch_scanline(h, arg >= 100 ? arg - 100 : arg);
-        h->fuse_wta = 0;
+        h->fly.wta_left_done = 0;
+        e = adc_launch_scanline(h, arg >= 100 ? arg - 100 : arg, arg >= 100);
         break;
     case ADC_RUN_WTA: e = adc_launch_wta(h); break;
     case ADC_RUN_LRCHECK: e = adc_launch_lrcheck(h); break;
@@ -2044,14 +2041,12 @@ int adc_debug_run(adc_handle* h, int stage, int arg)
         if (e == hipSuccess) { int cont = 0; e = adc_voting_finish(h, &cont); }
         break;
     case ADC_RUN_INTERPOLATION: // arg 1: the f64 walk (k_interpolate_rays) also where the handle would take the table walk (itp_plan.h)
-        h->itp_force_f64 = arg == 1 ? 1 : 0;
-        e = adc_launch_interpolation(h);
-        h->itp_force_f64 = 0;
+        e = adc_launch_interpolation(h, arg == 1);
         break;
     case ADC_RUN_DISCONTINUITY: e = adc_launch_discontinuity(h); break;
     case ADC_RUN_MEDIAN: // arg 100: test hook -- arm the fallback path of the NEXT adc_wait (as if a band had timed out)
-        if (arg == 100) { h->force_median_fallback = 1; return 0; }
-        if (arg == 101) { h->force_median_fallback = 2; return 0; } // ... as if a speculative seam had differed (chained form redone)
+        if (arg == 100) { h->fly.force_median_fallback = 1; return 0; }
+        if (arg == 101) { h->fly.force_median_fallback = 2; return 0; } // ... as if a speculative seam had differed (chained form redone)
         e = adc_launch_median(h);
         break;
     default: return 1;

@@ -778,15 +778,15 @@ static AggKnobs agg_knobs()
 
 static_assert(AGG_ARMS_ASSUMED == LEARN_ARMS_ASSUMED && AGG_ARMS_FULL == LEARN_ARMS_FULL, "learn_plan.h names AggArms values");
 // what the handle knows, by value (the aggregation only READS the handle's arm and density state)
-static AggInputs agg_inputs(const adc_handle* h, const AggKnobs& kn, int iterations, bool fuse_cost, bool fuse_agg_so)
+static AggInputs agg_inputs(const adc_handle* h, const AggKnobs& kn, int iterations, AggArms arms, bool redo, bool fuse_cost, bool fuse_agg_so)
 {
     AggInputs in = {};
     in.W = h->p.W; in.H = h->p.H; in.Dp = h->p.Dp; in.cross_L1 = h->p.opt.cross_L1; in.iterations = iterations;
-    in.arms = (AggArms)h->armmax_valid;
+    in.arms = arms;
     const AdcLearned& L = h->learned;
     for (int c = 0; c < 2; c++) { in.armmax[c] = L.armmax_host[c]; in.armmax_small[c] = L.armmax_small[c]; in.rec_nz[c] = L.rec_nz[c]; }
     in.rec_nz_known = L.rec_nz_known != 0;
-    in.in_redo = h->in_redo != 0;
+    in.in_redo = redo;
     in.dual = L.agg_dual > 0;
     in.fuse_cost = fuse_cost;
     in.fuse_agg_so = fuse_agg_so;
@@ -906,8 +906,9 @@ static hipError_t agg_execute(adc_handle* h, const AggPlan& plan, float* const v
 
 // vol_a -> (H,V | V,H alternating) -> vol_a.  Every iteration is two launches: a -> b -> a.
 //   fuse_cost    the first pass computes the matching cost itself (k_agg_march<.., COSTIN>: vol_a holds nothing yet)
-//   fuse_agg_so  the last pass may move into the first scanline pass (so_agg_fused)
-hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, bool fuse_agg_so)
+//   fuse_agg_so  the last pass may move into the first scanline pass (fly.so_agg_fused)
+//   arms, redo   what the caller knows about the arm maxima of this image (AggArms, agg_plan.h); adc_wait is redoing the Match
+hipError_t adc_launch_aggregate(adc_handle* h, int iterations, AggArms arms, bool redo, bool fuse_cost, bool fuse_agg_so)
 {
     if ((h->paper & ADC_PAPER_RIGHT_ARMS) && h->arms_r) return adc_paper_aggregate(h, iterations); // opt-in paper mode (k_paper.hip)
     {   // allow > 64 KiB dynamic LDS for the ring (large cross_L1): a per-DEVICE function attribute -- set once for every
@@ -930,9 +931,9 @@ hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, b
     h->agg_first_fused = 0;
     h->agg_dual_last = 0;
     h->agg_sparse_last = 0;
-    h->so_agg_fused = 0; // (round-5 advisor finding: a Match that failed between this stage and the scanline stage must not leave it set)
+    h->fly.so_agg_fused = 0; // (a new plan; a Match that failed between this stage and the scanline stage went through abort_match, whose one reset of fly covers it)
     const AggKnobs kn = agg_knobs();
-    const AggInputs in = agg_inputs(h, kn, iterations, fuse_cost, fuse_agg_so);
+    const AggInputs in = agg_inputs(h, kn, iterations, arms, redo, fuse_cost, fuse_agg_so);
     float* const vol[2] = {h->vol_a, h->vol_b};
     hipError_t e = hipSuccess;
     AggPlan plan;
@@ -948,20 +949,20 @@ hipError_t adc_launch_aggregate(adc_handle* h, int iterations, bool fuse_cost, b
         plan = agg_plan(in, kn, AggGate{0, 0}, false);
         e = agg_execute(h, plan, vol, true);
     }
-    if (plan.tail_moved) { h->so_agg_fused = 1; h->agg_so_fusions++; }
+    if (plan.tail_moved) { h->fly.so_agg_fused = 1; h->agg_so_fusions++; }
     // the result must be in vol_a (cost_aggr_): swap the two volume pointers if it ended up in the other one
     if (e == hipSuccess && plan.result != 0) { h->vol_a = vol[1]; h->vol_b = vol[0]; }
     return e;
 }
 
-// The dividing H pass of the last iteration that adc_launch_aggregate left to the scanline stage (so_agg_fused), as a launch of
+// The dividing H pass of the last iteration that adc_launch_aggregate left to the scanline stage (fly.so_agg_fused), as a launch of
 // its own: what run_so falls back to when its segment plan at scanline time cannot take the pass over after all (round-5 advisor
-// finding: that used to fail the Match).  Full ring: valid whatever the arms are.
+// finding: that used to fail the Match).  Full ring: valid whatever the arms are -- agg_plan_tail reads neither the arm knowledge nor "redo".
 hipError_t adc_launch_aggregate_tail(adc_handle* h)
 {
     const AggKnobs kn = agg_knobs();
     AggPlan plan;
-    plan.launch.push_back(agg_plan_tail(agg_inputs(h, kn, 1, false, false), kn));
+    plan.launch.push_back(agg_plan_tail(agg_inputs(h, kn, 1, AGG_ARMS_UNKNOWN, false, false, false), kn));
     float* const vol[2] = {h->vol_a, h->vol_b};
     const hipError_t e = agg_execute(h, plan, vol, false);
     if (e == hipSuccess) { h->vol_a = vol[1]; h->vol_b = vol[0]; }

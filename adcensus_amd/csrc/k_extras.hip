@@ -82,7 +82,7 @@ hipError_t adc_launch_confidence(adc_handle* h)
 {
     const AdcParams& p = h->p;
     const int P = p.W * p.H; // (adc_create: W * H <= 2^30)
-    hipLaunchKernelGGL(k_confidence, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->heavy, h->vol_a, h->req.conf, P, p.D, p.Dp);
+    hipLaunchKernelGGL(k_confidence, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->heavy, h->vol_a, h->fly.req.conf, P, p.D, p.Dp);
     return hipGetLastError();
 }
 
@@ -109,7 +109,7 @@ hipError_t adc_launch_provenance(adc_handle* h)
     const AdcParams& p = h->p;
     const int P = p.W * p.H;
     const int filling = p.opt.do_lr_check && p.opt.do_filling;
-    hipLaunchKernelGGL(k_provenance, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, h->label, h->disp_l, h->req.prov, h->req.conf, P,
+    hipLaunchKernelGGL(k_provenance, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, h->label, h->disp_l, h->fly.req.prov, h->fly.req.conf, P,
                        filling);
     return hipGetLastError();
 }

@@ -275,11 +275,11 @@ size_t adc_outputs_scratch_bytes(int W, int H)
     return (4 + (P + OUT_TILE - 1) / OUT_TILE) * sizeof(uint32_t);
 }
 
-// The three launchers: disp is any device-resident map of the handle's geometry, img the left image; what h->req.out asks for decides
+// The three launchers: disp is any device-resident map of the handle's geometry, img the left image; what h->fly.req.out asks for decides
 // what a kernel does.  capi.hip (enqueue_outputs) orders them and owns every other HIP call of the path.
 static OutArgs out_args(adc_handle* h, const float* disp, const uint8_t* img)
 {
-    const AdcOutReq& r = h->req.out;
+    const AdcOutReq& r = h->fly.req.out;
     OutArgs g;
     g.disp = disp;
     g.img = img;
@@ -306,7 +306,7 @@ hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_
 hipError_t adc_launch_out_scan(adc_handle* h)
 {
     const int P = h->p.W * h->p.H;
-    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, h->stream, h->out_words, (P + OUT_TILE - 1) / OUT_TILE, h->req.out.cloud_count);
+    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, h->stream, h->out_words, (P + OUT_TILE - 1) / OUT_TILE, h->fly.req.out.cloud_count);
     return hipGetLastError();
 }
 

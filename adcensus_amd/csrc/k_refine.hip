@@ -524,15 +524,15 @@ __global__ __launch_bounds__(256) void k_interp_scatter(const int32_t* __restric
     for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) disp[list[e]] = fill[e];
 }
 
-hipError_t adc_launch_interpolation(adc_handle* h)
+hipError_t adc_launch_interpolation(adc_handle* h, bool force_f64)
 {
     const AdcParams& p = h->p;
     const int P = p.W * p.H;
     const int dmaxa = p.dmax < 0 ? -p.dmax : p.dmax, dmina = p.dmin < 0 ? -p.dmin : p.dmin;
     const int max_search = dmaxa > dmina ? dmaxa : dmina; // multistep_refiner.cpp:236
     // (h->ray_tab: upload_tables built the ray table -- the predicate of itp_plan.h held and no entry sat on a rounding tie;
-    // h->itp_force_f64: debug switch, adc_debug_run(ADC_RUN_INTERPOLATION, 1))
-    if (h->ray_tab && !h->itp_force_f64 && max_search == h->ray_tab_rows && max_search == h->itp_ms && adc_itp_table_walk_ok(p.W, p.H, h->itp_ms)) {
+    // force_f64: debug switch, adc_debug_run(ADC_RUN_INTERPOLATION, 1))
+    if (h->ray_tab && !force_f64 && max_search == h->ray_tab_rows && max_search == h->itp_ms && adc_itp_table_walk_ok(p.W, p.H, h->itp_ms)) {
         // Round 6: ONE list pass, ONE set of map launches for both passes, fills written IN PLACE.  The reference computes the fill
         // values of a whole list from the UNCHANGED map and writes them back afterwards (fill_disps, multistep_refiner.cpp:246-303); a
         // walk here never reads the map at a pixel its own pass writes: it tests the CODE map (a snapshot) and fetches map values only at
@@ -1272,7 +1272,7 @@ hipError_t adc_median_fallback(adc_handle* h)
     // banded kernel, which needs no assumption (and may itself report a time-out), then the single-workgroup kernel
     AdcMedianForm form = ADC_MED_AS_ENQUEUED;
     for (;;) {
-        form = learn_median_next(&h->learned, &h->lstats, form, h->pin_flags[ADC_PIN_MEDIAN], h->med_spec_last, h->med_seg_last, h->force_median_fallback);
+        form = learn_median_next(&h->learned, &h->lstats, form, h->pin_flags[ADC_PIN_MEDIAN], h->med_spec_last, h->med_seg_last, h->fly.force_median_fallback);
         if (form == ADC_MED_DONE) return hipSuccess;
         hipError_t e = form == ADC_MED_SINGLE_WG ? launch_median_wavefront(h, h->disp_tmp, h->disp_l)
                                                  : launch_median_banded(h, h->disp_tmp, h->disp_l, form == ADC_MED_BANDS_WHOLE_ROWS ? h->med_spec_last : 0);

@@ -1011,7 +1011,7 @@ static hipError_t launch_so(adc_handle* h, const float* src, float* dst, bool ve
 }
 
 template <int VPL>
-static hipError_t run_so(adc_handle* h, int passes)
+static hipError_t run_so(adc_handle* h, int passes, bool fuse_wta)
 {
     // scanline_optimizer.cpp:54-60 (cost_aggr_ == vol_a, cost_init_ == vol_b)
     hipError_t e = adc_launch_so_classes(h, h->heavy); // the path-ordered d1 words (tiny)
@@ -1023,10 +1023,10 @@ static hipError_t run_so(adc_handle* h, int passes)
             if (e == hipSuccess) e = adc_paper_accumulate(h, h->vol_c, h->vol_b, r == 0, r == 3);
         }
         { float* t = h->vol_a; h->vol_a = h->vol_c; h->vol_c = t; }
-        h->wta_left_done = 0;
-        if (e == hipSuccess && h->fuse_wta) { // (the left view cannot ride on a pass here: computed from the averaged volume)
+        h->fly.wta_left_done = 0;
+        if (e == hipSuccess && fuse_wta) { // (the left view cannot ride on a pass here: computed from the averaged volume)
             e = adc_launch_wta_left(h);
-            h->wta_left_done = 1;
+            h->fly.wta_left_done = 1;
         }
         return e;
     }
@@ -1036,8 +1036,8 @@ static hipError_t run_so(adc_handle* h, int passes)
     const int nseg = (passes >= 2 && so_use_dpp()) ? adc_so_segments(h, &warm) : 1;
     h->so_nseg_last = nseg;
     if (e == hipSuccess && nseg > 1) e = hipMemsetAsync(h->armmax + 2, 0, sizeof(int), h->heavy);
-    bool agg = h->so_agg_fused != 0; // vol_a holds the volume BEFORE the last aggregation pass (adc_launch_aggregate dropped it)
-    h->so_agg_fused = 0;
+    bool agg = h->fly.so_agg_fused != 0; // vol_a holds the volume BEFORE the last aggregation pass (adc_launch_aggregate dropped it)
+    h->fly.so_agg_fused = 0;
     // (round-5 advisor finding) adc_launch_aggregate asked adc_so_can_fuse_agg at ITS time; should the plan here differ after all
     // (whole rows, the pinned family, a single pass), the dropped pass runs as a launch of its own instead of failing the Match
     if (agg && e == hipSuccess && (nseg <= 1 || passes < 1 || VPL != 2 || so_uses_pin(h->p.H, nseg))) {
@@ -1054,10 +1054,10 @@ static hipError_t run_so(adc_handle* h, int passes)
     }
     if (e == hipSuccess && passes >= 3) e = launch_so<VPL>(h, h->vol_a, h->vol_b, true, +1);
     if (e == hipSuccess && passes >= 4) {
-        // production pipeline: the left-view winner-takes-all rides on the last pass (capi.hip sets fuse_wta)
-        float* disp = (h->fuse_wta && so_use_dpp()) ? h->disp_l : nullptr;
+        // production pipeline: the left-view winner-takes-all rides on the last pass (run_heavy passes fuse_wta)
+        float* disp = (fuse_wta && so_use_dpp()) ? h->disp_l : nullptr;
         e = launch_so<VPL>(h, h->vol_b, h->vol_a, true, -1, disp);
-        h->wta_left_done = disp ? 1 : 0;
+        h->fly.wta_left_done = disp ? 1 : 0;
     }
     if (e == hipSuccess && (passes == 1 || passes == 3)) // debug: leave the partial result in vol_a
         e = hipMemcpyAsync(h->vol_a, h->vol_b, (size_t)h->p.W * h->p.H * h->p.Dp * sizeof(float), hipMemcpyDeviceToDevice,
@@ -1065,13 +1065,13 @@ static hipError_t run_so(adc_handle* h, int passes)
     return e;
 }
 
-hipError_t adc_launch_scanline(adc_handle* h, int passes)
+hipError_t adc_launch_scanline(adc_handle* h, int passes, bool fuse_wta)
 {
     if (passes <= 0 || passes > 4) passes = 4;
-    if (h->p.VPL == 1) return run_so<1>(h, passes);
-    if (h->p.VPL == 2) return run_so<2>(h, passes);
-    if (h->p.VPL == 4) return run_so<4>(h, passes);
-    if (h->p.VPL == 8) return run_so<8>(h, passes);
-    if (h->p.VPL == 16) return run_so<16>(h, passes);
-    return run_so<32>(h, passes);
+    if (h->p.VPL == 1) return run_so<1>(h, passes, fuse_wta);
+    if (h->p.VPL == 2) return run_so<2>(h, passes, fuse_wta);
+    if (h->p.VPL == 4) return run_so<4>(h, passes, fuse_wta);
+    if (h->p.VPL == 8) return run_so<8>(h, passes, fuse_wta);
+    if (h->p.VPL == 16) return run_so<16>(h, passes, fuse_wta);
+    return run_so<32>(h, passes, fuse_wta);
 }

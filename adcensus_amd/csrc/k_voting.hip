@@ -726,7 +726,7 @@ hipError_t adc_run_region_voting(adc_handle* h)
     // the state the last kernel published (slot chain & 1), read by adc_wait / adc_voting_finish
     if (h->pin_flags)
         e = hipMemcpyAsync(h->pin_flags + 16, h->vote_counters + 16 * (h->irv_chain & 1), 8 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-    h->irv_pending = 1;
+    h->fly.irv_pending = 1;
     return e;
 }
 
@@ -736,8 +736,8 @@ hipError_t adc_run_region_voting(adc_handle* h)
 hipError_t adc_voting_finish(adc_handle* h, int* continued)
 {
     *continued = 0;
-    if (!h->irv_pending || !h->pin_flags) return hipSuccess;
-    h->irv_pending = 0;
+    if (!h->fly.irv_pending || !h->pin_flags) return hipSuccess;
+    h->fly.irv_pending = 0;
     hipError_t e;
     int32_t* st = h->pin_flags + 16;
     int guard = 0;

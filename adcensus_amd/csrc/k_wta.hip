@@ -290,8 +290,8 @@ hipError_t adc_launch_wta(adc_handle* h)
     static const bool march_on = [] { const char* e = getenv("ADC_WTA_MARCH"); return e ? atoi(e) != 0 : true; }();
     static const int ncu_env = [] { const char* e = getenv("ADC_WTA_NCU"); return e ? atoi(e) : 0; }();
     static const int nseg_env = [] { const char* e = getenv("ADC_WTA_NSEG"); return e ? atoi(e) : 0; }();
-    const bool left = !h->wta_left_done; // the last scanline pass of the pipeline already produced the left view
-    h->wta_left_done = 0;
+    const bool left = !h->fly.wta_left_done; // the last scanline pass of the pipeline already produced the left view
+    h->fly.wta_left_done = 0;
     if (march_on && p.VPL <= 2) {
         static std::mutex attr_mu; // (per-DEVICE function attribute and CU count: see adc_launch_aggregate)
         static bool attr_set[64] = {false};

@@ -155,7 +155,7 @@ class HandleModel:
         return min(self.small_L, max(1, self.armmax_host[c]) + consts()["assume_margin"])
 
     def scenario(self):
-        valid = AGG_ARMS_ASSUMED if self.arm_known else AGG_ARMS_FULL  # run_heavy: armmax_valid
+        valid = AGG_ARMS_ASSUMED if self.arm_known else AGG_ARMS_FULL  # run_heavy: the AggArms it passes
         cap = min(self.small_L, max(1, self.armmax_host[0]) + (consts()["assume_margin"] if valid == AGG_ARMS_ASSUMED else 0))
         env = "ADC_AGG_SPARSE_DENSITY=%de-6,ADC_AGG_GATHER_DENSITY=%de-6,ADC_COST_FLAT_DENSITY=%de-6" % (
             self.thr["sparse"], self.thr["gather"], self.thr["flat"])
