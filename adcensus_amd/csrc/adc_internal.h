@@ -326,6 +326,14 @@ struct adc_handle {
 hipError_t adc_launch_gray_census(adc_handle* h);
 hipError_t adc_launch_cost(adc_handle* h, float* vol_out);
 hipError_t adc_launch_cost_records(adc_handle* h);
+// The pipeline's front end (run_heavy without a paper mode; the debug stages, the paper modes and the redo paths keep the plain kernels):
+// one pass over both images = gray + census, packed left image, colour-step maps and cost records ...
+hipError_t adc_launch_front(adc_handle* h);
+hipError_t adc_launch_rrec_markers(adc_handle* h); // ... whose marker columns of the right records are written once per handle (alloc_all)
+// ... and behind it the arm words cleared, arms + maxima, then support counts, region boxes and aggregation records from one kernel
+hipError_t adc_launch_arm_words_clear(adc_handle* h);
+hipError_t adc_launch_build_arms(adc_handle* h);
+hipError_t adc_launch_sup_records(adc_handle* h);
 // first aggregation pass of the short-arm plan, element-wise (k_cost_agg_flat): writes the volume the small-ring fused-cost march would;
 // cap = the ring depth that march would have had, (small_variant, small_L) = its gate.  hipErrorInvalidValue: the geometry does not fit.
 bool adc_cost_agg_flat_fits(const adc_handle* h, int cap);

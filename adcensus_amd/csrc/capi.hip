@@ -151,6 +151,7 @@ static hipError_t alloc_all(adc_handle* h)
     h->rrec_padl = (p.dmin + p.Dp - 1 > 0 ? p.dmin + p.Dp - 1 : 0) + 1;
     h->rrec_pitch = h->rrec_padl + p.W + (p.dmin < 0 ? -p.dmin : 0) + 1;
     HIP_TRY(MEM_ONCE(h->cost_rrec, (size_t)p.H * h->rrec_pitch * 16));
+    HIP_TRY(adc_launch_rrec_markers(h)); // (the out-of-image columns never change: adc_launch_front writes the image's own columns only)
     HIP_TRY(MEM_ONCE(h->cost_lrec, P * 16));
     h->med_hpitch = ((p.W + 2 * p.H + 64 + 15) / 16) * 16;
     HIP_TRY(MEM_ONCE(h->med_hand, adc_median_hand_rows(p.H) * h->med_hpitch * sizeof(float))); // (bands + chains of <= 4 speculative copies per band, per column segment)
@@ -432,6 +433,17 @@ static hipError_t run_heavy(adc_handle* h, AdcRedo redo)
         MARK(2, h->heavy);
         HIP_OK(hipMemsetAsync(h->armmax + 2, 0, 2 * sizeof(int), h->heavy)); // failed seams, "assumed ring too shallow" flag
     } else {
+    // Without a paper mode the images are read ONCE (k_front: gray, census, packed left image, colour steps, cost records) and the
+    // support counts and the aggregation records come out of one kernel; the paper modes, a redo and ADC_FUSE_COST=0 run the plain
+    // kernels.  Either form is four enqueue steps.
+    const bool front = fuse_cost_now && h->paper == 0 && redo == ADC_REDO_NONE;
+    if (front) {
+        HIP_OK(adc_launch_front(h));             // ComputeCost, ADCensusStereo.cpp:84
+        MARK(1, h->heavy);
+        HIP_OK(adc_launch_arm_words_clear(h));   // CostAggregation, :92
+        HIP_OK(adc_launch_build_arms(h));
+        HIP_OK(adc_launch_sup_records(h));
+    } else {
     HIP_OK(adc_launch_gray_census(h));           // ComputeCost, ADCensusStereo.cpp:84
     // ADC_FUSE_COST (default on): the cost volume is never written -- the first aggregation pass computes each cost
     // in registers from packed pixel records (k_agg_march<.., COSTIN>); otherwise K2 writes it and pass 1 reads it back
@@ -439,6 +451,7 @@ static hipError_t run_heavy(adc_handle* h, AdcRedo redo)
     else HIP_OK(adc_launch_cost(h, h->vol_a));
     MARK(1, h->heavy);
     HIP_OK(adc_launch_arms(h));                  // CostAggregation, :92
+    }
     MARK(2, h->heavy);
     {   // The maximum arm lengths decide the ring depth of the aggregation kernels and whether same-direction pass pairs
         // can share a launch (k_aggregate.hip).  The host does NOT wait for them: it assumes the maxima of the previous
@@ -456,7 +469,7 @@ static hipError_t run_heavy(adc_handle* h, AdcRedo redo)
             arms = (AggArms)learn_arm_assumption(h->learned);
         }
     }
-    HIP_OK(adc_launch_records(h));
+    if (!front) HIP_OK(adc_launch_records(h));
     } // (!from_aggregation)
     {   // aggregator_.Aggregate(4), :164; the last pass may move into the scanline stage (the launcher decides: short-arm plan, arms <= 4, segmented row passes)
         const hipError_t e_ = adc_launch_aggregate(h, 4, arms, redo != ADC_REDO_NONE, fuse_cost_now, true);

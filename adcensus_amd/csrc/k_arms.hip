@@ -65,6 +65,14 @@ __device__ __forceinline__ uchar4 arm_lengths(const uint32_t* __restrict__ img, 
     return make_uchar4((unsigned char)len[0], (unsigned char)len[1], (unsigned char)len[2], (unsigned char)len[3]);
 }
 
+// maximum over the 64 lanes of a wave (every lane active), in every lane
+__device__ __forceinline__ int wave_max(int v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = adc_imax(v, __shfl_xor(v, m));
+    return v;
+}
+
 __global__ __launch_bounds__(256) void k_build_arms(const uint32_t* __restrict__ img_l, uchar4* __restrict__ arms, int W,
                                                     int H, int L1, int L2, int t1, int t2, int* __restrict__ armmax)
 {
@@ -78,9 +86,13 @@ __global__ __launch_bounds__(256) void k_build_arms(const uint32_t* __restrict__
     a = arm_lengths(img_l, W, H, x, y, L1, L2, t1, t2); // {left, right, top, bottom}
     arms[(size_t)y * W + x] = a;
     }
-    // image-wide maximum arm per direction (lets the aggregation pick its window depth from the data)
-    atomicMax(&smax[0], adc_imax((int)a.x, (int)a.y));
-    atomicMax(&smax[1], adc_imax((int)a.z, (int)a.w));
+    // image-wide maximum arm per direction (lets the aggregation pick its window depth from the data): reduced inside the wave
+    // first, one LDS atomic per wave and direction (256 same-address atomics per direction serialise in the LDS)
+    const int mh = wave_max(adc_imax((int)a.x, (int)a.y)), mv = wave_max(adc_imax((int)a.z, (int)a.w));
+    if ((threadIdx.x & 63) == 0) {
+        if (mh) atomicMax(&smax[0], mh);
+        if (mv) atomicMax(&smax[1], mv);
+    }
     __syncthreads();
     // monotone maximum: skip the (serialising, same-address) atomic when the value already there is large enough;
     // a stale read can only be too small, which just means one redundant atomic
@@ -185,6 +197,80 @@ __global__ __launch_bounds__(256) void k_make_records(const uchar4* __restrict__
     }
 }
 
+// k_sup_counts + k_make_records in one kernel (the pipeline's form): the thread that has summed ch, cv and the region box packs the
+// pixel's records itself -- no second read of arms, sup_h and sup_v.  Same values in the same buffers as the two kernels.  A workgroup
+// owns SR_TW x SR_TH pixels; the transposed rec_v / rec2_v go through an LDS tile, so that a wave stores runs of SR_TH records along y
+// (32 / 64 contiguous bytes) where every lane of k_make_records writes into a line of its own.
+#define SR_TW 32
+#define SR_TH 8
+__global__ __launch_bounds__(SR_TW* SR_TH) void k_sup_records(const uchar4* __restrict__ arms, uint16_t* __restrict__ sup_h,
+                                                              uint16_t* __restrict__ sup_v, uchar4* __restrict__ bbox,
+                                                              uint32_t* __restrict__ rec_h, uint32_t* __restrict__ rec_v,
+                                                              uint2* __restrict__ rec2_h, uint2* __restrict__ rec2_v, int W, int H, int L,
+                                                              int* __restrict__ armmax)
+{
+    __shared__ uint32_t s_rv[SR_TW][SR_TH + 1];
+    __shared__ uint2 s_rv2[SR_TW][SR_TH + 1];
+    __shared__ int snz[2];
+    const int x0 = blockIdx.x * SR_TW, y0 = blockIdx.y * SR_TH;
+    const int x = x0 + (threadIdx.x & (SR_TW - 1)), y = y0 + (threadIdx.x / SR_TW);
+    if (threadIdx.x < 2) snz[threadIdx.x] = 0;
+    bool nzh = false, nzv = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        const uchar4 a = arms[p];
+        uint32_t ch = 0, cv = 0;
+        int mla = 0, mra = 0;
+        for (int t = -(int)a.z; t <= (int)a.w; t++) {
+            const uchar4 q = arms[(size_t)(y + t) * W + x];
+            ch += (uint32_t)q.x + (uint32_t)q.y + 1u;
+            mla = adc_imax(mla, (int)q.x);
+            mra = adc_imax(mra, (int)q.y);
+        }
+        bbox[p] = make_uchar4(0, 0, (unsigned char)mla, (unsigned char)mra);
+        for (int t = -(int)a.x; t <= (int)a.y; t++) {
+            const uchar4 q = arms[p + t];
+            cv += (uint32_t)q.z + (uint32_t)q.w + 1u;
+        }
+        ch = (uint32_t)(uint16_t)ch; // (what k_make_records reads back from the 16-bit maps)
+        cv = (uint32_t)(uint16_t)cv;
+        sup_h[p] = (uint16_t)ch;
+        sup_v[p] = (uint16_t)cv;
+        const uint32_t rh = (uint32_t)a.x | ((uint32_t)a.y << 8) | (cv << 16);
+        const uint32_t rv = (uint32_t)a.z | ((uint32_t)a.w << 8) | (ch << 16);
+        rec_h[p] = rh;
+        s_rv[x - x0][y - y0] = rv;
+        nzh = adc_rec_changes_pixel(rh, true);
+        nzv = adc_rec_changes_pixel(rv, true);
+        if (rec2_h) {
+            const uint32_t nh = (uint32_t)a.x + a.y + 1u, nv = (uint32_t)a.z + a.w + 1u;
+            const uint32_t bias = (uint32_t)L + 1u;
+            rec2_h[p] = make_uint2((((uint32_t)a.x + bias) & 255u) | ((nh & 255u) << 8) | (cv << 16), __float_as_uint(1.0f / (float)cv));
+            s_rv2[x - x0][y - y0] = make_uint2((((uint32_t)a.z + bias) & 255u) | ((nv & 255u) << 8) | (ch << 16), __float_as_uint(1.0f / (float)ch));
+        }
+    }
+    __syncthreads();
+    {   // the tile, transposed: consecutive lanes = consecutive y of one column
+        const int tx = threadIdx.x / SR_TH, ty = threadIdx.x & (SR_TH - 1);
+        if (x0 + tx < W && y0 + ty < H) {
+            const size_t q = (size_t)(x0 + tx) * H + (y0 + ty);
+            rec_v[q] = s_rv[tx][ty];
+            if (rec2_v) rec2_v[q] = s_rv2[tx][ty];
+        }
+    }
+    // record densities, as in k_make_records
+    const int ch_ = __popcll(__ballot(nzh)), cv_ = __popcll(__ballot(nzv));
+    if ((threadIdx.x & 63) == 0) {
+        if (ch_) atomicAdd(&snz[0], ch_);
+        if (cv_) atomicAdd(&snz[1], cv_);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && snz[threadIdx.x] != 0) {
+        const int shard = (int)((blockIdx.y * gridDim.x + blockIdx.x) % ADC_NZ_SHARDS);
+        atomicAdd(&armmax[ADC_NZ_BASE + ((int)threadIdx.x * ADC_NZ_SHARDS + shard) * ADC_NZ_STRIDE], snz[threadIdx.x]);
+    }
+}
+
 hipError_t adc_launch_records(adc_handle* h)
 {
     const AdcParams& p = h->p;
@@ -236,6 +322,30 @@ hipError_t adc_launch_arms_rest(adc_handle* h)
     dim3 grid2(grid.x, grid.y, 2);
     hipLaunchKernelGGL(k_color_diffs, grid2, block, 0, h->heavy, h->img_l, h->img_r, h->cdiff_lh, h->cdiff_lv, h->cdiff_rh,
                        h->cdiff_rv, p.W, p.H);
+    return hipGetLastError();
+}
+// The pipeline's form of the stage (run_heavy, no paper mode), behind adc_launch_front, which has packed the left image and written
+// the colour-step maps: the arm words cleared, arms + maxima, then support counts, region boxes and the aggregation records from ONE
+// kernel.  Three launchers, one operation each: run_heavy enqueues them one after the other.
+hipError_t adc_launch_arm_words_clear(adc_handle* h)
+{
+    // [0],[1] maxima, [3] "assumed ring depth too small" flag (k_aggregate.hip), [ADC_NZ_BASE..] record densities (k_sup_records)
+    return hipMemsetAsync(h->armmax, 0, ADC_ARMMAX_WORDS * sizeof(int), h->heavy);
+}
+hipError_t adc_launch_build_arms(adc_handle* h)
+{
+    const AdcParams& p = h->p;
+    hipLaunchKernelGGL(k_build_arms, dim3((p.W + 63) / 64, (p.H + 3) / 4, 1), dim3(256, 1, 1), 0, h->heavy, h->bgrx_l,
+                       reinterpret_cast<uchar4*>(h->arms), p.W, p.H, p.opt.cross_L1, p.opt.cross_L2, p.opt.cross_t1, p.opt.cross_t2, h->armmax);
+    return hipGetLastError();
+}
+hipError_t adc_launch_sup_records(adc_handle* h)
+{
+    const AdcParams& p = h->p;
+    hipLaunchKernelGGL(k_sup_records, dim3((p.W + SR_TW - 1) / SR_TW, (p.H + SR_TH - 1) / SR_TH), dim3(SR_TW * SR_TH), 0, h->heavy,
+                       reinterpret_cast<const uchar4*>(h->arms), h->sup_h, h->sup_v, reinterpret_cast<uchar4*>(h->irv_bbox), h->rec_h,
+                       h->rec_v, reinterpret_cast<uint2*>(h->rec2_h), reinterpret_cast<uint2*>(h->rec2_v), p.W, p.H,
+                       adc_imax(0, adc_imin(p.opt.cross_L1, 255)), h->armmax);
     return hipGetLastError();
 }
 hipError_t adc_launch_arms(adc_handle* h) // (the whole stage: debug surface)

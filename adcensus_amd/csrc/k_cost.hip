@@ -81,8 +81,101 @@ hipError_t adc_launch_gray_census(adc_handle* h)
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------- K1, pipeline form
+// One pass over both images (grid z = image) in place of k_gray_census, k_pack_bgr, k_color_diffs and k_cost_records: a workgroup
+// loads its tile plus the census halo as packed B | G<<8 | R<<16 into LDS once, derives the gray tile from it (adc_gray, the unfused
+// f64 form) and writes per pixel the gray value, the 9x7 census (same interior rule, same skip for W <= 9 or H <= 7), the colour
+// steps dh / dv against the left / upper neighbour in the tile (0 at x = 0 / y = 0), the cost record {bgr, census lo, census hi, 0}
+// and -- left image -- the packed pixel.  The marker columns of the right records are not written here: they never change for a
+// handle (k_rrec_markers, once behind the allocation).  Same values in the same buffers as the four kernels.
+__global__ __launch_bounds__(CT_W* CT_H) void k_front(const uint8_t* __restrict__ img_l, const uint8_t* __restrict__ img_r,
+                                                       uint8_t* __restrict__ gray_l, uint8_t* __restrict__ gray_r,
+                                                       uint64_t* __restrict__ census_l, uint64_t* __restrict__ census_r,
+                                                       uint32_t* __restrict__ bgrx_l, uint8_t* __restrict__ lh, uint8_t* __restrict__ lv,
+                                                       uint8_t* __restrict__ rh, uint8_t* __restrict__ rv, uint4* __restrict__ lrec,
+                                                       uint4* __restrict__ rrec, int W, int H, int pitch, int padl)
+{
+    __shared__ uint8_t tile[CT_LH][CT_LW + 2];
+    __shared__ uint32_t sbgr[CT_LH][CT_LW];
+    const bool left = blockIdx.z == 0;
+    const uint8_t* img = left ? img_l : img_r;
+    const int x0 = blockIdx.x * CT_W, y0 = blockIdx.y * CT_H;
+    const int tid = threadIdx.y * CT_W + threadIdx.x;
+    for (int i = tid; i < CT_LH * CT_LW; i += CT_W * CT_H) {
+        const int ly = i / CT_LW, lx = i % CT_LW;
+        const int gx = x0 + lx - 3, gy = y0 + ly - 4;
+        uint8_t g = 0;
+        uint32_t c = 0;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const uint8_t* p = img + ((size_t)gy * W + gx) * 3;
+            c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+            g = adc_gray(p[0], p[1], p[2]);
+        }
+        tile[ly][lx] = g;
+        sbgr[ly][lx] = c;
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x, y = y0 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const int lx = threadIdx.x + 3, ly = threadIdx.y + 4;
+    const size_t p = (size_t)y * W + x;
+    const uint8_t c = tile[ly][lx];
+    (left ? gray_l : gray_r)[p] = c;
+    uint64_t v = 0;
+    if (W > 9 && H > 7 && y >= 4 && y < H - 4 && x >= 3 && x < W - 3) { // interior only (adcensus_util.cpp:12,17-18); others stay 0
+#pragma unroll
+        for (int r = -4; r <= 4; r++)
+#pragma unroll
+            for (int cc = -3; cc <= 3; cc++) {
+                v <<= 1;
+                v += (tile[ly + r][lx + cc] < c) ? 1u : 0u;
+            }
+    }
+    (left ? census_l : census_r)[p] = v;
+    const uint32_t me = sbgr[ly][lx];
+    (left ? lh : rh)[p] = x > 0 ? (uint8_t)adc_color_dist_max_u32(me, sbgr[ly][lx - 1]) : 0;
+    (left ? lv : rv)[p] = y > 0 ? (uint8_t)adc_color_dist_max_u32(me, sbgr[ly - 1][lx]) : 0;
+    const uint4 rec = make_uint4(me, (uint32_t)v, (uint32_t)(v >> 32), 0u);
+    if (left) {
+        bgrx_l[p] = me;
+        lrec[p] = rec;
+    } else {
+        rrec[(size_t)y * pitch + padl + x] = rec;
+    }
+}
+
+hipError_t adc_launch_front(adc_handle* h)
+{
+    const AdcParams& p = h->p;
+    dim3 grid((p.W + CT_W - 1) / CT_W, (p.H + CT_H - 1) / CT_H, 2), block(CT_W, CT_H, 1);
+    hipLaunchKernelGGL(k_front, grid, block, 0, h->heavy, h->img_l, h->img_r, h->gray_l, h->gray_r, h->census_l, h->census_r, h->bgrx_l,
+                       h->cdiff_lh, h->cdiff_lv, h->cdiff_rh, h->cdiff_rv, reinterpret_cast<uint4*>(h->cost_lrec),
+                       reinterpret_cast<uint4*>(h->cost_rrec), p.W, p.H, h->rrec_pitch, h->rrec_padl);
+    h->bgrx_valid = 1;
+    return hipGetLastError();
+}
+
+// The out-of-image marker columns of the right records (cost_computor.cpp:101-104: bgrx = 0xFFFFFFFF -> cost 1.0), padl to the left
+// of a row and pitch - padl - W to its right.  A handle's geometry is fixed, so they are written once, behind the allocation
+// (k_cost_records rewrites them with every launch; k_front leaves them alone).
+__global__ __launch_bounds__(256) void k_rrec_markers(uint4* __restrict__ rrec, int W, int H, int pitch, int padl)
+{
+    const int y = blockIdx.y;
+    int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pitch - W) return;
+    if (i >= padl) i += W;
+    rrec[(size_t)y * pitch + i] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+}
+hipError_t adc_launch_rrec_markers(adc_handle* h)
+{
+    const AdcParams& p = h->p;
+    hipLaunchKernelGGL(k_rrec_markers, dim3((h->rrec_pitch - p.W + 255) / 256, p.H), dim3(256), 0, h->stream, reinterpret_cast<uint4*>(h->cost_rrec),
+                       p.W, p.H, h->rrec_pitch, h->rrec_padl);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------- K2
-#define COST_TX 32           // pixels of one row per block
+#define COST_TX 32          // pixels of one row per block
 #define COST_MAXSEG (COST_TX + ADC_MAX_DISP_RANGE)
 
 template <int VPL>
