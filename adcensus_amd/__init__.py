@@ -235,6 +235,32 @@ class RegReport(C.Structure):
     _fields_ = [("src_valid", C.c_uint32), ("src_projected", C.c_uint32), ("dst_filled", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
+
+
+class VoxelGrid(C.Structure):
+    """adc_voxel_grid: leaf (edge of a voxel, unit of the calibration's baseline), the crop z_min <= Z <= z_max of the camera-frame Z,
+    flags (VOXEL_POSE), and the pose R (row-major) / t looked at only with the flag."""
+    _fields_ = [("leaf", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("flags", C.c_uint32), ("R", C.c_float * 9),
+                ("t", C.c_float * 3), ("reserved_", C.c_uint32 * 4)]
+
+    def __init__(self, leaf=0.0, z_min=0.0, z_max=float("inf"), pose=None):
+        """pose: None, or (R, t) with R 3x3 (or 9 numbers, row-major) and t 3 numbers."""
+        super().__init__()
+        self.leaf, self.z_min, self.z_max = float(leaf), float(z_min), float(z_max)
+        self.R[0] = self.R[4] = self.R[8] = 1.0
+        if pose is not None:
+            R, t = pose
+            self.R = (C.c_float * 9)(*[float(x) for x in np.asarray(R, np.float32).ravel()])
+            self.t = (C.c_float * 3)(*[float(x) for x in np.asarray(t, np.float32).ravel()])
+            self.flags = VOXEL_POSE
+
+
+class VoxelReport(C.Structure):
+    """adc_voxel_report: cloud-valid pixels, points kept after crop and range, voxels."""
+    _fields_ = [("points_valid", C.c_uint32), ("points_kept", C.c_uint32), ("voxels", C.c_uint32)]
+
+
 POINT_DTYPE = np.dtype({"names": ["x", "y", "z", "r", "g", "b", "pad"], "formats": ["<f4", "<f4", "<f4", "u1", "u1", "u1", "u1"],
                         "offsets": [0, 4, 8, 12, 13, 14, 15], "itemsize": 16})
 
@@ -344,6 +370,13 @@ def lib():
         L.adc_get_register_report.argtypes = [vp, C.POINTER(RegReport)]
         for name in ("adc_set_register_target", "adc_clear_register_target", "adc_register_depth_device", "adc_align_color_device",
                      "adc_register_depth", "adc_align_color", "adc_get_register_report"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
+        L.adc_clear_cloud_voxel_grid.argtypes = [vp]
+        L.adc_get_voxel_report.argtypes = [vp, C.POINTER(VoxelReport)]
+        L.adc_farm_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
+        for name in ("adc_set_cloud_voxel_grid", "adc_clear_cloud_voxel_grid", "adc_get_voxel_report", "adc_farm_set_cloud_voxel_grid"):
             getattr(L, name).restype = C.c_int
     L.adc_wait.argtypes = [vp]
     L.adc_wait.restype = C.c_int
@@ -518,6 +551,13 @@ class PairFarm:
         """The speckle filter of ADCensusStereo.set_speckle_filter on every pipeline (adc_farm_set_speckle_filter); drain() first."""
         if lib().adc_farm_set_speckle_filter(self._f, int(max_size), float(max_diff)) != 0:
             raise RuntimeError("adc_farm_set_speckle_filter failed: " + last_error())
+
+    def set_cloud_voxel_grid(self, leaf, z_min=0.0, z_max=float("inf"), pose=None):
+        """The voxel grid of ADCensusStereo.set_cloud_voxel_grid on every pipeline (adc_farm_set_cloud_voxel_grid); leaf=None clears
+        it; drain() first."""
+        grid = None if leaf is None else VoxelGrid(leaf, z_min, z_max, pose)
+        if lib().adc_farm_set_cloud_voxel_grid(self._f, None if grid is None else C.byref(grid)) != 0:
+            raise RuntimeError("adc_farm_set_cloud_voxel_grid failed: " + last_error())
 
     def set_rectify_maps(self, side, raw, map_x, map_y):
         """ADCensusStereo.set_rectify_maps on every pipeline (adc_farm_set_rectify_maps); drain() first."""
@@ -807,6 +847,27 @@ class ADCensusStereo:
         if lib().adc_get_speckle_stats(self._h, C.byref(c), C.byref(rc), C.byref(rp)) != 0:
             raise RuntimeError("adc_get_speckle_stats failed")
         return int(c.value), int(rc.value), int(rp.value)
+
+    def set_cloud_voxel_grid(self, leaf, z_min=0.0, z_max=float("inf"), pose=None):
+        """Every later cloud of this object (all entry points) holds one point per occupied voxel of edge `leaf` among the points with
+        z_min <= Z <= z_max -- mean position and colour, pad = min(points, 255), in the order of the voxels' first pixels; the counts
+        count voxels (adc_set_cloud_voxel_grid).  pose: None or (R, t), the camera-frame point's way into the frame of the grid.  A
+        cloud then needs a calibration.  Raises when refused (a bad parameter, a Match pending) or on a HIP failure."""
+        grid = VoxelGrid(leaf, z_min, z_max, pose)
+        if lib().adc_set_cloud_voxel_grid(self._h, C.byref(grid)) != 0:
+            raise RuntimeError("adc_set_cloud_voxel_grid failed: " + last_error())
+
+    def clear_cloud_voxel_grid(self):
+        """Every later cloud is the plain cloud again (adc_clear_cloud_voxel_grid)."""
+        if lib().adc_clear_cloud_voxel_grid(self._h) != 0:
+            raise RuntimeError("adc_clear_cloud_voxel_grid failed: " + last_error())
+
+    def voxel_report(self):
+        """{"points_valid", "points_kept", "voxels"} of the last voxel cloud that wait() or a synchronous call has completed."""
+        rep = VoxelReport()
+        if lib().adc_get_voxel_report(self._h, C.byref(rep)) != 0:
+            raise RuntimeError("adc_get_voxel_report failed: " + last_error())
+        return {"points_valid": int(rep.points_valid), "points_kept": int(rep.points_kept), "voxels": int(rep.voxels)}
 
     # -- rectification of raw images in front of the match (adc_set_rectify_*) -------------------
     def set_rectify_maps(self, side, raw, map_x, map_y):

@@ -6,7 +6,7 @@
 // adc_destroy releases exactly that registry.  adc_create allocates what every Match needs (alloc_all: images, per-pixel maps, volumes,
 // tables, refinement state, pin_in / pin_out / pin_flags; upload_tables: ray_tab).  Everything optional is allocated by the first call
 // that needs it and kept until adc_destroy: out_words, map_buf[], os_cloud (products); sp_* (speckle filter); rect[], pin_raw
-// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
+// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
 // os_cloud, the raw buffers, ev_raw, reg_zbuf and the target-sized regs_* grow with the largest size asked for; their capacities count
 // elements of the field's own type.
 //
@@ -33,6 +33,7 @@
 #include "learn_plan.h"
 #include "agg_plan.h" // AggArms
 #include "dev_mem.h"
+#include "voxel_point.h" // VoxGrid
 
 #define ADC_WAVE 64
 
@@ -152,6 +153,7 @@ struct AdcRectSide {
 #define ADC_PIN_MEDIAN 0   // error flag of the banded median's hand-off (k_refine.hip)
 #define ADC_PIN_CLOUD 8    // point count of the last cloud (k_outputs.hip): adc_get_cloud_count
 #define ADC_PIN_SPECKLE 9  // three stat words of the last speckle filter run (k_speckle.hip): adc_get_speckle_stats
+#define ADC_PIN_VOXEL 12   // voxels, points_valid, points_kept of the last voxel cloud (k_voxel.hip): adc_get_voxel_report
 struct adc_handle {
     AdcParams p;
     int device;
@@ -260,6 +262,12 @@ struct adc_handle {
     float sp_max_diff;
     int32_t* sp_parent;   // device scratch, allocated on first use: parent [P], size [P], then the three stat words
     float* sp_map;        // the filtered map of a Match (out of place: a redo of adc_wait may patch disp_l only in part)
+    // optional voxel-grid filter of the cloud (k_voxel.hip; off = vox_set 0: the cloud's own kernels run, nothing of this is enqueued)
+    int vox_set;          // handle state (adc_set_cloud_voxel_grid): every later cloud is the voxel cloud
+    VoxGrid vox_grid;     // the caller's parameters and inv = 1.0f / leaf
+    void* vox_table;      // device scratch, allocated by the first set call: the hash table (adc_voxel_table_bytes, 64-byte slots) ...
+    uint32_t* vox_slot;   // ... the slot of every pixel [P] ...
+    uint32_t* vox_words;  // ... and the count words: voxels, points_valid, points_kept, then three counts per tile
     // optional rectification of raw images in front of the Match (k_rectify.hip; on = both sides set, off: nothing of it is enqueued)
     AdcRectSide rect[2];  // ADC_SIDE_LEFT, ADC_SIDE_RIGHT
     uint8_t* pin_raw;     // pinned staging of the two raw images (left at 0, right behind it)
@@ -366,9 +374,16 @@ hipError_t adc_launch_lrcheck(adc_handle* h);
 hipError_t adc_launch_confidence(adc_handle* h);                // k_extras.hip: vol_a -> req.conf (heavy stream, behind the WTA)
 hipError_t adc_launch_provenance(adc_handle* h);                // label, disp_l -> req.prov, req.conf = 0 where filled (object stream)
 size_t adc_outputs_scratch_bytes(int W, int H);                 // k_outputs.hip: bytes of out_words
-hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img); // disp -> depth, min / max words, tile counts
+// with_cloud = false: the cloud of the request is somebody else's (the voxel-grid filter), only depth / disp8 are computed
+hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img, bool with_cloud); // disp -> depth, min / max words, tile counts
 hipError_t adc_launch_out_scan(adc_handle* h);                  // tile counts -> tile bases, count words
-hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img);    // disp, img -> disp8, cloud
+hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img, bool with_cloud);    // disp, img -> disp8, cloud
+size_t adc_voxel_table_bytes(int W, int H);                     // k_voxel.hip: bytes of vox_table (cleared once per cloud)
+size_t adc_voxel_words_bytes(int W, int H);                     // ... and of vox_words
+hipError_t adc_launch_vox_insert(adc_handle* h, const float* disp, const uint8_t* img); // disp, img -> table, vox_slot, valid / kept per tile
+hipError_t adc_launch_vox_count(adc_handle* h);                 // leaders per tile; vox_slot keeps the leaders' slots only
+hipError_t adc_launch_vox_scan(adc_handle* h);                  // leader counts -> tile bases; the three report words, the count words
+hipError_t adc_launch_vox_emit(adc_handle* h);                  // table, vox_slot -> cloud
 hipError_t adc_launch_disp16(adc_handle* h, const float* disp, float scale, uint16_t* out);                  // disp -> 16-bit fixed point (k_disp16)
 size_t adc_speckle_scratch_words(int W, int H);                 // k_speckle.hip: int32 words of sp_parent
 hipError_t adc_launch_speckle_runs(adc_handle* h, const float* src, float max_diff);    // src -> row runs in parent, size = 0, stat words = 0

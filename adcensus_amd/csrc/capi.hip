@@ -537,18 +537,35 @@ static void collect_timings(adc_handle* h)
     }
 }
 
+// The voxel cloud of h->fly.req.out (k_voxel.hip): the table cleared, four launches with geometry-only grids, then the count word on
+// its way to pin_flags[ADC_PIN_CLOUD] as for the plain cloud (adc_wait, the staging and the farm deliver min(count, capacity)
+// records without knowing which cloud it is) and the three report words to pin_flags[ADC_PIN_VOXEL..] (adc_get_voxel_report)
+static hipError_t enqueue_voxel_cloud(adc_handle* h, const float* disp, const uint8_t* img)
+{
+    HIP_OK(hipMemsetAsync(h->vox_table, 0, adc_voxel_table_bytes(h->p.W, h->p.H), h->stream));
+    HIP_OK(adc_launch_vox_insert(h, disp, img));
+    HIP_OK(adc_launch_vox_count(h));
+    HIP_OK(adc_launch_vox_scan(h));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_CLOUD, h->vox_words, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream)); // adc_get_cloud_count
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_VOXEL, h->vox_words, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(adc_launch_vox_emit(h));
+    return hipSuccess;
+}
+
 // depth / point cloud / 8-bit image of h->fly.req.out from a device-resident map (k_outputs.hip), on the object stream; only what was
 // asked for is launched
 static hipError_t enqueue_outputs(adc_handle* h, const float* disp, const uint8_t* img)
 {
     const AdcOutReq& r = h->fly.req.out;
+    const bool voxel = r.cloud && h->vox_set; // the cloud is the voxel cloud: its part of measure / scan / emit is replaced
     if (r.disp8) HIP_OK(hipMemsetAsync(h->out_words, 0, 2 * sizeof(uint32_t), h->stream)); // (the min / max words)
-    HIP_OK(adc_launch_out_measure(h, disp, img));
-    if (r.cloud) {
+    if (!voxel || r.depth || r.disp8) HIP_OK(adc_launch_out_measure(h, disp, img, !voxel));
+    if (r.cloud && !voxel) {
         HIP_OK(adc_launch_out_scan(h));
         HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_CLOUD, h->out_words + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream)); // adc_get_cloud_count
     }
-    if (r.cloud || r.disp8) HIP_OK(adc_launch_out_emit(h, disp, img));
+    if ((r.cloud && !voxel) || r.disp8) HIP_OK(adc_launch_out_emit(h, disp, img, !voxel));
+    if (voxel) HIP_TRY(enqueue_voxel_cloud(h, disp, img));
     return hipSuccess;
 }
 
@@ -655,7 +672,7 @@ static void abort_match(adc_handle* h)
     (void)hipGetLastError();
     inflight_reset(h);
     learn_forget_densities(&h->learned);
-    if (h->pin_flags) { h->pin_flags[ADC_PIN_MEDIAN] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[ADC_PIN_SPECKLE] = h->pin_flags[ADC_PIN_SPECKLE + 1] = h->pin_flags[ADC_PIN_SPECKLE + 2] = 0; }
+    if (h->pin_flags) { h->pin_flags[ADC_PIN_MEDIAN] = 0; h->pin_flags[ADC_PIN_ARM + 0] = h->pin_flags[ADC_PIN_ARM + 1] = h->pin_flags[ADC_PIN_ARM + 2] = h->pin_flags[ADC_PIN_ARM + 3] = 0; h->pin_flags[ADC_PIN_SPECKLE] = h->pin_flags[ADC_PIN_SPECKLE + 1] = h->pin_flags[ADC_PIN_SPECKLE + 2] = 0; h->pin_flags[ADC_PIN_VOXEL] = h->pin_flags[ADC_PIN_VOXEL + 1] = h->pin_flags[ADC_PIN_VOXEL + 2] = 0; }
     images_own(h, true);
 }
 // the failure epilogue of the Match path: the message, everything in flight back to idle; code 2
@@ -941,6 +958,9 @@ static int outputs_prepare(adc_handle* h, const adc_outputs* o, const char* who,
     } else if (o->depth) {
         g_last_error = std::string(who) + ": depth needs a calibration";
         return 1;
+    } else if (o->cloud && h->vox_set) {
+        g_last_error = std::string(who) + ": a cloud with a voxel grid set needs a calibration";
+        return 1;
     }
     if (device_pointers && o->cloud && ((uintptr_t)o->cloud & 15u)) { g_last_error = std::string(who) + ": the cloud address must be 16-byte aligned"; return 1; }
     const size_t P = (size_t)h->p.W * h->p.H;
@@ -1173,6 +1193,65 @@ int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed
     if (components) *components = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE];
     if (removed_components) *removed_components = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE + 1];
     if (removed_pixels) *removed_pixels = (uint32_t)h->pin_flags[ADC_PIN_SPECKLE + 2];
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ voxel-grid filter of the cloud (k_voxel.hip)
+// Handle state; enqueue_outputs runs the voxel launches in place of the cloud's part of its own, so every entry point and every redo
+// of adc_wait (each ends in enqueue_output) delivers the voxel cloud of the map it delivers.
+static bool voxel_grid_ok(const adc_voxel_grid* g, const char* who)
+{
+    const char* bad = nullptr;
+    if (!(__builtin_isfinite(g->leaf) && g->leaf > 0.0f)) bad = "leaf must be finite and > 0";
+    else if (!(g->z_min <= g->z_max)) bad = "z_min <= z_max is required (neither may be NaN)";
+    else if (g->flags & ~ADC_VOXEL_POSE) bad = "unknown flags";
+    else if (g->reserved[0] | g->reserved[1] | g->reserved[2] | g->reserved[3]) bad = "the reserved words must be 0";
+    for (int i = 0; !bad && (g->flags & ADC_VOXEL_POSE) && i < 12; i++)
+        if (!__builtin_isfinite(i < 9 ? g->R[i] : g->t[i - 9])) bad = "the pose has a non-finite field";
+    if (!bad) return true;
+    g_last_error = std::string(who) + ": " + bad;
+    return false;
+}
+
+int adc_set_cloud_voxel_grid(adc_handle* h, const adc_voxel_grid* grid)
+{
+    if (!h) { g_last_error = "adc_set_cloud_voxel_grid: null handle"; return 1; }
+    if (!grid) { g_last_error = "adc_set_cloud_voxel_grid: null grid"; return 1; }
+    if (!voxel_grid_ok(grid, "adc_set_cloud_voxel_grid")) return 1;
+    if (match_in_flight(h)) { g_last_error = "adc_set_cloud_voxel_grid: a Match is pending (adc_wait first)"; return 1; }
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    if (MEM_ONCE(h->vox_table, adc_voxel_table_bytes(h->p.W, h->p.H)) != hipSuccess || MEM_ONCE(h->vox_slot, P * sizeof(uint32_t)) != hipSuccess ||
+        MEM_ONCE(h->vox_words, adc_voxel_words_bytes(h->p.W, h->p.H)) != hipSuccess) {
+        h->vox_set = 0;
+        return scratch_failed("adc_set_cloud_voxel_grid");
+    }
+    VoxGrid v;
+    memset(&v, 0, sizeof(v));
+    v.leaf = grid->leaf;
+    v.inv = 1.0f / grid->leaf;
+    v.z_min = grid->z_min; v.z_max = grid->z_max;
+    v.flags = grid->flags;
+    if (grid->flags & ADC_VOXEL_POSE) { memcpy(v.R, grid->R, sizeof(v.R)); memcpy(v.t, grid->t, sizeof(v.t)); }
+    h->vox_grid = v;
+    h->vox_set = 1;
+    return 0;
+}
+
+int adc_clear_cloud_voxel_grid(adc_handle* h)
+{
+    if (!h) { g_last_error = "adc_clear_cloud_voxel_grid: null handle"; return 1; }
+    if (match_in_flight(h)) { g_last_error = "adc_clear_cloud_voxel_grid: a Match is pending (adc_wait first)"; return 1; }
+    h->vox_set = 0;
+    return 0;
+}
+
+int adc_get_voxel_report(adc_handle* h, adc_voxel_report* out)
+{
+    if (!h || !out || !h->pin_flags) { g_last_error = "adc_get_voxel_report: null argument"; return 1; }
+    out->voxels = (uint32_t)h->pin_flags[ADC_PIN_VOXEL];
+    out->points_valid = (uint32_t)h->pin_flags[ADC_PIN_VOXEL + 1];
+    out->points_kept = (uint32_t)h->pin_flags[ADC_PIN_VOXEL + 2];
     return 0;
 }
 
@@ -1803,6 +1882,17 @@ static bool farm_idle(adc_farm* f, const char* who)
     for (size_t i = 0; i < f->pipes.size(); i++)
         if (f->in_flight[i]) { g_last_error = std::string(who) + ": a pair is in flight (adc_farm_drain first)"; return false; }
     return true;
+}
+int adc_farm_set_cloud_voxel_grid(adc_farm* f, const adc_voxel_grid* grid)
+{
+    if (!f) { g_last_error = "adc_farm_set_cloud_voxel_grid: null farm"; return 1; }
+    if (grid && !voxel_grid_ok(grid, "adc_farm_set_cloud_voxel_grid")) return 1;
+    if (!farm_idle(f, "adc_farm_set_cloud_voxel_grid")) return 1;
+    for (size_t i = 0; i < f->pipes.size(); i++) {
+        const int rc = grid ? adc_set_cloud_voxel_grid(f->pipes[i], grid) : adc_clear_cloud_voxel_grid(f->pipes[i]);
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 int adc_farm_set_rectify_maps(adc_farm* f, int side, const adc_raw_format* raw, const float* map_x, const float* map_y)
 {

@@ -277,14 +277,14 @@ size_t adc_outputs_scratch_bytes(int W, int H)
 
 // The three launchers: disp is any device-resident map of the handle's geometry, img the left image; what h->fly.req.out asks for decides
 // what a kernel does.  capi.hip (enqueue_outputs) orders them and owns every other HIP call of the path.
-static OutArgs out_args(adc_handle* h, const float* disp, const uint8_t* img)
+static OutArgs out_args(adc_handle* h, const float* disp, const uint8_t* img, bool with_cloud)
 {
     const AdcOutReq& r = h->fly.req.out;
     OutArgs g;
     g.disp = disp;
     g.img = img;
     g.depth = r.depth;
-    g.cloud = static_cast<uint4*>(r.cloud);
+    g.cloud = with_cloud ? static_cast<uint4*>(r.cloud) : nullptr;
     g.disp8 = r.disp8;
     g.words = h->out_words;
     g.count_out = r.cloud_count;
@@ -296,9 +296,9 @@ static OutArgs out_args(adc_handle* h, const float* disp, const uint8_t* img)
     return g;
 }
 
-hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img)
+hipError_t adc_launch_out_measure(adc_handle* h, const float* disp, const uint8_t* img, bool with_cloud)
 {
-    const OutArgs g = out_args(h, disp, img);
+    const OutArgs g = out_args(h, disp, img, with_cloud);
     hipLaunchKernelGGL(k_out_measure, dim3((unsigned)((g.P + OUT_TILE - 1) / OUT_TILE)), dim3(OUT_WG), 0, h->stream, g);
     return hipGetLastError();
 }
@@ -310,9 +310,9 @@ hipError_t adc_launch_out_scan(adc_handle* h)
     return hipGetLastError();
 }
 
-hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img)
+hipError_t adc_launch_out_emit(adc_handle* h, const float* disp, const uint8_t* img, bool with_cloud)
 {
-    const OutArgs g = out_args(h, disp, img);
+    const OutArgs g = out_args(h, disp, img, with_cloud);
     hipLaunchKernelGGL(k_out_emit, dim3((unsigned)((g.P + OUT_TILE - 1) / OUT_TILE)), dim3(OUT_WG), 0, h->stream, g);
     return hipGetLastError();
 }

@@ -263,4 +263,7 @@ bool ADCensusStereo::AlignColor(const float32* map, int input_kind, const adc_ca
 {
     return impl_ && adc_align_color(impl_, map, input_kind, calib, target_bgr, bgr_out, valid) == 0;
 }
+bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
+bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
+bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }
 const char* ADCensusStereo::LastError() const { return adc_last_error(); }

@@ -14,6 +14,9 @@
 // writes the device-side outputs of ADCensusStereo::MatchOut:
 //   <out>-depth.pfm  float32 depth Z = f * B / (|d| + doffs), +inf where invalid
 //   <out>-cloud.ply  binary little-endian PLY of the valid pixels in raster order: x y z float, red green blue uchar
+// --voxel LEAF[,ZMIN,ZMAX] (anywhere after the program name; needs --calib) switches the device-side voxel-grid filter of the cloud on
+// (ADCensusStereo::SetCloudVoxelGrid): <out>-cloud.ply and <out>-cloud.txt ("x y z r g b") then hold one point per occupied voxel of edge
+// LEAF (the unit of the calibration's baseline) among the points with ZMIN <= Z <= ZMAX (default: 0 and +inf).
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -321,6 +324,27 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_voxel = false; // (--voxel and its value likewise; checked before anything touches a device)
+    adc_voxel_grid voxel_grid;
+    memset(&voxel_grid, 0, sizeof(voxel_grid));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--voxel")) {
+            char tail = 0;
+            voxel_grid.z_min = 0.f;
+            voxel_grid.z_max = INFINITY;
+            int n = i + 1 < argc ? sscanf(argv[i + 1], "%f,%f,%f%c", &voxel_grid.leaf, &voxel_grid.z_min, &voxel_grid.z_max, &tail) : 0;
+            if (n == 1 && sscanf(argv[i + 1], "%f%c", &voxel_grid.leaf, &tail) != 1) n = 0; // (LEAF alone: nothing may follow it)
+            if ((n != 1 && n != 3) || !std::isfinite(voxel_grid.leaf) || voxel_grid.leaf <= 0.f ||
+                !(voxel_grid.z_min <= voxel_grid.z_max)) {
+                printf("--voxel needs LEAF[,ZMIN,ZMAX] (LEAF > 0 and finite, ZMIN <= ZMAX)\n");
+                return -1;
+            }
+            with_voxel = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_voxel && !with_calib) { printf("--voxel refused: it needs --calib\n"); return -1; }
     bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
     RectifyFile rect_file[2];
     for (int i = 1; i < argc; i++)
@@ -524,6 +548,7 @@ int main(int argc, char** argv)
     auto t1 = std::chrono::steady_clock::now();
     printf("AD-Census Initializing Done! Timing :	%lf s\n\n", std::chrono::duration<double>(t1 - t0).count());
     if (speckle_size > 0 && !ad_census.SetSpeckleFilter(speckle_size, speckle_diff)) { printf("speckle filter refused: %s\n", ad_census.LastError()); return -2; }
+    if (with_voxel && !ad_census.SetCloudVoxelGrid(&voxel_grid)) { printf("voxel grid refused: %s\n", ad_census.LastError()); return -2; }
     std::vector<uint8> rect_left; // (the rectified left image: the colours of the cloud file)
     if (with_rectify || with_raw) {
         std::vector<uint8> rect_right((size_t)w * h * 3, 0), rgb((size_t)w * h * 3);
@@ -573,7 +598,14 @@ int main(int argc, char** argv)
     if (!write_png(out + "-d.png", gray.data(), w, h, 1) || !write_png(out + "-c.png", col.data(), w, h, 3)) printf("cannot write %s-d.png / -c.png\n", out.c_str());
     // SaveDisparityCloud (main.cpp:212-230): x y |d| r g b, colours of the left image (stored B,G,R)
     FILE* f = fopen((out + "-cloud.txt").c_str(), "w");
-    if (f) {
+    if (f && with_voxel) { // the voxel rows: x y z r g b of every voxel, in the order of the cloud
+        adc_voxel_report vrep = {0, 0, 0};
+        ad_census.GetVoxelReport(&vrep);
+        printf("\nVoxel grid, leaf %g: %u valid points, %u kept, %u voxels\n", voxel_grid.leaf, vrep.points_valid, vrep.points_kept, vrep.voxels);
+        const size_t count = (size_t)ad_census.CloudCount();
+        for (size_t i = 0; i < count && i < cloud.size(); i++) fprintf(f, "%f %f %f %d %d %d\n", cloud[i].x, cloud[i].y, cloud[i].z, cloud[i].r, cloud[i].g, cloud[i].b);
+        fclose(f);
+    } else if (f) {
         for (int i = 0; i < h; i++)
             for (int j = 0; j < w; j++) {
                 const float32 a = fabsf(disparity[(size_t)i * w + j]);
@@ -672,8 +704,9 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < (size_t)w * h; i++) { rgb[3 * i] = aligned[3 * i + 2]; rgb[3 * i + 1] = aligned[3 * i + 1]; rgb[3 * i + 2] = aligned[3 * i]; }
             if (!write_png(out + "-aligned.png", rgb.data(), w, h, 3)) printf("cannot write %s-aligned.png\n", out.c_str());
             // the cloud holds the valid pixels (a = |d| finite, a + doffs > 0) in raster order: the k-th of them is the k-th point
+            // (a voxel cloud keeps the mean colours of the left image: a voxel is not a pixel)
             size_t k = 0;
-            for (size_t i = 0; i < (size_t)w * h && k < cloud.size(); i++) {
+            for (size_t i = 0; i < (size_t)w * h && k < cloud.size() && !with_voxel; i++) {
                 const float32 a = fabsf(disparity[i]);
                 if (!(std::isfinite(a) && a + calib.doffs > 0.0f)) continue;
                 cloud[k].r = aligned[3 * i + 2]; cloud[k].g = aligned[3 * i + 1]; cloud[k].b = aligned[3 * i];

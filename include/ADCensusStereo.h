@@ -32,6 +32,8 @@ struct adc_eval_report;
 struct adc_calib;
 struct adc_reg_target;
 struct adc_reg_report;
+struct adc_voxel_grid;
+struct adc_voxel_report;
 
 class ADCensusStereo {
 public:
@@ -134,6 +136,15 @@ public:
     /** The other direction: bgr_out uint8 [H][W][3] takes, per source pixel, the colour of target_bgr uint8 [Ht][Wt][3] at the pixel's
      *  projection (0 and valid = 0 where there is none); valid uint8 [H][W] may be null. */
     bool AlignColor(const float32* map, int input_kind, const adc_calib* calib, const uint8* target_bgr, uint8* bgr_out, uint8* valid);
+    /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
+     *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
+     *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then
+     *  needs a calibration.  State of the matcher object underneath: needs Initialize, and Initialize / Reset drop it.  false: a refused
+     *  grid (leaf not finite or <= 0, z_min > z_max or NaN, a non-finite pose), a Match pending, a HIP failure. */
+    bool SetCloudVoxelGrid(const adc_voxel_grid* grid);
+    bool ClearCloudVoxelGrid();
+    /** Valid points, points kept after crop and range, and voxels of the last voxel cloud completed on this object. */
+    bool GetVoxelReport(adc_voxel_report* report) const;
     const char* LastError() const;
 
 private:

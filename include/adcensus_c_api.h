@@ -233,6 +233,59 @@ int adc_set_speckle_filter(adc_handle* h, int32_t max_size, float max_diff);
 int adc_filter_speckles_device(adc_handle* h, void* d_disp_inout, int32_t max_size, float max_diff, void* d_labels);
 int adc_get_speckle_stats(adc_handle* h, uint32_t* components, uint32_t* removed_components, uint32_t* removed_pixels);
 
+/* -------------------------------------------------------------------------------------------
+ * Optional voxel-grid filter of the cloud on the device (k_voxel.hip), in front of the cloud's compaction: one adc_point per occupied
+ * voxel instead of one per valid pixel (PCL's VoxelGrid with integer means).  OFF by default: without a call of
+ * adc_set_cloud_voxel_grid every cloud is exactly what it was (same kernels, same launches, pad = 0).  tests/voxel_ref.py holds the
+ * definition in numpy; all float arithmetic is IEEE binary32, one rounding per operation, nothing fused, divisions correctly rounded.
+ *
+ *   parameters leaf (finite, > 0, in the unit of the calibration's baseline); z_min <= z_max (not NaN; z_max may be +inf); flags
+ *              (ADC_VOXEL_POSE); R row-major and t, looked at only with the flag and finite then; reserved words, all 0.
+ *              inv = 1.0f / leaf is computed once on the host.
+ *   point      validity and (X, Y, Z) of a pixel are exactly those of adc_outputs.cloud WITH a calibration; the colour is the left
+ *              image's.  A cloud request without a calibration while a grid is set is refused with 1.
+ *   crop       a pixel is kept iff z_min <= Z && Z <= z_max (the camera-frame Z, before any pose)
+ *   pose       with the flag Xw = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0], rows 1 and 2 likewise; without it Xw = X, ...
+ *   voxel      per axis u = Xw * inv; in range iff fabsf(u) < 1048576.0f (NaN fails; a point out of range on any axis is dropped);
+ *              i = floorf(u); f = u - i (one rounding: exactly 1.0f for a tiny negative u); q = min((uint32_t)(f * 65536.0f), 65535)
+ *              key = (uint64)(ix + 2^20) << 42 | (uint64)(iy + 2^20) << 21 | (uint64)(iz + 2^20)
+ *   aggregate  over the kept points of a voxel: n, the sums of q per axis, the sums of r, g, b, and leader = the lowest raster
+ *              index y * W + x among them.  Every sum is an integer (64 bits): the order of arrival cannot matter.
+ *   record     mq = (Sq + n / 2) / n in integers; x = ((float)ix + (float)mq * 0x1p-16f) * leaf (the inner product is exact: two
+ *              roundings), y and z likewise; r, g, b = (S + n / 2) / n; pad = min(n, 255)
+ *   order      voxels in ascending order of leader (the raster order of their first pixels).  count = voxels, whatever the capacity;
+ *              the first min(count, cloud_capacity) records are written and nothing behind them.  cloud_count and
+ *              adc_get_cloud_count report voxels.
+ *   report     adc_voxel_report: points_valid (cloud-valid pixels), points_kept (after crop and range), voxels
+ *
+ * adc_set_cloud_voxel_grid      handle state, like the speckle filter: every later cloud through every entry point (adc_match_out,
+ *                               _device_out, adc_reproject_device, adc_match_products, _async_products, _device_products,
+ *                               adc_farm_submit_products) is the voxel cloud, also behind every redo adc_wait can take.  Depth and
+ *                               disp8 are not touched.  Device scratch (a hash table of 64-byte slots, the smallest power of two
+ *                               >= 2 * W * H of them, and 4 bytes per pixel) is allocated by the first call and freed by adc_destroy.
+ *                               The struct is read before the call returns.
+ * adc_clear_cloud_voxel_grid    every later cloud is the plain cloud again.
+ * adc_get_voxel_report          of the last voxel cloud that adc_wait or a synchronous call has completed on this handle.
+ * adc_farm_set_cloud_voxel_grid all pipelines of a farm; a NULL grid clears it.
+ * Return codes: 0; 1 with adc_last_error and nothing changed (NULL handle / grid / report, a bad parameter, the setters while a
+ * Match / a pair is in flight); 2 on a HIP failure (the grid is then unset, the handle stays usable).
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_VOXEL_POSE (0x1u) /* R, t take the camera-frame point into the frame of the grid */
+typedef struct adc_voxel_grid {
+    float leaf;
+    float z_min, z_max;
+    uint32_t flags;
+    float R[9];
+    float t[3];
+    uint32_t reserved[4]; /* 0 */
+} adc_voxel_grid; /* 80 bytes */
+typedef struct adc_voxel_report {
+    uint32_t points_valid, points_kept, voxels;
+} adc_voxel_report;
+int adc_set_cloud_voxel_grid(adc_handle* h, const adc_voxel_grid* grid);
+int adc_clear_cloud_voxel_grid(adc_handle* h);
+int adc_get_voxel_report(adc_handle* h, adc_voxel_report* out);
+
 /* Host buffers, asynchronous (pinned staging inside the handle); adc_wait() completes it and
  * copies the result to disp_left given here. */
 int adc_match_async(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right, float* disp_left);
@@ -271,6 +324,8 @@ int adc_farm_wait(adc_farm* f, uint64_t ticket);
 int64_t adc_farm_drain(adc_farm* f);
 /* adc_set_speckle_filter on every pipeline of the farm (above); 1 while a pair is in flight (adc_farm_drain first). */
 int adc_farm_set_speckle_filter(adc_farm* f, int32_t max_size, float max_diff);
+/* adc_set_cloud_voxel_grid on every pipeline of the farm (above), NULL: adc_clear_cloud_voxel_grid; 1 while a pair is in flight. */
+int adc_farm_set_cloud_voxel_grid(adc_farm* f, const adc_voxel_grid* grid);
 
 /* -------------------------------------------------------------------------------------------
  * Optional rectification of raw camera images on the device (k_rectify.hip), off by default.  Handle state like the speckle filter:
