@@ -424,6 +424,11 @@ def lib():
     L.adc_debug_set_images.restype = C.c_int
     L.adc_debug_run.argtypes = [vp, C.c_int, C.c_int]
     L.adc_debug_run.restype = C.c_int
+    if hasattr(L, "adc_debug_read_itp_code"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_debug_itp_code_geometry.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.adc_debug_itp_code_geometry.restype = C.c_int
+        L.adc_debug_read_itp_code.argtypes = [vp, C.c_int, vp]
+        L.adc_debug_read_itp_code.restype = C.c_int
     L.adc_farm_create.argtypes = [i32, i32, C.POINTER(ADCensusOption), C.c_int, C.c_int]
     L.adc_farm_create.restype = vp
     L.adc_farm_destroy.argtypes = [vp]
@@ -1124,6 +1129,17 @@ class ADCensusStereo:
         rc = lib().adc_debug_write(self._h, which, a.ctypes.data)
         if rc != 0:
             raise RuntimeError("adc_debug_write(%d) failed: %s" % (which, last_error()))
+
+    def debug_read_itp_code(self, which_pass):
+        """Test hook: (padded code map of interpolation pass 0 / 1 as u8 [rows][pitch], columns of padding on the left)."""
+        pitch, rows, gx = C.c_int(0), C.c_int(0), C.c_int(0)
+        if lib().adc_debug_itp_code_geometry(self._h, C.byref(pitch), C.byref(rows), C.byref(gx)) != 0:
+            raise RuntimeError("adc_debug_itp_code_geometry failed: " + last_error())
+        out = np.empty((rows.value, pitch.value), dtype=np.uint8)
+        rc = lib().adc_debug_read_itp_code(self._h, int(which_pass), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("adc_debug_read_itp_code(%d) failed: %s" % (which_pass, last_error()))
+        return out, gx.value
 
     def debug_set_images(self, img_left, img_right):
         l, r = _img(img_left), _img(img_right)

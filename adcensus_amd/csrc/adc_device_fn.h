@@ -236,7 +236,7 @@ ADC_HD int adc_itp_coldist(const uint8_t* rowd, int cw, int ch, int cx, int cy)
 #define ADC_ITP_NS 8
 #endif
 #define ADC_ITP_LPAD 64
-ADC_HD int adc_itp_code_pitch(int W, int ms) { return (W + 2 * ms + 8 + 3) & ~3; } // (+8: k_itp_code stores whole dwords around the image's columns)
+ADC_HD int adc_itp_code_pitch(int W, int ms) { return (W + 2 * ms + 8 + 3) & ~3; } // (+8: k_itp_setup stores whole dwords around the image's columns)
 ADC_HD int adc_itp_code_rows(int H, int ms) { return H + ms; }
 static_assert((ADC_ITP_CAP + 1 - 1) * ADC_ITP_CELL - 1 < ADC_ITP_OUTSIDE && ADC_ITP_NS + (ADC_ITP_CAP * ADC_ITP_CELL - 1) + ADC_ITP_NS <= ADC_ITP_LPAD,
               "skip codes stay below the end codes; the table padding covers a trip behind the largest skip");

@@ -2080,6 +2080,26 @@ int adc_debug_write(adc_handle* h, int which, const void* src)
     return hipStreamSynchronize(h->stream) == hipSuccess ? 0 : 2;
 }
 
+int adc_debug_itp_code_geometry(adc_handle* h, int* pitch, int* rows, int* gx)
+{
+    if (!h || !pitch || !rows || !gx) return 1;
+    if (h->itp_pitch == 0) { g_last_error = "adc_debug_itp_code_geometry: this handle has no code maps (itp_plan.h)"; return 1; }
+    *pitch = h->itp_pitch;
+    *rows = adc_itp_code_rows(h->p.H, h->itp_ms);
+    *gx = h->itp_ms;
+    return 0;
+}
+
+int adc_debug_read_itp_code(adc_handle* h, int pass, void* dst)
+{
+    int pitch, rows, gx;
+    if (!dst || pass < 0 || pass > 1 || adc_debug_itp_code_geometry(h, &pitch, &rows, &gx) != 0) return 1;
+    hipSetDevice(h->device);
+    const uint8_t* code = h->itp_cells + adc_itp_code_offset(h->p.W, h->p.H) + (size_t)pass * adc_itp_code_stride(h->p.W, h->p.H, h->itp_ms);
+    if (hipMemcpyAsync(dst, code, (size_t)pitch * rows, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return 2;
+    return hipStreamSynchronize(h->stream) == hipSuccess ? 0 : 2;
+}
+
 int adc_debug_set_images(adc_handle* h, const uint8_t* left, const uint8_t* right)
 {
     if (!h || !left || !right) return 1;

@@ -265,66 +265,106 @@ __device__ __forceinline__ int packed_l1(uint32_t a, uint32_t b) // adc_color_di
 #define ITP_CELL ADC_ITP_CELL
 // cell / row / distance maps (one byte per cell each), then -- 16-byte aligned -- the padded code map of the walk
 // (per pass: cell / row / distance maps; behind both sets -- 16-byte aligned -- the two padded code maps of the walk)
-static size_t itp_cell_stride(int W, int H) { return adc_itp_cell_stride(W, H); } // (itp_plan.h: the layout and the byte counts)
-static size_t itp_code_offset(int W, int H) { return adc_itp_code_offset(W, H); }
+static size_t itp_code_offset(int W, int H) { return adc_itp_code_offset(W, H); } // (itp_plan.h: the layout and the byte counts)
 static size_t itp_code_stride(int W, int H, int ms) { return adc_itp_code_stride(W, H, ms); }
-// Validity of both interpolation passes in one set of launches (round 6): the second pass sees the first pass's fills, and EVERY target
+// Validity of both interpolation passes in one launch (round 6): the second pass sees the first pass's fills, and EVERY target
 // of the first pass is filled (a pixel no ray finds a value for gets 0.0f: multistep_refiner.cpp:246,270-272) -- so the second pass's
-// validity = valid pixels + invalid pixels of the mismatch list, known before the first pass runs.  Map 1 of every kernel (blockIdx.y)
-// is the second pass's.
-__device__ __forceinline__ bool itp_valid(const float* __restrict__ disp, const uint8_t* __restrict__ label, size_t p, int pass2)
+// validity = valid pixels + invalid pixels of the mismatch list, known before the first pass runs:
+//   itp_valid(p, pass) = disp[p] != ADC_INVALID_FLOAT || (pass == 1 && label[p] == ADC_LABEL_MISMATCH)
+// Cell maps, both distance passes and the code maps of the walk (adc_device_fn.h) in ONE tile kernel: nothing but the two padded code maps
+// leaves the workgroup (the three cell maps per pass of itp_plan.h's layout stay allocated and unused on this path).
+//   tile      ITP_T_DW dwords of ITP_T_CR * ITP_CELL code-map rows.  The dwords start at padded column gx & ~3, so dword k holds the
+//             pixels x = 4k - (gx & 3) .. + 3: the tile's pixels lie in ITP_T_CX = ITP_T_DW * 2 + 2 cell columns from ITP_T_DW * 2 * bx - 2 on.
+//   phase A   one wave per cell row (six rows per wave) of the tile plus a halo of ADC_ITP_CAP cells on every side, one lane per cell column (ITP_T_CX + 2 *
+//             ADC_ITP_CAP <= 64): the lane reads its cell's 2 x 2 pixels once for both passes; cells and pixels outside the image are
+//             absent.  A ballot per pass is the cell row as a bit mask, and adc_itp_rowdist is the distance from the lane's own bit to the
+//             nearest set bit of the 16 bits on either side of it: one shift, one count per side.  Row distances go to LDS, so do the
+//             pixel bits of the tile's own cells.
+//   phase B   adc_itp_coldist on the row distances in LDS, |dy| ascending: max(rowdist, |dy|) >= |dy|, so the scan ends where |dy| reaches
+//             the best so far.  A cell row outside the image has row distance ADC_ITP_CAP + 1 here, which is the value the scan starts from:
+//             the same as leaving the row out.  LDS keeps adc_itp_skip of the distance.
+//   phase C   four pixels of an image row per thread, one 32-bit store; the padding around the image (ADC_ITP_OUTSIDE) is written once,
+//             when the object is created.  `code` points at the first map's row 0, `gx` = columns of padding on the left.
+#define ITP_T_DW 14
+#define ITP_T_CX (ITP_T_DW * 4 / ITP_CELL + 2)
+#define ITP_T_CR 64
+#define ITP_T_HR (ITP_T_CR + 2 * ADC_ITP_CAP)
+#define ITP_T_WAVES 16
+static_assert(ITP_CELL == 2 && ADC_ITP_CAP == 16 && ITP_T_CX + 2 * ADC_ITP_CAP <= 64 && ITP_T_CX <= 32 && ITP_T_CR * 32 == 2048 && ITP_T_HR % ITP_T_WAVES == 0, "k_itp_setup: one lane per cell column, shifts below");
+__global__ __launch_bounds__(64 * ITP_T_WAVES) void k_itp_setup(const float* __restrict__ disp, const uint8_t* __restrict__ label, uint8_t* __restrict__ code,
+                                                                int W, int H, int pitch, int gx, size_t code_stride, int32_t* __restrict__ counters)
 {
-    return disp[p] != ADC_INVALID_FLOAT || (pass2 && label[p] == ADC_LABEL_MISMATCH);
-}
-__global__ __launch_bounds__(256) void k_itp_cells(const float* __restrict__ disp, const uint8_t* __restrict__ label, uint8_t* __restrict__ cell, int W, int H, int cw, int ch, size_t map_stride)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= cw * ch) return;
-    const int cy = c / cw, cx = c - cy * cw;
-    bool any = false;
+    __shared__ uint8_t rowd[2][ITP_T_HR][32]; // [pass][cell row with halo][tile cell column]
+    __shared__ uint8_t pixv[ITP_T_CR][32];    // pixel (r, q) of the cell valid: bit r * 2 + q in the first pass, bit 4 + r * 2 + q in the second
+    __shared__ uint8_t skip[2][ITP_T_CR][32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) counters[threadIdx.x] = 0; // the list lengths of k_interp_list2, which runs behind this kernel
+    const int cx0 = (int)blockIdx.x * (ITP_T_DW * 2) - 2 - ADC_ITP_CAP; // cell column of lane 0
+    const int cy0 = (int)blockIdx.y * ITP_T_CR - ADC_ITP_CAP;           // cell row of the tile's first row with halo
+    const int x0 = (cx0 + lane) * ITP_CELL;
+    // (the set-up waits for memory, not for bandwidth: every wave issues the loads of all its cell rows before it uses the first)
+    constexpr int NR = ITP_T_HR / ITP_T_WAVES;
+    float dv[NR][ITP_CELL * ITP_CELL];
+    uint8_t lv[NR][ITP_CELL * ITP_CELL];
 #pragma unroll
-    for (int r = 0; r < ITP_CELL; r++)
+    for (int j = 0; j < NR; j++)
 #pragma unroll
-        for (int q = 0; q < ITP_CELL; q++) {
-            const int y = cy * ITP_CELL + r, x = cx * ITP_CELL + q;
-            if (y < H && x < W) any = any || itp_valid(disp, label, (size_t)y * W + x, (int)blockIdx.y);
+        for (int t = 0; t < ITP_CELL * ITP_CELL; t++) {
+            const int y = (cy0 + wave + j * ITP_T_WAVES) * ITP_CELL + t / ITP_CELL, x = x0 + t % ITP_CELL;
+            const size_t p = ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) ? (size_t)y * W + x : 0; // (outside: any pixel, not looked at)
+            dv[j][t] = disp[p];
+            lv[j][t] = label[p];
         }
-    cell[blockIdx.y * map_stride + c] = any ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_itp_rowdist(const uint8_t* __restrict__ cell, uint8_t* __restrict__ rowd, int cw, int ch, size_t map_stride)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= cw * ch) return;
-    rowd[blockIdx.y * map_stride + c] = (uint8_t)adc_itp_rowdist(cell + blockIdx.y * map_stride, cw, c % cw, c / cw);
-}
-__global__ __launch_bounds__(256) void k_itp_coldist(const uint8_t* __restrict__ rowd, uint8_t* __restrict__ cdist, int cw, int ch, size_t map_stride)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= cw * ch) return;
-    cdist[blockIdx.y * map_stride + c] = (uint8_t)adc_itp_coldist(rowd + blockIdx.y * map_stride, cw, ch, c % cw, c / cw);
-}
-
-// The code map of the walk (adc_device_fn.h): four pixels of an image row per thread, one 32-bit store; the padding around the image
-// (ADC_ITP_OUTSIDE) is written once, when the object is created.  `code` points at the map's row 0, `gx` = columns of padding on the left.
-__global__ __launch_bounds__(256) void k_itp_code(const float* __restrict__ disp, const uint8_t* __restrict__ label, const uint8_t* __restrict__ cdist,
-                                                  uint8_t* __restrict__ code, int W, int H, int cw, int pitch, int gx, size_t cell_stride, size_t code_stride)
-{
-    cdist += blockIdx.y * cell_stride;
-    code += blockIdx.y * code_stride;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int q4 = (W + 3) >> 2; // threads per row; thread (y, k) covers the padded columns (gx & ~3) + 4k .. + 3
-    if (i >= q4 * H + H) return;
-    const int y = i / (q4 + 1), k = i - y * (q4 + 1);
-    const int c0 = (gx & ~3) + 4 * k;
-    uint32_t v = 0u;
 #pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const int x = c0 + b - gx;
-        uint32_t c = ADC_ITP_OUTSIDE;
-        if (x >= 0 && x < W) c = itp_valid(disp, label, (size_t)y * W + x, (int)blockIdx.y) ? (uint32_t)ADC_ITP_VALID : (uint32_t)adc_itp_skip(cdist[(y / ITP_CELL) * cw + (x / ITP_CELL)]);
-        v |= c << (8 * b);
+    for (int j = 0; j < NR; j++) {
+        const int lr = wave + j * ITP_T_WAVES;
+        uint32_t bits = 0u;
+#pragma unroll
+        for (int t = 0; t < ITP_CELL * ITP_CELL; t++) {
+            const int y = (cy0 + lr) * ITP_CELL + t / ITP_CELL, x = x0 + t % ITP_CELL;
+            const bool in = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+            const bool inv = dv[j][t] == ADC_INVALID_FLOAT, mis = lv[j][t] == ADC_LABEL_MISMATCH; // (itp_valid of both passes)
+            bits |= (in && !inv ? 1u : 0u) << t | (in && (!inv || mis) ? 1u : 0u) << (4 + t);
+        }
+        const unsigned long long m[2] = {__ballot((bits & 15u) != 0u), __ballot(bits != 0u)}; // (valid in the first pass: valid in the second)
+        if (lane >= ADC_ITP_CAP && lane < ADC_ITP_CAP + 32) {
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint32_t lo = (uint32_t)(m[k] >> (lane - ADC_ITP_CAP)) & 0x1ffffu; // bit 16 = the cell itself, bit 16 - n = n cells to the left
+                const uint32_t hi = (uint32_t)(m[k] >> lane) & 0x1ffffu;                  // bit 0 = the cell itself, bit n = n cells to the right
+                const int dl = lo ? __clz((int)lo) - 15 : ADC_ITP_CAP + 1, dr = hi ? __ffs((int)hi) - 1 : ADC_ITP_CAP + 1;
+                rowd[k][lr][lane - ADC_ITP_CAP] = (uint8_t)adc_imin(dl, dr);
+            }
+            if (lr >= ADC_ITP_CAP && lr < ADC_ITP_CAP + ITP_T_CR) pixv[lr - ADC_ITP_CAP][lane - ADC_ITP_CAP] = (uint8_t)bits;
+        }
     }
-    *reinterpret_cast<uint32_t*>(code + (size_t)y * pitch + c0) = v; // (pitch and c0 are multiples of 4; c0 + 3 <= gx + W + 6 < pitch: adc_itp_code_pitch)
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * ITP_T_CR * 32; i += 64 * ITP_T_WAVES) {
+        const int col = i & 31, row = (i >> 5) & (ITP_T_CR - 1), k = i >> 11;
+        int best = ADC_ITP_CAP + 1;
+        for (int dy = 0; dy <= ADC_ITP_CAP && dy < best; dy++)
+            best = adc_imin(best, adc_imax(adc_imin((int)rowd[k][row + ADC_ITP_CAP - dy][col], (int)rowd[k][row + ADC_ITP_CAP + dy][col]), dy));
+        skip[k][row][col] = (uint8_t)adc_itp_skip(best);
+    }
+    __syncthreads();
+    const int q4 = (W + 3) >> 2; // dwords 0 .. q4 of a row: dword k covers the padded columns (gx & ~3) + 4k .. + 3
+    for (int i = threadIdx.x; i < 2 * ITP_T_CR * ITP_CELL * ITP_T_DW; i += 64 * ITP_T_WAVES) {
+        const int kl = i % ITP_T_DW, r = (i / ITP_T_DW) & (ITP_T_CR * ITP_CELL - 1), pass = i / (ITP_T_DW * ITP_T_CR * ITP_CELL);
+        const int k = (int)blockIdx.x * ITP_T_DW + kl, y = (int)blockIdx.y * (ITP_T_CR * ITP_CELL) + r;
+        if (k > q4 || y >= H) continue;
+        uint32_t v = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int x = 4 * k + b - (gx & 3);
+            uint32_t c = ADC_ITP_OUTSIDE;
+            if ((unsigned)x < (unsigned)W) {
+                const int lc = (x >> 1) - (cx0 + ADC_ITP_CAP), lrow = r >> 1;
+                c = ((pixv[lrow][lc] >> (pass * 4 + (r & 1) * 2 + (x & 1))) & 1) ? (uint32_t)ADC_ITP_VALID : (uint32_t)skip[pass][lrow][lc];
+            }
+            v |= c << (8 * b);
+        }
+        *reinterpret_cast<uint32_t*>(code + pass * code_stride + (size_t)y * pitch + (gx & ~3) + 4 * k) = v; // (pitch and gx & ~3 are multiples of 4; the last byte is column gx + W + 6 < pitch at the most: adc_itp_code_pitch)
+    }
 }
 
 // Round 6: the walk on the CODE MAP (adc_device_fn.h).  SQ counters of the round-5 kernel said 11 400 vector-ALU instructions per wave
@@ -538,19 +578,14 @@ hipError_t adc_launch_interpolation(adc_handle* h, bool force_f64)
         // walk here never reads the map at a pixel its own pass writes: it tests the CODE map (a snapshot) and fetches map values only at
         // hits, which are valid pixels of that snapshot -- targets are invalid in it.  The second pass's snapshot counts the first
         // pass's targets as valid (all of them get filled), and its walk runs behind the first one: it reads their fills.
-        hipError_t e;
-        if ((e = hipMemsetAsync(h->interp_counters, 0, 8 * sizeof(int32_t), h->stream)) != hipSuccess) return e;
+        // The set-up kernel runs first: it also clears the two list lengths (no runtime fill in front of the list pass).
+        const size_t ks = itp_code_stride(p.W, p.H, h->itp_ms);
+        uint8_t* code = h->itp_cells + itp_code_offset(p.W, p.H);
+        hipLaunchKernelGGL(k_itp_setup, dim3((((p.W + 3) >> 2) + 1 + ITP_T_DW - 1) / ITP_T_DW, (p.H + ITP_T_CR * ITP_CELL - 1) / (ITP_T_CR * ITP_CELL)), dim3(64 * ITP_T_WAVES), 0,
+                           h->stream, h->disp_l, h->label, code, p.W, p.H, h->itp_pitch, h->itp_ms, ks, h->interp_counters);
         hipLaunchKernelGGL(k_interp_list2, dim3((P + 256 * ITP_LIST_PPT - 1) / (256 * ITP_LIST_PPT)), dim3(256), 0, h->stream, h->label, h->disp_l,
                            h->interp_list, h->interp_list + P, h->interp_counters, P);
         if (!h->bgrx_valid) hipLaunchKernelGGL(k_pack_bgr, dim3((P + 255) / 256), dim3(256), 0, h->stream, h->img_l, h->bgrx_l, P);
-        const int cw = (p.W + ITP_CELL - 1) / ITP_CELL, ch = (p.H + ITP_CELL - 1) / ITP_CELL, nc = cw * ch;
-        const size_t cs = itp_cell_stride(p.W, p.H), ks = itp_code_stride(p.W, p.H, h->itp_ms);
-        uint8_t* code = h->itp_cells + itp_code_offset(p.W, p.H);
-        hipLaunchKernelGGL(k_itp_cells, dim3((nc + 255) / 256, 2), dim3(256), 0, h->stream, h->disp_l, h->label, h->itp_cells, p.W, p.H, cw, ch, cs);
-        hipLaunchKernelGGL(k_itp_rowdist, dim3((nc + 255) / 256, 2), dim3(256), 0, h->stream, h->itp_cells, h->itp_cells + nc, cw, ch, cs);
-        hipLaunchKernelGGL(k_itp_coldist, dim3((nc + 255) / 256, 2), dim3(256), 0, h->stream, h->itp_cells + nc, h->itp_cells + 2 * nc, cw, ch, cs);
-        hipLaunchKernelGGL(k_itp_code, dim3((((p.W + 3) / 4 + 1) * p.H + 255) / 256, 2), dim3(256), 0, h->stream, h->disp_l, h->label, h->itp_cells + 2 * (size_t)nc,
-                           code, p.W, p.H, cw, h->itp_pitch, h->itp_ms, cs, ks);
         const size_t lin_bytes = (size_t)(max_search + ADC_ITP_LPAD) * 16 * sizeof(int32_t);
         const bool tab_lds = lin_bytes <= 40 * 1024; // (ranges up to 576; larger ones read the table from global memory)
         for (int k = 0; k < 2; k++) {

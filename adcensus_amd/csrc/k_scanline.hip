@@ -361,7 +361,7 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
         }                                                                                                      \
     } while (0)
     float Lp[VPL]; // previous path element's costs; padding lanes (d >= D) hold the sentinel
-    float minLp;
+    float minLp, lmin0; // (lmin0: the lane minimum of the first element, for its left-view winner)
     {
         const size_t pix = so_pixel<VERT>(g, e0);
         float c[VPL];
@@ -382,47 +382,57 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
             lmin = Lp[k] < lmin ? Lp[k] : lmin;
         }
         minLp = wave_min_f32<DPP>(lmin);
+        lmin0 = lmin;
     }
     // d-1 / d+1 neighbours of the lane's first / last disparity in the CURRENT costs (sentinels beyond the range):
     // needed by the next DP step and by the fused winner-takes-all, so they are computed once, right after Lp
     float upN = lane_up<DPP>(Lp[VPL - 1], ADC_LARGE_FLOAT, lane);
     float dnN = lane_down<DPP>(Lp[0], ADC_LARGE_FLOAT, lane);
-// Left-view winner of path element I, whose final costs are in Lp / minLp (pads hold Large_Float).  Only the cheap,
-// mostly scalar part runs per step: winner index (lowest set bit of a ballot against the path minimum -- lowest d
-// wins ties, like the reference's strict '>' scan), its two neighbour costs (readlane), and the minimum; they are
-// parked in lane (I & 63) of four accumulator registers.  Every 64 elements (and at the end of the path) SO_WTA_FLUSH
+// Left-view winner of path element I, whose final costs are in Lp / minLp (pads hold Large_Float) and whose lane minimum is LM.
+// Only the cheap, mostly scalar part runs per step.  The winning lane is the lowest set bit of ONE ballot of the lane minimum against
+// the path minimum: the lowest lane holds the lowest disparity, which wins ties like the reference's strict '>' scan.  Inside a lane
+// the first k with Lp[k] == minLp wins, and both neighbours of that k are already in the lane (upN / Lp[k - 1], Lp[k + 1] / dnN): the
+// lane picks its own k and neighbour costs, readlanes at the winning lane move them out (with two disparities per lane k is a bit of
+// the compare's own mask).  They are parked with the minimum in
+// lane (I & 63) of four accumulator registers (v_writelane).  Every 64 elements (and at the end of the path) the flush below
 // evaluates the edge rules and the sub-pixel parabola for 64 pixels at once, one pixel per lane.
     int wtaB = 0;
     float wtaC1 = 0.f, wtaC2 = 0.f, wtaM = 0.f;
-#define SO_WTA(I)                                                                                          \
+    int wtaNext = adc_imin(63, g.plen - 1); // the next element behind which the parked pixels are flushed
+#define SO_WTA(I, LM)                                                                                      \
     if constexpr (WTA) {                                                                                   \
-        int bi_ = 0x7fffffff;                                                                              \
-        _Pragma("unroll") for (int k = 0; k < VPL; k++)                                                    \
+        const unsigned long long m_ = __ballot((LM) == minLp);                                             \
+        const int lw_ = (int)__builtin_ctzll(m_); /* (m_ != 0: minLp is the minimum of the lanes' LM) */   \
+        int kw_ = VPL - 1;                                                                                 \
+        float s1_ = VPL == 1 ? upN : Lp[VPL == 1 ? 0 : VPL - 2], s2_ = dnN;                                \
+        bool e0_ = true;                                                                                   \
+        _Pragma("unroll") for (int k = VPL - 2; k >= 0; k--)                                               \
         {                                                                                                  \
-            const unsigned long long m_ = __ballot(Lp[k] == minLp);                                        \
-            const int c_ = m_ ? (int)__builtin_ctzll(m_) * VPL + k : 0x7fffffff;                           \
-            bi_ = c_ < bi_ ? c_ : bi_;                                                                     \
+            const bool e_ = Lp[k] == minLp;                                                                \
+            if (VPL > 2) kw_ = e_ ? k : kw_;                                                               \
+            s1_ = e_ ? (k == 0 ? upN : Lp[k == 0 ? 0 : k - 1]) : s1_;                                      \
+            s2_ = e_ ? Lp[k + 1 < VPL ? k + 1 : k] : s2_;                                                  \
+            e0_ = e_;                                                                                      \
         }                                                                                                  \
-        /* the reference scan only updates on cost < min, starting at Large_Float: nothing below -> best stays 0 */ \
-        const int best_ = minLp < ADC_LARGE_FLOAT ? bi_ + dmin : 0;                                        \
-        /* its two neighbour costs: every lane already holds the d-1 / d+1 neighbours of its own disparities */ \
-        const int idx_ = (best_ - dmin) & (64 * VPL - 1);                                                  \
-        const int kw_ = idx_ % VPL, lw_ = idx_ / VPL;                                                      \
-        float s1_ = upN, s2_ = VPL == 1 ? dnN : Lp[VPL == 1 ? 0 : 1];                                      \
-        _Pragma("unroll") for (int k = 1; k < VPL; k++)                                                    \
-        {                                                                                                  \
-            s1_ = kw_ == k ? Lp[k - 1] : s1_;                                                              \
-            s2_ = kw_ == k ? (k == VPL - 1 ? dnN : Lp[k == VPL - 1 ? k : k + 1]) : s2_;                    \
-        }                                                                                                  \
+        /* (two disparities per lane: k is one bit of the ballot the selects above need anyway) */         \
+        const int kk_ = VPL == 1 ? 0 : (VPL == 2 ? (int)((~__ballot(e0_) >> lw_) & 1ull) : __builtin_amdgcn_readlane(kw_, lw_)); \
         const int c1_ = __builtin_amdgcn_readlane(__float_as_int(s1_), lw_);                               \
         const int c2_ = __builtin_amdgcn_readlane(__float_as_int(s2_), lw_);                               \
+        /* the reference scan only updates on cost < min, starting at Large_Float: nothing below -> best stays 0 (every cost and */ \
+        /* sentinel is Large_Float then, whichever lane the neighbours come from).  The compare runs on the bit patterns, in the  */ \
+        /* scalar unit: Large_Float is positive and no cost is a NaN, so a < Large_Float exactly when bits(a) < bits(Large_Float) */ \
+        /* as signed integers (a negative float is a negative integer). */                                 \
+        const int best_ = __float_as_int(minLp) < __float_as_int(ADC_LARGE_FLOAT) ? lw_ * VPL + kk_ + dmin : 0; \
         const int slot_ = (I)&63;                                                                          \
-        const bool mine_ = lane == slot_; /* park the four scalars in lane (I & 63) */                       \
-        wtaB = mine_ ? best_ : wtaB;                                                                       \
-        wtaC1 = mine_ ? __int_as_float(c1_) : wtaC1;                                                       \
-        wtaC2 = mine_ ? __int_as_float(c2_) : wtaC2;                                                       \
-        wtaM = mine_ ? minLp : wtaM;                                                                       \
-        if (slot_ == 63 || (I) == g.plen - 1) {                                                            \
+        /* park the four scalars in lane (I & 63): two scalar sources of one VALU instruction are one too many for the constant */ \
+        /* bus unless the lane select is m0 */                                                             \
+        asm("s_mov_b32 m0, %4\n\tv_writelane_b32 %0, %5, m0\n\tv_writelane_b32 %1, %6, m0\n\t"             \
+            "v_writelane_b32 %2, %7, m0\n\tv_writelane_b32 %3, %8, m0"                                     \
+            : "+v"(wtaB), "+v"(wtaC1), "+v"(wtaC2), "+v"(wtaM)                                             \
+            : "s"(slot_), "s"(best_), "s"(c1_), "s"(c2_), "s"(minLp)                                       \
+            : "m0");                                                                                       \
+        if ((I) == wtaNext) { /* slot 63, or the end of the path */                                        \
+            wtaNext = adc_imin(wtaNext + 64, g.plen - 1);                                                  \
             const int e_ = ((I) & ~63) + lane; /* path element parked in this lane */                      \
             if (e_ <= (I)) {                                                                               \
                 float o_;                                                                                  \
@@ -433,7 +443,7 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
             }                                                                                              \
         }                                                                                                  \
     }
-    SO_WTA(0);
+    SO_WTA(0, lmin0);
     if (plen_v <= 1) return;
 
     int mcur = dir > 0 ? e0 + 1 : g.plen - 2 - e0; // coordinate of path element e0 + 1, advanced by every SO_STEP
@@ -476,7 +486,7 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
         minLp = wave_min_f32<DPP>(omin_);                                                                  \
         upN = lane_up<DPP>(Lp[VPL - 1], ADC_LARGE_FLOAT, lane);                                            \
         dnN = lane_down<DPP>(Lp[0], ADC_LARGE_FLOAT, lane);                                                \
-        SO_WTA(I);                                                                                         \
+        SO_WTA(I, omin_);                                                                                  \
         mcur += dir;                                                                                       \
     } while (0)
 // output store of the prefetch path: running pointer (path elements are visited in order)
@@ -520,7 +530,7 @@ __device__ __forceinline__ void so_body(const float* __restrict__ src, float* __
             upN = lane_up<DPP>(Lp[VPL - 1], ADC_LARGE_FLOAT, lane);                                        \
             dnN = lane_down<DPP>(Lp[0], ADC_LARGE_FLOAT, lane);                                            \
         }                                                                                                  \
-        SO_WTA(I);                                                                                         \
+        SO_WTA(I, omin_);                                                                                  \
     } while (0)
 
     if constexpr (VPL <= 2) {

@@ -744,6 +744,12 @@ enum {
 int adc_debug_read(adc_handle* h, int which, void* dst);
 /* Overwrites a device buffer from host (padding volumes). */
 int adc_debug_write(adc_handle* h, int which, const void* src);
+/* The padded code maps the interpolation's table walk reads (one byte per pixel: 255 valid, 254 outside the image, else the steps a
+ * ray may skip behind this pixel), as the last ADC_RUN_INTERPOLATION or Match left them.  Geometry: `pitch` bytes per row, `rows`
+ * rows, the image's column 0 at padded column `gx`, its row 0 at row 0.  pass 0 = the mismatch list's map, 1 = the occlusion list's;
+ * dst holds pitch * rows bytes.  Both return 1 on a handle that has no code maps (its search range or width rules the table walk out). */
+int adc_debug_itp_code_geometry(adc_handle* h, int* pitch, int* rows, int* gx);
+int adc_debug_read_itp_code(adc_handle* h, int pass, void* dst);
 /* Uploads the image pair without running anything. */
 int adc_debug_set_images(adc_handle* h, const uint8_t* bgr_left, const uint8_t* bgr_right);
 
