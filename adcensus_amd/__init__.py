@@ -235,6 +235,24 @@ class RegReport(C.Structure):
     _fields_ = [("src_valid", C.c_uint32), ("src_projected", C.c_uint32), ("dst_filled", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+NORMALS_MAX_RADIUS = 7  # ADC_NORMALS_MAX_RADIUS
+
+
+class NormalsParams(C.Structure):
+    """adc_normals_params: radius r in [1, 7] (a (2r+1) x (2r+1) window), max_diff in (0, 64] pixels of disparity (the gate that keeps
+    a window from fitting across a depth step), min_points in [3, (2r+1)^2]; flags and the reserved words 0."""
+    _fields_ = [("radius", C.c_int32), ("max_diff", C.c_float), ("min_points", C.c_int32), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 4)]
+
+    def __init__(self, radius=2, max_diff=1.0, min_points=5, flags=0):
+        super().__init__()
+        self.radius, self.max_diff, self.min_points, self.flags = int(radius), float(max_diff), int(min_points), int(flags)
+
+
+class NormalsReport(C.Structure):
+    """adc_normals_report: usable centres, and of those the fitted ones, those with fewer than min_points taps, the degenerate ones."""
+    _fields_ = [("usable", C.c_uint32), ("fitted", C.c_uint32), ("few_points", C.c_uint32), ("degenerate", C.c_uint32)]
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -370,6 +388,12 @@ def lib():
         L.adc_get_register_report.argtypes = [vp, C.POINTER(RegReport)]
         for name in ("adc_set_register_target", "adc_clear_register_target", "adc_register_depth_device", "adc_align_color_device",
                      "adc_register_depth", "adc_align_color", "adc_get_register_report"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_normals_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_normals_device.argtypes = [vp, vp, C.POINTER(Calib), C.POINTER(NormalsParams), vp, vp]
+        L.adc_normals.argtypes = [vp, vp, C.POINTER(Calib), C.POINTER(NormalsParams), vp, vp, C.POINTER(NormalsReport)]
+        L.adc_get_normals_report.argtypes = [vp, C.POINTER(NormalsReport)]
+        for name in ("adc_normals_device", "adc_normals", "adc_get_normals_report"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
@@ -1055,6 +1079,37 @@ class ADCensusStereo:
         rep = RegReport()
         if lib().adc_get_register_report(self._h, C.byref(rep)) != 0:
             raise RuntimeError("adc_get_register_report failed: " + last_error())
+        return rep
+
+    # -- surface normals from a disparity map (adc_normals_device / adc_normals / adc_get_normals_report) --------------------------
+    def normals_device(self, d_disp, calib, params=None, d_normals=None, d_normals8=None):
+        """Camera-facing surface normals of a device-resident float32 [H][W] disparity map (adc_normals_device; ints: device
+        addresses, normals float32 [H][W][4] 16-byte aligned / normals8 uint8 [H][W][4] or None; params a NormalsParams or None for
+        r = 2, max_diff = 1.0, min_points = 5); asynchronous, call wait(), then normals_report().  False when refused (a Match
+        pending, a bad calibration or parameter, no output, a misaligned address) or on a HIP failure."""
+        c = _calib(calib)
+        return lib().adc_normals_device(self._h, d_disp, None if c is None else C.byref(c), None if params is None else C.byref(params), d_normals,
+                                        d_normals8) == 0
+
+    def normals(self, disp, calib, params=None, normals=True, normals8=True):
+        """Host convenience (adc_normals): returns (normals float32 [H][W][4] or None, normals8 uint8 [H][W][4] or None,
+        NormalsReport).  Raises on failure."""
+        m = np.ascontiguousarray(disp, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        n = np.empty((self.height, self.width, 4), np.float32) if normals else None
+        n8 = np.empty((self.height, self.width, 4), np.uint8) if normals8 else None
+        c = _calib(calib)
+        rep = NormalsReport()
+        if lib().adc_normals(self._h, m.ctypes.data, None if c is None else C.byref(c), None if params is None else C.byref(params),
+                             None if n is None else n.ctypes.data, None if n8 is None else n8.ctypes.data, C.byref(rep)) != 0:
+            raise RuntimeError("adc_normals failed: " + last_error())
+        return n, n8, rep
+
+    def normals_report(self):
+        """The NormalsReport of the last normals call wait() has completed (adc_get_normals_report)."""
+        rep = NormalsReport()
+        if lib().adc_get_normals_report(self._h, C.byref(rep)) != 0:
+            raise RuntimeError("adc_get_normals_report failed: " + last_error())
         return rep
 
     def match_device(self, d_left, d_right, d_disp):

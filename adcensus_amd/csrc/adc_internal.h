@@ -6,7 +6,7 @@
 // adc_destroy releases exactly that registry.  adc_create allocates what every Match needs (alloc_all: images, per-pixel maps, volumes,
 // tables, refinement state, pin_in / pin_out / pin_flags; upload_tables: ray_tab).  Everything optional is allocated by the first call
 // that needs it and kept until adc_destroy: out_words, map_buf[], os_cloud (products); sp_* (speckle filter); rect[], pin_raw
-// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
+// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); nrm_*, nrms_* (surface normals); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
 // os_cloud, the raw buffers, ev_raw, reg_zbuf and the target-sized regs_* grow with the largest size asked for; their capacities count
 // elements of the field's own type.
 //
@@ -131,6 +131,7 @@ struct AdcInFlight {
     int force_median_fallback; // test hook (adc_debug_run ADC_RUN_MEDIAN 100 / 101): the next adc_wait takes the fallback path -> adc_wait
     int ev_pending;       // adc_evaluate_device: an evaluation was enqueued -> adc_wait moves ev_pin and ev_echo into ev_report
     int reg_pending;      // adc_register_depth_device: a registration was enqueued -> adc_wait moves reg_pin into reg_report
+    int nrm_pending;      // adc_normals_device: a normals kernel was enqueued -> adc_wait moves pin_flags[ADC_PIN_NORMALS..] into nrm_report
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
 static_assert(std::is_trivially_copyable<AdcInFlight>::value, "AdcInFlight is reset with memset");
@@ -154,6 +155,7 @@ struct AdcRectSide {
 #define ADC_PIN_CLOUD 8    // point count of the last cloud (k_outputs.hip): adc_get_cloud_count
 #define ADC_PIN_SPECKLE 9  // three stat words of the last speckle filter run (k_speckle.hip): adc_get_speckle_stats
 #define ADC_PIN_VOXEL 12   // voxels, points_valid, points_kept of the last voxel cloud (k_voxel.hip): adc_get_voxel_report
+#define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
     int device;
@@ -310,6 +312,13 @@ struct adc_handle {
     size_t regs_index_cap;
     uint8_t* regs_tbgr;
     size_t regs_tbgr_cap;
+    // optional surface normals from a disparity map (k_normals.hip; nothing of it exists before the first adc_normals_device)
+    uint32_t* nrm_rep;        // the four report words the kernel adds to (adc_normals_report); read back into pin_flags[ADC_PIN_NORMALS..]
+    adc_normals_report nrm_report; // adc_get_normals_report
+    int nrm_report_valid;
+    float* nrms_map;          // device scratch of adc_normals (host callers), each allocated on the first call that needs it
+    float* nrms_out;
+    uint8_t* nrms_out8;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -405,7 +414,9 @@ hipError_t adc_launch_eval_measure(adc_handle* h, const float* disp, const uint8
 hipError_t adc_launch_reg_scatter(adc_handle* h, const float* map, int kind, const adc_calib* calib, uint32_t flags); // k_register.hip: map -> keys in reg_zbuf, src counts
 hipError_t adc_launch_reg_resolve(adc_handle* h, float* depth, int32_t* index);                                       // reg_zbuf -> depth, index, dst_filled
 hipError_t adc_launch_reg_align(adc_handle* h, const float* map, int kind, const adc_calib* calib, const uint8_t* tbgr, uint8_t* out, uint8_t* valid);
-#define ADC_MEDB_MAX_SEG 12                    // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
+// k_normals.hip: map -> normals / normals8 (each may be NULL), counts added to nrm_rep; G = the gate in 1/1024 pixel
+hipError_t adc_launch_normals(adc_handle* h, const float* disp, const adc_calib* calib, int radius, int32_t G, int min_points, float* normals, uint8_t* normals8);
+#define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)
 int adc_irv_grid(size_t pixels);                // workgroups of the voting chain for an image of this size

@@ -881,7 +881,8 @@ static int wait_deliver(adc_handle* h)
     match_req_clear(h);
     return 0;
 }
-// (5) an evaluation / a registration has completed: its report words have arrived in the pinned block (adc_get_eval_report, adc_get_register_report)
+// (5) an evaluation / a registration / a normals call has completed: its report words have arrived in the pinned block (adc_get_eval_report,
+//     adc_get_register_report, adc_get_normals_report)
 static void wait_take_reports(adc_handle* h)
 {
     if (h->fly.ev_pending) {
@@ -894,6 +895,11 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->reg_report, h->reg_pin, sizeof(h->reg_report));
         h->reg_report_valid = 1;
         h->fly.reg_pending = 0;
+    }
+    if (h->fly.nrm_pending) {
+        memcpy(&h->nrm_report, h->pin_flags + ADC_PIN_NORMALS, sizeof(h->nrm_report));
+        h->nrm_report_valid = 1;
+        h->fly.nrm_pending = 0;
     }
 }
 
@@ -1762,6 +1768,91 @@ int adc_get_register_report(adc_handle* h, adc_reg_report* out)
     if (!h || !out) { g_last_error = "adc_get_register_report: null argument"; return 1; }
     if (!h->reg_report_valid) { g_last_error = "adc_get_register_report: no registration has completed on this handle"; return 1; }
     *out = h->reg_report;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ surface normals from a disparity map (k_normals.hip)
+// Stand-alone entry points in the style of the registration: the device form enqueues on the object stream and is completed by
+// adc_wait, which moves the four report words from pin_flags[ADC_PIN_NORMALS..] into nrm_report.
+static const adc_normals_params NRM_DEFAULT = {2, 1.0f, 5, 0u, {0u, 0u, 0u, 0u}};
+
+// validates a request; 0 with *p and *G filled, or 1 with adc_last_error (device: the outputs are device addresses -> alignment)
+static int nrm_check(adc_handle* h, const void* map, const adc_calib* calib, const adc_normals_params* params, const void* normals, const void* normals8, bool device,
+                     adc_normals_params* p, int32_t* G, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : NRM_DEFAULT;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (!calib) why = "null calibration";
+    else if (!(__builtin_isfinite(calib->focal_px) && __builtin_isfinite(calib->baseline) && __builtin_isfinite(calib->cx) && __builtin_isfinite(calib->cy) &&
+               __builtin_isfinite(calib->doffs)))
+        why = "the calibration has a non-finite field";
+    else if (!(calib->focal_px > 0.0f)) why = "the calibration's focal_px must be positive";
+    else if (p->radius < 1 || p->radius > ADC_NORMALS_MAX_RADIUS) why = "radius must lie in [1, 7]";
+    else if (!(__builtin_isfinite(p->max_diff) && p->max_diff > 0.0f && p->max_diff <= 64.0f)) why = "max_diff must be finite and lie in (0, 64]";
+    else if (p->min_points < 3 || p->min_points > (2 * p->radius + 1) * (2 * p->radius + 1)) why = "min_points must lie in [3, (2 * radius + 1)^2]";
+    else if (p->flags != 0u) why = "unknown flag";
+    else if (p->reserved_[0] | p->reserved_[1] | p->reserved_[2] | p->reserved_[3]) why = "a reserved word is not 0";
+    else if (!normals && !normals8) why = "no output requested";
+    else if (device && ((uintptr_t)normals & 15u)) why = "d_normals must be 16-byte aligned";
+    else if (device && ((uintptr_t)normals8 & 3u)) why = "d_normals8 must be 4-byte aligned";
+    else if (device && ((uintptr_t)map & 3u)) why = "d_disp must be 4-byte aligned";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    *G = (int32_t)__builtin_rintf(p->max_diff * 1024.0f);
+    return 0;
+}
+
+static hipError_t enqueue_normals(adc_handle* h, const float* map, const adc_calib* calib, const adc_normals_params& p, int32_t G, float* normals, uint8_t* normals8)
+{
+    HIP_TRY(MEM_ONCE(h->nrm_rep, sizeof(adc_normals_report)));
+    HIP_OK(hipMemsetAsync(h->nrm_rep, 0, sizeof(adc_normals_report), h->stream));
+    HIP_OK(adc_launch_normals(h, map, calib, p.radius, G, p.min_points, normals, normals8));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_NORMALS, h->nrm_rep, sizeof(adc_normals_report), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_normals_device(adc_handle* h, const void* d_disp, const adc_calib* calib, const adc_normals_params* params, void* d_normals, void* d_normals8)
+{
+    const char* who = "adc_normals_device";
+    adc_normals_params p;
+    int32_t G = 0;
+    if (nrm_check(h, d_disp, calib, params, d_normals, d_normals8, true, &p, &G, who) != 0) return 1;
+    hipSetDevice(h->device);
+    if (enqueue_normals(h, static_cast<const float*>(d_disp), calib, p, G, static_cast<float*>(d_normals), static_cast<uint8_t*>(d_normals8)) != hipSuccess)
+        return fail_call(h, who);
+    h->fly.nrm_pending = 1;
+    return 0;
+}
+
+int adc_normals(adc_handle* h, const float* disp, const adc_calib* calib, const adc_normals_params* params, float* normals, uint8_t* normals8, adc_normals_report* report)
+{
+    const char* who = "adc_normals";
+    adc_normals_params p;
+    int32_t G = 0;
+    if (nrm_check(h, disp, calib, params, normals, normals8, false, &p, &G, who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = MEM_ONCE(h->nrms_map, P * 4);
+    if (e == hipSuccess && normals) e = MEM_ONCE(h->nrms_out, P * 16);
+    if (e == hipSuccess && normals8) e = MEM_ONCE(h->nrms_out8, P * 4);
+    if (e != hipSuccess) return scratch_failed(who);
+    if ((e = ADC_HIP(hipMemcpy(h->nrms_map, disp, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_normals: upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_normals_device(h, h->nrms_map, calib, &p, normals ? h->nrms_out : nullptr, normals8 ? h->nrms_out8 : nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (normals && (e = ADC_HIP(hipMemcpy(normals, h->nrms_out, P * 16, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_normals: normals copy-out", e); return 2; }
+    if (normals8 && (e = ADC_HIP(hipMemcpy(normals8, h->nrms_out8, P * 4, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_normals: normals8 copy-out", e); return 2; }
+    if (report) *report = h->nrm_report;
+    return 0;
+}
+
+int adc_get_normals_report(adc_handle* h, adc_normals_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_normals_report: null argument"; return 1; }
+    if (!h->nrm_report_valid) { g_last_error = "adc_get_normals_report: no normals call has completed on this handle"; return 1; }
+    *out = h->nrm_report;
     return 0;
 }
 

@@ -263,6 +263,12 @@ bool ADCensusStereo::AlignColor(const float32* map, int input_kind, const adc_ca
 {
     return impl_ && adc_align_color(impl_, map, input_kind, calib, target_bgr, bgr_out, valid) == 0;
 }
+bool ADCensusStereo::Normals(const float32* disp, const adc_calib* calib, const adc_normals_params* params, float32* normals, uint8* normals8,
+                             adc_normals_report* report)
+{
+    return impl_ && adc_normals(impl_, disp, calib, params, normals, normals8, report) == 0;
+}
+bool ADCensusStereo::GetNormalsReport(adc_normals_report* report) { return impl_ && adc_get_normals_report(impl_, report) == 0; }
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

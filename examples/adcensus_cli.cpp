@@ -17,6 +17,11 @@
 // --voxel LEAF[,ZMIN,ZMAX] (anywhere after the program name; needs --calib) switches the device-side voxel-grid filter of the cloud on
 // (ADCensusStereo::SetCloudVoxelGrid): <out>-cloud.ply and <out>-cloud.txt ("x y z r g b") then hold one point per occupied voxel of edge
 // LEAF (the unit of the calibration's baseline) among the points with ZMIN <= Z <= ZMAX (default: 0 and +inf).
+// --normals R[,DIFF[,MIN]] (anywhere after the program name; needs --calib) computes camera-facing surface normals from the run's
+// disparity map on the device (ADCensusStereo::Normals: a plane fit over the (2R+1) x (2R+1) window, R in 1..7, among the taps within
+// DIFF pixels of disparity of the centre, default 1, needing at least MIN of them, default 5): <out>-n.png holds the normal map
+// (R, G, B = 128 + 127 * nx, ny, nz; black where there is no normal), and without --voxel the points of <out>-cloud.ply gain the float
+// properties nx ny nz (0 0 0 for a point without a normal).  A malformed flag is refused while the arguments are parsed.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -345,6 +350,30 @@ int main(int argc, char** argv)
             break;
         }
     if (with_voxel && !with_calib) { printf("--voxel refused: it needs --calib\n"); return -1; }
+    bool with_normals = false; // (--normals and its value likewise; checked before anything touches a device)
+    adc_normals_params normals_params;
+    memset(&normals_params, 0, sizeof(normals_params));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--normals")) {
+            char tail = 0;
+            normals_params.max_diff = 1.0f;
+            normals_params.min_points = 5;
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int n = sscanf(v, "%d,%f,%d%c", &normals_params.radius, &normals_params.max_diff, &normals_params.min_points, &tail);
+            if (n == 1 && sscanf(v, "%d%c", &normals_params.radius, &tail) != 1) n = 0; // (R alone: nothing may follow it)
+            if (n == 2 && sscanf(v, "%d,%f%c", &normals_params.radius, &normals_params.max_diff, &tail) != 2) n = 0;
+            const int side = (n >= 1 && normals_params.radius >= 1 && normals_params.radius <= ADC_NORMALS_MAX_RADIUS) ? 2 * normals_params.radius + 1 : 0;
+            if (n < 1 || n > 3 || side == 0 || !std::isfinite(normals_params.max_diff) || !(normals_params.max_diff > 0.f && normals_params.max_diff <= 64.f) ||
+                normals_params.min_points < 3 || normals_params.min_points > side * side) {
+                printf("--normals refused: it needs R[,DIFF[,MIN]] (R in 1..7, 0 < DIFF <= 64, 3 <= MIN <= (2R+1)^2)\n");
+                return -1;
+            }
+            with_normals = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
+    if (with_normals && !with_calib) { printf("--normals refused: it needs --calib\n"); return -1; }
     bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
     RectifyFile rect_file[2];
     for (int i = 1; i < argc; i++)
@@ -714,14 +743,42 @@ int main(int argc, char** argv)
             }
         }
     }
+    std::vector<float32> point_normals; // (--normals without --voxel: three floats per cloud point)
+    if (with_normals) { // the normal map of the delivered disparity map; the host pairs normals and cloud points, which share the pixel
+        std::vector<float32> nrm((size_t)w * h * 4);
+        std::vector<uint8> nrm8((size_t)w * h * 4), rgb((size_t)w * h * 3);
+        adc_normals_report rep;
+        if (!ad_census.Normals(disparity.data(), &calib, &normals_params, nrm.data(), nrm8.data(), &rep)) {
+            printf("normals refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        printf("\nNormals, radius %d: %u usable pixels, %u fitted, %u with too few points, %u degenerate\n", normals_params.radius, rep.usable, rep.fitted,
+               rep.few_points, rep.degenerate);
+        for (size_t i = 0; i < (size_t)w * h; i++) { rgb[3 * i] = nrm8[4 * i]; rgb[3 * i + 1] = nrm8[4 * i + 1]; rgb[3 * i + 2] = nrm8[4 * i + 2]; }
+        if (!write_png(out + "-n.png", rgb.data(), w, h, 3)) printf("cannot write %s-n.png\n", out.c_str());
+        if (!with_voxel) {
+            // the cloud holds the valid pixels (a = |d| finite, a + doffs > 0) in raster order: the k-th of them is the k-th point
+            for (size_t i = 0; i < (size_t)w * h; i++) {
+                const float32 a = fabsf(disparity[i]);
+                if (!(std::isfinite(a) && a + calib.doffs > 0.0f)) continue;
+                point_normals.insert(point_normals.end(), nrm.begin() + 4 * i, nrm.begin() + 4 * i + 3);
+            }
+        }
+    }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);
         const size_t count = (size_t)ad_census.CloudCount();
+        const bool ply_normals = with_normals && !with_voxel && point_normals.size() >= 3 * count;
         FILE* ply = fopen((out + "-cloud.ply").c_str(), "wb");
         if (ply) {
-            fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
-                         "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", count);
-            for (size_t i = 0; i < count; i++) { fwrite(&cloud[i].x, 4, 3, ply); fwrite(&cloud[i].r, 1, 3, ply); }
+            fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+                         "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", count,
+                    ply_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");
+            for (size_t i = 0; i < count; i++) {
+                fwrite(&cloud[i].x, 4, 3, ply);
+                if (ply_normals) fwrite(&point_normals[3 * i], 4, 3, ply);
+                fwrite(&cloud[i].r, 1, 3, ply);
+            }
             fclose(ply);
         } else printf("cannot write %s-cloud.ply\n", out.c_str());
     }

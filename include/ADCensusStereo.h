@@ -15,6 +15,7 @@
  * SetRectifyMaps / SetRectifyModel / ClearRectify / Rectify (optional rectification of raw camera images on the device, off by default),
  * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device),
  * SetRegisterTarget / ClearRegisterTarget / RegisterDepth / AlignColor (optional registration of depth into a second camera on the device),
+ * Normals / GetNormalsReport (optional camera-facing surface normals from a disparity map on the device),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -34,6 +35,8 @@ struct adc_reg_target;
 struct adc_reg_report;
 struct adc_voxel_grid;
 struct adc_voxel_report;
+struct adc_normals_params;
+struct adc_normals_report;
 
 class ADCensusStereo {
 public:
@@ -136,6 +139,14 @@ public:
     /** The other direction: bgr_out uint8 [H][W][3] takes, per source pixel, the colour of target_bgr uint8 [Ht][Wt][3] at the pixel's
      *  projection (0 and valid = 0 where there is none); valid uint8 [H][W] may be null. */
     bool AlignColor(const float32* map, int input_kind, const adc_calib* calib, const uint8* target_bgr, uint8* bgr_out, uint8* valid);
+    /** Optional surface normals from a float32 [H][W] host disparity map on the device (adc_normals, include/adcensus_c_api.h holds the
+     *  definition: a windowed plane fit in disparity space, solved exactly in integers).  calib the rectified left camera; params may be
+     *  null (r = 2, max_diff = 1.0, min_points = 5).  normals float32 [H][W][4] = the unit normal facing the camera and the support
+     *  count, zeros where there is none; normals8 uint8 [H][W][4] = the same as a normal-map image; either may be null, not both.
+     *  report may be null. */
+    bool Normals(const float32* disp, const adc_calib* calib, const adc_normals_params* params, float32* normals, uint8* normals8,
+                 adc_normals_report* report);
+    bool GetNormalsReport(adc_normals_report* report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

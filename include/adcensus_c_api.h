@@ -26,6 +26,8 @@
  *                         farm; plus a 16-bit fixed-point disparity map (adc_disp16_device: that kernel on any map)
  *   adc_set_register_target / adc_register_depth_device / adc_align_color_device   depth registered into a second camera on the
  *                         device (z-buffered scatter), and that camera's colours gathered into the left view
+ *   adc_normals_device /  camera-facing surface normals from any disparity map: a windowed plane fit in disparity space, solved
+ *   adc_normals           exactly in integers (float32 x 4 and / or a normal-map image of 4 bytes per pixel)
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -663,6 +665,69 @@ int adc_register_depth(adc_handle* h, const float* map, int input_kind, const ad
 int adc_align_color(adc_handle* h, const float* map, int input_kind, const adc_calib* calib, const uint8_t* target_bgr, uint8_t* bgr_out,
                     uint8_t* valid);
 int adc_get_register_report(adc_handle* h, adc_reg_report* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Surface normals from a disparity map on the device (a windowed plane fit in disparity space; k_normals.hip, the arithmetic is
+ * adcensus_amd/csrc/normals_fit.h, tests/normals_ref.py holds the same definition in numpy and the kernel matches it bit for bit).
+ * A plane in space is a plane in (x, y, disparity): the fit needs nine integer sums per pixel, its normal equations solve exactly in
+ * 64-bit integers and the 3D normal follows in closed form; every sum is an integer, so the result does not depend on the order of
+ * evaluation.  All float arithmetic is IEEE binary32, one rounding per operation, nothing fused, divisions and sqrtf correctly
+ * rounded, in the order written.
+ *
+ * Input: a float32 [H][W] map d of the handle's geometry (signed; a = fabsf(d)) and an adc_calib of the rectified LEFT camera.  Only
+ * focal_px, cx, cy and doffs enter the arithmetic; baseline is validated as elsewhere but cancels out.
+ * Parameters (adc_normals_params): radius r in [1, 7]; max_diff finite, in (0, 64] pixels; min_points in [3, (2r+1)^2]; flags = 0 and
+ * the reserved words 0.  The host computes G = (int32)rintf(max_diff * 1024.0f) once.
+ * Usable pixel: a finite and a < 32768.0f (+inf, -inf, NaN and huge values of a caller's own map are not usable); its fixed-point
+ * disparity is q = (int32)rintf(a * 1024.0f).
+ * Support of a usable centre (x, y): the taps (dx, dy) in [-r, r]^2 that lie inside the image, are usable and satisfy |e| <= G with
+ * e = q_tap - q_centre.  The centre is always a tap.  The gate keeps a window from fitting across a depth step.
+ * Sums (integers): n; Sx = sum dx, Sy = sum dy; Sxx, Sxy, Syy; Se = sum e, Sxe = sum dx*e, Sye = sum dy*e.  With r <= 7 and
+ * G <= 65536 every one of them fits int32.
+ * Solve, exact in int64: M = [[Sxx, Sxy, Sx], [Sxy, Syy, Sy], [Sx, Sy, n]]; Dt = det M (a Gram determinant: >= 0, and 0 when the taps
+ * are collinear); Na, Nb, Nc the determinants with column 0, 1 or 2 replaced by (Sxe, Sye, Se); |N*| < 2^57.  A fit exists iff
+ * n >= min_points and Dt > 0.
+ * Floats (each int64 -> float conversion is ONE rounding to nearest even):
+ *   Df = (float)Dt;  ga = ((float)Na / Df) * 0x1p-10f, gb likewise from Nb
+ *   dc = ((float)q_centre * 0x1p-10f) + (((float)Nc / Df) * 0x1p-10f);  s = dc + doffs; a fit needs s > 0
+ *   nx = ga * focal_px, ny = gb * focal_px, nz = ((ga * (cx - (float)x)) + (gb * (cy - (float)y))) + s
+ *   L = sqrtf(((nx*nx) + (ny*ny)) + (nz*nz)); it must be finite and > 0
+ * Why this is the normal: the fitted plane d = ga x' + gb y' + c maps to the 3D plane (ga f) X + (gb f) Y + nz Z = f B, and
+ * (nx, ny, nz) dotted with the pixel's viewing ray has the sign of s, so -(nx, ny, nz) / L always faces the camera.
+ * Outputs, device addresses, each optional but at least one:
+ *   normals   float32 [H][W][4], 16-byte aligned: (-nx/L, -ny/L, -nz/L, (float)n); (0, 0, 0, 0) where there is no normal
+ *   normals8  uint8 [H][W][4], 4-byte aligned: per component (uint8)((int)rintf(v * 127.0f) + 128), the fourth byte 255;
+ *             0, 0, 0, 0 where there is no normal (what a normal-map image holds)
+ *   adc_normals_report: usable, fitted, few_points (usable centre, n < min_points), degenerate (enough points but Dt == 0, s <= 0, or
+ *   L not finite or 0); usable = fitted + few_points + degenerate.  Read back through the handle's pinned block behind the kernel,
+ *   available after adc_wait.
+ *
+ * adc_normals_device      asynchronous on the handle's stream, completed by adc_wait.  params NULL: r = 2, max_diff = 1.0,
+ *                         min_points = 5.  The first call allocates the four report words (adc_create allocates nothing of this).
+ * adc_normals             the same with HOST pointers, synchronous; device scratch is allocated on the first call that needs it
+ *                         (freed by adc_destroy); report may be NULL.
+ * adc_get_normals_report  the report of the last call that adc_wait (or adc_normals) has completed.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued (a NULL handle, map or calib, a calibration adc_match_out would refuse,
+ * a parameter out of range, a nonzero flag or reserved word, no output requested, a misaligned device address, a Match pending --
+ * adc_wait first, for the reason given at adc_evaluate_device); 2 on a HIP failure (the handle stays usable).  The normals are not a
+ * product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_NORMALS_MAX_RADIUS 7
+typedef struct adc_normals_params {
+    int32_t radius;      /* r in [1, 7]: the window is (2r+1) x (2r+1) */
+    float max_diff;      /* the gate in pixels of disparity, (0, 64] */
+    int32_t min_points;  /* [3, (2r+1)^2] */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved_[4];
+} adc_normals_params;
+typedef struct adc_normals_report {
+    uint32_t usable, fitted, few_points, degenerate;
+} adc_normals_report;
+int adc_normals_device(adc_handle* h, const void* d_disp, const adc_calib* calib, const adc_normals_params* params, void* d_normals,
+                       void* d_normals8);
+int adc_normals(adc_handle* h, const float* disp, const adc_calib* calib, const adc_normals_params* params, float* normals,
+                uint8_t* normals8, adc_normals_report* report);
+int adc_get_normals_report(adc_handle* h, adc_normals_report* out);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
