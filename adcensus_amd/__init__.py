@@ -253,6 +253,25 @@ class NormalsReport(C.Structure):
     _fields_ = [("usable", C.c_uint32), ("fitted", C.c_uint32), ("few_points", C.c_uint32), ("degenerate", C.c_uint32)]
 
 
+MESH_MAX_STEP = 16  # ADC_MESH_MAX_STEP
+
+
+class MeshParams(C.Structure):
+    """adc_mesh_params: max_diff >= 0 pixels of disparity (+inf: no gate) joins two lattice pixels into an edge; step in [1, 16]: every
+    step-th column and row forms the lattice; flags and the reserved words 0."""
+    _fields_ = [("max_diff", C.c_float), ("step", C.c_int32), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 5)]
+
+    def __init__(self, max_diff=1.0, step=1, flags=0):
+        super().__init__()
+        self.max_diff, self.step, self.flags = float(max_diff), int(step), int(flags)
+
+
+class MeshReport(C.Structure):
+    """adc_mesh_report: valid lattice pixels, vertices, triangles, cells that emit two triangles / one; triangles = 2 * cells_two + cells_one."""
+    _fields_ = [("lattice_valid", C.c_uint32), ("vertices", C.c_uint32), ("triangles", C.c_uint32), ("cells_two", C.c_uint32), ("cells_one", C.c_uint32),
+                ("reserved_", C.c_uint32 * 3)]
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -394,6 +413,12 @@ def lib():
         L.adc_normals.argtypes = [vp, vp, C.POINTER(Calib), C.POINTER(NormalsParams), vp, vp, C.POINTER(NormalsReport)]
         L.adc_get_normals_report.argtypes = [vp, C.POINTER(NormalsReport)]
         for name in ("adc_normals_device", "adc_normals", "adc_get_normals_report"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_mesh_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_mesh_device.argtypes = [vp, vp, vp, C.POINTER(Calib), C.POINTER(MeshParams), vp, C.c_uint64, vp, vp, C.c_uint64, vp]
+        L.adc_mesh.argtypes = [vp, vp, vp, C.POINTER(Calib), C.POINTER(MeshParams), vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MeshReport)]
+        L.adc_get_mesh_report.argtypes = [vp, C.POINTER(MeshReport)]
+        for name in ("adc_mesh_device", "adc_mesh", "adc_get_mesh_report"):
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
@@ -1110,6 +1135,47 @@ class ADCensusStereo:
         rep = NormalsReport()
         if lib().adc_get_normals_report(self._h, C.byref(rep)) != 0:
             raise RuntimeError("adc_get_normals_report failed: " + last_error())
+        return rep
+
+    # -- triangle mesh from a disparity map (adc_mesh_device / adc_mesh / adc_get_mesh_report) -------------------------------------
+    def mesh_device(self, d_disp, calib=None, params=None, d_bgr_left=None, d_vertices=None, vertex_capacity=0, d_vertex_index=None, d_triangles=None,
+                    triangle_capacity=0, d_counts=None):
+        """Triangle mesh of a device-resident float32 [H][W] disparity map (adc_mesh_device; ints: device addresses or None; vertices
+        adc_point records, 16-byte aligned; vertex_index int32; triangles uint32 x 3; counts uint32 [2] = vertices, triangles; params
+        a MeshParams or None for max_diff = 1.0, step = 1; calib None for no calibration); asynchronous, call wait(), then
+        mesh_report().  False when refused (a Match pending, a bad calibration or parameter, no output, a misaligned address) or on a
+        HIP failure."""
+        c = _calib(calib)
+        return lib().adc_mesh_device(self._h, d_disp, d_bgr_left, None if c is None else C.byref(c), None if params is None else C.byref(params), d_vertices,
+                                     int(vertex_capacity), d_vertex_index, d_triangles, int(triangle_capacity), d_counts) == 0
+
+    def mesh(self, disp, calib=None, params=None, bgr_left=None):
+        """Host convenience (adc_mesh): returns (vertices POINT_DTYPE [n], vertex_index int32 [n], triangles uint32 [m][3], MeshReport);
+        sized at the worst case of the lattice and trimmed to the counts.  Raises on failure."""
+        m = np.ascontiguousarray(disp, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        img = None
+        if bgr_left is not None:
+            img = np.ascontiguousarray(bgr_left, dtype=np.uint8)
+            assert img.size == 3 * m.size, img.shape
+        step = 1 if params is None else int(params.step)
+        wl, hl = ((self.width - 1) // step + 1, (self.height - 1) // step + 1) if 1 <= step <= MESH_MAX_STEP else (1, 1)
+        vcap, tcap = wl * hl, 2 * (wl - 1) * (hl - 1)
+        v = np.zeros(vcap, POINT_DTYPE)
+        vi = np.zeros(vcap, np.int32)
+        t = np.zeros((max(tcap, 1), 3), np.uint32)
+        c = _calib(calib)
+        rep = MeshReport()
+        if lib().adc_mesh(self._h, m.ctypes.data, None if img is None else img.ctypes.data, None if c is None else C.byref(c),
+                          None if params is None else C.byref(params), v.ctypes.data, vcap, vi.ctypes.data, t.ctypes.data, tcap, C.byref(rep)) != 0:
+            raise RuntimeError("adc_mesh failed: " + last_error())
+        return v[:rep.vertices].copy(), vi[:rep.vertices].copy(), t[:rep.triangles].copy(), rep
+
+    def mesh_report(self):
+        """The MeshReport of the last mesh call wait() has completed (adc_get_mesh_report)."""
+        rep = MeshReport()
+        if lib().adc_get_mesh_report(self._h, C.byref(rep)) != 0:
+            raise RuntimeError("adc_get_mesh_report failed: " + last_error())
         return rep
 
     def match_device(self, d_left, d_right, d_disp):

@@ -6,7 +6,7 @@
 // adc_destroy releases exactly that registry.  adc_create allocates what every Match needs (alloc_all: images, per-pixel maps, volumes,
 // tables, refinement state, pin_in / pin_out / pin_flags; upload_tables: ray_tab).  Everything optional is allocated by the first call
 // that needs it and kept until adc_destroy: out_words, map_buf[], os_cloud (products); sp_* (speckle filter); rect[], pin_raw
-// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); nrm_*, nrms_* (surface normals); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
+// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); nrm_*, nrms_* (surface normals); msh_*, mshs_* (triangle mesh); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
 // os_cloud, the raw buffers, ev_raw, reg_zbuf and the target-sized regs_* grow with the largest size asked for; their capacities count
 // elements of the field's own type.
 //
@@ -132,6 +132,7 @@ struct AdcInFlight {
     int ev_pending;       // adc_evaluate_device: an evaluation was enqueued -> adc_wait moves ev_pin and ev_echo into ev_report
     int reg_pending;      // adc_register_depth_device: a registration was enqueued -> adc_wait moves reg_pin into reg_report
     int nrm_pending;      // adc_normals_device: a normals kernel was enqueued -> adc_wait moves pin_flags[ADC_PIN_NORMALS..] into nrm_report
+    int msh_pending;      // adc_mesh_device: a mesh was enqueued -> adc_wait moves pin_flags[ADC_PIN_MESH..] into msh_report
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
 static_assert(std::is_trivially_copyable<AdcInFlight>::value, "AdcInFlight is reset with memset");
@@ -155,6 +156,7 @@ struct AdcRectSide {
 #define ADC_PIN_CLOUD 8    // point count of the last cloud (k_outputs.hip): adc_get_cloud_count
 #define ADC_PIN_SPECKLE 9  // three stat words of the last speckle filter run (k_speckle.hip): adc_get_speckle_stats
 #define ADC_PIN_VOXEL 12   // voxels, points_valid, points_kept of the last voxel cloud (k_voxel.hip): adc_get_voxel_report
+#define ADC_PIN_MESH 1     // lattice_valid, vertices, triangles, cells_two, cells_one of the last mesh call (k_mesh.hip): adc_get_mesh_report
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -319,6 +321,18 @@ struct adc_handle {
     float* nrms_map;          // device scratch of adc_normals (host callers), each allocated on the first call that needs it
     float* nrms_out;
     uint8_t* nrms_out8;
+    // optional triangle mesh from a disparity map (k_mesh.hip; nothing of it exists before the first adc_mesh_device)
+    uint32_t* msh_words;      // one block sized for step 1 (adc_mesh_scratch_bytes): report words, per-chunk bases, used words, cell codes
+    adc_mesh_report msh_report; // adc_get_mesh_report
+    int msh_report_valid;
+    float* mshs_map;          // device scratch of adc_mesh (host callers), each allocated on the first call that needs it
+    uint8_t* mshs_img;
+    adc_point* mshs_vtx;          // (these three grow with the largest capacity asked for)
+    size_t mshs_vtx_cap;
+    int32_t* mshs_vidx;
+    size_t mshs_vidx_cap;
+    uint32_t* mshs_tri;
+    size_t mshs_tri_cap;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -416,6 +430,24 @@ hipError_t adc_launch_reg_resolve(adc_handle* h, float* depth, int32_t* index); 
 hipError_t adc_launch_reg_align(adc_handle* h, const float* map, int kind, const adc_calib* calib, const uint8_t* tbgr, uint8_t* out, uint8_t* valid);
 // k_normals.hip: map -> normals / normals8 (each may be NULL), counts added to nrm_rep; G = the gate in 1/1024 pixel
 hipError_t adc_launch_normals(adc_handle* h, const float* disp, const adc_calib* calib, int radius, int32_t G, int min_points, float* normals, uint8_t* normals8);
+// k_mesh.hip: the three launches of a mesh (measure: cell codes, used words, per-chunk counts, report counts; scan: bases, totals,
+// the caller's count words; emit: vertices, vertex_index, triangles -- each output may be NULL) on the words of msh_words
+struct AdcMeshReq {
+    const float* disp;
+    const uint8_t* img;        // may be NULL: colours 0
+    const adc_calib* calib;    // may be NULL
+    float max_diff;
+    int step;
+    void* vertices;
+    int32_t* vertex_index;
+    uint32_t* triangles;
+    uint32_t vertex_capacity, triangle_capacity;
+    uint32_t* counts;          // the caller's device words, may be NULL
+};
+size_t adc_mesh_scratch_bytes(int W, int H);
+hipError_t adc_launch_mesh_measure(adc_handle* h, const AdcMeshReq& r);
+hipError_t adc_launch_mesh_scan(adc_handle* h, const AdcMeshReq& r);
+hipError_t adc_launch_mesh_emit(adc_handle* h, const AdcMeshReq& r);
 #define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

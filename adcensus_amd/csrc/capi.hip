@@ -881,8 +881,9 @@ static int wait_deliver(adc_handle* h)
     match_req_clear(h);
     return 0;
 }
-// (5) an evaluation / a registration / a normals call has completed: its report words have arrived in the pinned block (adc_get_eval_report,
-//     adc_get_register_report, adc_get_normals_report)
+#define MSH_PIN_WORDS 5 // the counts of adc_mesh_report in front of its reserved words: pin_flags[ADC_PIN_MESH .. ADC_PIN_MESH + 4]
+// (5) an evaluation / a registration / a normals / a mesh call has completed: its report words have arrived in the pinned block (adc_get_eval_report,
+//     adc_get_register_report, adc_get_normals_report, adc_get_mesh_report)
 static void wait_take_reports(adc_handle* h)
 {
     if (h->fly.ev_pending) {
@@ -900,6 +901,12 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->nrm_report, h->pin_flags + ADC_PIN_NORMALS, sizeof(h->nrm_report));
         h->nrm_report_valid = 1;
         h->fly.nrm_pending = 0;
+    }
+    if (h->fly.msh_pending) {
+        memset(&h->msh_report, 0, sizeof(h->msh_report));
+        memcpy(&h->msh_report, h->pin_flags + ADC_PIN_MESH, MSH_PIN_WORDS * sizeof(uint32_t));
+        h->msh_report_valid = 1;
+        h->fly.msh_pending = 0;
     }
 }
 
@@ -1853,6 +1860,114 @@ int adc_get_normals_report(adc_handle* h, adc_normals_report* out)
     if (!h || !out) { g_last_error = "adc_get_normals_report: null argument"; return 1; }
     if (!h->nrm_report_valid) { g_last_error = "adc_get_normals_report: no normals call has completed on this handle"; return 1; }
     *out = h->nrm_report;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ triangle mesh from a disparity map (k_mesh.hip)
+// Stand-alone entry points in the style of the normals: the device form enqueues on the object stream and is completed by adc_wait,
+// which moves the five report counts from pin_flags[ADC_PIN_MESH..] into msh_report.
+static const adc_mesh_params MSH_DEFAULT = {1.0f, 1, 0u, {0u, 0u, 0u, 0u, 0u}};
+
+// validates a request; 0 with *p filled, or 1 with adc_last_error (device: the outputs are device addresses -> alignment)
+static int msh_check(adc_handle* h, const void* map, const void* img, const adc_calib* calib, const adc_mesh_params* params, const void* vertices, const void* vindex,
+                     const void* triangles, const void* counts, bool device, adc_mesh_params* p, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : MSH_DEFAULT;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (calib && !(__builtin_isfinite(calib->focal_px) && __builtin_isfinite(calib->baseline) && __builtin_isfinite(calib->cx) && __builtin_isfinite(calib->cy) &&
+                        __builtin_isfinite(calib->doffs)))
+        why = "the calibration has a non-finite field";
+    else if (calib && !(calib->focal_px > 0.0f)) why = "the calibration's focal_px must be positive";
+    else if (!(p->max_diff >= 0.0f)) why = "max_diff must not be NaN and must be >= 0";
+    else if (p->step < 1 || p->step > ADC_MESH_MAX_STEP) why = "step must lie in [1, 16]";
+    else if (p->flags != 0u) why = "unknown flag";
+    else if (p->reserved_[0] | p->reserved_[1] | p->reserved_[2] | p->reserved_[3] | p->reserved_[4]) why = "a reserved word is not 0";
+    else if (!vertices && !triangles) why = "no output requested (neither vertices nor triangles)";
+    else if (vindex && !vertices) why = "a vertex_index needs vertices";
+    else if (device && ((uintptr_t)vertices & 15u)) why = "d_vertices must be 16-byte aligned";
+    else if (device && (((uintptr_t)vindex | (uintptr_t)triangles | (uintptr_t)counts | (uintptr_t)map) & 3u)) why = "d_disp, d_vertex_index, d_triangles and d_counts must be 4-byte aligned";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    (void)img; // (bytes: any address)
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static uint32_t msh_cap32(uint64_t c) { return c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c; } // (a mesh has fewer than 2^32 records)
+
+static hipError_t enqueue_mesh(adc_handle* h, const AdcMeshReq& r)
+{
+    HIP_TRY(MEM_ONCE(h->msh_words, adc_mesh_scratch_bytes(h->p.W, h->p.H)));
+    HIP_OK(hipMemsetAsync(h->msh_words, 0, sizeof(adc_mesh_report), h->stream));
+    HIP_OK(adc_launch_mesh_measure(h, r));
+    HIP_OK(adc_launch_mesh_scan(h, r));
+    HIP_OK(adc_launch_mesh_emit(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_MESH, h->msh_words, MSH_PIN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_mesh_device(adc_handle* h, const void* d_disp, const void* d_bgr_left, const adc_calib* calib, const adc_mesh_params* params, void* d_vertices,
+                    uint64_t vertex_capacity, void* d_vertex_index, void* d_triangles, uint64_t triangle_capacity, void* d_counts)
+{
+    const char* who = "adc_mesh_device";
+    adc_mesh_params p;
+    if (msh_check(h, d_disp, d_bgr_left, calib, params, d_vertices, d_vertex_index, d_triangles, d_counts, true, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    AdcMeshReq r;
+    r.disp = static_cast<const float*>(d_disp);
+    r.img = static_cast<const uint8_t*>(d_bgr_left);
+    r.calib = calib;
+    r.max_diff = p.max_diff;
+    r.step = p.step;
+    r.vertices = d_vertices;
+    r.vertex_index = static_cast<int32_t*>(d_vertex_index);
+    r.triangles = static_cast<uint32_t*>(d_triangles);
+    r.vertex_capacity = msh_cap32(vertex_capacity);
+    r.triangle_capacity = msh_cap32(triangle_capacity);
+    r.counts = static_cast<uint32_t*>(d_counts);
+    if (enqueue_mesh(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.msh_pending = 1;
+    return 0;
+}
+
+int adc_mesh(adc_handle* h, const float* disp, const uint8_t* bgr_left, const adc_calib* calib, const adc_mesh_params* params, adc_point* vertices,
+             uint64_t vertex_capacity, int32_t* vertex_index, uint32_t* triangles, uint64_t triangle_capacity, adc_mesh_report* report)
+{
+    const char* who = "adc_mesh";
+    adc_mesh_params p;
+    if (msh_check(h, disp, bgr_left, calib, params, vertices, vertex_index, triangles, nullptr, false, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    // no more records than the lattice can give (a device buffer of at least one record stands for a capacity of 0: it counts only)
+    const size_t Wl = (size_t)((h->p.W - 1) / p.step + 1), Hl = (size_t)((h->p.H - 1) / p.step + 1);
+    const size_t vmax = Wl * Hl, tmax = 2 * (Wl - 1) * (Hl - 1);
+    const size_t vcap = vertex_capacity < vmax ? (size_t)vertex_capacity : vmax, tcap = triangle_capacity < tmax ? (size_t)triangle_capacity : tmax;
+    hipError_t e = MEM_ONCE(h->mshs_map, P * 4);
+    if (e == hipSuccess && bgr_left) e = MEM_ONCE(h->mshs_img, P * 3);
+    if (e == hipSuccess && vertices) e = MEM_GROW(h->mshs_vtx, h->mshs_vtx_cap, vcap ? vcap : 1, sizeof(adc_point));
+    if (e == hipSuccess && vertex_index) e = MEM_GROW(h->mshs_vidx, h->mshs_vidx_cap, vcap ? vcap : 1, sizeof(int32_t));
+    if (e == hipSuccess && triangles) e = MEM_GROW(h->mshs_tri, h->mshs_tri_cap, 3 * (tcap ? tcap : 1), sizeof(uint32_t));
+    if (e != hipSuccess) return scratch_failed(who);
+    if ((e = ADC_HIP(hipMemcpy(h->mshs_map, disp, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_mesh: upload", e); (void)hipGetLastError(); return 2; }
+    if (bgr_left && (e = ADC_HIP(hipMemcpy(h->mshs_img, bgr_left, P * 3, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_mesh: image upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_mesh_device(h, h->mshs_map, bgr_left ? h->mshs_img : nullptr, calib, &p, vertices ? h->mshs_vtx : nullptr, vcap, vertex_index ? h->mshs_vidx : nullptr,
+                             triangles ? h->mshs_tri : nullptr, tcap, nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    const size_t nv = h->msh_report.vertices < vcap ? h->msh_report.vertices : vcap, nt = h->msh_report.triangles < tcap ? h->msh_report.triangles : tcap;
+    if (vertices && nv && (e = ADC_HIP(hipMemcpy(vertices, h->mshs_vtx, nv * sizeof(adc_point), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_mesh: vertex copy-out", e); return 2; }
+    if (vertex_index && nv && (e = ADC_HIP(hipMemcpy(vertex_index, h->mshs_vidx, nv * sizeof(int32_t), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_mesh: vertex_index copy-out", e); return 2; }
+    if (triangles && nt && (e = ADC_HIP(hipMemcpy(triangles, h->mshs_tri, nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_mesh: triangle copy-out", e); return 2; }
+    if (report) *report = h->msh_report;
+    return 0;
+}
+
+int adc_get_mesh_report(adc_handle* h, adc_mesh_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_mesh_report: null argument"; return 1; }
+    if (!h->msh_report_valid) { g_last_error = "adc_get_mesh_report: no mesh call has completed on this handle"; return 1; }
+    *out = h->msh_report;
     return 0;
 }
 

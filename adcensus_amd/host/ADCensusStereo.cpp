@@ -269,6 +269,12 @@ bool ADCensusStereo::Normals(const float32* disp, const adc_calib* calib, const 
     return impl_ && adc_normals(impl_, disp, calib, params, normals, normals8, report) == 0;
 }
 bool ADCensusStereo::GetNormalsReport(adc_normals_report* report) { return impl_ && adc_get_normals_report(impl_, report) == 0; }
+bool ADCensusStereo::Mesh(const float32* disp, const uint8* bgr_left, const adc_calib* calib, const adc_mesh_params* params, adc_point* vertices,
+                          uint64 vertex_capacity, sint32* vertex_index, uint32* triangles, uint64 triangle_capacity, adc_mesh_report* report)
+{
+    return impl_ && adc_mesh(impl_, disp, bgr_left, calib, params, vertices, vertex_capacity, vertex_index, triangles, triangle_capacity, report) == 0;
+}
+bool ADCensusStereo::GetMeshReport(adc_mesh_report* report) { return impl_ && adc_get_mesh_report(impl_, report) == 0; }
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

@@ -22,6 +22,13 @@
 // DIFF pixels of disparity of the centre, default 1, needing at least MIN of them, default 5): <out>-n.png holds the normal map
 // (R, G, B = 128 + 127 * nx, ny, nz; black where there is no normal), and without --voxel the points of <out>-cloud.ply gain the float
 // properties nx ny nz (0 0 0 for a point without a normal).  A malformed flag is refused while the arguments are parsed.
+// --mesh DIFF[,STEP] (anywhere after the program name; does not need --calib) triangulates the run's disparity map on the device
+// (ADCensusStereo::Mesh: gated grid cells over the lattice of every STEP-th pixel, STEP in 1..16, default 1; two lattice pixels are joined
+// when their disparities differ by at most DIFF >= 0, inf = no gate) and writes <out>-mesh.ply, a binary little-endian PLY: element
+// vertex with x y z float (without --calib x, y, |d|), nx ny nz float only with --normals (gathered through the mesh's vertex_index; 0 0 0
+// where there is no normal), red green blue uchar; element face with property list uchar int vertex_indices.  The mesh comes from the
+// map, so --voxel does not touch it and with --speckle it has the filter's holes.  A malformed flag is refused while the arguments are
+// parsed.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -374,6 +381,25 @@ int main(int argc, char** argv)
             break;
         }
     if (with_normals && !with_calib) { printf("--normals refused: it needs --calib\n"); return -1; }
+    bool with_mesh = false; // (--mesh and its value likewise; checked before anything touches a device)
+    adc_mesh_params mesh_params;
+    memset(&mesh_params, 0, sizeof(mesh_params));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--mesh")) {
+            char tail = 0;
+            mesh_params.step = 1;
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int n = sscanf(v, "%f,%d%c", &mesh_params.max_diff, &mesh_params.step, &tail);
+            if (n == 1 && sscanf(v, "%f%c", &mesh_params.max_diff, &tail) != 1) n = 0; // (DIFF alone: nothing may follow it)
+            if (n < 1 || n > 2 || !(mesh_params.max_diff >= 0.f) || mesh_params.step < 1 || mesh_params.step > ADC_MESH_MAX_STEP) {
+                printf("--mesh refused: it needs DIFF[,STEP] (DIFF >= 0 or inf, STEP in 1..16)\n");
+                return -1;
+            }
+            with_mesh = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
     bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
     RectifyFile rect_file[2];
     for (int i = 1; i < argc; i++)
@@ -744,8 +770,9 @@ int main(int argc, char** argv)
         }
     }
     std::vector<float32> point_normals; // (--normals without --voxel: three floats per cloud point)
+    std::vector<float32> nrm;           // (--normals: four floats per pixel; the mesh gathers its vertex normals from it)
     if (with_normals) { // the normal map of the delivered disparity map; the host pairs normals and cloud points, which share the pixel
-        std::vector<float32> nrm((size_t)w * h * 4);
+        nrm.resize((size_t)w * h * 4);
         std::vector<uint8> nrm8((size_t)w * h * 4), rgb((size_t)w * h * 3);
         adc_normals_report rep;
         if (!ad_census.Normals(disparity.data(), &calib, &normals_params, nrm.data(), nrm8.data(), &rep)) {
@@ -764,6 +791,36 @@ int main(int argc, char** argv)
                 point_normals.insert(point_normals.end(), nrm.begin() + 4 * i, nrm.begin() + 4 * i + 3);
             }
         }
+    }
+    if (with_mesh) { // the mesh of the delivered disparity map, sized at the lattice's worst case
+        const size_t wl = (size_t)((w - 1) / mesh_params.step + 1), hl = (size_t)((h - 1) / mesh_params.step + 1);
+        const size_t vcap = wl * hl, tcap = 2 * (wl - 1) * (hl - 1);
+        std::vector<adc_point> vertices(vcap);
+        std::vector<sint32> vertex_index(vcap);
+        std::vector<uint32> triangles(3 * tcap + 3);
+        adc_mesh_report rep;
+        const uint8* colours = (with_rectify || with_raw) ? rect_left.data() : left.data();
+        if (!ad_census.Mesh(disparity.data(), colours, with_calib ? &calib : nullptr, &mesh_params, vertices.data(), vcap, vertex_index.data(), triangles.data(), tcap,
+                            &rep)) {
+            printf("mesh refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        printf("\nMesh, step %d: %u valid lattice pixels, %u vertices, %u triangles, %u cells of two, %u cells of one\n", mesh_params.step, rep.lattice_valid,
+               rep.vertices, rep.triangles, rep.cells_two, rep.cells_one);
+        FILE* ply = fopen((out + "-mesh.ply").c_str(), "wb");
+        if (ply) {
+            fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %u\nproperty float x\nproperty float y\nproperty float z\n%s"
+                         "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %u\nproperty list uchar int vertex_indices\nend_header\n",
+                    rep.vertices, with_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", rep.triangles);
+            for (size_t i = 0; i < rep.vertices; i++) {
+                fwrite(&vertices[i].x, 4, 3, ply);
+                if (with_normals) fwrite(&nrm[4 * (size_t)vertex_index[i]], 4, 3, ply);
+                fwrite(&vertices[i].r, 1, 3, ply);
+            }
+            const uint8 three = 3;
+            for (size_t i = 0; i < rep.triangles; i++) { fwrite(&three, 1, 1, ply); fwrite(&triangles[3 * i], 4, 3, ply); }
+            fclose(ply);
+        } else printf("cannot write %s-mesh.ply\n", out.c_str());
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

@@ -16,6 +16,7 @@
  * SetGroundTruth / ClearGroundTruth / Evaluate / EvalReport (optional scoring of a map against ground truth on the device),
  * SetRegisterTarget / ClearRegisterTarget / RegisterDepth / AlignColor (optional registration of depth into a second camera on the device),
  * Normals / GetNormalsReport (optional camera-facing surface normals from a disparity map on the device),
+ * Mesh / GetMeshReport (optional triangle mesh from a disparity map on the device),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -37,6 +38,9 @@ struct adc_voxel_grid;
 struct adc_voxel_report;
 struct adc_normals_params;
 struct adc_normals_report;
+struct adc_mesh_params;
+struct adc_mesh_report;
+struct adc_point;
 
 class ADCensusStereo {
 public:
@@ -147,6 +151,15 @@ public:
     bool Normals(const float32* disp, const adc_calib* calib, const adc_normals_params* params, float32* normals, uint8* normals8,
                  adc_normals_report* report);
     bool GetNormalsReport(adc_normals_report* report);
+    /** Optional triangle mesh from a float32 [H][W] host disparity map on the device (adc_mesh, include/adcensus_c_api.h holds the
+     *  definition: gated grid cells over the lattice of every step-th pixel).  bgr_left uint8 [H][W][3] may be null (colours 0), calib
+     *  may be null (vertices (x, y, |d|)), params may be null (max_diff = 1.0, step = 1).  vertices takes the first
+     *  min(count, vertex_capacity) adc_point records, vertex_index (may be null) their source raster indices, triangles the first
+     *  min(count, triangle_capacity) records of three uint32 vertex numbers; vertices or triangles may be null, not both.  report may
+     *  be null. */
+    bool Mesh(const float32* disp, const uint8* bgr_left, const adc_calib* calib, const adc_mesh_params* params, adc_point* vertices,
+              uint64 vertex_capacity, sint32* vertex_index, uint32* triangles, uint64 triangle_capacity, adc_mesh_report* report);
+    bool GetMeshReport(adc_mesh_report* report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

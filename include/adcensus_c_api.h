@@ -28,6 +28,8 @@
  *                         device (z-buffered scatter), and that camera's colours gathered into the left view
  *   adc_normals_device /  camera-facing surface normals from any disparity map: a windowed plane fit in disparity space, solved
  *   adc_normals           exactly in integers (float32 x 4 and / or a normal-map image of 4 bytes per pixel)
+ *   adc_mesh_device /     a triangle mesh from any disparity map: gated grid cells over a lattice of every step-th pixel, vertices
+ *   adc_mesh              as cloud points, triangles as vertex numbers, both compacted in raster order
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -728,6 +730,72 @@ int adc_normals_device(adc_handle* h, const void* d_disp, const adc_calib* calib
 int adc_normals(adc_handle* h, const float* disp, const adc_calib* calib, const adc_normals_params* params, float* normals,
                 uint8_t* normals8, adc_normals_report* report);
 int adc_get_normals_report(adc_handle* h, adc_normals_report* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Triangle mesh from a disparity map on the device (gated grid cells; k_mesh.hip, the cell rule is adcensus_amd/csrc/mesh_cell.h,
+ * tests/mesh_ref.py holds the same definition in numpy and the kernels match it bit for bit, in whatever order the waves run).
+ * All float arithmetic is IEEE binary32, one rounding per operation, nothing fused.
+ *
+ * Input: a float32 [H][W] map d of the handle's geometry, a = fabsf(d); an optional adc_calib (NULL: no calibration); an optional left
+ * image uint8 [H][W][3] in B,G,R order (NULL: colours 0).
+ * Parameters (adc_mesh_params, 32 bytes): float max_diff, not NaN and >= 0 (+inf is allowed and means no gate); int32_t step in
+ * [1, 16]; uint32_t flags = 0; uint32_t reserved_[5] = 0.  NULL params: max_diff = 1.0, step = 1.
+ * Lattice: columns x = i * step for i in [0, Wl), Wl = (W - 1) / step + 1; rows y = j * step for j in [0, Hl), Hl = (H - 1) / step + 1.
+ * A lattice pixel's validity, position and colour are exactly those of adc_outputs.cloud: with a calibration valid <=> a finite and
+ * a + doffs > 0, Z = fb / s, X = ((x - cx) * Z) / focal_px, Y = ((y - cy) * Z) / focal_px; without one valid <=> a != +inf, point
+ * (x, y, a); r, g, b from the left image; pad = 0.
+ * Edge: two lattice pixels p, q are joined iff both are valid and fabsf(a_p - a_q) <= max_diff (one subtraction; a NaN fails).
+ * Cell (i, j) for i < Wl - 1, j < Hl - 1, corners A = lattice (i, j), B = (i+1, j), C = (i, j+1), D = (i+1, j+1):
+ *   four valid corners: the diagonal is AD iff fabsf(a_A - a_D) <= fabsf(a_B - a_C) (ties go to AD; a NaN comparison is false, so BC).
+ *                       With AD the candidates are T0 = (A, C, D) and T1 = (A, D, B); with BC T0 = (A, C, B) and T1 = (B, C, D).
+ *   exactly three:      one candidate -- D missing: (A, C, B); A missing: (B, C, D); B missing: (A, C, D); C missing: (A, D, B).
+ *   fewer:              no candidate.
+ *   A candidate is emitted iff all three of its edges are joined.  Every listed winding has the same sign in pixel coordinates (x
+ *   right, y down); with Z > 0 the geometric normal (v1 - v0) x (v2 - v0) of a fronto-parallel patch points at the camera, which agrees
+ *   with adc_normals.
+ * Triangles: cells in raster order (j, then i), within a cell T0 before T1; a record is three uint32 vertex numbers; `triangles` is
+ * the number of all of them.
+ * Vertices: the lattice pixels that are a corner of at least one emitted triangle, in raster order; a record is one adc_point
+ * (16 bytes).  vertex_index (optional), int32 per vertex: the source raster index y * W + x -- gather anything else through it
+ * (normals, confidence, provenance).  The vertex numbers in the triangles are positions in this full list.
+ * Capacities: the first min(vertices, vertex_capacity) vertex records and vertex_index words are written and nothing behind them; the
+ * first min(triangles, triangle_capacity) triangle records are written and nothing behind them; triangles keep their true vertex
+ * numbers whatever the vertex capacity.  Wl * Hl vertices and 2 (Wl - 1)(Hl - 1) triangles always suffice.  A capacity of 0 with a
+ * non-NULL pointer counts only.
+ * Report (adc_mesh_report, uint32 each): lattice_valid, vertices, triangles, cells_two, cells_one (cells that emit two triangles /
+ * one), three reserved words; triangles = 2 * cells_two + cells_one.  Read back through the handle's pinned block behind the
+ * kernels, available after adc_wait.  d_counts (optional): uint32[2] = {vertices, triangles}, written on the stream, so that a GPU
+ * consumer need not synchronise.
+ *
+ * adc_mesh_device      asynchronous on the handle's stream, completed by adc_wait.  d_vertices (16-byte aligned), d_vertex_index,
+ *                      d_triangles, d_counts (4-byte aligned) are device addresses; at least one of d_vertices / d_triangles.  Only what
+ *                      was asked for runs.  The first call allocates the scratch (adc_create allocates nothing of this).
+ * adc_mesh             the same with HOST pointers, synchronous; device scratch is allocated on the first call that needs it (freed
+ *                      by adc_destroy); copies out only min(count, capacity) records; report may be NULL.
+ * adc_get_mesh_report  the report of the last call that adc_wait (or adc_mesh) has completed.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued (a NULL handle or map, a calibration adc_match_out would refuse, a bad
+ * parameter, flag or reserved word, neither vertices nor triangles requested, a vertex_index without vertices, d_vertices not
+ * 16-byte aligned or any other device address not 4-byte aligned, a Match pending -- adc_wait first, for the reason given at
+ * adc_evaluate_device); 2 on a HIP failure (the handle stays usable).  The mesh is not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_MESH_MAX_STEP 16
+typedef struct adc_mesh_params {
+    float max_diff;      /* the gate in pixels of disparity: not NaN, >= 0; +inf = no gate */
+    int32_t step;        /* [1, 16]: every step-th column and row forms the lattice */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved_[5];
+} adc_mesh_params;
+typedef struct adc_mesh_report {
+    uint32_t lattice_valid, vertices, triangles, cells_two, cells_one;
+    uint32_t reserved_[3];
+} adc_mesh_report;
+int adc_mesh_device(adc_handle* h, const void* d_disp, const void* d_bgr_left, const adc_calib* calib, const adc_mesh_params* params,
+                    void* d_vertices, uint64_t vertex_capacity, void* d_vertex_index, void* d_triangles, uint64_t triangle_capacity,
+                    void* d_counts);
+int adc_mesh(adc_handle* h, const float* disp, const uint8_t* bgr_left, const adc_calib* calib, const adc_mesh_params* params,
+             adc_point* vertices, uint64_t vertex_capacity, int32_t* vertex_index, uint32_t* triangles, uint64_t triangle_capacity,
+             adc_mesh_report* report);
+int adc_get_mesh_report(adc_handle* h, adc_mesh_report* out);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
