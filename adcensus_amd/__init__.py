@@ -272,6 +272,60 @@ class MeshReport(C.Structure):
                 ("reserved_", C.c_uint32 * 3)]
 
 
+TSDF_COLOR = 0x1  # ADC_TSDF_COLOR: a colour word per voxel
+TSDF_MAX_DIM = 2048  # ADC_TSDF_MAX_DIM
+TSDF_ENTRY_POINTS = ("adc_tsdf_create", "adc_tsdf_reset", "adc_tsdf_destroy", "adc_tsdf_integrate_device", "adc_tsdf_integrate", "adc_tsdf_extract_device",
+                     "adc_tsdf_extract", "adc_get_tsdf_report", "adc_tsdf_get_volume_device", "adc_tsdf_download", "adc_tsdf_upload")
+
+
+class TsdfParams(C.Structure):
+    """adc_tsdf_params: nx, ny, nz voxels (each in [4, 2048], nx a multiple of 4, at most 2^30 in all) of edge `voxel`; origin = the
+    world position of the corner of voxel (0, 0, 0); the truncation distance trunc; the crop z_min <= Zc <= z_max of the camera-frame
+    Z; max_weight in [1, 65535]; flags (TSDF_COLOR); the reserved words 0."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
+                ("z_min", C.c_float), ("z_max", C.c_float), ("max_weight", C.c_uint32), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 4)]
+
+    def __init__(self, nx=0, ny=0, nz=0, voxel=0.0, origin=(0.0, 0.0, 0.0), trunc=0.0, z_min=0.0, z_max=float("inf"), max_weight=64, flags=0):
+        super().__init__()
+        self.nx, self.ny, self.nz, self.voxel, self.trunc = int(nx), int(ny), int(nz), float(voxel), float(trunc)
+        self.origin = (C.c_float * 3)(*[float(v) for v in origin])
+        self.z_min, self.z_max, self.max_weight, self.flags = float(z_min), float(z_max), int(max_weight), int(flags)
+
+
+class TsdfFrame(C.Structure):
+    """adc_tsdf_frame: what the map holds (REG_FROM_DISPARITY / REG_FROM_DEPTH), the calibration, and R (row-major) / t, which take a
+    WORLD point into the rectified left camera frame: Xc = R * Xw + t.  Defaults: disparity, R = I, t = 0."""
+    _fields_ = [("kind", C.c_int32), ("calib", Calib), ("R", C.c_float * 9), ("t", C.c_float * 3), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 5)]
+
+    def __init__(self, calib=None, R=None, t=None, kind=0, flags=0):
+        super().__init__()
+        self.kind, self.flags = int(kind), int(flags)
+        if calib is not None:
+            self.calib = _calib(calib)
+        self.R = (C.c_float * 9)(*[float(x) for x in np.asarray((1, 0, 0, 0, 1, 0, 0, 0, 1) if R is None else R, np.float32).ravel()])
+        self.t = (C.c_float * 3)(*[float(x) for x in np.asarray((0, 0, 0) if t is None else t, np.float32).ravel()])
+
+
+class TsdfReport(C.Structure):
+    """adc_tsdf_report: voxels that projected into the image, and of those the ones whose pixel has no depth, the ones further than
+    trunc behind the surface, the ones updated."""
+    _fields_ = [("in_frustum", C.c_uint32), ("no_depth", C.c_uint32), ("occluded", C.c_uint32), ("updated", C.c_uint32), ("reserved_", C.c_uint32 * 4)]
+
+
+class TsdfExtractParams(C.Structure):
+    """adc_tsdf_extract_params: min_weight in [1, 65535] both voxels of a crossing need; the reserved words 0."""
+    _fields_ = [("min_weight", C.c_uint32), ("reserved_", C.c_uint32 * 7)]
+
+    def __init__(self, min_weight=1):
+        super().__init__()
+        self.min_weight = int(min_weight)
+
+
+class TsdfExtractReport(C.Structure):
+    """adc_tsdf_extract_report: voxels with w >= min_weight, surface points (crossings) whatever the capacity."""
+    _fields_ = [("voxels_seen", C.c_uint32), ("points", C.c_uint32), ("reserved_", C.c_uint32 * 6)]
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -419,6 +473,20 @@ def lib():
         L.adc_mesh.argtypes = [vp, vp, vp, C.POINTER(Calib), C.POINTER(MeshParams), vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MeshReport)]
         L.adc_get_mesh_report.argtypes = [vp, C.POINTER(MeshReport)]
         for name in ("adc_mesh_device", "adc_mesh", "adc_get_mesh_report"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_tsdf_create"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_tsdf_create.argtypes = [vp, C.POINTER(TsdfParams)]
+        L.adc_tsdf_reset.argtypes = [vp]
+        L.adc_tsdf_destroy.argtypes = [vp]
+        L.adc_tsdf_integrate_device.argtypes = [vp, vp, vp, C.POINTER(TsdfFrame)]
+        L.adc_tsdf_integrate.argtypes = [vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfReport)]
+        L.adc_tsdf_extract_device.argtypes = [vp, C.POINTER(TsdfExtractParams), vp, C.c_uint64, vp]
+        L.adc_tsdf_extract.argtypes = [vp, C.POINTER(TsdfExtractParams), vp, C.c_uint64, C.POINTER(TsdfExtractReport)]
+        L.adc_get_tsdf_report.argtypes = [vp, C.POINTER(TsdfReport), C.POINTER(TsdfExtractReport)]
+        L.adc_tsdf_get_volume_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(TsdfParams)]
+        L.adc_tsdf_download.argtypes = [vp, vp, vp]
+        L.adc_tsdf_upload.argtypes = [vp, vp, vp]
+        for name in TSDF_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
@@ -1177,6 +1245,94 @@ class ADCensusStereo:
         if lib().adc_get_mesh_report(self._h, C.byref(rep)) != 0:
             raise RuntimeError("adc_get_mesh_report failed: " + last_error())
         return rep
+
+    # -- TSDF volume (adc_tsdf_*): frames fused into a volume on the device, and its surface points --------------------------------
+    def tsdf_create(self, params):
+        """Allocates and zeroes the volume of a TsdfParams (adc_tsdf_create); a second call replaces it.  False when refused or on a HIP failure."""
+        return lib().adc_tsdf_create(self._h, C.byref(params)) == 0
+
+    def tsdf_reset(self):
+        return lib().adc_tsdf_reset(self._h) == 0
+
+    def tsdf_destroy(self):
+        return lib().adc_tsdf_destroy(self._h) == 0
+
+    def tsdf_integrate_device(self, d_map, frame, d_bgr_left=None):
+        """One frame into the volume (adc_tsdf_integrate_device; ints: device addresses; frame a TsdfFrame); asynchronous, call
+        wait(), then tsdf_report().  False when refused (no volume, a Match pending, a bad frame, an image without a colour volume,
+        a misaligned address) or on a HIP failure."""
+        return lib().adc_tsdf_integrate_device(self._h, d_map, d_bgr_left, C.byref(frame)) == 0
+
+    def tsdf_integrate(self, depth_map, frame, bgr_left=None):
+        """Host convenience (adc_tsdf_integrate): returns the TsdfReport.  Raises on failure."""
+        m = np.ascontiguousarray(depth_map, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        img = None
+        if bgr_left is not None:
+            img = np.ascontiguousarray(bgr_left, dtype=np.uint8)
+            assert img.size == 3 * m.size, img.shape
+        rep = TsdfReport()
+        if lib().adc_tsdf_integrate(self._h, m.ctypes.data, None if img is None else img.ctypes.data, C.byref(frame), C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_integrate failed: " + last_error())
+        return rep
+
+    def tsdf_extract_device(self, d_points, capacity, params=None, d_count=None):
+        """The surface points of the volume (adc_tsdf_extract_device; d_points adc_point records, 16-byte aligned, or None with
+        capacity 0 to count only; d_count one uint32 device word or None; params a TsdfExtractParams or None for min_weight = 1);
+        asynchronous, call wait(), then tsdf_report()."""
+        return lib().adc_tsdf_extract_device(self._h, None if params is None else C.byref(params), d_points, int(capacity), d_count) == 0
+
+    def tsdf_extract(self, params=None, capacity=None):
+        """Host convenience (adc_tsdf_extract): returns (points POINT_DTYPE [min(points, capacity)], TsdfExtractReport).  capacity
+        None: a counting call first, then exactly as many records as there are.  Raises on failure."""
+        rep = TsdfExtractReport()
+        pp = None if params is None else C.byref(params)
+        if capacity is None:
+            if lib().adc_tsdf_extract(self._h, pp, None, 0, C.byref(rep)) != 0:
+                raise RuntimeError("adc_tsdf_extract failed: " + last_error())
+            capacity = rep.points
+        pts = np.zeros(max(int(capacity), 1), POINT_DTYPE)
+        if lib().adc_tsdf_extract(self._h, pp, pts.ctypes.data, int(capacity), C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_extract failed: " + last_error())
+        return pts[:min(rep.points, int(capacity))].copy(), rep
+
+    def tsdf_report(self):
+        """(TsdfReport or None, TsdfExtractReport or None) of the last integrate / extract call wait() has completed (adc_get_tsdf_report)."""
+        out = []
+        for cls, first in ((TsdfReport, True), (TsdfExtractReport, False)):
+            rep = cls()
+            rc = lib().adc_get_tsdf_report(self._h, C.byref(rep), None) if first else lib().adc_get_tsdf_report(self._h, None, C.byref(rep))
+            out.append(rep if rc == 0 else None)
+        return tuple(out)
+
+    def tsdf_volume_device(self):
+        """(device address of the voxel words, of the colour words or None, TsdfParams) for a GPU consumer (adc_tsdf_get_volume_device)."""
+        t, c, p = C.c_void_p(), C.c_void_p(), TsdfParams()
+        if lib().adc_tsdf_get_volume_device(self._h, C.byref(t), C.byref(c), C.byref(p)) != 0:
+            raise RuntimeError("adc_tsdf_get_volume_device failed: " + last_error())
+        return t.value, c.value, p
+
+    def tsdf_download(self):
+        """Host copy of the whole volume (adc_tsdf_download): (tsdf uint32 [nz][ny][nx], color the same or None)."""
+        _, c, p = self.tsdf_volume_device()
+        shape = (p.nz, p.ny, p.nx)
+        tsdf = np.zeros(shape, np.uint32)
+        color = np.zeros(shape, np.uint32) if c else None
+        if lib().adc_tsdf_download(self._h, tsdf.ctypes.data, None if color is None else color.ctypes.data) != 0:
+            raise RuntimeError("adc_tsdf_download failed: " + last_error())
+        return tsdf, color
+
+    def tsdf_upload(self, tsdf, color=None):
+        """Replaces the volume's words by host arrays of its shape (adc_tsdf_upload).  Raises on failure."""
+        _, _, p = self.tsdf_volume_device()
+        t = np.ascontiguousarray(tsdf, dtype=np.uint32)
+        assert t.shape == (p.nz, p.ny, p.nx), (t.shape, (p.nz, p.ny, p.nx))
+        c = None
+        if color is not None:
+            c = np.ascontiguousarray(color, dtype=np.uint32)
+            assert c.shape == t.shape, c.shape
+        if lib().adc_tsdf_upload(self._h, t.ctypes.data, None if c is None else c.ctypes.data) != 0:
+            raise RuntimeError("adc_tsdf_upload failed: " + last_error())
 
     def match_device(self, d_left, d_right, d_disp):
         """Device pointers (ints); asynchronous; call wait().  The two image buffers are BORROWED until wait() returns: do

@@ -6,7 +6,7 @@
 // adc_destroy releases exactly that registry.  adc_create allocates what every Match needs (alloc_all: images, per-pixel maps, volumes,
 // tables, refinement state, pin_in / pin_out / pin_flags; upload_tables: ray_tab).  Everything optional is allocated by the first call
 // that needs it and kept until adc_destroy: out_words, map_buf[], os_cloud (products); sp_* (speckle filter); rect[], pin_raw
-// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); nrm_*, nrms_* (surface normals); msh_*, mshs_* (triangle mesh); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
+// (rectification, raw formats); ev_*, evs_* (evaluation); reg_*, regs_* (registration); nrm_*, nrms_* (surface normals); msh_*, mshs_* (triangle mesh); tsdf_*, tsdfs_* (TSDF volume: adc_tsdf_create and the first calls of its entry points); vox_* (voxel grid); arms_r, bgrx_r, armmax_r, vol_c (paper modes).
 // os_cloud, the raw buffers, ev_raw, reg_zbuf and the target-sized regs_* grow with the largest size asked for; their capacities count
 // elements of the field's own type.
 //
@@ -133,6 +133,8 @@ struct AdcInFlight {
     int reg_pending;      // adc_register_depth_device: a registration was enqueued -> adc_wait moves reg_pin into reg_report
     int nrm_pending;      // adc_normals_device: a normals kernel was enqueued -> adc_wait moves pin_flags[ADC_PIN_NORMALS..] into nrm_report
     int msh_pending;      // adc_mesh_device: a mesh was enqueued -> adc_wait moves pin_flags[ADC_PIN_MESH..] into msh_report
+    int tsdf_pending;     // adc_tsdf_integrate_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF..] into tsdf_report
+    int tsdfx_pending;    // adc_tsdf_extract_device: an extraction was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_xreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
 static_assert(std::is_trivially_copyable<AdcInFlight>::value, "AdcInFlight is reset with memset");
@@ -157,6 +159,13 @@ struct AdcRectSide {
 #define ADC_PIN_SPECKLE 9  // three stat words of the last speckle filter run (k_speckle.hip): adc_get_speckle_stats
 #define ADC_PIN_VOXEL 12   // voxels, points_valid, points_kept of the last voxel cloud (k_voxel.hip): adc_get_voxel_report
 #define ADC_PIN_MESH 1     // lattice_valid, vertices, triangles, cells_two, cells_one of the last mesh call (k_mesh.hip): adc_get_mesh_report
+#define ADC_PIN_VOTING 16  // eight state words of the voting chain, read back behind every chain (k_voting.hip: adc_run_region_voting, adc_voting_finish)
+#define ADC_PIN_IRV_COLD 32 // staging of the voting chain's cold block, two slots of 16 words (k_voting.hip)
+// behind the mirror of the armmax words (ADC_PIN_ARM + ADC_ARMMAX_WORDS, adc_device_fn.h), where no Match writes: a Match may be enqueued
+// behind a pending TSDF call and one adc_wait completes both
+#define ADC_PIN_TSDF (ADC_PIN_ARM + ADC_ARMMAX_WORDS) // in_frustum, no_depth, occluded, updated of the last integrate call (k_tsdf.hip): adc_get_tsdf_report
+#define ADC_PIN_TSDF_EXTRACT (ADC_PIN_TSDF + 4)       // voxels_seen, points of the last extract call
+#define ADC_PIN_WORDS (ADC_PIN_TSDF + 8)              // int32 words of pin_flags
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -333,6 +342,22 @@ struct adc_handle {
     size_t mshs_vidx_cap;
     uint32_t* mshs_tri;
     size_t mshs_tri_cap;
+    // optional TSDF volume (k_tsdf.hip; nothing of it exists before the first adc_tsdf_create)
+    int tsdf_set;             // a volume exists (adc_tsdf_destroy / a failed adc_tsdf_create: 0)
+    adc_tsdf_params tsdf_params;
+    uint32_t* tsdf_vol;       // one word per voxel: (uint16)(int16)t | w << 16
+    uint32_t* tsdf_col;       // with ADC_TSDF_COLOR: r | g << 8 | b << 16 | cw << 24 per voxel
+    uint32_t* tsdf_rep;       // ADC_TSDF_REP_WORDS report words the kernels add to: integrate at 0, extract at ADC_TSDF_REP_EXTRACT
+    uint32_t* tsdf_tiles;     // per-tile counts / bases of the extraction, allocated on its first use; grows with the largest volume
+    size_t tsdf_tiles_cap;
+    adc_tsdf_report tsdf_report;          // adc_get_tsdf_report
+    int tsdf_report_valid;
+    adc_tsdf_extract_report tsdf_xreport;
+    int tsdf_xreport_valid;
+    float* tsdfs_map;         // device scratch of adc_tsdf_integrate / adc_tsdf_extract (host callers), each allocated on the first call that needs it
+    uint8_t* tsdfs_img;
+    adc_point* tsdfs_pts;     // (grows with the largest capacity asked for)
+    size_t tsdfs_pts_cap;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -448,6 +473,21 @@ size_t adc_mesh_scratch_bytes(int W, int H);
 hipError_t adc_launch_mesh_measure(adc_handle* h, const AdcMeshReq& r);
 hipError_t adc_launch_mesh_scan(adc_handle* h, const AdcMeshReq& r);
 hipError_t adc_launch_mesh_emit(adc_handle* h, const AdcMeshReq& r);
+// k_tsdf.hip: one frame into the handle's volume (counts added to tsdf_rep[0..3]); the three launches of an extraction on tsdf_tiles
+// (measure: crossings per tile, voxels_seen; scan: bases, points -> tsdf_rep and the caller's word; emit: the records)
+#define ADC_TSDF_REP_WORDS 16
+#define ADC_TSDF_REP_EXTRACT 8
+struct AdcTsdfExtReq {
+    uint32_t min_weight;
+    void* points;              // may be NULL: counts only
+    uint32_t capacity;
+    uint32_t* count;           // the caller's device word, may be NULL
+};
+size_t adc_tsdf_tile_count(const adc_tsdf_params* p);
+hipError_t adc_launch_tsdf_integrate(adc_handle* h, const float* map, const uint8_t* img, const adc_tsdf_frame* frame);
+hipError_t adc_launch_tsdf_measure(adc_handle* h, const AdcTsdfExtReq& r);
+hipError_t adc_launch_tsdf_scan(adc_handle* h, const AdcTsdfExtReq& r);
+hipError_t adc_launch_tsdf_emit(adc_handle* h, const AdcTsdfExtReq& r);
 #define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

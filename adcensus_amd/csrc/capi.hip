@@ -4,6 +4,7 @@
 #include "adc_internal.h"
 #include "adc_device_fn.h"
 #include "itp_plan.h"
+#include "tsdf_voxel.h" // tsdf_params_refusal, tsdf_frame_refusal
 
 #include <math.h>
 #include <stdio.h>
@@ -227,9 +228,9 @@ static hipError_t alloc_all(adc_handle* h)
     HIP_TRY(MEM_ONCE_PINNED(h->pin_in, P * 6));
     HIP_TRY(MEM_ONCE_PINNED(h->pin_out, P * 4));
     // (one block: the 64 flag words, then the mirror of the device's armmax words -- maxima, speculation flags, record densities)
-    HIP_TRY(MEM_ONCE_PINNED(h->pin_flags, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t)));
+    HIP_TRY(MEM_ONCE_PINNED(h->pin_flags, ADC_PIN_WORDS * sizeof(int32_t)));
     h->pin_nz = h->pin_flags + ADC_PIN_ARM + ADC_NZ_BASE; // record densities (k_make_records)
-    memset(h->pin_flags, 0, (ADC_PIN_ARM + ADC_ARMMAX_WORDS) * sizeof(int32_t)); // [0] median error, [ADC_PIN_ARM..] mirror of the armmax words (maxima, failed seams, violation flag, record densities), [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block
+    memset(h->pin_flags, 0, ADC_PIN_WORDS * sizeof(int32_t)); // the ADC_PIN_* words of adc_internal.h: [0] median error, [ADC_PIN_ARM..] mirror of the armmax words (maxima, failed seams, violation flag, record densities), [8] cloud count (k_outputs.hip), [9..11] speckle stats (k_speckle.hip), [16..23] voting state, [32..63] staging of the voting chain's cold block, behind the armmax mirror the TSDF reports
     HIP_OK(hipMemset(h->label, 0, P));
     HIP_OK(hipMemset(h->chg_a, 0, 2 * tiles));
     HIP_OK(hipMemset(h->vol_a, 0, VB));
@@ -907,6 +908,18 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->msh_report, h->pin_flags + ADC_PIN_MESH, MSH_PIN_WORDS * sizeof(uint32_t));
         h->msh_report_valid = 1;
         h->fly.msh_pending = 0;
+    }
+    if (h->fly.tsdf_pending) {
+        memset(&h->tsdf_report, 0, sizeof(h->tsdf_report));
+        memcpy(&h->tsdf_report, h->pin_flags + ADC_PIN_TSDF, 4 * sizeof(uint32_t));
+        h->tsdf_report_valid = 1;
+        h->fly.tsdf_pending = 0;
+    }
+    if (h->fly.tsdfx_pending) {
+        memset(&h->tsdf_xreport, 0, sizeof(h->tsdf_xreport));
+        memcpy(&h->tsdf_xreport, h->pin_flags + ADC_PIN_TSDF_EXTRACT, 2 * sizeof(uint32_t));
+        h->tsdf_xreport_valid = 1;
+        h->fly.tsdfx_pending = 0;
     }
 }
 
@@ -1969,6 +1982,256 @@ int adc_get_mesh_report(adc_handle* h, adc_mesh_report* out)
     if (!h->msh_report_valid) { g_last_error = "adc_get_mesh_report: no mesh call has completed on this handle"; return 1; }
     *out = h->msh_report;
     return 0;
+}
+
+// ------------------------------------------------------------------------------ TSDF volume (k_tsdf.hip)
+// The volume is handle state (tsdf_set, tsdf_params, tsdf_vol, tsdf_col).  The device forms of integrate and extract enqueue on the
+// object stream in the style of the mesh and are completed by adc_wait, which moves their report counts from
+// pin_flags[ADC_PIN_TSDF..] / pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_report / tsdf_xreport.  Like adc_mesh_device, neither looks at
+// its own pending flag: calls may follow one another on the stream without a wait, and the report is that of the last.
+static const adc_tsdf_extract_params TSDF_EXTRACT_DEFAULT = {1u, {0u, 0u, 0u, 0u, 0u, 0u, 0u}};
+
+static size_t tsdf_voxels(const adc_tsdf_params& p) { return (size_t)p.nx * (size_t)p.ny * (size_t)p.nz; }
+
+static void tsdf_release(adc_handle* h)
+{
+    dev_mem_release<HipMem>(&h->mem, &h->tsdf_vol);
+    dev_mem_release<HipMem>(&h->mem, &h->tsdf_col);
+    h->tsdf_set = 0;
+}
+
+static hipError_t tsdf_clear(adc_handle* h, const adc_tsdf_params& p)
+{
+    HIP_OK(hipMemsetAsync(h->tsdf_vol, 0, tsdf_voxels(p) * sizeof(uint32_t), h->stream));
+    if (h->tsdf_col) HIP_OK(hipMemsetAsync(h->tsdf_col, 0, tsdf_voxels(p) * sizeof(uint32_t), h->stream));
+    return hipSuccess;
+}
+
+static hipError_t tsdf_allocate(adc_handle* h, const adc_tsdf_params& p)
+{
+    HIP_TRY(MEM_ONCE(h->tsdf_vol, tsdf_voxels(p) * sizeof(uint32_t)));
+    if (p.flags & ADC_TSDF_COLOR) HIP_TRY(MEM_ONCE(h->tsdf_col, tsdf_voxels(p) * sizeof(uint32_t)));
+    HIP_TRY(MEM_ONCE(h->tsdf_rep, ADC_TSDF_REP_WORDS * sizeof(uint32_t)));
+    return tsdf_clear(h, p);
+}
+
+// the checks every call on an existing volume shares; null = go on
+static const char* tsdf_state_refusal(adc_handle* h)
+{
+    if (!h->tsdf_set) return "no volume (adc_tsdf_create first)";
+    if (match_in_flight(h)) return "a Match is pending (adc_wait first)";
+    return nullptr;
+}
+
+int adc_tsdf_create(adc_handle* h, const adc_tsdf_params* params)
+{
+    const char* who = "adc_tsdf_create";
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!params) why = "null params";
+    else if ((why = tsdf_params_refusal(*params)) != nullptr) {}
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    hipSetDevice(h->device);
+    tsdf_release(h); // (hipFree waits for whatever still reads the old volume)
+    if (tsdf_allocate(h, *params) != hipSuccess) {
+        const int rc = fail_call(h, who);
+        tsdf_release(h);
+        return rc;
+    }
+    h->tsdf_params = *params;
+    h->tsdf_set = 1;
+    return 0;
+}
+
+int adc_tsdf_reset(adc_handle* h)
+{
+    const char* who = "adc_tsdf_reset";
+    const char* why = !h ? "null handle" : tsdf_state_refusal(h);
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    hipSetDevice(h->device);
+    if (tsdf_clear(h, h->tsdf_params) != hipSuccess) return fail_call(h, who);
+    return 0;
+}
+
+int adc_tsdf_destroy(adc_handle* h)
+{
+    const char* why = !h ? "null handle" : match_in_flight(h) ? "a Match is pending (adc_wait first)" : nullptr;
+    if (why) { g_last_error = std::string("adc_tsdf_destroy: ") + why; return 1; }
+    if (!h->tsdf_set) return 0;
+    hipSetDevice(h->device);
+    tsdf_release(h);
+    return 0;
+}
+
+static int tsdf_integrate_check(adc_handle* h, const void* map, const void* img, const adc_tsdf_frame* frame, bool device, const char* who)
+{
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (!frame) why = "null frame";
+    else if ((why = tsdf_frame_refusal(*frame)) != nullptr) {}
+    else if (device && ((uintptr_t)map & 3u)) why = "d_map must be 4-byte aligned";
+    else if ((why = tsdf_state_refusal(h)) != nullptr) {}
+    else if (img && !(h->tsdf_params.flags & ADC_TSDF_COLOR)) why = "an image needs a colour volume (ADC_TSDF_COLOR)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static hipError_t enqueue_tsdf_integrate(adc_handle* h, const float* map, const uint8_t* img, const adc_tsdf_frame* frame)
+{
+    HIP_OK(hipMemsetAsync(h->tsdf_rep, 0, sizeof(adc_tsdf_report), h->stream));
+    HIP_OK(adc_launch_tsdf_integrate(h, map, img, frame));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF, h->tsdf_rep, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_integrate_device(adc_handle* h, const void* d_map, const void* d_bgr_left, const adc_tsdf_frame* frame)
+{
+    const char* who = "adc_tsdf_integrate_device";
+    if (tsdf_integrate_check(h, d_map, d_bgr_left, frame, true, who) != 0) return 1;
+    hipSetDevice(h->device);
+    if (enqueue_tsdf_integrate(h, static_cast<const float*>(d_map), static_cast<const uint8_t*>(d_bgr_left), frame) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdf_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_integrate(adc_handle* h, const float* map, const uint8_t* bgr_left, const adc_tsdf_frame* frame, adc_tsdf_report* report)
+{
+    const char* who = "adc_tsdf_integrate";
+    if (tsdf_integrate_check(h, map, bgr_left, frame, false, who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = MEM_ONCE(h->tsdfs_map, P * 4);
+    if (e == hipSuccess && bgr_left) e = MEM_ONCE(h->tsdfs_img, P * 3);
+    if (e != hipSuccess) return scratch_failed(who);
+    if ((e = ADC_HIP(hipMemcpy(h->tsdfs_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_integrate: upload", e); (void)hipGetLastError(); return 2; }
+    if (bgr_left && (e = ADC_HIP(hipMemcpy(h->tsdfs_img, bgr_left, P * 3, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_integrate: image upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_tsdf_integrate_device(h, h->tsdfs_map, bgr_left ? h->tsdfs_img : nullptr, frame);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (report) *report = h->tsdf_report;
+    return 0;
+}
+
+static int tsdf_extract_check(adc_handle* h, const adc_tsdf_extract_params* params, const void* points, uint64_t capacity, const void* count, bool device,
+                              adc_tsdf_extract_params* p, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : TSDF_EXTRACT_DEFAULT;
+    if (!h) why = "null handle";
+    else if (p->min_weight < 1u || p->min_weight > 65535u) why = "min_weight must lie in [1, 65535]";
+    else if (p->reserved_[0] | p->reserved_[1] | p->reserved_[2] | p->reserved_[3] | p->reserved_[4] | p->reserved_[5] | p->reserved_[6]) why = "a reserved word is not 0";
+    else if (!points && capacity != 0) why = "null points with a capacity";
+    else if (device && ((uintptr_t)points & 15u)) why = "d_points must be 16-byte aligned";
+    else if (device && ((uintptr_t)count & 3u)) why = "d_count must be 4-byte aligned";
+    else if ((why = tsdf_state_refusal(h)) != nullptr) {}
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static hipError_t enqueue_tsdf_extract(adc_handle* h, const AdcTsdfExtReq& r)
+{
+    HIP_TRY(MEM_GROW(h->tsdf_tiles, h->tsdf_tiles_cap, adc_tsdf_tile_count(&h->tsdf_params), sizeof(uint32_t)));
+    HIP_OK(hipMemsetAsync(h->tsdf_rep + ADC_TSDF_REP_EXTRACT, 0, sizeof(adc_tsdf_extract_report), h->stream));
+    HIP_OK(adc_launch_tsdf_measure(h, r));
+    HIP_OK(adc_launch_tsdf_scan(h, r));
+    if (r.points && r.capacity) HIP_OK(adc_launch_tsdf_emit(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_EXTRACT, h->tsdf_rep + ADC_TSDF_REP_EXTRACT, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_extract_device(adc_handle* h, const adc_tsdf_extract_params* params, void* d_points, uint64_t capacity, void* d_count)
+{
+    const char* who = "adc_tsdf_extract_device";
+    adc_tsdf_extract_params p;
+    if (tsdf_extract_check(h, params, d_points, capacity, d_count, true, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    AdcTsdfExtReq r;
+    r.min_weight = p.min_weight;
+    r.points = d_points;
+    r.capacity = msh_cap32(capacity);
+    r.count = static_cast<uint32_t*>(d_count);
+    if (enqueue_tsdf_extract(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdfx_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_extract(adc_handle* h, const adc_tsdf_extract_params* params, adc_point* points, uint64_t capacity, adc_tsdf_extract_report* report)
+{
+    const char* who = "adc_tsdf_extract";
+    adc_tsdf_extract_params p;
+    if (tsdf_extract_check(h, params, points, capacity, nullptr, false, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    // no more records than the volume can give: three crossings per voxel
+    const size_t most = 3 * tsdf_voxels(h->tsdf_params);
+    size_t cap = capacity < most ? (size_t)capacity : most;
+    hipError_t e = hipSuccess;
+    int rc = 0;
+    if (points && cap > h->tsdfs_pts_cap) {
+        // the point scratch would have to grow: count first, so that it never holds more records than the volume has crossings (a
+        // generous capacity on a 512^3 volume would otherwise pin up to 6 GB until adc_destroy)
+        rc = adc_tsdf_extract_device(h, &p, nullptr, 0, nullptr);
+        if (rc == 0) rc = adc_wait(h);
+        if (rc != 0) return rc;
+        if (h->tsdf_xreport.points < cap) cap = h->tsdf_xreport.points;
+        if (cap == 0) { // (no crossing: the counting pass was the call)
+            if (report) *report = h->tsdf_xreport;
+            return 0;
+        }
+    }
+    if (points && cap && (e = MEM_GROW(h->tsdfs_pts, h->tsdfs_pts_cap, cap, sizeof(adc_point))) != hipSuccess) return scratch_failed(who);
+    rc = adc_tsdf_extract_device(h, &p, points && cap ? h->tsdfs_pts : nullptr, points ? cap : 0, nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    const size_t n = h->tsdf_xreport.points < cap ? h->tsdf_xreport.points : cap;
+    if (points && n && (e = ADC_HIP(hipMemcpy(points, h->tsdfs_pts, n * sizeof(adc_point), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_extract: copy-out", e); return 2; }
+    if (report) *report = h->tsdf_xreport;
+    return 0;
+}
+
+int adc_get_tsdf_report(adc_handle* h, adc_tsdf_report* integrate_report, adc_tsdf_extract_report* extract_report)
+{
+    if (!h || (!integrate_report && !extract_report)) { g_last_error = "adc_get_tsdf_report: null argument"; return 1; }
+    if (integrate_report && !h->tsdf_report_valid) { g_last_error = "adc_get_tsdf_report: no integrate call has completed on this handle"; return 1; }
+    if (extract_report && !h->tsdf_xreport_valid) { g_last_error = "adc_get_tsdf_report: no extract call has completed on this handle"; return 1; }
+    if (integrate_report) *integrate_report = h->tsdf_report;
+    if (extract_report) *extract_report = h->tsdf_xreport;
+    return 0;
+}
+
+int adc_tsdf_get_volume_device(adc_handle* h, void** d_tsdf, void** d_color, adc_tsdf_params* params)
+{
+    const char* why = !h ? "null handle" : !h->tsdf_set ? "no volume (adc_tsdf_create first)" : nullptr;
+    if (why) { g_last_error = std::string("adc_tsdf_get_volume_device: ") + why; return 1; }
+    if (d_tsdf) *d_tsdf = h->tsdf_vol;
+    if (d_color) *d_color = h->tsdf_col;
+    if (params) *params = h->tsdf_params;
+    return 0;
+}
+
+// the whole volume to (to_host) or from the host: waits for the stream, then one blocking copy per plane of words
+static int tsdf_transfer(adc_handle* h, void* tsdf, void* color, bool to_host, const char* who)
+{
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!tsdf) why = "null tsdf";
+    else if ((why = tsdf_state_refusal(h)) != nullptr) {}
+    else if (color && !h->tsdf_col) why = "a colour pointer needs a colour volume (ADC_TSDF_COLOR)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    hipSetDevice(h->device);
+    const size_t bytes = tsdf_voxels(h->tsdf_params) * sizeof(uint32_t);
+    hipError_t e = ADC_HIP(hipStreamSynchronize(h->stream));
+    if (e == hipSuccess) e = to_host ? ADC_HIP(hipMemcpy(tsdf, h->tsdf_vol, bytes, hipMemcpyDeviceToHost)) : ADC_HIP(hipMemcpy(h->tsdf_vol, tsdf, bytes, hipMemcpyHostToDevice));
+    if (e == hipSuccess && color) e = to_host ? ADC_HIP(hipMemcpy(color, h->tsdf_col, bytes, hipMemcpyDeviceToHost)) : ADC_HIP(hipMemcpy(h->tsdf_col, color, bytes, hipMemcpyHostToDevice));
+    if (e != hipSuccess) { set_error(who, e); (void)hipGetLastError(); return 2; }
+    return 0;
+}
+
+int adc_tsdf_download(adc_handle* h, uint32_t* tsdf, uint32_t* color) { return tsdf_transfer(h, tsdf, color, true, "adc_tsdf_download"); }
+int adc_tsdf_upload(adc_handle* h, const uint32_t* tsdf, const uint32_t* color)
+{
+    return tsdf_transfer(h, const_cast<uint32_t*>(tsdf), const_cast<uint32_t*>(color), false, "adc_tsdf_upload");
 }
 
 // ------------------------------------------------------------------------------ pair farm

@@ -11,7 +11,7 @@
 #pragma once
 #include <stddef.h>
 
-#define DEV_MEM_SLOTS 192 // a handle registers about 110 fields
+#define DEV_MEM_SLOTS 192 // a handle registers about 120 fields
 #define DEV_MEM_FULL (-1) // returned in place of M's code: every slot is taken (nothing was allocated)
 enum DevMemKind { DEV_MEM_DEVICE = 0, DEV_MEM_PINNED = 1 };
 

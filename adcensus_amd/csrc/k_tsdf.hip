@@ -1,0 +1,339 @@
+// k_tsdf.hip -- the TSDF volume (include/adcensus_c_api.h: adc_tsdf_integrate_device, adc_tsdf_extract_device; the voxel rule is
+// tsdf_voxel.h): one frame fused into the volume, and the volume's surface points compacted in voxel order.
+//
+//   k_tsdf_integrate  x is the fastest axis of the volume.  A lane owns FOUR consecutive voxels of a row (nx is a multiple of 4: one
+//                     16-byte group), a wave 256 voxels of a row, and walks TSDF_ROWS_PER_WAVE rows.  The projection and the update
+//                     decision come FIRST: a lane loads its group of voxel words only when one of its four voxels is updated, and
+//                     stores it only then (the unchanged words of the group go back with their own bits: nobody else owns them).
+//                     The traffic is 8 bytes per updated voxel (16 with colour) rounded up to 16-byte groups, plus the gather from
+//                     the map -- not 8 bytes per voxel of the volume.  The products with yw and zw are formed once per row.  Per
+//                     workgroup one integer atomic per report count.
+//   k_tsdf_measure    the volume in linear chunks of 64 voxels, a lane per voxel, four chunks = one tile of 256 voxels per wave and
+//                     turn; the +x neighbour comes from the next lane (lane 63: one extra word), +y and +z from loads nx and nx * ny
+//                     words away, and only for a voxel that counts as seen.  Per tile the number of crossings.
+//   k_tsdf_scan       one workgroup: exclusive scan of the tile counts in place; the total -> the report and the caller's count word
+//   k_tsdf_emit       the crossings again, each record behind its tile's base at the prefix two ballots of the per-lane counts
+//                     (0 to 3) give.
+// Every count is an integer, every rank a prefix of ballots, every voxel has one owner: no result depends on the order of the waves.
+#include "adc_internal.h"
+#include "tsdf_voxel.h"
+
+#define TSDF_WG 256
+#define TSDF_WAVES (TSDF_WG / ADC_WAVE)
+#define TSDF_ROWS_PER_WAVE 4
+#define TSDF_ROW_VOXELS (ADC_WAVE * 4)               // voxels of a row one wave covers
+#define TSDF_TILE 256                                // voxels per tile of the extraction
+#define TSDF_TILES_PER_WAVE 4
+
+struct TsdfIntArgs {
+    TsdfVol vol;
+    TsdfCam cam;
+    const float* map;
+    const uint8_t* img;     // may be null
+    uint32_t* tsdf;
+    uint32_t* color;        // may be null
+    uint32_t* rep;          // [0] in_frustum [1] no_depth [2] occluded [3] updated
+    int xchunks, rows;      // 256-voxel pieces of a row; rows = ny * nz
+};
+
+__global__ __launch_bounds__(TSDF_WG) void k_tsdf_integrate(const TsdfIntArgs g)
+{
+    __shared__ uint32_t s_cnt[4][TSDF_WAVES];
+    const int lane = (int)threadIdx.x & (ADC_WAVE - 1), wave = (int)threadIdx.x / ADC_WAVE;
+    const int xc = (int)(blockIdx.x % (unsigned)g.xchunks), rb = (int)(blockIdx.x / (unsigned)g.xchunks);
+    const int i0 = xc * TSDF_ROW_VOXELS + lane * 4;
+    const bool in = i0 < g.vol.nx; // (nx is a multiple of 4: all four voxels or none)
+    const bool with_colour = g.color != nullptr && g.img != nullptr;
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (int r = 0; r < TSDF_ROWS_PER_WAVE; r++) {
+        const int row = (rb * TSDF_WAVES + wave) * TSDF_ROWS_PER_WAVE + r;
+        if (row >= g.rows || !in) continue;
+        const int k = row / g.vol.ny, j = row - k * g.vol.ny;
+        const TsdfRow rt = tsdf_row(g.vol, g.cam, j, k);
+        int code[4], q[4], pixel[4];
+        bool band[4], any = false, any_colour = false;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            q[e] = 0; pixel[e] = 0; band[e] = false;
+            code[e] = tsdf_decide(g.vol, g.cam, rt, i0 + e, g.map, &q[e], &pixel[e], &band[e]);
+            cnt[0] += code[e] != TSDF_SKIP ? 1u : 0u;
+            cnt[1] += code[e] == TSDF_NO_DEPTH ? 1u : 0u;
+            cnt[2] += code[e] == TSDF_OCCLUDED ? 1u : 0u;
+            cnt[3] += code[e] == TSDF_UPDATE ? 1u : 0u;
+            any = any || code[e] == TSDF_UPDATE;
+            any_colour = any_colour || (code[e] == TSDF_UPDATE && band[e]);
+        }
+        if (!any) continue;
+        const size_t at = (size_t)row * (size_t)g.vol.nx + (size_t)i0;
+        uint4* pw = reinterpret_cast<uint4*>(g.tsdf + at);
+        uint4 w4 = *pw;
+        uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (code[e] == TSDF_UPDATE) w[e] = tsdf_update(w[e], q[e], g.vol.max_weight);
+        w4.x = w[0]; w4.y = w[1]; w4.z = w[2]; w4.w = w[3];
+        *pw = w4;
+        if (with_colour && any_colour) {
+            uint4* pc = reinterpret_cast<uint4*>(g.color + at);
+            uint4 c4 = *pc;
+            uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (code[e] == TSDF_UPDATE && band[e]) c[e] = tsdf_colour_update(c[e], g.img + (size_t)pixel[e] * 3, g.vol.max_weight);
+            c4.x = c[0]; c4.y = c[1]; c4.z = c[2]; c4.w = c[3];
+            *pc = c4;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        uint32_t v = cnt[c];
+        for (int o = ADC_WAVE / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o, ADC_WAVE);
+        if (lane == 0) s_cnt[c][wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        uint32_t t = 0;
+        for (int w = 0; w < TSDF_WAVES; w++) t += s_cnt[threadIdx.x][w];
+        if (t) atomicAdd(&g.rep[threadIdx.x], t);
+    }
+}
+
+struct TsdfExtArgs {
+    TsdfVol vol;
+    const uint32_t* tsdf;
+    const uint32_t* color;  // may be null
+    uint32_t min_weight;
+    int N, ntiles, nxy;     // voxels, tiles of TSDF_TILE voxels, nx * ny
+    uint32_t* rep;          // [0] voxels_seen [1] points
+    uint32_t* tbase;        // per tile: crossings -> (scan) crossings of all tiles before it
+    uint4* points;          // may be null
+    uint32_t cap;
+    uint32_t* count;        // may be null
+};
+
+// the crossings of voxel n as a mask (bit 0 x, 1 y, 2 z); word = its voxel word, nb[] the neighbour words of the set bits, (i, j, k) its place
+__device__ __forceinline__ uint32_t tsdf_lane_crossings(const TsdfExtArgs& g, int n, int lane, uint32_t* word, uint32_t nb[3], int* i, int* j, int* k, bool* seen)
+{
+    const bool in = n < g.N;
+    *word = in ? g.tsdf[n] : 0u;
+    const int row = n / g.vol.nx;
+    *i = n - row * g.vol.nx;
+    *k = row / g.vol.ny;
+    *j = row - *k * g.vol.ny;
+    *seen = in && tsdf_seen(*word, g.min_weight);
+    nb[0] = (uint32_t)__shfl_down((int)*word, 1, ADC_WAVE); // (every lane of the wave takes part)
+    nb[1] = nb[2] = 0u;
+    if (!*seen) return 0u;
+    uint32_t mask = 0u;
+    if (*i + 1 < g.vol.nx) { // (then n + 1 lies in the same row, inside the volume)
+        if (lane == ADC_WAVE - 1) nb[0] = g.tsdf[n + 1];
+        mask |= tsdf_crossing(*word, nb[0], g.min_weight) ? 1u : 0u;
+    }
+    if (*j + 1 < g.vol.ny) {
+        nb[1] = g.tsdf[n + g.vol.nx];
+        mask |= tsdf_crossing(*word, nb[1], g.min_weight) ? 2u : 0u;
+    }
+    if (*k + 1 < g.vol.nz) {
+        nb[2] = g.tsdf[n + g.nxy];
+        mask |= tsdf_crossing(*word, nb[2], g.min_weight) ? 4u : 0u;
+    }
+    return mask;
+}
+
+__global__ __launch_bounds__(TSDF_WG) void k_tsdf_measure(const TsdfExtArgs g)
+{
+    __shared__ uint32_t s_seen[TSDF_WAVES];
+    const int lane = (int)threadIdx.x & (ADC_WAVE - 1), wave = (int)threadIdx.x / ADC_WAVE;
+    uint32_t n_seen = 0;
+#pragma unroll 1
+    for (int t = 0; t < TSDF_TILES_PER_WAVE; t++) {
+        const int tile = ((int)blockIdx.x * TSDF_WAVES + wave) * TSDF_TILES_PER_WAVE + t;
+        if (tile >= g.ntiles) continue; // (uniform in the wave)
+        uint32_t total = 0;
+#pragma unroll 1
+        for (int c = 0; c < TSDF_TILE / ADC_WAVE; c++) {
+            const int n = tile * TSDF_TILE + c * ADC_WAVE + lane;
+            uint32_t word, nb[3];
+            int i, j, k;
+            bool seen;
+            const uint32_t mask = tsdf_lane_crossings(g, n, lane, &word, nb, &i, &j, &k, &seen);
+            const uint32_t cnt = (uint32_t)__popc(mask);
+            total += (uint32_t)__popcll(__ballot((cnt & 1u) != 0)) + 2u * (uint32_t)__popcll(__ballot((cnt & 2u) != 0));
+            n_seen += (uint32_t)__popcll(__ballot(seen));
+        }
+        if (lane == 0) g.tbase[tile] = total;
+    }
+    if (lane == 0) s_seen[wave] = n_seen;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < TSDF_WAVES; w++) t += s_seen[w];
+        if (t) atomicAdd(&g.rep[0], t);
+    }
+}
+
+// One workgroup of 1024: the tile counts -> exclusive prefix sums in place, TSDF_SCAN_TILE entries at a time with a carry (the form
+// of k_mesh_scan, one array); the total goes to the report word and to the caller's device word.  A lane owns four consecutive
+// entries: the 524288 tiles of a 512^3 volume take 128 turns and 0.31 ms, a third of the extraction; sixteen entries per lane (32
+// turns) were measured and took 0.47 ms, the lane's serial loads 64 bytes apart cost more than the barriers saved (profiles/tsdf_timing.md).
+#define TSDF_SCAN_PER_LANE 4
+#define TSDF_SCAN_TILE (1024 * TSDF_SCAN_PER_LANE)
+__global__ __launch_bounds__(1024) void k_tsdf_scan(uint32_t* __restrict__ tbase, int ntiles, uint32_t* __restrict__ rep, uint32_t* __restrict__ count)
+{
+    __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_carry;
+    const int lane = (int)threadIdx.x & (ADC_WAVE - 1), wave = (int)threadIdx.x / ADC_WAVE;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (int c = 0; c < ntiles; c += TSDF_SCAN_TILE) {
+        const int i0 = c + (int)threadIdx.x * TSDF_SCAN_PER_LANE;
+        uint32_t v[TSDF_SCAN_PER_LANE], sv = 0;
+#pragma unroll
+        for (int k = 0; k < TSDF_SCAN_PER_LANE; k++) {
+            v[k] = i0 + k < ntiles ? tbase[i0 + k] : 0u;
+            sv += v[k];
+        }
+        uint32_t iv = sv; // inclusive over the lanes of the wave
+        for (int o = 1; o < ADC_WAVE; o <<= 1) {
+            const uint32_t uv = (uint32_t)__shfl_up((int)iv, o, ADC_WAVE);
+            if (lane >= o) iv += uv;
+        }
+        if (lane == ADC_WAVE - 1) s_wave[wave] = iv;
+        __syncthreads();
+        uint32_t bv = s_carry, total = 0;
+        for (int w = 0; w < 16; w++) {
+            const uint32_t wv = s_wave[w];
+            if (w < wave) bv += wv;
+            total += wv;
+        }
+        bv += iv - sv; // entries of all lanes, waves and turns in front of this lane's first
+#pragma unroll
+        for (int k = 0; k < TSDF_SCAN_PER_LANE; k++)
+            if (i0 + k < ntiles) {
+                tbase[i0 + k] = bv;
+                bv += v[k];
+            }
+        __syncthreads();
+        if (threadIdx.x == 0) s_carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        rep[1] = s_carry;
+        if (count) *count = s_carry;
+    }
+}
+
+__global__ __launch_bounds__(TSDF_WG) void k_tsdf_emit(const TsdfExtArgs g)
+{
+    const int lane = (int)threadIdx.x & (ADC_WAVE - 1), wave = (int)threadIdx.x / ADC_WAVE;
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll 1
+    for (int t = 0; t < TSDF_TILES_PER_WAVE; t++) {
+        const int tile = ((int)blockIdx.x * TSDF_WAVES + wave) * TSDF_TILES_PER_WAVE + t;
+        if (tile >= g.ntiles) continue; // (uniform in the wave)
+        uint32_t base = g.tbase[tile];
+        if (base >= g.cap) continue;    // (uniform: every record of this tile lies behind the capacity)
+#pragma unroll 1
+        for (int c = 0; c < TSDF_TILE / ADC_WAVE; c++) {
+            const int n = tile * TSDF_TILE + c * ADC_WAVE + lane;
+            uint32_t word, nb[3];
+            int i, j, k;
+            bool seen;
+            const uint32_t mask = tsdf_lane_crossings(g, n, lane, &word, nb, &i, &j, &k, &seen);
+            const uint32_t cnt = (uint32_t)__popc(mask);
+            const unsigned long long b0 = __ballot((cnt & 1u) != 0), b1 = __ballot((cnt & 2u) != 0);
+            uint32_t rank = base + (uint32_t)__popcll(b0 & below) + 2u * (uint32_t)__popcll(b1 & below);
+            base += (uint32_t)__popcll(b0) + 2u * (uint32_t)__popcll(b1);
+            if (!mask || rank >= g.cap) continue;
+            const uint32_t ca = g.color ? g.color[n] : 0u;
+            const int off[3] = {1, g.vol.nx, g.nxy};
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                if (!(mask & (1u << a))) continue;
+                if (rank < g.cap) {
+                    const uint32_t cb = g.color ? g.color[n + off[a]] : 0u;
+                    uint32_t rec[4];
+                    tsdf_point(g.vol, i, j, k, a, word, nb[a], ca, cb, rec);
+                    uint4 pt;
+                    pt.x = rec[0]; pt.y = rec[1]; pt.z = rec[2]; pt.w = rec[3];
+                    g.points[rank] = pt;
+                }
+                rank++;
+            }
+        }
+    }
+}
+
+static int tsdf_tiles(const adc_tsdf_params& p)
+{
+    const long long N = (long long)p.nx * p.ny * p.nz;
+    return (int)((N + TSDF_TILE - 1) / TSDF_TILE);
+}
+
+size_t adc_tsdf_tile_count(const adc_tsdf_params* p) { return (size_t)tsdf_tiles(*p); }
+
+hipError_t adc_launch_tsdf_integrate(adc_handle* h, const float* map, const uint8_t* img, const adc_tsdf_frame* frame)
+{
+    if (!h->tsdf_vol || !h->tsdf_rep) return hipErrorInvalidValue;
+    TsdfIntArgs g;
+    g.vol = tsdf_vol(h->tsdf_params);
+    g.cam = tsdf_cam(*frame, h->p.W, h->p.H);
+    g.map = map;
+    g.img = img;
+    g.tsdf = h->tsdf_vol;
+    g.color = h->tsdf_col;
+    g.rep = h->tsdf_rep;
+    g.xchunks = (g.vol.nx + TSDF_ROW_VOXELS - 1) / TSDF_ROW_VOXELS;
+    g.rows = g.vol.ny * g.vol.nz;
+    const int rows_per_wg = TSDF_WAVES * TSDF_ROWS_PER_WAVE;
+    const unsigned blocks = (unsigned)g.xchunks * (unsigned)((g.rows + rows_per_wg - 1) / rows_per_wg);
+    hipLaunchKernelGGL(k_tsdf_integrate, dim3(blocks), dim3(TSDF_WG), 0, h->stream, g);
+    return hipGetLastError();
+}
+
+static TsdfExtArgs tsdf_ext_args(adc_handle* h, const AdcTsdfExtReq& r)
+{
+    TsdfExtArgs g;
+    g.vol = tsdf_vol(h->tsdf_params);
+    g.tsdf = h->tsdf_vol;
+    g.color = h->tsdf_col;
+    g.min_weight = r.min_weight;
+    g.N = g.vol.nx * g.vol.ny * g.vol.nz;
+    g.ntiles = tsdf_tiles(h->tsdf_params);
+    g.nxy = g.vol.nx * g.vol.ny;
+    g.rep = h->tsdf_rep + ADC_TSDF_REP_EXTRACT;
+    g.tbase = h->tsdf_tiles;
+    g.points = static_cast<uint4*>(r.points);
+    g.cap = r.points ? r.capacity : 0u;
+    g.count = r.count;
+    return g;
+}
+
+static unsigned tsdf_ext_blocks(const TsdfExtArgs& g)
+{
+    const int per_wg = TSDF_WAVES * TSDF_TILES_PER_WAVE;
+    return (unsigned)((g.ntiles + per_wg - 1) / per_wg);
+}
+
+hipError_t adc_launch_tsdf_measure(adc_handle* h, const AdcTsdfExtReq& r)
+{
+    if (!h->tsdf_vol || !h->tsdf_rep || !h->tsdf_tiles) return hipErrorInvalidValue;
+    const TsdfExtArgs g = tsdf_ext_args(h, r);
+    hipLaunchKernelGGL(k_tsdf_measure, dim3(tsdf_ext_blocks(g)), dim3(TSDF_WG), 0, h->stream, g);
+    return hipGetLastError();
+}
+
+hipError_t adc_launch_tsdf_scan(adc_handle* h, const AdcTsdfExtReq& r)
+{
+    const TsdfExtArgs g = tsdf_ext_args(h, r);
+    hipLaunchKernelGGL(k_tsdf_scan, dim3(1), dim3(1024), 0, h->stream, g.tbase, g.ntiles, g.rep, g.count);
+    return hipGetLastError();
+}
+
+hipError_t adc_launch_tsdf_emit(adc_handle* h, const AdcTsdfExtReq& r)
+{
+    const TsdfExtArgs g = tsdf_ext_args(h, r);
+    hipLaunchKernelGGL(k_tsdf_emit, dim3(tsdf_ext_blocks(g)), dim3(TSDF_WG), 0, h->stream, g);
+    return hipGetLastError();
+}

@@ -691,7 +691,7 @@ static hipError_t irv_launch(adc_handle* h, int k0, int count)
         if (!h->irv_cold_valid || memcmp(h->irv_cold_host, &c, sizeof(c)) != 0) { // (the same block Match after Match unless buffers swapped roles)
             // two staging slots, alternating: a slot is rewritten two changes later at the earliest -- a handle has one Match in flight,
             // so the copy that read it has long drained
-            int32_t* slot = h->pin_flags + 32 + 16 * (h->irv_cold_flip & 1);
+            int32_t* slot = h->pin_flags + ADC_PIN_IRV_COLD + 16 * (h->irv_cold_flip & 1);
             h->irv_cold_flip ^= 1;
             memcpy(slot, &c, sizeof(c));
             const hipError_t e = hipMemcpyAsync(h->irv_cold, slot, sizeof(IrvCold), hipMemcpyHostToDevice, h->stream);
@@ -725,7 +725,7 @@ hipError_t adc_run_region_voting(adc_handle* h)
     h->irv_chain = budget;
     // the state the last kernel published (slot chain & 1), read by adc_wait / adc_voting_finish
     if (h->pin_flags)
-        e = hipMemcpyAsync(h->pin_flags + 16, h->vote_counters + 16 * (h->irv_chain & 1), 8 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(h->pin_flags + ADC_PIN_VOTING, h->vote_counters + 16 * (h->irv_chain & 1), 8 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
     h->fly.irv_pending = 1;
     return e;
 }
@@ -739,7 +739,7 @@ hipError_t adc_voting_finish(adc_handle* h, int* continued)
     if (!h->fly.irv_pending || !h->pin_flags) return hipSuccess;
     h->fly.irv_pending = 0;
     hipError_t e;
-    int32_t* st = h->pin_flags + 16;
+    int32_t* st = h->pin_flags + ADC_PIN_VOTING;
     int guard = 0;
     // A chain whose write-back kernel (FINAL) was the LAST kernel of the budget has finished as well: the result is in disp_l and the
     // state it published carries the statistics.  Continuing it would only run idle kernels -- and report *continued, upon which

@@ -275,6 +275,21 @@ bool ADCensusStereo::Mesh(const float32* disp, const uint8* bgr_left, const adc_
     return impl_ && adc_mesh(impl_, disp, bgr_left, calib, params, vertices, vertex_capacity, vertex_index, triangles, triangle_capacity, report) == 0;
 }
 bool ADCensusStereo::GetMeshReport(adc_mesh_report* report) { return impl_ && adc_get_mesh_report(impl_, report) == 0; }
+
+bool ADCensusStereo::TsdfCreate(const adc_tsdf_params* params) { return impl_ && adc_tsdf_create(impl_, params) == 0; }
+bool ADCensusStereo::TsdfReset() { return impl_ && adc_tsdf_reset(impl_) == 0; }
+bool ADCensusStereo::TsdfIntegrate(const float32* map, const uint8* bgr_left, const adc_tsdf_frame* frame, adc_tsdf_report* report)
+{
+    return impl_ && adc_tsdf_integrate(impl_, map, bgr_left, frame, report) == 0;
+}
+bool ADCensusStereo::TsdfExtract(const adc_tsdf_extract_params* params, adc_point* points, uint64 capacity, adc_tsdf_extract_report* report)
+{
+    return impl_ && adc_tsdf_extract(impl_, params, points, capacity, report) == 0;
+}
+bool ADCensusStereo::GetTsdfReport(adc_tsdf_report* integrate_report, adc_tsdf_extract_report* extract_report)
+{
+    return impl_ && adc_get_tsdf_report(impl_, integrate_report, extract_report) == 0;
+}
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

@@ -29,6 +29,13 @@
 // where there is no normal), red green blue uchar; element face with property list uchar int vertex_indices.  The mesh comes from the
 // map, so --voxel does not touch it and with --speckle it has the filter's holes.  A malformed flag is refused while the arguments are
 // parsed.
+// --tsdf NX,NY,NZ,VOXEL,OX,OY,OZ[,TRUNC[,MINW]] (anywhere after the program name; needs --calib) fuses the run's disparity map and left
+// image into a TSDF volume on the device (ADCensusStereo::TsdfCreate / TsdfIntegrate / TsdfExtract: NX x NY x NZ voxels of edge VOXEL,
+// NX a multiple of 4, the corner of voxel (0, 0, 0) at the world position OX, OY, OZ, truncation TRUNC, default 3 * VOXEL, a colour
+// volume) and writes the surface points between voxels of weight >= MINW, default 1, to <out>-tsdf.ply, a binary little-endian PLY:
+// element vertex with x y z float, red green blue uchar, in the world frame.  --pose FILE (only with --tsdf): FILE holds 12 numbers, R
+// row-major then t, which take a world point into the left camera (Xc = R * Xw + t); default: the identity.  A malformed flag or file
+// is refused while the arguments are parsed.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -400,6 +407,60 @@ int main(int argc, char** argv)
             argc -= i + 1 < argc ? 2 : 1;
             break;
         }
+    bool with_tsdf = false, with_pose = false; // (--tsdf, --pose and their values likewise; the pose file is read and checked here)
+    adc_tsdf_params tsdf_params;
+    adc_tsdf_extract_params tsdf_extract;
+    adc_tsdf_frame tsdf_frame;
+    memset(&tsdf_params, 0, sizeof(tsdf_params));
+    memset(&tsdf_extract, 0, sizeof(tsdf_extract));
+    memset(&tsdf_frame, 0, sizeof(tsdf_frame));
+    tsdf_frame.R[0] = tsdf_frame.R[4] = tsdf_frame.R[8] = 1.0f;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf")) {
+            char tail = 0;
+            adc_tsdf_params& t = tsdf_params;
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int minw = 1;
+            int n = sscanf(v, "%d,%d,%d,%f,%f,%f,%f,%f,%d%c", &t.nx, &t.ny, &t.nz, &t.voxel, &t.origin[0], &t.origin[1], &t.origin[2], &t.trunc, &minw, &tail);
+            if (n == 7 && sscanf(v, "%d,%d,%d,%f,%f,%f,%f%c", &t.nx, &t.ny, &t.nz, &t.voxel, &t.origin[0], &t.origin[1], &t.origin[2], &tail) != 7) n = 0;
+            if (n == 8 && sscanf(v, "%d,%d,%d,%f,%f,%f,%f,%f%c", &t.nx, &t.ny, &t.nz, &t.voxel, &t.origin[0], &t.origin[1], &t.origin[2], &t.trunc, &tail) != 8) n = 0;
+            if (n == 7) t.trunc = 3.0f * t.voxel;
+            t.z_min = 0.0f;
+            t.z_max = INFINITY;
+            t.max_weight = 64;
+            t.flags = ADC_TSDF_COLOR;
+            const bool dims = n >= 7 && n <= 9 && t.nx >= 4 && t.ny >= 4 && t.nz >= 4 && t.nx <= ADC_TSDF_MAX_DIM && t.ny <= ADC_TSDF_MAX_DIM && t.nz <= ADC_TSDF_MAX_DIM &&
+                              t.nx % 4 == 0 && (unsigned long long)t.nx * t.ny * t.nz <= (1ull << 30);
+            if (!dims || !(std::isfinite(t.voxel) && t.voxel > 0.f) || !std::isfinite(t.origin[0]) || !std::isfinite(t.origin[1]) || !std::isfinite(t.origin[2]) ||
+                !(std::isfinite(t.trunc) && t.trunc > 0.f) || minw < 1 || minw > 65535) {
+                printf("--tsdf refused: it needs NX,NY,NZ,VOXEL,OX,OY,OZ[,TRUNC[,MINW]] (sizes in 4..2048, NX a multiple of 4, at most 2^30 voxels, VOXEL > 0, TRUNC > 0, MINW in 1..65535)\n");
+                return -1;
+            }
+            tsdf_extract.min_weight = (uint32)minw;
+            with_tsdf = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--pose")) {
+            FILE* f = i + 1 < argc ? fopen(argv[i + 1], "r") : nullptr;
+            float v[12];
+            int n = 0;
+            char extra = 0;
+            while (f && n < 12 && fscanf(f, "%f", &v[n]) == 1 && std::isfinite(v[n])) n++;
+            const bool clean = f && n == 12 && fscanf(f, " %c", &extra) != 1;
+            if (f) fclose(f);
+            if (!clean) { printf("--pose refused: it needs a file of 12 finite numbers (R row-major, then t)\n"); return -1; }
+            for (int k = 0; k < 9; k++) tsdf_frame.R[k] = v[k];
+            for (int k = 0; k < 3; k++) tsdf_frame.t[k] = v[9 + k];
+            with_pose = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_tsdf && !with_calib) { printf("--tsdf refused: it needs --calib\n"); return -1; }
+    if (with_pose && !with_tsdf) { printf("--pose refused: it needs --tsdf\n"); return -1; }
     bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
     RectifyFile rect_file[2];
     for (int i = 1; i < argc; i++)
@@ -821,6 +882,36 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < rep.triangles; i++) { fwrite(&three, 1, 1, ply); fwrite(&triangles[3 * i], 4, 3, ply); }
             fclose(ply);
         } else printf("cannot write %s-mesh.ply\n", out.c_str());
+    }
+    if (with_tsdf) { // the delivered disparity map and the left image fused into a fresh volume, then its surface points
+        tsdf_frame.kind = ADC_REG_FROM_DISPARITY;
+        tsdf_frame.calib = calib;
+        adc_tsdf_report irep;
+        adc_tsdf_extract_report xrep;
+        const uint8* colours = (with_rectify || with_raw) ? rect_left.data() : left.data();
+        std::vector<adc_point> points;
+        bool ok = ad_census.TsdfCreate(&tsdf_params) && ad_census.TsdfIntegrate(disparity.data(), colours, &tsdf_frame, &irep) &&
+                  ad_census.TsdfExtract(&tsdf_extract, nullptr, 0, &xrep); // (counts only: the file is sized by the report)
+        if (ok && xrep.points) {
+            points.resize(xrep.points);
+            ok = ad_census.TsdfExtract(&tsdf_extract, points.data(), points.size(), &xrep) && xrep.points == points.size();
+        }
+        if (!ok) {
+            printf("tsdf refused: %s\n", ad_census.LastError());
+            return -2;
+        }
+        printf("\nTSDF: %u voxels in the frustum, %u without depth, %u occluded, %u updated; %u voxels seen, %u surface points\n", irep.in_frustum, irep.no_depth,
+               irep.occluded, irep.updated, xrep.voxels_seen, xrep.points);
+        FILE* ply = fopen((out + "-tsdf.ply").c_str(), "wb");
+        if (ply) {
+            fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                         "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", points.size());
+            for (size_t i = 0; i < points.size(); i++) {
+                fwrite(&points[i].x, 4, 3, ply);
+                fwrite(&points[i].r, 1, 3, ply);
+            }
+            fclose(ply);
+        } else printf("cannot write %s-tsdf.ply\n", out.c_str());
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

@@ -17,6 +17,7 @@
  * SetRegisterTarget / ClearRegisterTarget / RegisterDepth / AlignColor (optional registration of depth into a second camera on the device),
  * Normals / GetNormalsReport (optional camera-facing surface normals from a disparity map on the device),
  * Mesh / GetMeshReport (optional triangle mesh from a disparity map on the device),
+ * TsdfCreate / TsdfReset / TsdfIntegrate / TsdfExtract / GetTsdfReport (optional TSDF volume on the device: maps of many frames fused, surface points),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -40,6 +41,11 @@ struct adc_normals_params;
 struct adc_normals_report;
 struct adc_mesh_params;
 struct adc_mesh_report;
+struct adc_tsdf_params;
+struct adc_tsdf_frame;
+struct adc_tsdf_report;
+struct adc_tsdf_extract_params;
+struct adc_tsdf_extract_report;
 struct adc_point;
 
 class ADCensusStereo {
@@ -160,6 +166,18 @@ public:
     bool Mesh(const float32* disp, const uint8* bgr_left, const adc_calib* calib, const adc_mesh_params* params, adc_point* vertices,
               uint64 vertex_capacity, sint32* vertex_index, uint32* triangles, uint64 triangle_capacity, adc_mesh_report* report);
     bool GetMeshReport(adc_mesh_report* report);
+    /** Optional TSDF volume on the device (adc_tsdf_*, include/adcensus_c_api.h holds the definition).  TsdfCreate allocates and
+     *  zeroes a volume (a second call replaces it; adc_tsdf_params: size, voxel, origin, trunc, crop, max_weight, ADC_TSDF_COLOR),
+     *  TsdfReset empties it.  TsdfIntegrate fuses one float32 [H][W] host map (a disparity or a depth map, frame->kind) seen from
+     *  frame->R, frame->t (WORLD -> camera); bgr_left uint8 [H][W][3] may be null and needs a colour volume; report may be null.
+     *  TsdfExtract writes the first min(points, capacity) surface points (adc_point, world frame) and reports how many there are;
+     *  params may be null (min_weight = 1), points may be null with capacity 0 (counts only), report may be null.  GetTsdfReport: the
+     *  reports of the last completed calls; either may be null. */
+    bool TsdfCreate(const adc_tsdf_params* params);
+    bool TsdfReset();
+    bool TsdfIntegrate(const float32* map, const uint8* bgr_left, const adc_tsdf_frame* frame, adc_tsdf_report* report);
+    bool TsdfExtract(const adc_tsdf_extract_params* params, adc_point* points, uint64 capacity, adc_tsdf_extract_report* report);
+    bool GetTsdfReport(adc_tsdf_report* integrate_report, adc_tsdf_extract_report* extract_report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

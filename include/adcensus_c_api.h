@@ -30,6 +30,8 @@
  *   adc_normals           exactly in integers (float32 x 4 and / or a normal-map image of 4 bytes per pixel)
  *   adc_mesh_device /     a triangle mesh from any disparity map: gated grid cells over a lattice of every step-th pixel, vertices
  *   adc_mesh              as cloud points, triangles as vertex numbers, both compacted in raster order
+ *   adc_tsdf_create / adc_tsdf_integrate_device / adc_tsdf_extract_device / ...   a TSDF volume in the handle: the maps of many
+ *                         frames fused per voxel in integers, and the volume's surface points in voxel order
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -796,6 +798,124 @@ int adc_mesh(adc_handle* h, const float* disp, const uint8_t* bgr_left, const ad
              adc_point* vertices, uint64_t vertex_capacity, int32_t* vertex_index, uint32_t* triangles, uint64_t triangle_capacity,
              adc_mesh_report* report);
 int adc_get_mesh_report(adc_handle* h, adc_mesh_report* out);
+
+/* -------------------------------------------------------------------------------------------
+ * TSDF volume on the device: depth maps of many frames fused into one truncated signed distance volume, and the surface points of
+ * that volume (k_tsdf.hip; the voxel rule is adcensus_amd/csrc/tsdf_voxel.h, tests/tsdf_ref.py holds the same definition in numpy and
+ * the kernels match it bit for bit, in whatever order the waves run: one thread owns a voxel, every accumulated quantity is an
+ * integer).  Optional and off by default: the volume is handle state, adc_create allocates nothing of it, and no Match path changes.
+ * All float arithmetic is IEEE binary32, one rounding per operation, nothing fused, parenthesised as written.
+ *
+ * Parameters (adc_tsdf_params, 64 bytes): int32 nx, ny, nz, each in [4, 2048], nx a multiple of 4, nx * ny * nz <= 2^30; float voxel
+ * (the edge of a voxel), finite and > 0; float origin[3], finite, the world position of the CORNER of voxel (0, 0, 0); float trunc,
+ * finite and > 0; float z_min, z_max, not NaN, 0 <= z_min <= z_max, z_max may be +inf; uint32 max_weight in [1, 65535]; uint32 flags:
+ * ADC_TSDF_COLOR allocates a colour word per voxel; uint32 reserved_[4] = 0.  The host computes inv_trunc = 1.0f / trunc once.
+ * Voxel (i, j, k) has the index n = (k * ny + j) * nx + i and is one uint32 word (uint16)(int16)t | w << 16: t in [-32767, 32767] is
+ * the distance in units of trunc / 32767, w the weight (a stored t of -32768, which only adc_tsdf_upload can bring in, is read as
+ * -32767).  With the colour flag there is a second uint32 per voxel: r | g << 8 | b << 16 | cw << 24.  All bytes zero = an empty volume.
+ *
+ * Frame (adc_tsdf_frame, 96 bytes): int32 kind, ADC_REG_FROM_DISPARITY or ADC_REG_FROM_DEPTH; an adc_calib; float R[9] row-major and
+ * float t[3], which take a WORLD point into the rectified left CAMERA frame, Xc = R * Xw + t (for a camera-to-world pose (Rcw, c):
+ * R = transpose(Rcw), t = -(R * c)); every field finite; uint32 flags = 0, uint32 reserved_[5] = 0.  fb = focal_px * baseline is one
+ * multiply.  Validity and Z of a map value are exactly those of adc_register_depth_device (ADC_REG_FROM_*).
+ *
+ * Integrate.  Voxels are independent; a skipped voxel keeps its bits.  For voxel (i, j, k):
+ *   1. centre: xw = origin[0] + ((float)i + 0.5f) * voxel; yw from j and origin[1], zw from k and origin[2] in the same way.
+ *   2. camera frame: Xc = ((R[0]*xw + R[1]*yw) + R[2]*zw) + t[0]; Yc from R[3..5], t[1]; Zc from R[6..8], t[2].
+ *   3. skip unless Zc is finite, Zc > 0 and z_min <= Zc && Zc <= z_max.
+ *   4. project: rz = 1.0f / Zc; u = ((Xc * focal_px) * rz) + cx; v = ((Yc * focal_px) * rz) + cy; skip unless fabsf(u) < 32768.0f &&
+ *      fabsf(v) < 32768.0f (a NaN fails).
+ *   5. pixel: x = (int)floorf(u + 0.5f), y = (int)floorf(v + 0.5f); skip unless 0 <= x < W && 0 <= y < H.  No float reaches an
+ *      address before that test.  The voxel now counts as in_frustum.
+ *   6. depth: D = the Z of map[y][x] by the frame's kind; a pixel without depth: skip, count no_depth.
+ *   7. signed distance: sdf = D - Zc; if !(sdf >= -trunc): skip, count occluded.  (D = +inf from an overflowing fb / s is free space.)
+ *   8. quantise: f = fminf(sdf * inv_trunc, 1.0f); q = (int)floorf(f * 32767.0f + 0.5f)   (q >= -32767 whatever the rounding).
+ *   9. update from the old t, w in non-negative integers: m = w + 1; t' = (t*w + q + 32767*m + m/2) / m - 32767;
+ *      w' = min(w + 1, max_weight); count updated.  (The numerator stays below 2^32.)
+ *  10. colour, only with a colour volume, an image given and fabsf(sdf) <= trunc: cm = cw + 1; each channel becomes
+ *      (c*cw + c_obs + cm/2) / cm with c_obs from the left image at (x, y), stored B,G,R; cw' = min(cw + 1, min(max_weight, 255)).
+ * Integrate report (adc_tsdf_report, uint32 each): in_frustum (voxels that reached step 6), no_depth, occluded, updated, four
+ * reserved words; in_frustum = no_depth + occluded + updated.
+ *
+ * Extract (surface points).  Parameters (adc_tsdf_extract_params, 32 bytes): uint32 min_weight in [1, 65535], uint32 reserved_[7] = 0;
+ * NULL: min_weight = 1.  For voxel a = (i, j, k) and an axis x, y or z whose neighbour b = a + 1 on that axis lies inside the volume,
+ * the pair is a crossing iff w_a >= min_weight && w_b >= min_weight && (t_a < 0) != (t_b < 0).  s = (float)t_a / ((float)t_a -
+ * (float)t_b): both conversions and the difference are exact, so there is one rounding.  The point is a's centre as in step 1 with
+ * s * voxel added to the coordinate of that axis.  A record is an adc_point in the WORLD frame; r, g, b come from a when s <= 0.5f and
+ * from b otherwise (0 without a colour volume); pad = min(min(w_a, w_b), 255).  Order: ascending n of a; within a voxel x, then y, then
+ * z.  `points` is the number of crossings whatever the capacity: the first min(points, capacity) records are written and nothing
+ * behind them; a capacity of 0 with a non-NULL pointer counts only.  d_count (optional): one uint32 device word = points, written on
+ * the stream.  A voxel whose t is exactly 0 can yield two coincident points: the crossing in front of it ends on its centre (s = 1
+ * from a - 1) and the crossing behind it starts there (s = 0).
+ * Extract report (adc_tsdf_extract_report, uint32 each): voxels_seen (w >= min_weight), points, six reserved words.
+ *
+ * adc_tsdf_create            allocates and zeroes the volume (4 bytes per voxel, 8 with ADC_TSDF_COLOR); a second call replaces it.
+ * adc_tsdf_reset             an empty volume again: one memset per plane of words.
+ * adc_tsdf_destroy           gives the volume's memory back early (adc_destroy frees it too); 0 also when there was none.
+ * adc_tsdf_integrate_device  one frame; d_map float32 [H][W] of the handle's geometry (4-byte aligned), d_bgr_left uint8 [H][W][3] or
+ *                            NULL.  Asynchronous on the handle's stream, completed by adc_wait; successive calls may be enqueued
+ *                            without a wait between them (the stream orders them; the report is that of the last).
+ * adc_tsdf_integrate         the same with HOST pointers, synchronous; device scratch is allocated on the first call that needs it.
+ * adc_tsdf_extract_device    the surface points; d_points is 16-byte aligned, d_count 4-byte aligned; asynchronous, completed by adc_wait.
+ *                            The first call allocates the scratch (per-tile counts).
+ * adc_tsdf_extract           the same with HOST pointers, synchronous; copies out min(points, capacity) records; points may be NULL
+ *                            with capacity 0 (counts only).  Its device scratch holds min(points, capacity) records: when it has to
+ *                            grow, the call counts first, so a generous capacity costs no memory.
+ * adc_get_tsdf_report        the reports of the last completed integrate / extract call; either pointer may be NULL (not both); a
+ *                            report that is asked for and does not exist yet is refused.
+ * adc_tsdf_get_volume_device the device addresses of the voxel words and the colour words (NULL without a colour volume) and the
+ *                            parameters, for a GPU consumer such as a ray caster; each out pointer may be NULL.
+ * adc_tsdf_download / adc_tsdf_upload   host copies of the whole volume, synchronous (they wait for the handle's stream first): tsdf
+ *                            uint32 [nz][ny][nx], color the same or NULL.  To save and restore a volume.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued or changed (a NULL argument, a bad parameter, flag or reserved word, no
+ * volume, a calibration adc_match_out would refuse, a non-finite R or t, a misaligned device address, an image given without a colour
+ * volume -- refused, not ignored --, a colour pointer given to download / upload without a colour volume, a Match pending -- adc_wait
+ * first, for the reason given at adc_evaluate_device); 2 on a HIP failure (the handle stays usable; after a failed adc_tsdf_create
+ * there is no volume).  The volume is not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_TSDF_COLOR 1u
+#define ADC_TSDF_MAX_DIM 2048
+typedef struct adc_tsdf_params {
+    int32_t nx, ny, nz;
+    float voxel;
+    float origin[3];
+    float trunc;
+    float z_min, z_max;
+    uint32_t max_weight;
+    uint32_t flags;      /* ADC_TSDF_COLOR */
+    uint32_t reserved_[4];
+} adc_tsdf_params; /* 64 bytes */
+typedef struct adc_tsdf_frame {
+    int32_t kind;        /* ADC_REG_FROM_DISPARITY / ADC_REG_FROM_DEPTH */
+    adc_calib calib;
+    float R[9], t[3];    /* world -> camera */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved_[5];
+} adc_tsdf_frame; /* 96 bytes */
+typedef struct adc_tsdf_report {
+    uint32_t in_frustum, no_depth, occluded, updated;
+    uint32_t reserved_[4];
+} adc_tsdf_report;
+typedef struct adc_tsdf_extract_params {
+    uint32_t min_weight; /* [1, 65535] */
+    uint32_t reserved_[7];
+} adc_tsdf_extract_params;
+typedef struct adc_tsdf_extract_report {
+    uint32_t voxels_seen, points;
+    uint32_t reserved_[6];
+} adc_tsdf_extract_report;
+int adc_tsdf_create(adc_handle* h, const adc_tsdf_params* params);
+int adc_tsdf_reset(adc_handle* h);
+int adc_tsdf_destroy(adc_handle* h);
+int adc_tsdf_integrate_device(adc_handle* h, const void* d_map, const void* d_bgr_left, const adc_tsdf_frame* frame);
+int adc_tsdf_integrate(adc_handle* h, const float* map, const uint8_t* bgr_left, const adc_tsdf_frame* frame, adc_tsdf_report* report);
+int adc_tsdf_extract_device(adc_handle* h, const adc_tsdf_extract_params* params, void* d_points, uint64_t capacity, void* d_count);
+int adc_tsdf_extract(adc_handle* h, const adc_tsdf_extract_params* params, adc_point* points, uint64_t capacity,
+                     adc_tsdf_extract_report* report);
+int adc_get_tsdf_report(adc_handle* h, adc_tsdf_report* integrate_report, adc_tsdf_extract_report* extract_report);
+int adc_tsdf_get_volume_device(adc_handle* h, void** d_tsdf, void** d_color, adc_tsdf_params* params);
+int adc_tsdf_download(adc_handle* h, uint32_t* tsdf, uint32_t* color);
+int adc_tsdf_upload(adc_handle* h, const uint32_t* tsdf, const uint32_t* color);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
