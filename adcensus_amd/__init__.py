@@ -326,6 +326,16 @@ class TsdfExtractReport(C.Structure):
     _fields_ = [("voxels_seen", C.c_uint32), ("points", C.c_uint32), ("reserved_", C.c_uint32 * 6)]
 
 
+TSDF_MESH_ENTRY_POINTS = ("adc_tsdf_mesh_device", "adc_tsdf_mesh", "adc_get_tsdf_mesh_report")
+
+
+class TsdfMeshReport(C.Structure):
+    """adc_tsdf_mesh_report: voxels with w >= min_weight; vertices (the crossings) and triangles whatever the capacities; cells whose
+    eight corners are seen, and those of them that emit at least one triangle."""
+    _fields_ = [("voxels_seen", C.c_uint32), ("vertices", C.c_uint32), ("triangles", C.c_uint32), ("cells_seen", C.c_uint32), ("cells_surface", C.c_uint32),
+                ("reserved_", C.c_uint32 * 3)]
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -486,6 +496,10 @@ def lib():
         L.adc_tsdf_get_volume_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(TsdfParams)]
         L.adc_tsdf_download.argtypes = [vp, vp, vp]
         L.adc_tsdf_upload.argtypes = [vp, vp, vp]
+    if hasattr(L, "adc_tsdf_mesh_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_tsdf_mesh_device.argtypes = [vp, C.POINTER(TsdfExtractParams), vp, C.c_uint64, vp, C.c_uint64, vp]
+        L.adc_tsdf_mesh.argtypes = [vp, C.POINTER(TsdfExtractParams), vp, C.c_uint64, vp, C.c_uint64, C.POINTER(TsdfMeshReport)]
+        L.adc_get_tsdf_mesh_report.argtypes = [vp, C.POINTER(TsdfMeshReport)]
         for name in TSDF_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
@@ -1304,6 +1318,37 @@ class ADCensusStereo:
             rc = lib().adc_get_tsdf_report(self._h, C.byref(rep), None) if first else lib().adc_get_tsdf_report(self._h, None, C.byref(rep))
             out.append(rep if rc == 0 else None)
         return tuple(out)
+
+    def tsdf_mesh_device(self, d_vertices, vertex_capacity, d_triangles, triangle_capacity, params=None, d_counts=None):
+        """The triangle mesh of the volume (adc_tsdf_mesh_device; ints: device addresses; d_vertices adc_point records, 16-byte
+        aligned, d_triangles three uint32 per record, either None when that list is not wanted, a capacity of 0 counts only; d_counts
+        two uint32 device words or None; params a TsdfExtractParams or None for min_weight = 1); asynchronous, call wait(), then
+        tsdf_mesh_report()."""
+        return lib().adc_tsdf_mesh_device(self._h, None if params is None else C.byref(params), d_vertices, int(vertex_capacity), d_triangles,
+                                          int(triangle_capacity), d_counts) == 0
+
+    def tsdf_mesh(self, params=None, vertices=True, triangles=True):
+        """Host convenience (adc_tsdf_mesh): a counting call, then exactly as many records as there are.  Returns (vertices POINT_DTYPE
+        [.] or None, triangles uint32 [.][3] or None, TsdfMeshReport).  Raises on failure."""
+        rep = TsdfMeshReport()
+        pp = None if params is None else C.byref(params)
+        if not (vertices or triangles):
+            raise ValueError("tsdf_mesh: neither vertices nor triangles requested")
+        token = np.zeros(1, POINT_DTYPE)  # (a non-NULL pointer with a capacity of 0 counts only)
+        if lib().adc_tsdf_mesh(self._h, pp, token.ctypes.data if vertices else None, 0, token.ctypes.data if triangles else None, 0, C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_mesh failed: " + last_error())
+        nv, nt = rep.vertices, rep.triangles
+        vtx = np.zeros(max(nv, 1), POINT_DTYPE)
+        tri = np.zeros((max(nt, 1), 3), np.uint32)
+        if lib().adc_tsdf_mesh(self._h, pp, vtx.ctypes.data if vertices else None, nv if vertices else 0, tri.ctypes.data if triangles else None,
+                               nt if triangles else 0, C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_mesh failed: " + last_error())
+        return (vtx[:nv].copy() if vertices else None), (tri[:nt].copy() if triangles else None), rep
+
+    def tsdf_mesh_report(self):
+        """The TsdfMeshReport of the last mesh call wait() has completed (adc_get_tsdf_mesh_report), or None."""
+        rep = TsdfMeshReport()
+        return rep if lib().adc_get_tsdf_mesh_report(self._h, C.byref(rep)) == 0 else None
 
     def tsdf_volume_device(self):
         """(device address of the voxel words, of the colour words or None, TsdfParams) for a GPU consumer (adc_tsdf_get_volume_device)."""

@@ -135,6 +135,7 @@ struct AdcInFlight {
     int msh_pending;      // adc_mesh_device: a mesh was enqueued -> adc_wait moves pin_flags[ADC_PIN_MESH..] into msh_report
     int tsdf_pending;     // adc_tsdf_integrate_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF..] into tsdf_report
     int tsdfx_pending;    // adc_tsdf_extract_device: an extraction was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_xreport
+    int tsdfm_pending;    // adc_tsdf_mesh_device: a mesh of the volume was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
 static_assert(std::is_trivially_copyable<AdcInFlight>::value, "AdcInFlight is reset with memset");
@@ -165,7 +166,8 @@ struct AdcRectSide {
 // behind a pending TSDF call and one adc_wait completes both
 #define ADC_PIN_TSDF (ADC_PIN_ARM + ADC_ARMMAX_WORDS) // in_frustum, no_depth, occluded, updated of the last integrate call (k_tsdf.hip): adc_get_tsdf_report
 #define ADC_PIN_TSDF_EXTRACT (ADC_PIN_TSDF + 4)       // voxels_seen, points of the last extract call
-#define ADC_PIN_WORDS (ADC_PIN_TSDF + 8)              // int32 words of pin_flags
+#define ADC_PIN_TSDF_MESH (ADC_PIN_TSDF + 8)          // voxels_seen, vertices, triangles, cells_seen, cells_surface of the last TSDF mesh call
+#define ADC_PIN_WORDS (ADC_PIN_TSDF + 16)             // int32 words of pin_flags
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -358,6 +360,14 @@ struct adc_handle {
     uint8_t* tsdfs_img;
     adc_point* tsdfs_pts;     // (grows with the largest capacity asked for)
     size_t tsdfs_pts_cap;
+    // triangle mesh of the volume (adc_tsdf_mesh*; nothing of it exists before the first such call).  tsdf_tiles then holds two arrays
+    // of tiles (crossings, triangles); the extraction uses the first
+    uint32_t* tsdf_first;     // per voxel: the rank of its first crossing, written by the vertex pass of a call that writes triangles; grows with the largest volume
+    size_t tsdf_first_cap;
+    adc_tsdf_mesh_report tsdf_mreport;    // adc_get_tsdf_mesh_report
+    int tsdf_mreport_valid;
+    uint32_t* tsdfs_tri;      // device scratch of adc_tsdf_mesh (host callers): three words per triangle; grows with the largest capacity asked for
+    size_t tsdfs_tri_cap;
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -488,6 +498,23 @@ hipError_t adc_launch_tsdf_integrate(adc_handle* h, const float* map, const uint
 hipError_t adc_launch_tsdf_measure(adc_handle* h, const AdcTsdfExtReq& r);
 hipError_t adc_launch_tsdf_scan(adc_handle* h, const AdcTsdfExtReq& r);
 hipError_t adc_launch_tsdf_emit(adc_handle* h, const AdcTsdfExtReq& r);
+// the triangle mesh of the volume: one fused measure (crossings and triangles per tile into the two halves of tsdf_tiles; voxels_seen,
+// cells_seen, cells_surface added to tsdf_rep[ADC_TSDF_REP_MESH..]), the scan once per list (which: 0 vertices, 1 triangles), the vertex
+// pass (records; with_first also tsdf_first), the triangle pass
+#define ADC_TSDF_REP_MESH 10
+#define ADC_TSDF_MESH_WORDS 5 // the counts of adc_tsdf_mesh_report in front of its reserved words
+struct AdcTsdfMeshReq {
+    uint32_t min_weight;
+    void* vertices;            // may be NULL
+    uint32_t vertex_capacity;
+    void* triangles;           // may be NULL
+    uint32_t triangle_capacity;
+    uint32_t* counts;          // the caller's two device words, may be NULL
+};
+hipError_t adc_launch_tsdf_mesh_measure(adc_handle* h, const AdcTsdfMeshReq& r);
+hipError_t adc_launch_tsdf_mesh_scan(adc_handle* h, const AdcTsdfMeshReq& r, int which);
+hipError_t adc_launch_tsdf_mesh_vertices(adc_handle* h, const AdcTsdfMeshReq& r, bool with_first);
+hipError_t adc_launch_tsdf_mesh_triangles(adc_handle* h, const AdcTsdfMeshReq& r);
 #define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

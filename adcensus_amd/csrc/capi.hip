@@ -5,6 +5,7 @@
 #include "adc_device_fn.h"
 #include "itp_plan.h"
 #include "tsdf_voxel.h" // tsdf_params_refusal, tsdf_frame_refusal
+#include "tsdf_cell.h"  // tsdf_mesh_refusal
 
 #include <math.h>
 #include <stdio.h>
@@ -920,6 +921,12 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->tsdf_xreport, h->pin_flags + ADC_PIN_TSDF_EXTRACT, 2 * sizeof(uint32_t));
         h->tsdf_xreport_valid = 1;
         h->fly.tsdfx_pending = 0;
+    }
+    if (h->fly.tsdfm_pending) {
+        memset(&h->tsdf_mreport, 0, sizeof(h->tsdf_mreport));
+        memcpy(&h->tsdf_mreport, h->pin_flags + ADC_PIN_TSDF_MESH, ADC_TSDF_MESH_WORDS * sizeof(uint32_t));
+        h->tsdf_mreport_valid = 1;
+        h->fly.tsdfm_pending = 0;
     }
 }
 
@@ -2232,6 +2239,113 @@ int adc_tsdf_download(adc_handle* h, uint32_t* tsdf, uint32_t* color) { return t
 int adc_tsdf_upload(adc_handle* h, const uint32_t* tsdf, const uint32_t* color)
 {
     return tsdf_transfer(h, const_cast<uint32_t*>(tsdf), const_cast<uint32_t*>(color), false, "adc_tsdf_upload");
+}
+
+// ------------------------------------------------------------------------------ triangle mesh of the TSDF volume (k_tsdf.hip)
+// In the style of the extraction: the device form enqueues on the object stream and is completed by adc_wait, which moves the five
+// report counts from pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport.  Both counts are always taken; the vertex pass runs when vertex
+// records or triangles are written (the triangles need every voxel's first rank), the triangle pass when triangles are written.
+static int tsdf_mesh_check(adc_handle* h, const adc_tsdf_extract_params* params, const void* vertices, uint64_t vertex_capacity, const void* triangles,
+                           uint64_t triangle_capacity, const void* counts, bool device, adc_tsdf_extract_params* p, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : TSDF_EXTRACT_DEFAULT;
+    if (!h) why = "null handle";
+    else if (p->min_weight < 1u || p->min_weight > 65535u) why = "min_weight must lie in [1, 65535]";
+    else if (p->reserved_[0] | p->reserved_[1] | p->reserved_[2] | p->reserved_[3] | p->reserved_[4] | p->reserved_[5] | p->reserved_[6]) why = "a reserved word is not 0";
+    else if (!vertices && !triangles) why = "neither vertices nor triangles requested";
+    else if (!vertices && vertex_capacity != 0) why = "null vertices with a capacity";
+    else if (!triangles && triangle_capacity != 0) why = "null triangles with a capacity";
+    else if (device && ((uintptr_t)vertices & 15u)) why = "d_vertices must be 16-byte aligned";
+    else if (device && ((uintptr_t)triangles & 3u)) why = "d_triangles must be 4-byte aligned";
+    else if (device && ((uintptr_t)counts & 3u)) why = "d_counts must be 4-byte aligned";
+    else if ((why = tsdf_state_refusal(h)) != nullptr) {}
+    else if ((why = tsdf_mesh_refusal(h->tsdf_params)) != nullptr) {}
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+// what adc_tsdf_mesh passes for a list that is requested with a capacity of 0 (counted, never written: no kernel receives it)
+alignas(16) static unsigned char tsdf_count_only[16];
+
+static hipError_t enqueue_tsdf_mesh(adc_handle* h, const AdcTsdfMeshReq& r)
+{
+    const bool tris = r.triangles && r.triangle_capacity, verts = r.vertices && r.vertex_capacity;
+    HIP_TRY(MEM_GROW(h->tsdf_tiles, h->tsdf_tiles_cap, 2 * adc_tsdf_tile_count(&h->tsdf_params), sizeof(uint32_t)));
+    if (tris) HIP_TRY(MEM_GROW(h->tsdf_first, h->tsdf_first_cap, tsdf_voxels(h->tsdf_params), sizeof(uint32_t)));
+    HIP_OK(hipMemsetAsync(h->tsdf_rep + ADC_TSDF_REP_MESH, 0, ADC_TSDF_MESH_WORDS * sizeof(uint32_t), h->stream));
+    HIP_OK(adc_launch_tsdf_mesh_measure(h, r));
+    HIP_OK(adc_launch_tsdf_mesh_scan(h, r, 0));
+    HIP_OK(adc_launch_tsdf_mesh_scan(h, r, 1));
+    if (tris || verts) HIP_OK(adc_launch_tsdf_mesh_vertices(h, r, tris));
+    if (tris) HIP_OK(adc_launch_tsdf_mesh_triangles(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_MESH, h->tsdf_rep + ADC_TSDF_REP_MESH, ADC_TSDF_MESH_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_mesh_device(adc_handle* h, const adc_tsdf_extract_params* params, void* d_vertices, uint64_t vertex_capacity, void* d_triangles,
+                         uint64_t triangle_capacity, void* d_counts)
+{
+    const char* who = "adc_tsdf_mesh_device";
+    adc_tsdf_extract_params p;
+    if (tsdf_mesh_check(h, params, d_vertices, vertex_capacity, d_triangles, triangle_capacity, d_counts, true, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    AdcTsdfMeshReq r;
+    r.min_weight = p.min_weight;
+    r.vertices = d_vertices;
+    r.vertex_capacity = msh_cap32(vertex_capacity);
+    r.triangles = d_triangles;
+    r.triangle_capacity = msh_cap32(triangle_capacity);
+    r.counts = static_cast<uint32_t*>(d_counts);
+    if (enqueue_tsdf_mesh(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdfm_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_mesh(adc_handle* h, const adc_tsdf_extract_params* params, adc_point* vertices, uint64_t vertex_capacity, uint32_t* triangles,
+                  uint64_t triangle_capacity, adc_tsdf_mesh_report* report)
+{
+    const char* who = "adc_tsdf_mesh";
+    adc_tsdf_extract_params p;
+    if (tsdf_mesh_check(h, params, vertices, vertex_capacity, triangles, triangle_capacity, nullptr, false, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    // no more records than the volume can give: three crossings per voxel, M triangles per cell (below 2^32 by the count limit)
+    const adc_tsdf_params& tp = h->tsdf_params;
+    const size_t most_v = 3 * tsdf_voxels(tp), most_t = (size_t)TSDF_MC_MAX_TRIS * (size_t)(tp.nx - 1) * (size_t)(tp.ny - 1) * (size_t)(tp.nz - 1);
+    size_t vcap = vertex_capacity < most_v ? (size_t)vertex_capacity : most_v, tcap = triangle_capacity < most_t ? (size_t)triangle_capacity : most_t;
+    hipError_t e = hipSuccess;
+    int rc = 0;
+    if ((vertices && vcap > h->tsdfs_pts_cap) || (triangles && tcap > h->tsdfs_tri_cap)) {
+        // a scratch would have to grow: count first, so that neither ever holds more records than the volume has (adc_tsdf_extract)
+        rc = adc_tsdf_mesh_device(h, &p, vertices ? tsdf_count_only : nullptr, 0, triangles ? tsdf_count_only : nullptr, 0, nullptr);
+        if (rc == 0) rc = adc_wait(h);
+        if (rc != 0) return rc;
+        if (h->tsdf_mreport.vertices < vcap) vcap = h->tsdf_mreport.vertices;
+        if (h->tsdf_mreport.triangles < tcap) tcap = h->tsdf_mreport.triangles;
+        if ((!vertices || vcap == 0) && (!triangles || tcap == 0)) { // (nothing to write: the counting pass was the call)
+            if (report) *report = h->tsdf_mreport;
+            return 0;
+        }
+    }
+    if (vertices && vcap && (e = MEM_GROW(h->tsdfs_pts, h->tsdfs_pts_cap, vcap, sizeof(adc_point))) != hipSuccess) return scratch_failed(who);
+    if (triangles && tcap && (e = MEM_GROW(h->tsdfs_tri, h->tsdfs_tri_cap, tcap, 3 * sizeof(uint32_t))) != hipSuccess) return scratch_failed(who);
+    rc = adc_tsdf_mesh_device(h, &p, !vertices ? nullptr : vcap ? (void*)h->tsdfs_pts : (void*)tsdf_count_only, vertices ? vcap : 0,
+                              !triangles ? nullptr : tcap ? (void*)h->tsdfs_tri : (void*)tsdf_count_only, triangles ? tcap : 0, nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    const size_t nv = h->tsdf_mreport.vertices < vcap ? h->tsdf_mreport.vertices : vcap, nt = h->tsdf_mreport.triangles < tcap ? h->tsdf_mreport.triangles : tcap;
+    if (vertices && nv && (e = ADC_HIP(hipMemcpy(vertices, h->tsdfs_pts, nv * sizeof(adc_point), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_mesh: vertex copy-out", e); return 2; }
+    if (triangles && nt && (e = ADC_HIP(hipMemcpy(triangles, h->tsdfs_tri, nt * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_mesh: triangle copy-out", e); return 2; }
+    if (report) *report = h->tsdf_mreport;
+    return 0;
+}
+
+int adc_get_tsdf_mesh_report(adc_handle* h, adc_tsdf_mesh_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_tsdf_mesh_report: null argument"; return 1; }
+    if (!h->tsdf_mreport_valid) { g_last_error = "adc_get_tsdf_mesh_report: no mesh call has completed on this handle"; return 1; }
+    *out = h->tsdf_mreport;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------ pair farm

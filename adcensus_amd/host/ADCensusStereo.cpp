@@ -290,6 +290,12 @@ bool ADCensusStereo::GetTsdfReport(adc_tsdf_report* integrate_report, adc_tsdf_e
 {
     return impl_ && adc_get_tsdf_report(impl_, integrate_report, extract_report) == 0;
 }
+bool ADCensusStereo::TsdfMesh(const adc_tsdf_extract_params* params, adc_point* vertices, uint64 vertex_capacity, uint32* triangles, uint64 triangle_capacity,
+                              adc_tsdf_mesh_report* report)
+{
+    return impl_ && adc_tsdf_mesh(impl_, params, vertices, vertex_capacity, triangles, triangle_capacity, report) == 0;
+}
+bool ADCensusStereo::GetTsdfMeshReport(adc_tsdf_mesh_report* report) { return impl_ && adc_get_tsdf_mesh_report(impl_, report) == 0; }
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

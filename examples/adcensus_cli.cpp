@@ -36,6 +36,9 @@
 // element vertex with x y z float, red green blue uchar, in the world frame.  --pose FILE (only with --tsdf): FILE holds 12 numbers, R
 // row-major then t, which take a world point into the left camera (Xc = R * Xw + t); default: the identity.  A malformed flag or file
 // is refused while the arguments are parsed.
+// --tsdf-mesh (only with --tsdf; refused otherwise while the arguments are parsed) also writes the volume's surface as a triangle mesh
+// (ADCensusStereo::TsdfMesh: marching cubes on the device) to <out>-tsdf-mesh.ply, a binary little-endian PLY: the vertex element as in
+// <out>-tsdf.ply, then element face with property list uchar int vertex_indices; and prints one line with the report's five counts.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -459,6 +462,15 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    bool with_tsdf_mesh = false; // (--tsdf-mesh, no value)
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf-mesh")) {
+            with_tsdf_mesh = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
+    if (with_tsdf_mesh && !with_tsdf) { printf("--tsdf-mesh refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf && !with_calib) { printf("--tsdf refused: it needs --calib\n"); return -1; }
     if (with_pose && !with_tsdf) { printf("--pose refused: it needs --tsdf\n"); return -1; }
     bool with_rectify = false; // (--rectify and its value likewise; both files are read and checked here)
@@ -912,6 +924,39 @@ int main(int argc, char** argv)
             }
             fclose(ply);
         } else printf("cannot write %s-tsdf.ply\n", out.c_str());
+        if (with_tsdf_mesh) { // the same volume as a triangle mesh: the vertex list is the point list above
+            adc_tsdf_mesh_report mrep;
+            std::vector<adc_point> vertices;
+            std::vector<uint32> triangles;
+            adc_point no_vertex;
+            uint32 no_triangle = 0;
+            ok = ad_census.TsdfMesh(&tsdf_extract, &no_vertex, 0, &no_triangle, 0, &mrep); // (counts only: the file is sized by the report)
+            if (ok && (mrep.vertices || mrep.triangles)) {
+                vertices.resize(mrep.vertices ? mrep.vertices : 1);
+                triangles.resize(mrep.triangles ? 3 * (size_t)mrep.triangles : 3);
+                const uint32 nv = mrep.vertices, nt = mrep.triangles;
+                ok = ad_census.TsdfMesh(&tsdf_extract, vertices.data(), nv, triangles.data(), nt, &mrep) && mrep.vertices == nv && mrep.triangles == nt;
+            }
+            if (!ok) {
+                printf("tsdf mesh refused: %s\n", ad_census.LastError());
+                return -2;
+            }
+            printf("TSDF mesh: %u voxels seen, %u vertices, %u triangles, %u cells seen, %u surface cells\n", mrep.voxels_seen, mrep.vertices, mrep.triangles,
+                   mrep.cells_seen, mrep.cells_surface);
+            ply = fopen((out + "-tsdf-mesh.ply").c_str(), "wb");
+            if (ply) {
+                fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %u\nproperty float x\nproperty float y\nproperty float z\n"
+                             "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %u\nproperty list uchar int vertex_indices\nend_header\n",
+                        mrep.vertices, mrep.triangles);
+                for (size_t i = 0; i < mrep.vertices; i++) {
+                    fwrite(&vertices[i].x, 4, 3, ply);
+                    fwrite(&vertices[i].r, 1, 3, ply);
+                }
+                const uint8 three = 3;
+                for (size_t i = 0; i < mrep.triangles; i++) { fwrite(&three, 1, 1, ply); fwrite(&triangles[3 * i], 4, 3, ply); }
+                fclose(ply);
+            } else printf("cannot write %s-tsdf-mesh.ply\n", out.c_str());
+        }
     }
     if (with_calib) {
         write_pfm(out + "-depth.pfm", depth.data(), w, h);

@@ -18,6 +18,7 @@
  * Normals / GetNormalsReport (optional camera-facing surface normals from a disparity map on the device),
  * Mesh / GetMeshReport (optional triangle mesh from a disparity map on the device),
  * TsdfCreate / TsdfReset / TsdfIntegrate / TsdfExtract / GetTsdfReport (optional TSDF volume on the device: maps of many frames fused, surface points),
+ * TsdfMesh / GetTsdfMeshReport (the volume's surface as a triangle mesh),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -46,6 +47,7 @@ struct adc_tsdf_frame;
 struct adc_tsdf_report;
 struct adc_tsdf_extract_params;
 struct adc_tsdf_extract_report;
+struct adc_tsdf_mesh_report;
 struct adc_point;
 
 class ADCensusStereo {
@@ -178,6 +180,13 @@ public:
     bool TsdfIntegrate(const float32* map, const uint8* bgr_left, const adc_tsdf_frame* frame, adc_tsdf_report* report);
     bool TsdfExtract(const adc_tsdf_extract_params* params, adc_point* points, uint64 capacity, adc_tsdf_extract_report* report);
     bool GetTsdfReport(adc_tsdf_report* integrate_report, adc_tsdf_extract_report* extract_report);
+    /** The volume's surface as a triangle mesh (adc_tsdf_mesh: marching cubes on the device).  The vertices are the points of
+     *  TsdfExtract in the same order; a triangle is three uint32 vertex numbers.  The first min(count, capacity) records of each list
+     *  are written; a list whose pointer is null is not wanted (at least one must be), a capacity of 0 counts only; params and report
+     *  may be null.  GetTsdfMeshReport: the report of the last completed call. */
+    bool TsdfMesh(const adc_tsdf_extract_params* params, adc_point* vertices, uint64 vertex_capacity, uint32* triangles, uint64 triangle_capacity,
+                  adc_tsdf_mesh_report* report);
+    bool GetTsdfMeshReport(adc_tsdf_mesh_report* report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

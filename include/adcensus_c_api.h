@@ -32,6 +32,8 @@
  *   adc_mesh              as cloud points, triangles as vertex numbers, both compacted in raster order
  *   adc_tsdf_create / adc_tsdf_integrate_device / adc_tsdf_extract_device / ...   a TSDF volume in the handle: the maps of many
  *                         frames fused per voxel in integers, and the volume's surface points in voxel order
+ *   adc_tsdf_mesh_device / the volume's surface as a triangle mesh (marching cubes): the surface points as vertices, triangles as
+ *   adc_tsdf_mesh         vertex numbers in cell order
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -916,6 +918,65 @@ int adc_get_tsdf_report(adc_handle* h, adc_tsdf_report* integrate_report, adc_ts
 int adc_tsdf_get_volume_device(adc_handle* h, void** d_tsdf, void** d_color, adc_tsdf_params* params);
 int adc_tsdf_download(adc_handle* h, uint32_t* tsdf, uint32_t* color);
 int adc_tsdf_upload(adc_handle* h, const uint32_t* tsdf, const uint32_t* color);
+
+/* -------------------------------------------------------------------------------------------
+ * Triangle mesh of the TSDF volume on the device (marching cubes; k_tsdf.hip, the cell rule is adcensus_amd/csrc/tsdf_cell.h, the case
+ * table adcensus_amd/csrc/tsdf_mc_table.h is generated by tools/gen_tsdf_mc_table.py; tests/tsdf_mesh_ref.py holds the same definition
+ * in numpy and the kernels match it bit for bit, in whatever order the waves run).  A triangle is three integers chosen by integer
+ * comparisons; the vertices carry the only float arithmetic, that of adc_tsdf_extract.
+ *
+ * Parameters: adc_tsdf_extract_params (min_weight); NULL: min_weight = 1.
+ * Vertices: the point list of adc_tsdf_extract for the same min_weight -- the same records in the same order, including crossings
+ * that no triangle uses (next to unseen voxels, on the volume's border).  The vertex number of the crossing (owner voxel a, axis) is
+ * its position in that full list, whatever the vertex capacity.
+ * Cells: cell (i, j, k) exists for i < nx - 1, j < ny - 1, k < nz - 1 and has the index n = (k * ny + j) * nx + i.  Corner c in [0, 8)
+ * is voxel (i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1)).  A cell is seen iff all eight corners have w >= min_weight; only
+ * seen cells emit.  Case index: bit c is set iff t_c < 0 (a stored -32768 reads as -32767; t = 0 counts as positive, as for a
+ * crossing).  Every sign-changing edge of a seen cell is therefore a crossing of the vertex list.
+ * Cell edges: e = 4 * axis + m, m in [0, 4); the owner corner has the offsets (0, m & 1, m >> 1) for axis x, (m & 1, 0, m >> 1) for y,
+ * (m & 1, m >> 1, 0) for z; the edge runs from the owner to its +axis neighbour and its vertex is the crossing (owner voxel, axis).
+ * Case table (256 rows, generated): 1. on each of the six faces, a face with two sign-changing edges gets one segment joining them; a
+ * face with four (its negative corners on a diagonal) gets two, each joining the two edges that meet at a NEGATIVE corner -- the rule
+ * reads the face's four signs only, so the two cells that share a face draw the same segments and there are no cracks.  2. every
+ * sign-changing edge has one segment on each of its two faces, so the segments chain into closed loops; a loop is directed so that the
+ * geometric normal (v1 - v0) x (v2 - v0) of its triangles points from the negative corners to the positive side (case 1, corner 0
+ * negative, is the triangle (e0, e4, e8)), starts at its lowest edge number, and the loops are ordered by their lowest edge number.
+ * 3. a loop L0 .. L(m-1) becomes a fan (Ls, L(s+i), L(s+i+1)), i = 1 .. m - 2, indices modulo m: the apex is L0 wherever that is
+ * admissible, precisely s is the smallest index whose fan has no diagonal joining two edges of ONE face of the cell (such a diagonal
+ * lies in a face two cells share and could be drawn by both).  So on a closed surface every directed edge (a, b) occurs exactly once
+ * and (b, a) exactly once.  The largest number of triangles of a case is M = 5.
+ * Triangles: cells in ascending n, within a cell in table order; a record is three uint32 vertex numbers.  A voxel with t = 0 yields
+ * coincident vertices (see the extraction), so zero-area triangles occur and are kept.
+ * Capacities: the first min(vertices, vertex_capacity) vertex records and the first min(triangles, triangle_capacity) triangle records
+ * are written and nothing behind them; a capacity of 0 with a non-NULL pointer counts only.  Both counts are always taken (one fused
+ * pass over the volume); only the records that were asked for are written.  d_counts (optional): uint32[2] = {vertices, triangles},
+ * written on the stream.
+ * Report (adc_tsdf_mesh_report, uint32 each): voxels_seen, vertices, triangles, cells_seen, cells_surface (seen cells with at least
+ * one triangle), three reserved words.
+ * Count limit: the counts are 32-bit.  A call is refused when M * (nx - 1)(ny - 1)(nz - 1) > 2^32 - 1 (a volume of 2^30 voxels is;
+ * 1024 x 1024 x 800 is not).
+ * Cost: a call with triangles keeps one uint32 per voxel of device scratch (the rank of the voxel's first crossing; 4 bytes per voxel,
+ * 512 MB at 512^3), allocated on the first such call, growing with the largest volume, freed by adc_destroy; and two uint32 per tile
+ * of 256 voxels.
+ *
+ * adc_tsdf_mesh_device   asynchronous on the handle's stream, completed by adc_wait.  d_vertices (16-byte aligned), d_triangles and
+ *                        d_counts (4-byte aligned) are device addresses; at least one of d_vertices / d_triangles.
+ * adc_tsdf_mesh          the same with HOST pointers, synchronous; copies out min(count, capacity) records of each list.  Its device
+ *                        scratch holds min(count, capacity) records: when it has to grow, the call counts first.
+ * adc_get_tsdf_mesh_report  the report of the last call that adc_wait (or adc_tsdf_mesh) has completed.
+ * Return codes as for adc_tsdf_extract: 0; 1 with adc_last_error and nothing enqueued (also: neither list requested, a pointer that is
+ * NULL with a capacity, the count limit); 2 on a HIP failure (the handle and the volume stay usable).  A Match may be enqueued behind a
+ * pending call and one adc_wait completes both.  The mesh is not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct adc_tsdf_mesh_report {
+    uint32_t voxels_seen, vertices, triangles, cells_seen, cells_surface;
+    uint32_t reserved_[3];
+} adc_tsdf_mesh_report;
+int adc_tsdf_mesh_device(adc_handle* h, const adc_tsdf_extract_params* params, void* d_vertices, uint64_t vertex_capacity,
+                         void* d_triangles, uint64_t triangle_capacity, void* d_counts);
+int adc_tsdf_mesh(adc_handle* h, const adc_tsdf_extract_params* params, adc_point* vertices, uint64_t vertex_capacity,
+                  uint32_t* triangles, uint64_t triangle_capacity, adc_tsdf_mesh_report* report);
+int adc_get_tsdf_mesh_report(adc_handle* h, adc_tsdf_mesh_report* out);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
