@@ -336,6 +336,40 @@ class TsdfMeshReport(C.Structure):
                 ("reserved_", C.c_uint32 * 3)]
 
 
+TSDF_RAYCAST_ENTRY_POINTS = ("adc_tsdf_raycast_device", "adc_tsdf_raycast", "adc_get_tsdf_raycast_report")
+TSDF_RAY_MISS, TSDF_RAY_HIT, TSDF_RAY_NO_SURFACE, TSDF_RAY_BEHIND, TSDF_RAY_EXHAUSTED = range(5)  # ADC_TSDF_RAY_*
+
+
+class TsdfRaycastParams(C.Structure):
+    """adc_tsdf_raycast_params: the view (width, height in [1, 8192], focal_px, cx, cy; R row-major and t take a WORLD point into the
+    camera frame, as in TsdfFrame), the range z_near < z_far of camera depth, the advance `step` between samples and `skip` (>= step)
+    behind a sample in saturated free space, min_weight in [1, 65535], max_steps in [1, 16384] (no ray takes more samples); flags and
+    the reserved words 0.  Defaults: R = I, t = 0, skip = step."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("focal_px", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("R", C.c_float * 9),
+                ("t", C.c_float * 3), ("z_near", C.c_float), ("z_far", C.c_float), ("step", C.c_float), ("skip", C.c_float), ("min_weight", C.c_uint32),
+                ("max_steps", C.c_uint32), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 8)]
+
+    def __init__(self, width=0, height=0, focal_px=0.0, cx=0.0, cy=0.0, R=None, t=None, z_near=0.0, z_far=0.0, step=0.0, skip=None, min_weight=1,
+                 max_steps=4096, flags=0):
+        super().__init__()
+        self.width, self.height, self.focal_px, self.cx, self.cy = int(width), int(height), float(focal_px), float(cx), float(cy)
+        self.R = (C.c_float * 9)(*[float(x) for x in np.asarray((1, 0, 0, 0, 1, 0, 0, 0, 1) if R is None else R, np.float32).ravel()])
+        self.t = (C.c_float * 3)(*[float(x) for x in np.asarray((0, 0, 0) if t is None else t, np.float32).ravel()])
+        self.z_near, self.z_far, self.step, self.skip = float(z_near), float(z_far), float(step), float(step if skip is None else skip)
+        self.min_weight, self.max_steps, self.flags = int(min_weight), int(max_steps), int(flags)
+
+
+class TsdfRaycastReport(C.Structure):
+    """adc_tsdf_raycast_report: rays = width * height and how many of them ended with each status (they sum to rays); the number of
+    samples of all rays as two 32-bit halves (`samples` joins them)."""
+    _fields_ = [("rays", C.c_uint32), ("miss", C.c_uint32), ("hit", C.c_uint32), ("no_surface", C.c_uint32), ("behind", C.c_uint32), ("exhausted", C.c_uint32),
+                ("samples_lo", C.c_uint32), ("samples_hi", C.c_uint32), ("reserved_", C.c_uint32 * 8)]
+
+    @property
+    def samples(self):
+        return self.samples_lo | (self.samples_hi << 32)
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -501,6 +535,12 @@ def lib():
         L.adc_tsdf_mesh.argtypes = [vp, C.POINTER(TsdfExtractParams), vp, C.c_uint64, vp, C.c_uint64, C.POINTER(TsdfMeshReport)]
         L.adc_get_tsdf_mesh_report.argtypes = [vp, C.POINTER(TsdfMeshReport)]
         for name in TSDF_ENTRY_POINTS:
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_tsdf_raycast_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_tsdf_raycast_device.argtypes = [vp, C.POINTER(TsdfRaycastParams), vp, vp, vp, vp]
+        L.adc_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastParams), vp, vp, vp, vp, C.POINTER(TsdfRaycastReport)]
+        L.adc_get_tsdf_raycast_report.argtypes = [vp, C.POINTER(TsdfRaycastReport)]
+        for name in TSDF_RAYCAST_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
@@ -1349,6 +1389,33 @@ class ADCensusStereo:
         """The TsdfMeshReport of the last mesh call wait() has completed (adc_get_tsdf_mesh_report), or None."""
         rep = TsdfMeshReport()
         return rep if lib().adc_get_tsdf_mesh_report(self._h, C.byref(rep)) == 0 else None
+
+    def tsdf_raycast_device(self, params, d_depth=None, d_normals=None, d_bgr=None, d_status=None):
+        """The volume seen from a camera pose (adc_tsdf_raycast_device; params a TsdfRaycastParams; ints: device addresses of float32
+        [height][width], float32 [height][width][4] (16-byte aligned), uint8 [height][width][3] (needs a colour volume) and uint8
+        [height][width], each None when not wanted, at least one); asynchronous, call wait(), then tsdf_raycast_report().  False when
+        refused or on a HIP failure."""
+        return lib().adc_tsdf_raycast_device(self._h, None if params is None else C.byref(params), d_depth, d_normals, d_bgr, d_status) == 0
+
+    def tsdf_raycast(self, params, depth=True, normals=True, bgr=False, status=True):
+        """Host convenience (adc_tsdf_raycast): returns (depth float32 [H][W], normals float32 [H][W][4], bgr uint8 [H][W][3], status
+        uint8 [H][W], TsdfRaycastReport), None for an output that was not asked for.  Raises on failure."""
+        if not (depth or normals or bgr or status):
+            raise ValueError("tsdf_raycast: no output requested")
+        h, w = max(int(params.height), 0), max(int(params.width), 0)
+        d = np.zeros((h, w), np.float32) if depth else None
+        n = np.zeros((h, w, 4), np.float32) if normals else None
+        c = np.zeros((h, w, 3), np.uint8) if bgr else None
+        s = np.zeros((h, w), np.uint8) if status else None
+        rep = TsdfRaycastReport()
+        if lib().adc_tsdf_raycast(self._h, C.byref(params), *[None if a is None else a.ctypes.data for a in (d, n, c, s)], C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_raycast failed: " + last_error())
+        return d, n, c, s, rep
+
+    def tsdf_raycast_report(self):
+        """The TsdfRaycastReport of the last ray cast wait() has completed (adc_get_tsdf_raycast_report), or None."""
+        rep = TsdfRaycastReport()
+        return rep if lib().adc_get_tsdf_raycast_report(self._h, C.byref(rep)) == 0 else None
 
     def tsdf_volume_device(self):
         """(device address of the voxel words, of the colour words or None, TsdfParams) for a GPU consumer (adc_tsdf_get_volume_device)."""

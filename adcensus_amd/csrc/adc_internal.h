@@ -135,6 +135,7 @@ struct AdcInFlight {
     int msh_pending;      // adc_mesh_device: a mesh was enqueued -> adc_wait moves pin_flags[ADC_PIN_MESH..] into msh_report
     int tsdf_pending;     // adc_tsdf_integrate_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF..] into tsdf_report
     int tsdfx_pending;    // adc_tsdf_extract_device: an extraction was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_xreport
+    int tsdfr_pending;    // adc_tsdf_raycast_device: a ray cast was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_RAY..] into tsdf_rreport
     int tsdfm_pending;    // adc_tsdf_mesh_device: a mesh of the volume was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
@@ -167,7 +168,8 @@ struct AdcRectSide {
 #define ADC_PIN_TSDF (ADC_PIN_ARM + ADC_ARMMAX_WORDS) // in_frustum, no_depth, occluded, updated of the last integrate call (k_tsdf.hip): adc_get_tsdf_report
 #define ADC_PIN_TSDF_EXTRACT (ADC_PIN_TSDF + 4)       // voxels_seen, points of the last extract call
 #define ADC_PIN_TSDF_MESH (ADC_PIN_TSDF + 8)          // voxels_seen, vertices, triangles, cells_seen, cells_surface of the last TSDF mesh call
-#define ADC_PIN_WORDS (ADC_PIN_TSDF + 16)             // int32 words of pin_flags
+#define ADC_PIN_TSDF_RAY (ADC_PIN_TSDF + 16)          // rays, the five status counts, the 64-bit sample count of the last ray cast
+#define ADC_PIN_WORDS (ADC_PIN_TSDF + 24)             // int32 words of pin_flags
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -368,6 +370,11 @@ struct adc_handle {
     int tsdf_mreport_valid;
     uint32_t* tsdfs_tri;      // device scratch of adc_tsdf_mesh (host callers): three words per triangle; grows with the largest capacity asked for
     size_t tsdfs_tri_cap;
+    // ray cast of the volume (adc_tsdf_raycast*; nothing of it exists before the first adc_tsdf_raycast of a host caller)
+    adc_tsdf_raycast_report tsdf_rreport; // adc_get_tsdf_raycast_report
+    int tsdf_rreport_valid;
+    uint8_t* tsdfs_ray;       // device scratch of adc_tsdf_raycast (host callers): 24 bytes per pixel (depth, normals, bgr, status planes); grows with the largest view
+    size_t tsdfs_ray_cap;     // (pixels)
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -485,7 +492,7 @@ hipError_t adc_launch_mesh_scan(adc_handle* h, const AdcMeshReq& r);
 hipError_t adc_launch_mesh_emit(adc_handle* h, const AdcMeshReq& r);
 // k_tsdf.hip: one frame into the handle's volume (counts added to tsdf_rep[0..3]); the three launches of an extraction on tsdf_tiles
 // (measure: crossings per tile, voxels_seen; scan: bases, points -> tsdf_rep and the caller's word; emit: the records)
-#define ADC_TSDF_REP_WORDS 16
+#define ADC_TSDF_REP_WORDS 24
 #define ADC_TSDF_REP_EXTRACT 8
 struct AdcTsdfExtReq {
     uint32_t min_weight;
@@ -515,6 +522,18 @@ hipError_t adc_launch_tsdf_mesh_measure(adc_handle* h, const AdcTsdfMeshReq& r);
 hipError_t adc_launch_tsdf_mesh_scan(adc_handle* h, const AdcTsdfMeshReq& r, int which);
 hipError_t adc_launch_tsdf_mesh_vertices(adc_handle* h, const AdcTsdfMeshReq& r, bool with_first);
 hipError_t adc_launch_tsdf_mesh_triangles(adc_handle* h, const AdcTsdfMeshReq& r);
+// k_tsdf_raycast.hip: one launch, a lane per ray; the report words (the layout of adc_tsdf_raycast_report: rays, five status counts,
+// the 64-bit sample count at an 8-byte aligned place) are added to tsdf_rep[ADC_TSDF_REP_RAY..]
+#define ADC_TSDF_REP_RAY 16
+#define ADC_TSDF_RAY_WORDS 8 // the counts of adc_tsdf_raycast_report in front of its reserved words
+struct AdcTsdfRayReq {
+    adc_tsdf_raycast_params view;
+    float* depth;              // each may be NULL
+    float* normals;
+    uint8_t* bgr;
+    uint8_t* status;
+};
+hipError_t adc_launch_tsdf_raycast(adc_handle* h, const AdcTsdfRayReq& r);
 #define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

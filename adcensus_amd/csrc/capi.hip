@@ -6,6 +6,7 @@
 #include "itp_plan.h"
 #include "tsdf_voxel.h" // tsdf_params_refusal, tsdf_frame_refusal
 #include "tsdf_cell.h"  // tsdf_mesh_refusal
+#include "tsdf_ray.h"   // tsdf_raycast_refusal
 
 #include <math.h>
 #include <stdio.h>
@@ -927,6 +928,12 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->tsdf_mreport, h->pin_flags + ADC_PIN_TSDF_MESH, ADC_TSDF_MESH_WORDS * sizeof(uint32_t));
         h->tsdf_mreport_valid = 1;
         h->fly.tsdfm_pending = 0;
+    }
+    if (h->fly.tsdfr_pending) {
+        memset(&h->tsdf_rreport, 0, sizeof(h->tsdf_rreport));
+        memcpy(&h->tsdf_rreport, h->pin_flags + ADC_PIN_TSDF_RAY, ADC_TSDF_RAY_WORDS * sizeof(uint32_t));
+        h->tsdf_rreport_valid = 1;
+        h->fly.tsdfr_pending = 0;
     }
 }
 
@@ -2345,6 +2352,83 @@ int adc_get_tsdf_mesh_report(adc_handle* h, adc_tsdf_mesh_report* out)
     if (!h || !out) { g_last_error = "adc_get_tsdf_mesh_report: null argument"; return 1; }
     if (!h->tsdf_mreport_valid) { g_last_error = "adc_get_tsdf_mesh_report: no mesh call has completed on this handle"; return 1; }
     *out = h->tsdf_mreport;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ ray cast of the TSDF volume (k_tsdf_raycast.hip)
+// In the style of adc_tsdf_extract_device: enqueued on the object stream and completed by adc_wait, which moves the report words from
+// pin_flags[ADC_PIN_TSDF_RAY..] into tsdf_rreport.  The volume is only read.  Every refusal stands in front of the first HIP call.
+static int tsdf_raycast_check(adc_handle* h, const adc_tsdf_raycast_params* params, const void* depth, const void* normals, const void* bgr, const void* status,
+                              bool device, const char* who)
+{
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!params) why = "null params";
+    else if ((why = tsdf_raycast_refusal(*params)) != nullptr) {}
+    else if (!depth && !normals && !bgr && !status) why = "no output requested";
+    else if (device && ((uintptr_t)depth & 3u)) why = "d_depth must be 4-byte aligned";
+    else if (device && ((uintptr_t)normals & 15u)) why = "d_normals must be 16-byte aligned";
+    else if (!h->tsdf_set) why = "no volume (adc_tsdf_create first)";
+    else if (bgr && !(h->tsdf_params.flags & ADC_TSDF_COLOR)) why = "bgr needs a colour volume (ADC_TSDF_COLOR)";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static hipError_t enqueue_tsdf_raycast(adc_handle* h, const AdcTsdfRayReq& r)
+{
+    HIP_OK(hipMemsetAsync(h->tsdf_rep + ADC_TSDF_REP_RAY, 0, ADC_TSDF_RAY_WORDS * sizeof(uint32_t), h->stream));
+    HIP_OK(adc_launch_tsdf_raycast(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_RAY, h->tsdf_rep + ADC_TSDF_REP_RAY, ADC_TSDF_RAY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_raycast_device(adc_handle* h, const adc_tsdf_raycast_params* params, void* d_depth, void* d_normals, void* d_bgr, void* d_status)
+{
+    const char* who = "adc_tsdf_raycast_device";
+    if (tsdf_raycast_check(h, params, d_depth, d_normals, d_bgr, d_status, true, who) != 0) return 1;
+    hipSetDevice(h->device);
+    AdcTsdfRayReq r;
+    r.view = *params;
+    r.depth = static_cast<float*>(d_depth);
+    r.normals = static_cast<float*>(d_normals);
+    r.bgr = static_cast<uint8_t*>(d_bgr);
+    r.status = static_cast<uint8_t*>(d_status);
+    if (enqueue_tsdf_raycast(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdfr_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_raycast(adc_handle* h, const adc_tsdf_raycast_params* params, float* depth, float* normals, uint8_t* bgr, uint8_t* status,
+                     adc_tsdf_raycast_report* report)
+{
+    const char* who = "adc_tsdf_raycast";
+    if (tsdf_raycast_check(h, params, depth, normals, bgr, status, false, who) != 0) return 1;
+    hipSetDevice(h->device);
+    // the scratch: four planes behind one another, the normals first (16-byte aligned), then depth, bgr, status
+    const size_t P = (size_t)params->width * (size_t)params->height;
+    hipError_t e = MEM_GROW(h->tsdfs_ray, h->tsdfs_ray_cap, P, 24);
+    if (e != hipSuccess) return scratch_failed(who);
+    uint8_t* d_n = h->tsdfs_ray;
+    uint8_t* d_d = d_n + 16 * P;
+    uint8_t* d_c = d_d + 4 * P;
+    uint8_t* d_s = d_c + 3 * P;
+    int rc = adc_tsdf_raycast_device(h, params, depth ? d_d : nullptr, normals ? d_n : nullptr, bgr ? d_c : nullptr, status ? d_s : nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (depth && (e = ADC_HIP(hipMemcpy(depth, d_d, 4 * P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_raycast: depth copy-out", e); return 2; }
+    if (normals && (e = ADC_HIP(hipMemcpy(normals, d_n, 16 * P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_raycast: normals copy-out", e); return 2; }
+    if (bgr && (e = ADC_HIP(hipMemcpy(bgr, d_c, 3 * P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_raycast: bgr copy-out", e); return 2; }
+    if (status && (e = ADC_HIP(hipMemcpy(status, d_s, P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_raycast: status copy-out", e); return 2; }
+    if (report) *report = h->tsdf_rreport;
+    return 0;
+}
+
+int adc_get_tsdf_raycast_report(adc_handle* h, adc_tsdf_raycast_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_tsdf_raycast_report: null argument"; return 1; }
+    if (!h->tsdf_rreport_valid) { g_last_error = "adc_get_tsdf_raycast_report: no ray cast has completed on this handle"; return 1; }
+    *out = h->tsdf_rreport;
     return 0;
 }
 

@@ -296,6 +296,11 @@ bool ADCensusStereo::TsdfMesh(const adc_tsdf_extract_params* params, adc_point* 
     return impl_ && adc_tsdf_mesh(impl_, params, vertices, vertex_capacity, triangles, triangle_capacity, report) == 0;
 }
 bool ADCensusStereo::GetTsdfMeshReport(adc_tsdf_mesh_report* report) { return impl_ && adc_get_tsdf_mesh_report(impl_, report) == 0; }
+bool ADCensusStereo::TsdfRaycast(const TsdfRaycastParams* view, float32* depth, float32* normals, uint8* bgr, uint8* status, adc_tsdf_raycast_report* report)
+{
+    return impl_ && adc_tsdf_raycast(impl_, view, depth, normals, bgr, status, report) == 0;
+}
+bool ADCensusStereo::GetTsdfRaycastReport(adc_tsdf_raycast_report* report) { return impl_ && adc_get_tsdf_raycast_report(impl_, report) == 0; }
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

@@ -39,6 +39,12 @@
 // --tsdf-mesh (only with --tsdf; refused otherwise while the arguments are parsed) also writes the volume's surface as a triangle mesh
 // (ADCensusStereo::TsdfMesh: marching cubes on the device) to <out>-tsdf-mesh.ply, a binary little-endian PLY: the vertex element as in
 // <out>-tsdf.ply, then element face with property list uchar int vertex_indices; and prints one line with the report's five counts.
+// --tsdf-raycast W,H,F,CX,CY[,STEP[,SKIP]] (only with --tsdf; refused otherwise while the arguments are parsed) also ray-casts the volume
+// (ADCensusStereo::TsdfRaycast) into a view of W x H pixels with focal length F and principal point CX, CY: the depth map goes to
+// <out>-ray.pfm (0 where no surface is hit) and the normal map to <out>-ray-n.png in the encoding of --normals (byte = rint(127 * n) +
+// 128 per component, made on the host; 0, 0, 0 where there is no normal); one line with the report's counts is printed.  STEP defaults
+// to VOXEL / 2, SKIP to max(TRUNC / 2, STEP).  --view-pose FILE (only with --tsdf-raycast): the view's pose, a file like that of --pose;
+// default: the pose of --pose.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -470,6 +476,50 @@ int main(int argc, char** argv)
             argc -= 1;
             break;
         }
+    bool with_tsdf_raycast = false, with_view_pose = false; // (--tsdf-raycast, --view-pose and their values likewise)
+    adc_tsdf_raycast_params ray_view;
+    memset(&ray_view, 0, sizeof(ray_view));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf-raycast")) {
+            char tail = 0;
+            adc_tsdf_raycast_params& r = ray_view;
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int n = sscanf(v, "%d,%d,%f,%f,%f,%f,%f%c", &r.width, &r.height, &r.focal_px, &r.cx, &r.cy, &r.step, &r.skip, &tail);
+            if (n == 5 && sscanf(v, "%d,%d,%f,%f,%f%c", &r.width, &r.height, &r.focal_px, &r.cx, &r.cy, &tail) != 5) n = 0;
+            if (n == 6 && sscanf(v, "%d,%d,%f,%f,%f,%f%c", &r.width, &r.height, &r.focal_px, &r.cx, &r.cy, &r.step, &tail) != 6) n = 0;
+            if (n < 6) r.step = 0.0f; // (0: filled in from the volume below)
+            if (n < 7) r.skip = 0.0f;
+            if (n < 5 || n > 7 || r.width < 1 || r.height < 1 || r.width > 8192 || r.height > 8192 || !(std::isfinite(r.focal_px) && r.focal_px > 0.f) ||
+                !std::isfinite(r.cx) || !std::isfinite(r.cy) || (n >= 6 && !(std::isfinite(r.step) && r.step > 0.f)) ||
+                (n == 7 && !(std::isfinite(r.skip) && r.skip >= r.step))) {
+                printf("--tsdf-raycast refused: it needs W,H,F,CX,CY[,STEP[,SKIP]] (W, H in 1..8192, F > 0, STEP > 0, SKIP >= STEP)\n");
+                return -1;
+            }
+            with_tsdf_raycast = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--view-pose")) {
+            if (!with_tsdf_raycast) { printf("--view-pose refused: it needs --tsdf-raycast\n"); return -1; }
+            if (!with_tsdf) break; // (refused below, before the file is looked at)
+            FILE* f = i + 1 < argc ? fopen(argv[i + 1], "r") : nullptr;
+            float v[12];
+            int n = 0;
+            char extra = 0;
+            while (f && n < 12 && fscanf(f, "%f", &v[n]) == 1 && std::isfinite(v[n])) n++;
+            const bool clean = f && n == 12 && fscanf(f, " %c", &extra) != 1;
+            if (f) fclose(f);
+            if (!clean) { printf("--view-pose refused: it needs a file of 12 finite numbers (R row-major, then t)\n"); return -1; }
+            for (int k = 0; k < 9; k++) ray_view.R[k] = v[k];
+            for (int k = 0; k < 3; k++) ray_view.t[k] = v[9 + k];
+            with_view_pose = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (with_tsdf_raycast && !with_tsdf) { printf("--tsdf-raycast refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf_mesh && !with_tsdf) { printf("--tsdf-mesh refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf && !with_calib) { printf("--tsdf refused: it needs --calib\n"); return -1; }
     if (with_pose && !with_tsdf) { printf("--pose refused: it needs --tsdf\n"); return -1; }
@@ -956,6 +1006,33 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < mrep.triangles; i++) { fwrite(&three, 1, 1, ply); fwrite(&triangles[3 * i], 4, 3, ply); }
                 fclose(ply);
             } else printf("cannot write %s-tsdf-mesh.ply\n", out.c_str());
+        }
+        if (with_tsdf_raycast) { // the same volume seen from the view's pose: depth and normals, the normal image made here
+            if (!with_view_pose) {
+                memcpy(ray_view.R, tsdf_frame.R, sizeof(ray_view.R));
+                memcpy(ray_view.t, tsdf_frame.t, sizeof(ray_view.t));
+            }
+            if (!(ray_view.step > 0.0f)) ray_view.step = tsdf_params.voxel * 0.5f;
+            if (!(ray_view.skip > 0.0f)) ray_view.skip = tsdf_params.trunc * 0.5f > ray_view.step ? tsdf_params.trunc * 0.5f : ray_view.step;
+            ray_view.z_near = tsdf_params.voxel;
+            ray_view.z_far = 3.0e38f; // (the volume's box ends every ray)
+            ray_view.min_weight = tsdf_extract.min_weight;
+            ray_view.max_steps = 16384;
+            const size_t rp = (size_t)ray_view.width * ray_view.height;
+            std::vector<float32> ray_depth(rp), ray_normals(4 * rp);
+            std::vector<uint8> ray_rgb(3 * rp);
+            adc_tsdf_raycast_report rrep;
+            if (!ad_census.TsdfRaycast(&ray_view, ray_depth.data(), ray_normals.data(), nullptr, nullptr, &rrep)) {
+                printf("tsdf raycast refused: %s\n", ad_census.LastError());
+                return -2;
+            }
+            printf("TSDF raycast: %u rays, %u miss, %u hit, %u no surface, %u behind, %u exhausted, %llu samples\n", rrep.rays, rrep.miss, rrep.hit, rrep.no_surface,
+                   rrep.behind, rrep.exhausted, (unsigned long long)rrep.samples_lo | ((unsigned long long)rrep.samples_hi << 32));
+            for (size_t i = 0; i < rp; i++)
+                for (int k = 0; k < 3; k++)
+                    ray_rgb[3 * i + k] = ray_normals[4 * i + 3] > 0.0f ? (uint8)((int)rintf(ray_normals[4 * i + k] * 127.0f) + 128) : 0;
+            write_pfm(out + "-ray.pfm", ray_depth.data(), ray_view.width, ray_view.height);
+            if (!write_png(out + "-ray-n.png", ray_rgb.data(), ray_view.width, ray_view.height, 3)) printf("cannot write %s-ray-n.png\n", out.c_str());
         }
     }
     if (with_calib) {

@@ -19,6 +19,7 @@
  * Mesh / GetMeshReport (optional triangle mesh from a disparity map on the device),
  * TsdfCreate / TsdfReset / TsdfIntegrate / TsdfExtract / GetTsdfReport (optional TSDF volume on the device: maps of many frames fused, surface points),
  * TsdfMesh / GetTsdfMeshReport (the volume's surface as a triangle mesh),
+ * TsdfRaycast / GetTsdfRaycastReport (the volume seen from a camera pose: depth, normal, colour and status maps),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -48,6 +49,9 @@ struct adc_tsdf_report;
 struct adc_tsdf_extract_params;
 struct adc_tsdf_extract_report;
 struct adc_tsdf_mesh_report;
+struct adc_tsdf_raycast_params;
+struct adc_tsdf_raycast_report;
+typedef adc_tsdf_raycast_params TsdfRaycastParams; // the view of TsdfRaycast: include/adcensus_c_api.h holds its fields
 struct adc_point;
 
 class ADCensusStereo {
@@ -187,6 +191,12 @@ public:
     bool TsdfMesh(const adc_tsdf_extract_params* params, adc_point* vertices, uint64 vertex_capacity, uint32* triangles, uint64 triangle_capacity,
                   adc_tsdf_mesh_report* report);
     bool GetTsdfMeshReport(adc_tsdf_mesh_report* report);
+    /** The volume seen from a camera pose (adc_tsdf_raycast: one ray per pixel marched through the volume on the device).  Host
+     *  buffers of the VIEW's size, each may be null (at least one must not be): depth float32 [height][width] (0 where no surface is
+     *  hit), normals float32 [height][width][4] in the camera frame, bgr uint8 [height][width][3] (needs a colour volume), status uint8
+     *  [height][width] (ADC_TSDF_RAY_*); report may be null.  GetTsdfRaycastReport: the report of the last completed call. */
+    bool TsdfRaycast(const TsdfRaycastParams* view, float32* depth, float32* normals, uint8* bgr, uint8* status, adc_tsdf_raycast_report* report);
+    bool GetTsdfRaycastReport(adc_tsdf_raycast_report* report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

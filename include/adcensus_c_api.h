@@ -34,6 +34,8 @@
  *                         frames fused per voxel in integers, and the volume's surface points in voxel order
  *   adc_tsdf_mesh_device / the volume's surface as a triangle mesh (marching cubes): the surface points as vertices, triangles as
  *   adc_tsdf_mesh         vertex numbers in cell order
+ *   adc_tsdf_raycast_device / the volume's surface as seen from a camera pose: depth, normal, colour and status maps of a view, one
+ *   adc_tsdf_raycast      ray per pixel marched through the volume
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -977,6 +979,96 @@ int adc_tsdf_mesh_device(adc_handle* h, const adc_tsdf_extract_params* params, v
 int adc_tsdf_mesh(adc_handle* h, const adc_tsdf_extract_params* params, adc_point* vertices, uint64_t vertex_capacity,
                   uint32_t* triangles, uint64_t triangle_capacity, adc_tsdf_mesh_report* report);
 int adc_get_tsdf_mesh_report(adc_handle* h, adc_tsdf_mesh_report* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Ray cast of the TSDF volume on the device: the fused surface as seen from a camera pose, as depth, normal, colour and status maps
+ * (k_tsdf_raycast.hip; the ray rule is adcensus_amd/csrc/tsdf_ray.h, tests/tsdf_raycast_ref.py holds the same definition in numpy and
+ * the kernel matches it bit for bit, in whatever order the waves run: one thread owns a ray).  The predicted maps of frame-to-model
+ * tracking, a viewer's image, or a denoised depth map of the current frame.  The volume is only read.  All float arithmetic is IEEE
+ * binary32, one rounding per operation, nothing fused, parenthesised as written; divisions and the square root are correctly rounded.
+ *
+ * View (adc_tsdf_raycast_params, 128 bytes): int32 width, height, each in [1, 8192], independent of the handle's image size; float
+ * focal_px (finite, > 0), cx, cy (finite); float R[9] row-major and t[3], world -> camera as in adc_tsdf_frame, all finite; float
+ * z_near, z_far, finite, 0 < z_near < z_far; float step (finite, > 0), the advance in camera depth Z between samples, and float skip
+ * (finite, >= step), the advance behind a sample in saturated free space; uint32 min_weight in [1, 65535]; uint32 max_steps in
+ * [1, 16384], the largest number of samples of a ray: whatever the other parameters are, no ray takes more (the loop ends on this
+ * counter even where Z + step == Z); uint32 flags = 0; uint32 reserved_[8] = 0.  The usual choice is step = voxel / 2 and
+ * skip = trunc / 2; neither is enforced.  The host computes inv_voxel = 1.0f / voxel once.
+ *
+ * Ray of pixel (x, y).  Camera-frame direction (dx, dy, 1): dx = ((float)x - cx) / focal_px, dy = ((float)y - cy) / focal_px, so the
+ * ray parameter IS the camera-frame depth Z.  Per world axis a in {0, 1, 2}:
+ *   dw_a = ((R[a] * dx) + (R[3+a] * dy)) + R[6+a]                                (transpose(R) * (dx, dy, 1))
+ *   c_a  = -(((R[a] * t[0]) + (R[3+a] * t[1])) + (R[6+a] * t[2]))                (the camera centre)
+ *   g0_a = ((c_a - origin[a]) * inv_voxel) - 0.5f;   gd_a = dw_a * inv_voxel     (grid coordinates: voxel centres are the integers)
+ * The sample at depth Z lies at g_a = g0_a + (Z * gd_a).
+ * Clip (the slab method on the box of centres [0, n_a - 1]; part of the definition).  Z_lo = z_near, Z_hi = z_far; for a = 0, 1, 2:
+ * a non-finite g0_a or gd_a makes the ray a MISS; with gd_a == 0 the ray is a MISS unless 0 <= g0_a <= (float)(n_a - 1), and the axis
+ * constrains nothing else; otherwise t1 = (0.0f - g0_a) / gd_a, t2 = ((float)(n_a - 1) - g0_a) / gd_a, a non-finite t1 or t2 makes
+ * the ray a MISS, and Z_lo = max(Z_lo, min(t1, t2)), Z_hi = min(Z_hi, max(t1, t2)).  !(Z_lo <= Z_hi): MISS.
+ * March.  Z = Z_lo, no previous sample.  Repeat: if !(Z <= Z_hi) the status is NO_SURFACE; else if max_steps samples were taken it is
+ * EXHAUSTED; else take the sample at Z:
+ *   1. per axis: g_a as above; unless fabsf(g_a) < 32768.0f the sample is not inside; cell_a = (int)floorf(g_a), frac_a = g_a -
+ *      floorf(g_a) (exact).  The sample is inside iff 0 <= cell_a < n_a - 1 on every axis (integers).  No float reaches an address.
+ *   2. inside: the nearest voxel is cell_a + (frac_a >= 0.5f) per axis.  If it is seen (w >= min_weight) and its t == 32767
+ *      (saturated free space), the sample is FREE: f = 32767.0f, the next depth is Z + skip.
+ *   3. otherwise, if all eight corners of the cell (corner c = cell + (c & 1, (c >> 1) & 1, (c >> 2) & 1), as for the mesh) are
+ *      seen, f is the trilinear interpolant of their t (a stored -32768 reads as -32767) as floats: along x, then y, then z, each
+ *      lo + (frac * (hi - lo)) -- four, two, one.  The next depth is Z + step.
+ *   4. otherwise (not inside, or a corner unseen) the sample is UNSEEN: there is no previous sample any more; next depth Z + step.
+ *   A free or interpolated sample with f <= 0 ends the ray: with a previous sample (Z_prev, f_prev > 0) the status is HIT and
+ *   Zh = Z_prev + ((Z - Z_prev) * (f_prev / (f_prev - f))); without one it is BEHIND (the back of a surface, or its inside met through
+ *   unseen space).  With f > 0 the sample becomes the previous one.
+ * At a HIT the cell and the fractions are taken again at Zh (step 1).  If that sample is not inside, normal and colour are zeros.
+ *   Colour: the colour word of the nearest voxel (step 2); cw > 0: its B, G, R bytes, otherwise 0, 0, 0.
+ *   Normal: if all eight corners are seen, the gradient of the trilinear interpolant: gx is the blend of the four differences along x
+ *   (t1 - t0, t3 - t2, t5 - t4, t7 - t6) in y, then z; gy of (t2 - t0, t3 - t1, t6 - t4, t7 - t5) in x, then z; gz of (t4 - t0,
+ *   t5 - t1, t6 - t2, t7 - t3) in x, then y.  L = sqrtf(((gx * gx) + (gy * gy)) + (gz * gz)); unless L is finite and > 0 the record
+ *   is four zeros; n = (gx / L, gy / L, gz / L), rotated into the CAMERA frame: ((R[3r] * n0) + (R[3r+1] * n1)) + (R[3r+2] * n2).
+ *   The fourth float is the smallest weight of the eight corners.  No flip: the gradient points to the positive (free) side, which
+ *   at a HIT is the side the ray came from, so the z component is negative for a surface that faces the camera -- the sign
+ *   convention of adc_normals.  A corner unseen: four zeros; the depth stays.
+ * Outputs, each optional, at least one: depth float32 [height][width], Zh or 0.0f where the status is not HIT (0.0f is "no depth"
+ * for ADC_REG_FROM_DEPTH); normals float32 [height][width][4], 16-byte aligned; bgr uint8 [height][width][3], refused without a
+ * colour volume; status uint8 [height][width], an ADC_TSDF_RAY_* value.  Nothing is written behind the last pixel.
+ * Report (adc_tsdf_raycast_report, uint32 each): rays = width * height; miss, hit, no_surface, behind, exhausted (they sum to rays);
+ * samples_lo, samples_hi: the number of samples of all rays as a 64-bit count; eight reserved words.
+ *
+ * adc_tsdf_raycast_device      asynchronous on the handle's stream, completed by adc_wait; device addresses (d_depth 4-byte, d_normals
+ *                              16-byte aligned).  Calls may be enqueued back to back and behind adc_tsdf_integrate_device.
+ * adc_tsdf_raycast             the same with HOST pointers, synchronous; device scratch is allocated on first use and grows with the
+ *                              largest view.
+ * adc_get_tsdf_raycast_report  the report of the last call that adc_wait (or adc_tsdf_raycast) has completed; refused while none exists.
+ * Return codes as for adc_tsdf_extract: 0; 1 with adc_last_error and nothing enqueued (a NULL params, a bad field, flag or reserved
+ * word, no volume, no output requested, bgr without a colour volume, a misaligned device address, a Match pending); 2 on a HIP
+ * failure (the handle and the volume stay usable).  A Match may be enqueued behind a pending call and one adc_wait completes both.
+ * Not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_TSDF_RAY_MISS 0
+#define ADC_TSDF_RAY_HIT 1
+#define ADC_TSDF_RAY_NO_SURFACE 2
+#define ADC_TSDF_RAY_BEHIND 3
+#define ADC_TSDF_RAY_EXHAUSTED 4
+typedef struct adc_tsdf_raycast_params {
+    int32_t width, height;
+    float focal_px, cx, cy;
+    float R[9], t[3];    /* world -> camera */
+    float z_near, z_far;
+    float step, skip;
+    uint32_t min_weight; /* [1, 65535] */
+    uint32_t max_steps;  /* [1, 16384] */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved_[8];
+} adc_tsdf_raycast_params; /* 128 bytes */
+typedef struct adc_tsdf_raycast_report {
+    uint32_t rays, miss, hit, no_surface, behind, exhausted;
+    uint32_t samples_lo, samples_hi;
+    uint32_t reserved_[8];
+} adc_tsdf_raycast_report; /* 64 bytes */
+int adc_tsdf_raycast_device(adc_handle* h, const adc_tsdf_raycast_params* params, void* d_depth, void* d_normals, void* d_bgr,
+                            void* d_status);
+int adc_tsdf_raycast(adc_handle* h, const adc_tsdf_raycast_params* params, float* depth, float* normals, uint8_t* bgr, uint8_t* status,
+                     adc_tsdf_raycast_report* report);
+int adc_get_tsdf_raycast_report(adc_handle* h, adc_tsdf_raycast_report* out);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
