@@ -370,6 +370,43 @@ class TsdfRaycastReport(C.Structure):
         return self.samples_lo | (self.samples_hi << 32)
 
 
+TRACK_ENTRY_POINTS = ("adc_track_device", "adc_tsdf_track", "adc_get_track_result")
+TRACK_CONVERGED, TRACK_MAX_ITERATIONS, TRACK_LOST, TRACK_DEGENERATE, TRACK_DIVERGED = range(5)  # ADC_TRACK_*
+TRACK_MAX_ITERATIONS_LIMIT = 32
+
+
+class TrackParams(C.Structure):
+    """adc_track_params: iterations in [1, 32], stride in [1, 16], the distance gate max_dist (> 0), the angle gate min_cos in [-1, 1],
+    z_far (> 0: the farthest depth that takes part and the scale of the rotation columns), min_pixels >= 6, the convergence thresholds
+    eps_rot / eps_trans, the largest admissible step max_rot / max_trans, damping >= 0 (times the diagonal), pivot_ratio in [0, 1);
+    flags and the reserved words 0.  The defaults are those of a NULL pointer: API defaults, not measured optima."""
+    _fields_ = [("iterations", C.c_uint32), ("stride", C.c_uint32), ("max_dist", C.c_float), ("min_cos", C.c_float), ("z_far", C.c_float), ("min_pixels", C.c_uint32),
+                ("eps_rot", C.c_float), ("eps_trans", C.c_float), ("max_rot", C.c_float), ("max_trans", C.c_float), ("damping", C.c_float), ("pivot_ratio", C.c_float),
+                ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 3)]
+
+    def __init__(self, iterations=10, stride=1, max_dist=0.1, min_cos=0.8, z_far=8.0, min_pixels=64, eps_rot=1.0e-5, eps_trans=1.0e-5, max_rot=0.5, max_trans=0.5,
+                 damping=0.0, pivot_ratio=1.0e-6, flags=0):
+        super().__init__()
+        self.iterations, self.stride, self.min_pixels, self.flags = int(iterations), int(stride), int(min_pixels), int(flags)
+        self.max_dist, self.min_cos, self.z_far = float(max_dist), float(min_cos), float(z_far)
+        self.eps_rot, self.eps_trans, self.max_rot, self.max_trans = float(eps_rot), float(eps_trans), float(max_rot), float(max_trans)
+        self.damping, self.pivot_ratio = float(damping), float(pivot_ratio)
+
+
+class TrackIteration(C.Structure):
+    """adc_track_iteration: the used pixels, the rms residual and the norms of the step's rotation and translation of one solve"""
+    _fields_ = [("used", C.c_uint32), ("rms", C.c_float), ("rot", C.c_float), ("trans", C.c_float)]
+
+
+class TrackResult(C.Structure):
+    """adc_track_result: status (TRACK_*), the number of solves run, the last accepted pose R (row-major) / t, world -> camera, ready
+    for a TsdfFrame; the eight counts of the last reduce pass (the seven behind `pixels` sum to it); H (6 x 6, row-major) and b of the
+    last solve, twist order rotation then translation, model camera frame; one TrackIteration per solve run."""
+    _fields_ = [("status", C.c_uint32), ("solves", C.c_uint32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("pixels", C.c_uint32), ("no_depth", C.c_uint32),
+                ("outside", C.c_uint32), ("no_model", C.c_uint32), ("too_far", C.c_uint32), ("angle", C.c_uint32), ("out_of_range", C.c_uint32), ("used", C.c_uint32),
+                ("H", C.c_double * 36), ("b", C.c_double * 6), ("iteration", TrackIteration * TRACK_MAX_ITERATIONS_LIMIT), ("reserved_", C.c_uint32 * 6)]
+
+
 VOXEL_POSE = 0x1  # ADC_VOXEL_POSE: R, t of a VoxelGrid take the camera-frame point into the frame of the grid
 
 
@@ -541,6 +578,12 @@ def lib():
         L.adc_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastParams), vp, vp, vp, vp, C.POINTER(TsdfRaycastReport)]
         L.adc_get_tsdf_raycast_report.argtypes = [vp, C.POINTER(TsdfRaycastReport)]
         for name in TSDF_RAYCAST_ENTRY_POINTS:
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_track_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_track_device.argtypes = [vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfRaycastParams), vp, vp, C.POINTER(TrackParams), vp]
+        L.adc_tsdf_track.argtypes = [vp, vp, C.POINTER(TsdfFrame), C.POINTER(TrackParams), C.POINTER(TrackResult)]
+        L.adc_get_track_result.argtypes = [vp, C.POINTER(TrackResult)]
+        for name in TRACK_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_set_cloud_voxel_grid"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_set_cloud_voxel_grid.argtypes = [vp, C.POINTER(VoxelGrid)]
@@ -1416,6 +1459,30 @@ class ADCensusStereo:
         """The TsdfRaycastReport of the last ray cast wait() has completed (adc_get_tsdf_raycast_report), or None."""
         rep = TsdfRaycastReport()
         return rep if lib().adc_get_tsdf_raycast_report(self._h, C.byref(rep)) == 0 else None
+
+    def track_device(self, d_map, frame, model_view, d_model_depth, d_model_normals, params=None, d_frame_normals=None, d_result=None):
+        """The pose of the current frame against the model's predicted maps (adc_track_device; ints: device addresses of the frame's
+        float32 [H][W] map, the model's float32 depth and [.][.][4] normals as tsdf_raycast_device wrote them for `model_view`, a
+        TsdfRaycastParams; frame a TsdfFrame whose R, t are the initial guess; params a TrackParams or None for the defaults;
+        d_frame_normals as normals_device writes them, or None; d_result an 8-byte aligned device address for the record, or None);
+        asynchronous, call wait(), then track_result().  False when refused or on a HIP failure."""
+        return lib().adc_track_device(self._h, d_map, d_frame_normals, None if frame is None else C.byref(frame), None if model_view is None else C.byref(model_view),
+                                      d_model_depth, d_model_normals, None if params is None else C.byref(params), d_result) == 0
+
+    def tsdf_track(self, depth_map, frame, params=None):
+        """Host convenience (adc_tsdf_track): ray-casts the volume from the frame's guess and tracks the map against it; returns the
+        TrackResult.  Raises on failure."""
+        m = np.ascontiguousarray(depth_map, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        res = TrackResult()
+        if lib().adc_tsdf_track(self._h, m.ctypes.data, C.byref(frame), None if params is None else C.byref(params), C.byref(res)) != 0:
+            raise RuntimeError("adc_tsdf_track failed: " + last_error())
+        return res
+
+    def track_result(self):
+        """The TrackResult of the last track wait() has completed (adc_get_track_result), or None."""
+        res = TrackResult()
+        return res if lib().adc_get_track_result(self._h, C.byref(res)) == 0 else None
 
     def tsdf_volume_device(self):
         """(device address of the voxel words, of the colour words or None, TsdfParams) for a GPU consumer (adc_tsdf_get_volume_device)."""

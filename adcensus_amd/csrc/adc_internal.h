@@ -136,6 +136,7 @@ struct AdcInFlight {
     int tsdf_pending;     // adc_tsdf_integrate_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF..] into tsdf_report
     int tsdfx_pending;    // adc_tsdf_extract_device: an extraction was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_xreport
     int tsdfr_pending;    // adc_tsdf_raycast_device: a ray cast was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_RAY..] into tsdf_rreport
+    int track_pending;    // adc_track_device: a track was enqueued -> adc_wait moves the pinned record track_pin into track_result
     int tsdfm_pending;    // adc_tsdf_mesh_device: a mesh of the volume was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
@@ -375,6 +376,13 @@ struct adc_handle {
     int tsdf_rreport_valid;
     uint8_t* tsdfs_ray;       // device scratch of adc_tsdf_raycast (host callers): 24 bytes per pixel (depth, normals, bgr, status planes); grows with the largest view
     size_t tsdfs_ray_cap;     // (pixels)
+    // frame-to-model tracking (adc_track_device / adc_tsdf_track; nothing of it exists before the first call)
+    struct AdcTrackState* track_state; // device: the sums, the counts, the `done` word and the record the kernels work on (k_tsdf_track.hip)
+    adc_track_result* track_pin;       // pinned: the record of the last enqueued track; no Match writes here
+    adc_track_result track_result;     // adc_get_track_result
+    int track_result_valid;
+    int track_cus;            // CUs of the device: the reduce pass's grid is capped at a fixed multiple of it
+    float* tracks_map;        // device scratch of adc_tsdf_track (host callers), allocated by its first call: the model's normals, the map, the model's depth (24 bytes per pixel of the handle)
     // profiling
     int profiling, verbose;
     hipEvent_t ev[ADC_STAGE_COUNT + 1];
@@ -534,6 +542,26 @@ struct AdcTsdfRayReq {
     uint8_t* status;
 };
 hipError_t adc_launch_tsdf_raycast(adc_handle* h, const AdcTsdfRayReq& r);
+// k_tsdf_track.hip: the state the two kernels of a track share (all bytes zero in front of pass 0) and the two launches of pass
+// `iter`: the reduce pass adds its pixels' integers to sums / counts under the state's pose (the request's guess in pass 0); the solve
+// turns them into the next pose and the iteration record of res, clears them and sets `done` on a terminal status
+struct AdcTrackState {
+    long long sums[28];
+    uint32_t counts[8];
+    uint32_t done, pad_;
+    adc_track_result res;
+};
+struct AdcTrackReq {
+    adc_tsdf_frame frame;          // kind, calib; R, t: the guess
+    adc_tsdf_raycast_params model; // width, height, focal_px, cx, cy, R, t
+    adc_track_params params;
+    const float* map;
+    const float* fnormals;         // may be NULL
+    const float* mdepth;
+    const float* mnormals;
+};
+hipError_t adc_launch_track_reduce(adc_handle* h, const AdcTrackReq& r, uint32_t iter);
+hipError_t adc_launch_track_solve(adc_handle* h, const AdcTrackReq& r, uint32_t iter);
 #define ADC_MEDB_MAX_SEG 12                   // column segments per band link of the median, at most (k_refine.hip; sizes the hand-off / sink / seam buffers)
 size_t adc_median_hand_rows(int H);             // hand-off rows / store-sink blocks of the banded median (k_refine.hip)       // byte maps of the interpolation's empty-space skipping (k_refine.hip)
 int adc_irv_probe_xcd_mode(int device);         // 1 iff workgroup g of a launch runs on XCD g % 8 on this device (probed once)

@@ -7,6 +7,7 @@
 #include "tsdf_voxel.h" // tsdf_params_refusal, tsdf_frame_refusal
 #include "tsdf_cell.h"  // tsdf_mesh_refusal
 #include "tsdf_ray.h"   // tsdf_raycast_refusal
+#include "tsdf_track.h" // track_params_refusal, track_model_refusal, track_size_refusal
 
 #include <math.h>
 #include <stdio.h>
@@ -934,6 +935,11 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->tsdf_rreport, h->pin_flags + ADC_PIN_TSDF_RAY, ADC_TSDF_RAY_WORDS * sizeof(uint32_t));
         h->tsdf_rreport_valid = 1;
         h->fly.tsdfr_pending = 0;
+    }
+    if (h->fly.track_pending) {
+        h->track_result = *h->track_pin;
+        h->track_result_valid = 1;
+        h->fly.track_pending = 0;
     }
 }
 
@@ -2429,6 +2435,125 @@ int adc_get_tsdf_raycast_report(adc_handle* h, adc_tsdf_raycast_report* out)
     if (!h || !out) { g_last_error = "adc_get_tsdf_raycast_report: null argument"; return 1; }
     if (!h->tsdf_rreport_valid) { g_last_error = "adc_get_tsdf_raycast_report: no ray cast has completed on this handle"; return 1; }
     *out = h->tsdf_rreport;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ frame-to-model tracking (k_tsdf_track.hip)
+// In the style of adc_tsdf_raycast_device: enqueued on the object stream and completed by adc_wait, which moves the pinned record
+// into track_result.  One clear of the state, `iterations` pairs of (reduce, solve) up front -- a pair behind a terminal status is a
+// no-op on the device --, one read-back.  Every refusal stands in front of the first HIP call.
+static int track_check(adc_handle* h, const void* map, const void* fnormals, const adc_tsdf_frame* frame, const adc_tsdf_raycast_params* model, const void* mdepth,
+                       const void* mnormals, const adc_track_params* params, const void* result, bool device, bool needs_volume, adc_track_params* p, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : TRACK_DEFAULT;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (!frame) why = "null frame";
+    else if (device && !model) why = "null model view";
+    else if (device && !mdepth) why = "null model depth";
+    else if (device && !mnormals) why = "null model normals";
+    else if ((why = tsdf_frame_refusal(*frame)) != nullptr) {}
+    else if (device && (why = track_model_refusal(*model)) != nullptr) {}
+    else if ((why = track_params_refusal(*p)) != nullptr) {}
+    else if (device && ((uintptr_t)map & 3u)) why = "d_map must be 4-byte aligned";
+    else if (device && ((uintptr_t)fnormals & 15u)) why = "d_frame_normals must be 16-byte aligned";
+    else if (device && ((uintptr_t)mdepth & 3u)) why = "d_model_depth must be 4-byte aligned";
+    else if (device && ((uintptr_t)mnormals & 15u)) why = "d_model_normals must be 16-byte aligned";
+    else if (device && ((uintptr_t)result & 7u)) why = "d_result must be 8-byte aligned";
+    else if (needs_volume && !h->tsdf_set) why = "no volume (adc_tsdf_create first)";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    else if ((why = track_size_refusal(h->p.W, h->p.H, p->stride)) != nullptr) {}
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static hipError_t enqueue_track(adc_handle* h, const AdcTrackReq& r, void* d_result)
+{
+    HIP_OK(hipMemsetAsync(h->track_state, 0, sizeof(AdcTrackState), h->stream));
+    for (uint32_t k = 0; k < r.params.iterations; k++) {
+        HIP_OK(adc_launch_track_reduce(h, r, k));
+        HIP_OK(adc_launch_track_solve(h, r, k));
+    }
+    if (d_result) HIP_OK(hipMemcpyAsync(d_result, &h->track_state->res, sizeof(adc_track_result), hipMemcpyDeviceToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->track_pin, &h->track_state->res, sizeof(adc_track_result), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_track_device(adc_handle* h, const void* d_map, const void* d_frame_normals, const adc_tsdf_frame* frame, const adc_tsdf_raycast_params* model_view,
+                     const void* d_model_depth, const void* d_model_normals, const adc_track_params* params, void* d_result)
+{
+    const char* who = "adc_track_device";
+    AdcTrackReq r;
+    if (track_check(h, d_map, d_frame_normals, frame, model_view, d_model_depth, d_model_normals, params, d_result, true, false, &r.params, who) != 0) return 1;
+    hipSetDevice(h->device);
+    hipError_t e = MEM_ONCE(h->track_state, sizeof(AdcTrackState));
+    if (e == hipSuccess) e = MEM_ONCE_PINNED(h->track_pin, sizeof(adc_track_result));
+    if (e != hipSuccess) return scratch_failed(who);
+    if (!h->track_cus) {
+        int cus = 0;
+        if ((e = ADC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device))) != hipSuccess) {
+            set_error("adc_track_device: hipDeviceGetAttribute", e);
+            (void)hipGetLastError();
+            return 2;
+        }
+        h->track_cus = cus > 0 ? cus : 1;
+    }
+    r.frame = *frame;
+    r.model = *model_view;
+    r.map = static_cast<const float*>(d_map);
+    r.fnormals = static_cast<const float*>(d_frame_normals);
+    r.mdepth = static_cast<const float*>(d_model_depth);
+    r.mnormals = static_cast<const float*>(d_model_normals);
+    if (enqueue_track(h, r, d_result) != hipSuccess) return fail_call(h, who);
+    h->fly.track_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_track(adc_handle* h, const float* map, const adc_tsdf_frame* frame, const adc_track_params* params, adc_track_result* result)
+{
+    const char* who = "adc_tsdf_track";
+    adc_track_params p;
+    if (track_check(h, map, nullptr, frame, nullptr, nullptr, nullptr, params, nullptr, false, true, &p, who) != 0) return 1;
+    // the model: the volume as the frame's own camera sees it from the guess, as the CLI casts it
+    adc_tsdf_raycast_params view;
+    memset(&view, 0, sizeof(view));
+    view.width = h->p.W; view.height = h->p.H;
+    view.focal_px = frame->calib.focal_px; view.cx = frame->calib.cx; view.cy = frame->calib.cy;
+    memcpy(view.R, frame->R, sizeof(view.R));
+    memcpy(view.t, frame->t, sizeof(view.t));
+    view.z_near = h->tsdf_params.voxel;
+    view.z_far = 3.0e38f;
+    view.step = h->tsdf_params.voxel * 0.5f;
+    const float half = h->tsdf_params.trunc * 0.5f;
+    view.skip = half > view.step ? half : view.step;
+    view.min_weight = 1u;
+    view.max_steps = TSDF_RAY_MAX_STEPS;
+    const char* why = tsdf_raycast_refusal(view);
+    if (why) { g_last_error = std::string(who) + ": the model view: " + why; return 1; }
+    hipSetDevice(h->device);
+    // the scratch: the model's normals first (16-byte aligned), then the map, then the model's depth
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = MEM_ONCE(h->tracks_map, P * 24); // (a handle has one geometry: the first call's size is every call's)
+    if (e != hipSuccess) return scratch_failed(who);
+    float* d_n = h->tracks_map;
+    float* d_map = d_n + 4 * P;
+    float* d_d = d_map + P;
+    if ((e = ADC_HIP(hipMemcpy(d_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_track: upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_tsdf_raycast_device(h, &view, d_d, d_n, nullptr, nullptr);
+    if (rc == 0) rc = adc_track_device(h, d_map, nullptr, frame, &view, d_d, d_n, &p, nullptr);
+    if (rc == 0) rc = adc_wait(h);
+    else if (h->stream) { hipStreamSynchronize(h->stream); (void)hipGetLastError(); h->fly.tsdfr_pending = 0; } // (a ray cast without its track: drained, not reported)
+    if (rc != 0) return rc;
+    if (result) *result = h->track_result;
+    return 0;
+}
+
+int adc_get_track_result(adc_handle* h, adc_track_result* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_track_result: null argument"; return 1; }
+    if (!h->track_result_valid) { g_last_error = "adc_get_track_result: no track has completed on this handle"; return 1; }
+    *out = h->track_result;
     return 0;
 }
 

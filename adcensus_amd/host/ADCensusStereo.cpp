@@ -301,6 +301,16 @@ bool ADCensusStereo::TsdfRaycast(const TsdfRaycastParams* view, float32* depth, 
     return impl_ && adc_tsdf_raycast(impl_, view, depth, normals, bgr, status, report) == 0;
 }
 bool ADCensusStereo::GetTsdfRaycastReport(adc_tsdf_raycast_report* report) { return impl_ && adc_get_tsdf_raycast_report(impl_, report) == 0; }
+bool ADCensusStereo::Track(const void* d_map, const void* d_frame_normals, const adc_tsdf_frame* frame, const TsdfRaycastParams* model_view, const void* d_model_depth,
+                           const void* d_model_normals, const TrackParams* params, void* d_result)
+{
+    return impl_ && adc_track_device(impl_, d_map, d_frame_normals, frame, model_view, d_model_depth, d_model_normals, params, d_result) == 0;
+}
+bool ADCensusStereo::TsdfTrack(const float32* map, const adc_tsdf_frame* frame, const TrackParams* params, TrackResult* result)
+{
+    return impl_ && adc_tsdf_track(impl_, map, frame, params, result) == 0;
+}
+bool ADCensusStereo::GetTrackResult(TrackResult* result) { return impl_ && adc_get_track_result(impl_, result) == 0; }
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

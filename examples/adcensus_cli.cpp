@@ -45,6 +45,11 @@
 // 128 per component, made on the host; 0, 0, 0 where there is no normal); one line with the report's counts is printed.  STEP defaults
 // to VOXEL / 2, SKIP to max(TRUNC / 2, STEP).  --view-pose FILE (only with --tsdf-raycast): the view's pose, a file like that of --pose;
 // default: the pose of --pose.
+// --tsdf-track MAP.pfm[,GUESS.txt] (only with --tsdf; refused otherwise while the arguments are parsed) tracks a second frame against the
+// volume after the pair's map is fused (ADCensusStereo::TsdfTrack: the volume ray cast from the guess, then point-to-plane ICP on the
+// device): MAP.pfm is a disparity map of the pair's size and calibration, GUESS.txt a file like that of --pose, default: the pose of
+// --pose.  The parameters are the API's defaults with z_far = the distance from the guess camera to the volume's farthest corner.  One
+// report line is printed and the recovered pose goes to <out>-track.txt, 12 numbers in the format --pose reads.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -517,6 +522,31 @@ int main(int argc, char** argv)
             with_view_pose = true;
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2;
+            break;
+        }
+    bool with_tsdf_track = false, with_track_guess = false; // (--tsdf-track and its value likewise; the guess file is read and checked here)
+    std::string track_map;
+    float track_guess[12];
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf-track")) {
+            if (!with_tsdf) { printf("--tsdf-track refused: it needs --tsdf\n"); return -1; }
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            const size_t comma = v.find(',');
+            track_map = v.substr(0, comma);
+            if (track_map.empty()) { printf("--tsdf-track refused: it needs MAP.pfm[,GUESS.txt]\n"); return -1; }
+            if (comma != std::string::npos) {
+                FILE* f = fopen(v.substr(comma + 1).c_str(), "r");
+                int n = 0;
+                char extra = 0;
+                while (f && n < 12 && fscanf(f, "%f", &track_guess[n]) == 1 && std::isfinite(track_guess[n])) n++;
+                const bool clean = f && n == 12 && fscanf(f, " %c", &extra) != 1;
+                if (f) fclose(f);
+                if (!clean) { printf("--tsdf-track refused: the guess needs a file of 12 finite numbers (R row-major, then t)\n"); return -1; }
+                with_track_guess = true;
+            }
+            with_tsdf_track = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
             break;
         }
     if (with_tsdf_raycast && !with_tsdf) { printf("--tsdf-raycast refused: it needs --tsdf\n"); return -1; }
@@ -1033,6 +1063,49 @@ int main(int argc, char** argv)
                     ray_rgb[3 * i + k] = ray_normals[4 * i + 3] > 0.0f ? (uint8)((int)rintf(ray_normals[4 * i + k] * 127.0f) + 128) : 0;
             write_pfm(out + "-ray.pfm", ray_depth.data(), ray_view.width, ray_view.height);
             if (!write_png(out + "-ray-n.png", ray_rgb.data(), ray_view.width, ray_view.height, 3)) printf("cannot write %s-ray-n.png\n", out.c_str());
+        }
+        if (with_tsdf_track) { // a second frame tracked against the volume that now holds the pair's map
+            std::vector<float32> second;
+            int tw = 0, th = 0;
+            if (!load_pfm(track_map, second, tw, th) || tw != w || th != h) {
+                printf("tsdf track refused: cannot read %s as a one-channel PFM of %d x %d pixels\n", track_map.c_str(), w, h);
+                return -2;
+            }
+            adc_tsdf_frame guess = tsdf_frame;
+            if (with_track_guess) {
+                for (int k = 0; k < 9; k++) guess.R[k] = track_guess[k];
+                for (int k = 0; k < 3; k++) guess.t[k] = track_guess[9 + k];
+            }
+            // the API's defaults, but z_far: nothing in the volume is farther from the guess camera than the volume's farthest corner
+            adc_track_params tp = {10u, 1u, 0.1f, 0.8f, 8.0f, 64u, 1.0e-5f, 1.0e-5f, 0.5f, 0.5f, 0.0f, 1.0e-6f, 0u, {0u, 0u, 0u}};
+            double centre[3], far2 = 0.0;
+            for (int a = 0; a < 3; a++)
+                centre[a] = -((((double)guess.R[a] * (double)guess.t[0]) + ((double)guess.R[3 + a] * (double)guess.t[1])) + ((double)guess.R[6 + a] * (double)guess.t[2]));
+            const int dims[3] = {tsdf_params.nx, tsdf_params.ny, tsdf_params.nz};
+            for (int corner = 0; corner < 8; corner++) {
+                double d2 = 0.0;
+                for (int a = 0; a < 3; a++) {
+                    const double d = ((double)tsdf_params.origin[a] + ((double)(((corner >> a) & 1) ? dims[a] : 0) * (double)tsdf_params.voxel)) - centre[a];
+                    d2 = d2 + (d * d);
+                }
+                if (d2 > far2) far2 = d2;
+            }
+            tp.z_far = (float)sqrt(far2);
+            adc_track_result tr;
+            if (!ad_census.TsdfTrack(second.data(), &guess, &tp, &tr) || tr.solves < 1 || tr.solves > ADC_TRACK_MAX_ITERATIONS_LIMIT || tr.status > ADC_TRACK_DIVERGED) {
+                printf("tsdf track refused: %s\n", ad_census.LastError());
+                return -2;
+            }
+            static const char* const status_name[5] = {"converged", "max iterations", "lost", "degenerate", "diverged"};
+            const adc_track_iteration& last = tr.iteration[tr.solves - 1];
+            printf("TSDF track: %s after %u solves, %u of %u pixels used, rms %.9g, last step %.9g rad %.9g\n", status_name[tr.status], tr.solves, tr.used, tr.pixels,
+                   last.rms, last.rot, last.trans);
+            FILE* tf = fopen((out + "-track.txt").c_str(), "w");
+            if (tf) {
+                for (int k = 0; k < 9; k++) fprintf(tf, "%.9g\n", tr.R[k]);
+                for (int k = 0; k < 3; k++) fprintf(tf, "%.9g\n", tr.t[k]);
+                fclose(tf);
+            } else printf("cannot write %s-track.txt\n", out.c_str());
         }
     }
     if (with_calib) {

@@ -20,6 +20,7 @@
  * TsdfCreate / TsdfReset / TsdfIntegrate / TsdfExtract / GetTsdfReport (optional TSDF volume on the device: maps of many frames fused, surface points),
  * TsdfMesh / GetTsdfMeshReport (the volume's surface as a triangle mesh),
  * TsdfRaycast / GetTsdfRaycastReport (the volume seen from a camera pose: depth, normal, colour and status maps),
+ * Track / TsdfTrack / GetTrackResult (frame-to-model camera tracking against the ray cast's maps: the pose the next TsdfIntegrate needs),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -52,6 +53,10 @@ struct adc_tsdf_mesh_report;
 struct adc_tsdf_raycast_params;
 struct adc_tsdf_raycast_report;
 typedef adc_tsdf_raycast_params TsdfRaycastParams; // the view of TsdfRaycast: include/adcensus_c_api.h holds its fields
+struct adc_track_params;
+struct adc_track_result;
+typedef adc_track_params TrackParams;   // include/adcensus_c_api.h holds the fields
+typedef adc_track_result TrackResult;
 struct adc_point;
 
 class ADCensusStereo {
@@ -197,6 +202,16 @@ public:
      *  [height][width] (ADC_TSDF_RAY_*); report may be null.  GetTsdfRaycastReport: the report of the last completed call. */
     bool TsdfRaycast(const TsdfRaycastParams* view, float32* depth, float32* normals, uint8* bgr, uint8* status, adc_tsdf_raycast_report* report);
     bool GetTsdfRaycastReport(adc_tsdf_raycast_report* report);
+    /** Frame-to-model camera tracking (adc_track_device, point-to-plane ICP whose iterations stay on the device).  Track: DEVICE
+     *  addresses -- the frame's float32 [H][W] map, optionally its normals (float32 [H][W][4], may be null), the model's depth and
+     *  normals as adc_tsdf_raycast_device wrote them for `model_view`; frame->R, t are the initial guess; params may be null
+     *  (defaults); d_result (8-byte aligned, may be null) receives the record on the stream.  Asynchronous: Wait() completes it,
+     *  GetTrackResult reads the result of the last completed call.  TsdfTrack: a HOST map against the handle's volume, ray cast from the
+     *  frame's guess; synchronous; result may be null.  result->R, t go into the adc_tsdf_frame of the next TsdfIntegrate. */
+    bool Track(const void* d_map, const void* d_frame_normals, const adc_tsdf_frame* frame, const TsdfRaycastParams* model_view, const void* d_model_depth,
+               const void* d_model_normals, const TrackParams* params, void* d_result);
+    bool TsdfTrack(const float32* map, const adc_tsdf_frame* frame, const TrackParams* params, TrackResult* result);
+    bool GetTrackResult(TrackResult* result);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

@@ -1070,6 +1070,133 @@ int adc_tsdf_raycast(adc_handle* h, const adc_tsdf_raycast_params* params, float
                      adc_tsdf_raycast_report* report);
 int adc_get_tsdf_raycast_report(adc_handle* h, adc_tsdf_raycast_report* out);
 
+/* -------------------------------------------------------------------------------------------
+ * Frame-to-model camera tracking on the device: the pose of the current frame from its depth (or disparity) map and the model's
+ * predicted depth and normal maps, by projective point-to-plane ICP (k_tsdf_track.hip; the rule is adcensus_amd/csrc/tsdf_track.h,
+ * tests/tsdf_track_ref.py holds the same definition in numpy and the kernels match it bit for bit, in whatever order the waves run:
+ * everything summed over pixels is an integer).  The loop: adc_tsdf_raycast_device at the last pose, adc_track_device, then
+ * adc_tsdf_integrate_device at the recovered pose.  The iterations never return to the host.  Nothing here touches the volume.
+ *
+ * Inputs.  The current frame's map, float32 [H][W] of the handle's geometry, with an adc_tsdf_frame: kind and calib are read as
+ * adc_tsdf_integrate reads them (validity and Z of a map value: ADC_REG_FROM_*), R, t are the INITIAL GUESS, world -> camera.
+ * Optionally the frame's normals, float32 [H][W][4] as adc_normals_device writes them.  The model maps: depth float32 [mh][mw] and
+ * normals float32 [mh][mw][4] as adc_tsdf_raycast_device writes them, with the adc_tsdf_raycast_params they were cast with, of which
+ * only width, height (each in [1, 8192]), focal_px, cx, cy, R, t (Rm, tm below; all finite, focal_px > 0) are read.
+ *
+ * Parameters (adc_track_params, 64 bytes; NULL selects the defaults in brackets, which are API defaults and NOT measured optima):
+ * uint32 iterations in [1, 32] [10]; uint32 stride in [1, 16] [1]; float max_dist, finite, > 0 [0.1]; float min_cos in [-1, 1] [0.8];
+ * float z_far, finite, > 0 [8]; uint32 min_pixels >= 6 [64]; float eps_rot, eps_trans >= 0 [1e-5, 1e-5]; float max_rot, max_trans,
+ * finite, > 0 [0.5, 0.5]; float damping, finite, >= 0 [0]; float pivot_ratio in [0, 1) [1e-6]; uint32 flags = 0; uint32 reserved_[3] = 0.
+ * The host computes max_dist2 = max_dist * max_dist once (binary32).
+ *
+ * Reduce pass under the current estimate (Rk, tk), floats.  Binary32, one rounding per operation, nothing fused, parenthesised as
+ * written.  Every pixel (x, y) with x % stride == 0 && y % stride == 0 participates (`pixels` of them: ceil(W / stride) *
+ * ceil(H / stride), at most 2^26) and counts as exactly one of seven things:
+ *   1. depth: Z of map[y][x] by the frame's kind; a pixel without depth, or with !(Z <= z_far): no_depth.
+ *   2. camera point: Pc = ((((float)x - cx) / focal_px) * Z, (((float)y - cy) / focal_px) * Z, Z).
+ *   3. world point: d = Pc - tk; Pw_a = ((Rk[a] * d0) + (Rk[3+a] * d1)) + (Rk[6+a] * d2)                     (transpose(Rk) * d)
+ *   4. model camera: Pm_r = (((Rm[3r] * Pw0) + (Rm[3r+1] * Pw1)) + (Rm[3r+2] * Pw2)) + tm[r].
+ *   5. projection, as steps 3 to 5 of the integrate definition with the model view's intrinsics: Pm_2 finite and > 0; rz = 1.0f /
+ *      Pm_2; u = ((Pm_0 * fm) * rz) + cxm; v likewise; fabsf(u) < 32768.0f && fabsf(v) < 32768.0f; xm = (int)floorf(u + 0.5f), ym
+ *      likewise; 0 <= xm < mw && 0 <= ym < mh.  No float reaches an address before that integer test.  Otherwise: outside.
+ *   6. model sample: Dm = depth[ym][xm], nm = normals[ym][xm]; !(Dm > 0.0f) or !(nm[3] > 0.0f) (a NaN included): no_model.
+ *   7. distance gate: Qm = ((((float)xm - cxm) / fm) * Dm, (((float)ym - cym) / fm) * Dm, Dm); diff = Pm - Qm;
+ *      d2 = ((diff0 * diff0) + (diff1 * diff1)) + (diff2 * diff2); !(d2 <= max_dist2): far (the count too_far).
+ *   8. angle gate, only with frame normals given and the frame normal's fourth float > 0: nw = transpose(Rk) * nf as in step 3,
+ *      nr_r = ((Rm[3r] * nw0) + (Rm[3r+1] * nw1)) + (Rm[3r+2] * nw2); dot = ((nr0 * nm0) + (nr1 * nm1)) + (nr2 * nm2);
+ *      !(dot >= min_cos): angle.
+ *   9. residual r = ((nm0 * diff0) + (nm1 * diff1)) + (nm2 * diff2); Jacobian for a twist (omega, v) applied on the LEFT in the
+ *      model camera frame (Pm' = Pm + omega x Pm + v): J = (c, nm) with c = Pm x nm, c0 = (Pm1 * nm2) - (Pm2 * nm1), c1 = (Pm2 * nm0) -
+ *      (Pm0 * nm2), c2 = (Pm0 * nm1) - (Pm1 * nm0).
+ *  10. quantise, Q = 65536: the seven values s = (c0 / z_far, c1 / z_far, c2 / z_far, nm0, nm1, nm2, r / max_dist); unless
+ *      fabsf(s_i) < 4.0f for all seven (a NaN fails): out_of_range.  q_i = (int32)rintf(s_i * 65536.0f) (ties to even); the pixel is used.
+ *  11. sums, all int64 and exact: the 21 products q_i * q_j, i <= j < 6, by rows; the 6 products q_i * q_6; q_6 * q_6.
+ * No overflow: |q_i| <= 4 * 65536 = 2^18, a product is at most 2^36, at most 2^26 pixels participate, so every sum stays at or below
+ * 2^62.  The constants 65536, 4 and 2^26 may change only together with this derivation (it is repeated in tsdf_track.h).  The seven
+ * counts add up to pixels.  Because everything accumulated is an integer, no result depends on the order in which waves arrive.
+ *
+ * Solve, once per reduce pass, in binary64 with + - * / only, a fixed order, nothing fused (two square roots fill the norms of the
+ * iteration record and are read by no decision: every threshold is compared in squares).
+ *   scales: zs = (double)z_far / 65536, rs = (double)max_dist / 65536, sc = (zs, zs, zs, 1/65536, 1/65536, 1/65536);
+ *   H_ij = ((double)S_ij * sc_i) * sc_j (symmetric), b_i = ((double)S_i6 * sc_i) * rs, rms = sqrt((((double)S_66 * rs) * rs) / used).
+ *   used < min_pixels: LOST.
+ *   diag_i = H_ii + (damping * H_ii).  H = L D L^T without pivoting, column j = 0 .. 5: d_j = diag_j - sum over c < j, ascending,
+ *   of ((L_jc * L_jc) * d_c), subtracted one by one; unless d_j is finite and d_j > pivot_ratio * diag_j: DEGENERATE; for i > j:
+ *   L_ij = (H_ij - sum over c < j of ((L_ic * L_jc) * d_c)) / d_j.
+ *   H xi = -b: y_i = -b_i - sum over c < i of (L_ic * y_c); z_i = y_i / d_i; for i = 5 .. 0: xi_i = z_i - sum over c > i, ascending,
+ *   of (L_ci * xi_c).  xi = (omega, v).  w2 = ((omega0^2 + omega1^2) + omega2^2), v2 likewise.
+ *   !(w2 <= max_rot^2) or !(v2 <= max_trans^2) (squares of the doubles; a NaN included): DIVERGED.
+ *   After LOST, DEGENERATE or DIVERGED the pose stays the last accepted one, bit for bit.
+ *   Update.  The rotation of the step is the Cayley map of a = omega * 0.5 -- a rotation by rational arithmetic alone, no sin or cos,
+ *   on which a host's libm and the device library would not agree: aa = ((a0^2 + a1^2) + a2^2);
+ *   dR_ij = ((((i == j) ? 1 - aa : 0) + (2 * (a_i * a_j))) + (2 * X_ij)) / (1 + aa), X = [0 -a2 a1; a2 0 -a0; -a1 a0 0]; dT = (dR, v).
+ *   Tk <- ((Tk * Tm^-1) * dT^-1) * Tm with (R1, t1) * (R2, t2) = (R1 R2, R1 t2 + t1), every entry ((x + y) + z) [+ t1_i], and
+ *   (R, t)^-1 = (R^T, -(R^T t)).  Then one square-root-free step towards an orthonormal rotation: R <- R * ((3 I - R^T R) * 0.5).
+ *   R and t are rounded once to float: the estimate of the next reduce pass.
+ *   w2 < eps_rot^2 && v2 < eps_trans^2: CONVERGED (the step has been applied).  After `iterations` solves: MAX_ITERATIONS.
+ *
+ * Result (adc_track_result, 960 bytes): uint32 status (ADC_TRACK_*), uint32 solves (the number of solves run); float R[9], t[3], the
+ * last accepted pose, ready to be copied into an adc_tsdf_frame; uint32 pixels, no_depth, outside, no_model, too_far, angle,
+ * out_of_range, used of the last reduce pass; double H[36] (row-major 6 x 6) and b[6] of the last solve, undamped, twist order omega
+ * then v, model camera frame, for pose-graph users; adc_track_iteration iteration[32]: uint32 used, float rms (of the residual, in
+ * the map's unit), rot = |omega|, trans = |v| of each solve run (rot and trans are 0 where the solve ended before it had a step);
+ * uint32 reserved_[6] = 0.
+ *
+ * adc_track_device      asynchronous on the handle's stream, completed by adc_wait: one clear, `iterations` pairs of (reduce, solve)
+ *                       enqueued up front, one read-back.  Every kernel begins with a wave-uniform read of a `done` word and returns
+ *                       at once when a terminal status has set it.  No host synchronisation in between, no graph, no other stream.
+ *                       d_map and d_model_depth 4-byte, d_frame_normals (may be NULL) and d_model_normals 16-byte aligned; d_result
+ *                       (optional, 8-byte aligned) receives the same record on the stream for a GPU consumer.  May be enqueued
+ *                       directly behind adc_tsdf_raycast_device; a Match may be enqueued behind it and one adc_wait completes both.
+ *                       Its state and its pinned result block are its own, allocated on first use; it needs no volume.
+ * adc_tsdf_track        HOST pointers, synchronous; needs a volume: ray-casts it from the frame's own pose and intrinsics at W x H with
+ *                       step = voxel / 2, skip = max(trunc / 2, step), z_near = voxel, z_far = 3e38, min_weight 1, max_steps 16384,
+ *                       then tracks the map against those maps.  Device scratch is allocated on first use.
+ * adc_get_track_result  the result of the last call that adc_wait (or adc_tsdf_track) has completed; refused while none exists.
+ * Return codes: 0; 1 with adc_last_error and nothing enqueued (a NULL argument, a bad field, flag or reserved word, a non-finite pose,
+ * a calibration adc_tsdf_integrate would refuse, more than 2^26 participating pixels, a model view larger than 8192 on a side, a
+ * misaligned address, a Match pending, for adc_tsdf_track no volume) -- every refusal stands before the first HIP call; 2 on a HIP
+ * failure (the handle stays usable).  Not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_TRACK_CONVERGED 0
+#define ADC_TRACK_MAX_ITERATIONS 1
+#define ADC_TRACK_LOST 2
+#define ADC_TRACK_DEGENERATE 3
+#define ADC_TRACK_DIVERGED 4
+#define ADC_TRACK_MAX_ITERATIONS_LIMIT 32
+typedef struct adc_track_params {
+    uint32_t iterations;   /* [1, 32] */
+    uint32_t stride;       /* [1, 16] */
+    float max_dist;
+    float min_cos;
+    float z_far;
+    uint32_t min_pixels;   /* >= 6 */
+    float eps_rot, eps_trans;
+    float max_rot, max_trans;
+    float damping;
+    float pivot_ratio;     /* [0, 1) */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved_[3];
+} adc_track_params; /* 64 bytes */
+typedef struct adc_track_iteration {
+    uint32_t used;
+    float rms, rot, trans;
+} adc_track_iteration;
+typedef struct adc_track_result {
+    uint32_t status;       /* ADC_TRACK_* */
+    uint32_t solves;
+    float R[9], t[3];      /* world -> camera */
+    uint32_t pixels, no_depth, outside, no_model, too_far, angle, out_of_range, used;
+    double H[36], b[6];
+    adc_track_iteration iteration[ADC_TRACK_MAX_ITERATIONS_LIMIT];
+    uint32_t reserved_[6];
+} adc_track_result; /* 960 bytes */
+int adc_track_device(adc_handle* h, const void* d_map, const void* d_frame_normals, const adc_tsdf_frame* frame,
+                     const adc_tsdf_raycast_params* model_view, const void* d_model_depth, const void* d_model_normals,
+                     const adc_track_params* params, void* d_result);
+int adc_tsdf_track(adc_handle* h, const float* map, const adc_tsdf_frame* frame, const adc_track_params* params, adc_track_result* result);
+int adc_get_track_result(adc_handle* h, adc_track_result* out);
+
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
  * Level 2 records only the marks around the aggregation launches (adc_aggregate_info: the live duration of the roofline kernel) and
