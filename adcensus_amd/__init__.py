@@ -326,6 +326,45 @@ class TsdfExtractReport(C.Structure):
     _fields_ = [("voxels_seen", C.c_uint32), ("points", C.c_uint32), ("reserved_", C.c_uint32 * 6)]
 
 
+TSDF_FUSE_ENTRY_POINTS = ("adc_tsdf_weights_device", "adc_tsdf_weights", "adc_tsdf_fuse_device", "adc_tsdf_fuse", "adc_get_tsdf_fuse_report")
+TSDF_W_SCALE_CONFIDENCE = 1
+TSDF_FUSE_BILINEAR = 1
+
+
+class TsdfWeightParams(C.Structure):
+    """adc_tsdf_weight_params: the base weight of each fill class (FILL_WTA, _VOTING, _INTERPOLATION, _NONE), the confidence below
+    which a measured pixel gets 0, flags (TSDF_W_SCALE_CONFIDENCE), the power (0, 2, 4) of z_ref / Z the weight falls with; the
+    reserved words 0.  The defaults are those of a NULL params."""
+    _fields_ = [("class_weight", C.c_uint8 * 4), ("min_confidence", C.c_float), ("flags", C.c_uint32), ("depth_power", C.c_uint32), ("z_ref", C.c_float),
+                ("reserved_", C.c_uint32 * 11)]
+
+    def __init__(self, class_weight=(16, 4, 1, 0), min_confidence=0.0, flags=0, depth_power=4, z_ref=1.0):
+        super().__init__()
+        self.class_weight = (C.c_uint8 * 4)(*[int(v) for v in class_weight])
+        self.min_confidence, self.flags, self.depth_power, self.z_ref = float(min_confidence), int(flags), int(depth_power), float(z_ref)
+
+
+class TsdfWeightReport(C.Structure):
+    """adc_tsdf_weight_report: pixels with depth, with a weight above 0, measured pixels below min_confidence, weights of 255."""
+    _fields_ = [("valid", C.c_uint32), ("nonzero", C.c_uint32), ("below_confidence", C.c_uint32), ("saturated", C.c_uint32), ("reserved_", C.c_uint32 * 4)]
+
+
+class TsdfFuseParams(C.Structure):
+    """adc_tsdf_fuse_params: flags (TSDF_FUSE_BILINEAR) and the largest spread of the four map values around a projection, in the
+    map's own unit, over which they are still interpolated; the reserved words 0."""
+    _fields_ = [("flags", C.c_uint32), ("interp_gap", C.c_float), ("reserved_", C.c_uint32 * 6)]
+
+    def __init__(self, flags=0, interp_gap=0.0):
+        super().__init__()
+        self.flags, self.interp_gap = int(flags), float(interp_gap)
+
+
+class TsdfFuseReport(C.Structure):
+    """adc_tsdf_fuse_report: as TsdfReport, with the voxels whose pixel has the weight 0 and the ones that read the map interpolated."""
+    _fields_ = [("in_frustum", C.c_uint32), ("no_depth", C.c_uint32), ("unweighted", C.c_uint32), ("occluded", C.c_uint32), ("updated", C.c_uint32),
+                ("interpolated", C.c_uint32), ("reserved_", C.c_uint32 * 2)]
+
+
 TSDF_MESH_ENTRY_POINTS = ("adc_tsdf_mesh_device", "adc_tsdf_mesh", "adc_get_tsdf_mesh_report")
 
 
@@ -578,6 +617,14 @@ def lib():
         L.adc_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastParams), vp, vp, vp, vp, C.POINTER(TsdfRaycastReport)]
         L.adc_get_tsdf_raycast_report.argtypes = [vp, C.POINTER(TsdfRaycastReport)]
         for name in TSDF_RAYCAST_ENTRY_POINTS:
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_tsdf_fuse_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_tsdf_weights_device.argtypes = [vp, vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfWeightParams), vp]
+        L.adc_tsdf_weights.argtypes = [vp, vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfWeightParams), vp, C.POINTER(TsdfWeightReport)]
+        L.adc_tsdf_fuse_device.argtypes = [vp, vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfFuseParams)]
+        L.adc_tsdf_fuse.argtypes = [vp, vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfFuseParams), C.POINTER(TsdfFuseReport)]
+        L.adc_get_tsdf_fuse_report.argtypes = [vp, C.POINTER(TsdfFuseReport), C.POINTER(TsdfWeightReport)]
+        for name in TSDF_FUSE_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_track_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_track_device.argtypes = [vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfRaycastParams), vp, vp, C.POINTER(TrackParams), vp]
@@ -1399,6 +1446,59 @@ class ADCensusStereo:
         for cls, first in ((TsdfReport, True), (TsdfExtractReport, False)):
             rep = cls()
             rc = lib().adc_get_tsdf_report(self._h, C.byref(rep), None) if first else lib().adc_get_tsdf_report(self._h, None, C.byref(rep))
+            out.append(rep if rc == 0 else None)
+        return tuple(out)
+
+    # -- stereo-aware fusion (adc_tsdf_weights*, adc_tsdf_fuse*): per-pixel observation weights, gated bilinear map sampling ------
+    def tsdf_weights_device(self, d_map, frame, d_weight, params=None, d_provenance=None, d_confidence=None):
+        """The observation weights of a map (adc_tsdf_weights_device; ints: device addresses; d_weight uint8 [H][W]; frame a
+        TsdfFrame, of which kind and calib are read; params a TsdfWeightParams or None for the defaults); needs no volume;
+        asynchronous, call wait(), then tsdf_fuse_report().  False when refused or on a HIP failure."""
+        return lib().adc_tsdf_weights_device(self._h, d_map, d_provenance, d_confidence, C.byref(frame), None if params is None else C.byref(params), d_weight) == 0
+
+    def tsdf_weights(self, depth_map, frame, params=None, provenance=None, confidence=None):
+        """Host convenience (adc_tsdf_weights): returns (weight uint8 [H][W], TsdfWeightReport).  Raises on failure."""
+        m = np.ascontiguousarray(depth_map, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        prov = None if provenance is None else np.ascontiguousarray(provenance, dtype=np.uint8)
+        conf = None if confidence is None else np.ascontiguousarray(confidence, dtype=np.float32)
+        assert prov is None or prov.shape == m.shape, prov.shape
+        assert conf is None or conf.shape == m.shape, conf.shape
+        w = np.zeros(m.shape, np.uint8)
+        rep = TsdfWeightReport()
+        if lib().adc_tsdf_weights(self._h, m.ctypes.data, None if prov is None else prov.ctypes.data, None if conf is None else conf.ctypes.data, C.byref(frame),
+                                  None if params is None else C.byref(params), w.ctypes.data, C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_weights failed: " + last_error())
+        return w, rep
+
+    def tsdf_fuse_device(self, d_map, frame, d_weight=None, params=None, d_bgr_left=None):
+        """One weighted frame into the volume (adc_tsdf_fuse_device; ints: device addresses; d_weight uint8 [H][W] or None for 1
+        everywhere; params a TsdfFuseParams or None); asynchronous, call wait(), then tsdf_fuse_report().  False when refused (as
+        tsdf_integrate_device, or a bad params) or on a HIP failure."""
+        return lib().adc_tsdf_fuse_device(self._h, d_map, d_bgr_left, d_weight, C.byref(frame), None if params is None else C.byref(params)) == 0
+
+    def tsdf_fuse(self, depth_map, frame, weight=None, params=None, bgr_left=None):
+        """Host convenience (adc_tsdf_fuse): returns the TsdfFuseReport.  Raises on failure."""
+        m = np.ascontiguousarray(depth_map, dtype=np.float32)
+        assert m.shape == (self.height, self.width), (m.shape, (self.height, self.width))
+        img = None
+        if bgr_left is not None:
+            img = np.ascontiguousarray(bgr_left, dtype=np.uint8)
+            assert img.size == 3 * m.size, img.shape
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint8)
+        assert w is None or w.shape == m.shape, w.shape
+        rep = TsdfFuseReport()
+        if lib().adc_tsdf_fuse(self._h, m.ctypes.data, None if img is None else img.ctypes.data, None if w is None else w.ctypes.data, C.byref(frame),
+                               None if params is None else C.byref(params), C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_fuse failed: " + last_error())
+        return rep
+
+    def tsdf_fuse_report(self):
+        """(TsdfFuseReport or None, TsdfWeightReport or None) of the last fuse / weights call wait() has completed (adc_get_tsdf_fuse_report)."""
+        out = []
+        for cls, first in ((TsdfFuseReport, True), (TsdfWeightReport, False)):
+            rep = cls()
+            rc = lib().adc_get_tsdf_fuse_report(self._h, C.byref(rep), None) if first else lib().adc_get_tsdf_fuse_report(self._h, None, C.byref(rep))
             out.append(rep if rc == 0 else None)
         return tuple(out)
 

@@ -137,6 +137,8 @@ struct AdcInFlight {
     int tsdfx_pending;    // adc_tsdf_extract_device: an extraction was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_EXTRACT..] into tsdf_xreport
     int tsdfr_pending;    // adc_tsdf_raycast_device: a ray cast was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_RAY..] into tsdf_rreport
     int track_pending;    // adc_track_device: a track was enqueued -> adc_wait moves the pinned record track_pin into track_result
+    int tsdff_pending;    // adc_tsdf_fuse_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_FUSE..] into tsdf_freport
+    int tsdfw_pending;    // adc_tsdf_weights_device: a weight map was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_WEIGHT..] into tsdf_wreport
     int tsdfm_pending;    // adc_tsdf_mesh_device: a mesh of the volume was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
@@ -170,7 +172,9 @@ struct AdcRectSide {
 #define ADC_PIN_TSDF_EXTRACT (ADC_PIN_TSDF + 4)       // voxels_seen, points of the last extract call
 #define ADC_PIN_TSDF_MESH (ADC_PIN_TSDF + 8)          // voxels_seen, vertices, triangles, cells_seen, cells_surface of the last TSDF mesh call
 #define ADC_PIN_TSDF_RAY (ADC_PIN_TSDF + 16)          // rays, the five status counts, the 64-bit sample count of the last ray cast
-#define ADC_PIN_WORDS (ADC_PIN_TSDF + 24)             // int32 words of pin_flags
+#define ADC_PIN_TSDF_FUSE (ADC_PIN_TSDF + 24)         // in_frustum, no_depth, unweighted, occluded, updated, interpolated of the last fuse call (k_tsdf_fuse.hip)
+#define ADC_PIN_TSDF_WEIGHT (ADC_PIN_TSDF + 32)       // valid, nonzero, below_confidence, saturated of the last weights call
+#define ADC_PIN_WORDS (ADC_PIN_TSDF + 40)             // int32 words of pin_flags
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -376,6 +380,16 @@ struct adc_handle {
     int tsdf_rreport_valid;
     uint8_t* tsdfs_ray;       // device scratch of adc_tsdf_raycast (host callers): 24 bytes per pixel (depth, normals, bgr, status planes); grows with the largest view
     size_t tsdfs_ray_cap;     // (pixels)
+    // stereo-aware fusion (adc_tsdf_weights*, adc_tsdf_fuse*; nothing of it exists before the first such call; the fuse adds its counts
+    // to tsdf_rep[ADC_TSDF_REP_FUSE..])
+    uint32_t* tsdfw_rep;      // the four report words k_tsdf_obs_weight adds to (no volume needed), allocated by the first weights call
+    adc_tsdf_fuse_report tsdf_freport;    // adc_get_tsdf_fuse_report
+    int tsdf_freport_valid;
+    adc_tsdf_weight_report tsdf_wreport;
+    int tsdf_wreport_valid;
+    uint8_t* tsdfs_wgt;       // device scratch of adc_tsdf_weights / adc_tsdf_fuse (host callers): the weight map, its provenance and
+    uint8_t* tsdfs_prov;      // confidence inputs, each allocated on the first call that needs it (the map and the image use tsdfs_map, tsdfs_img)
+    float* tsdfs_conf;
     // frame-to-model tracking (adc_track_device / adc_tsdf_track; nothing of it exists before the first call)
     struct AdcTrackState* track_state; // device: the sums, the counts, the `done` word and the record the kernels work on (k_tsdf_track.hip)
     adc_track_result* track_pin;       // pinned: the record of the last enqueued track; no Match writes here
@@ -500,7 +514,7 @@ hipError_t adc_launch_mesh_scan(adc_handle* h, const AdcMeshReq& r);
 hipError_t adc_launch_mesh_emit(adc_handle* h, const AdcMeshReq& r);
 // k_tsdf.hip: one frame into the handle's volume (counts added to tsdf_rep[0..3]); the three launches of an extraction on tsdf_tiles
 // (measure: crossings per tile, voxels_seen; scan: bases, points -> tsdf_rep and the caller's word; emit: the records)
-#define ADC_TSDF_REP_WORDS 24
+#define ADC_TSDF_REP_WORDS 32
 #define ADC_TSDF_REP_EXTRACT 8
 struct AdcTsdfExtReq {
     uint32_t min_weight;
@@ -542,6 +556,28 @@ struct AdcTsdfRayReq {
     uint8_t* status;
 };
 hipError_t adc_launch_tsdf_raycast(adc_handle* h, const AdcTsdfRayReq& r);
+// k_tsdf_fuse.hip: the observation weights of a map (counts added to tsdfw_rep[0..3]) and one weighted frame into the handle's volume
+// (counts added to tsdf_rep[ADC_TSDF_REP_FUSE..])
+#define ADC_TSDF_REP_FUSE 24
+#define ADC_TSDF_FUSE_WORDS 6   // the counts of adc_tsdf_fuse_report in front of its reserved words
+#define ADC_TSDF_WEIGHT_WORDS 4 // the counts of adc_tsdf_weight_report in front of its reserved words
+struct AdcTsdfWeightReq {
+    adc_tsdf_frame frame;          // kind, calib
+    adc_tsdf_weight_params params;
+    const float* map;
+    const uint8_t* prov;           // may be NULL
+    const float* conf;             // may be NULL
+    uint8_t* weight;
+};
+struct AdcTsdfFuseReq {
+    adc_tsdf_frame frame;
+    adc_tsdf_fuse_params params;
+    const float* map;
+    const uint8_t* img;            // may be NULL
+    const uint8_t* weight;         // may be NULL: 1 everywhere
+};
+hipError_t adc_launch_tsdf_weights(adc_handle* h, const AdcTsdfWeightReq& r);
+hipError_t adc_launch_tsdf_fuse(adc_handle* h, const AdcTsdfFuseReq& r);
 // k_tsdf_track.hip: the state the two kernels of a track share (all bytes zero in front of pass 0) and the two launches of pass
 // `iter`: the reduce pass adds its pixels' integers to sums / counts under the state's pose (the request's guess in pass 0); the solve
 // turns them into the next pose and the iteration record of res, clears them and sets `done` on a terminal status

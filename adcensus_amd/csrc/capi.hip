@@ -8,6 +8,7 @@
 #include "tsdf_cell.h"  // tsdf_mesh_refusal
 #include "tsdf_ray.h"   // tsdf_raycast_refusal
 #include "tsdf_track.h" // track_params_refusal, track_model_refusal, track_size_refusal
+#include "tsdf_fuse.h"  // tsdf_weight_params_refusal, tsdf_fuse_params_refusal, the defaults
 
 #include <math.h>
 #include <stdio.h>
@@ -935,6 +936,18 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->tsdf_rreport, h->pin_flags + ADC_PIN_TSDF_RAY, ADC_TSDF_RAY_WORDS * sizeof(uint32_t));
         h->tsdf_rreport_valid = 1;
         h->fly.tsdfr_pending = 0;
+    }
+    if (h->fly.tsdff_pending) {
+        memset(&h->tsdf_freport, 0, sizeof(h->tsdf_freport));
+        memcpy(&h->tsdf_freport, h->pin_flags + ADC_PIN_TSDF_FUSE, ADC_TSDF_FUSE_WORDS * sizeof(uint32_t));
+        h->tsdf_freport_valid = 1;
+        h->fly.tsdff_pending = 0;
+    }
+    if (h->fly.tsdfw_pending) {
+        memset(&h->tsdf_wreport, 0, sizeof(h->tsdf_wreport));
+        memcpy(&h->tsdf_wreport, h->pin_flags + ADC_PIN_TSDF_WEIGHT, ADC_TSDF_WEIGHT_WORDS * sizeof(uint32_t));
+        h->tsdf_wreport_valid = 1;
+        h->fly.tsdfw_pending = 0;
     }
     if (h->fly.track_pending) {
         h->track_result = *h->track_pin;
@@ -2252,6 +2265,144 @@ int adc_tsdf_download(adc_handle* h, uint32_t* tsdf, uint32_t* color) { return t
 int adc_tsdf_upload(adc_handle* h, const uint32_t* tsdf, const uint32_t* color)
 {
     return tsdf_transfer(h, const_cast<uint32_t*>(tsdf), const_cast<uint32_t*>(color), false, "adc_tsdf_upload");
+}
+
+// ------------------------------------------------------------------------------ stereo-aware fusion (k_tsdf_fuse.hip)
+// In the style of the integrate: the device forms enqueue on the object stream and are completed by adc_wait, which moves the report
+// counts from pin_flags[ADC_PIN_TSDF_FUSE..] / pin_flags[ADC_PIN_TSDF_WEIGHT..] into tsdf_freport / tsdf_wreport.  The weights need no
+// volume: their four report words are an allocation of their own (tsdfw_rep, first call).  Every refusal stands in front of the first
+// HIP call.
+static int tsdf_weights_check(adc_handle* h, const void* map, const void* conf, const adc_tsdf_frame* frame, const adc_tsdf_weight_params* params, const void* weight,
+                              bool device, adc_tsdf_weight_params* p, const char* who)
+{
+    const char* why = nullptr;
+    *p = params ? *params : TSDF_WEIGHT_DEFAULT;
+    if (!h) why = "null handle";
+    else if (!map) why = "null map";
+    else if (!weight) why = "null weight";
+    else if (!frame) why = "null frame";
+    else if ((why = tsdf_frame_refusal(*frame)) != nullptr) {}
+    else if ((why = tsdf_weight_params_refusal(*p)) != nullptr) {}
+    else if (device && ((uintptr_t)map & 3u)) why = "d_map must be 4-byte aligned";
+    else if (device && ((uintptr_t)conf & 3u)) why = "d_confidence must be 4-byte aligned";
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+static hipError_t enqueue_tsdf_weights(adc_handle* h, const AdcTsdfWeightReq& r)
+{
+    HIP_TRY(MEM_ONCE(h->tsdfw_rep, 8 * sizeof(uint32_t)));
+    HIP_OK(hipMemsetAsync(h->tsdfw_rep, 0, ADC_TSDF_WEIGHT_WORDS * sizeof(uint32_t), h->stream));
+    HIP_OK(adc_launch_tsdf_weights(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_WEIGHT, h->tsdfw_rep, ADC_TSDF_WEIGHT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_weights_device(adc_handle* h, const void* d_map, const void* d_provenance, const void* d_confidence, const adc_tsdf_frame* frame,
+                            const adc_tsdf_weight_params* params, void* d_weight)
+{
+    const char* who = "adc_tsdf_weights_device";
+    AdcTsdfWeightReq r;
+    if (tsdf_weights_check(h, d_map, d_confidence, frame, params, d_weight, true, &r.params, who) != 0) return 1;
+    hipSetDevice(h->device);
+    r.frame = *frame;
+    r.map = static_cast<const float*>(d_map);
+    r.prov = static_cast<const uint8_t*>(d_provenance);
+    r.conf = static_cast<const float*>(d_confidence);
+    r.weight = static_cast<uint8_t*>(d_weight);
+    if (enqueue_tsdf_weights(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdfw_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_weights(adc_handle* h, const float* map, const uint8_t* provenance, const float* confidence, const adc_tsdf_frame* frame,
+                     const adc_tsdf_weight_params* params, uint8_t* weight, adc_tsdf_weight_report* report)
+{
+    const char* who = "adc_tsdf_weights";
+    adc_tsdf_weight_params p;
+    if (tsdf_weights_check(h, map, confidence, frame, params, weight, false, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = MEM_ONCE(h->tsdfs_map, P * 4);
+    if (e == hipSuccess) e = MEM_ONCE(h->tsdfs_wgt, P);
+    if (e == hipSuccess && provenance) e = MEM_ONCE(h->tsdfs_prov, P);
+    if (e == hipSuccess && confidence) e = MEM_ONCE(h->tsdfs_conf, P * 4);
+    if (e != hipSuccess) return scratch_failed(who);
+    if ((e = ADC_HIP(hipMemcpy(h->tsdfs_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_weights: upload", e); (void)hipGetLastError(); return 2; }
+    if (provenance && (e = ADC_HIP(hipMemcpy(h->tsdfs_prov, provenance, P, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_weights: provenance upload", e); (void)hipGetLastError(); return 2; }
+    if (confidence && (e = ADC_HIP(hipMemcpy(h->tsdfs_conf, confidence, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_weights: confidence upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_tsdf_weights_device(h, h->tsdfs_map, provenance ? h->tsdfs_prov : nullptr, confidence ? h->tsdfs_conf : nullptr, frame, &p, h->tsdfs_wgt);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if ((e = ADC_HIP(hipMemcpy(weight, h->tsdfs_wgt, P, hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_weights: copy-out", e); (void)hipGetLastError(); return 2; }
+    if (report) *report = h->tsdf_wreport;
+    return 0;
+}
+
+static int tsdf_fuse_check(adc_handle* h, const void* map, const void* img, const adc_tsdf_frame* frame, const adc_tsdf_fuse_params* params, bool device,
+                           adc_tsdf_fuse_params* p, const char* who)
+{
+    *p = params ? *params : TSDF_FUSE_DEFAULT;
+    const char* why = tsdf_fuse_params_refusal(*p);
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return tsdf_integrate_check(h, map, img, frame, device, who);
+}
+
+static hipError_t enqueue_tsdf_fuse(adc_handle* h, const AdcTsdfFuseReq& r)
+{
+    HIP_OK(hipMemsetAsync(h->tsdf_rep + ADC_TSDF_REP_FUSE, 0, ADC_TSDF_FUSE_WORDS * sizeof(uint32_t), h->stream));
+    HIP_OK(adc_launch_tsdf_fuse(h, r));
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_FUSE, h->tsdf_rep + ADC_TSDF_REP_FUSE, ADC_TSDF_FUSE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+int adc_tsdf_fuse_device(adc_handle* h, const void* d_map, const void* d_bgr_left, const void* d_weight, const adc_tsdf_frame* frame,
+                         const adc_tsdf_fuse_params* params)
+{
+    const char* who = "adc_tsdf_fuse_device";
+    AdcTsdfFuseReq r;
+    if (tsdf_fuse_check(h, d_map, d_bgr_left, frame, params, true, &r.params, who) != 0) return 1;
+    hipSetDevice(h->device);
+    r.frame = *frame;
+    r.map = static_cast<const float*>(d_map);
+    r.img = static_cast<const uint8_t*>(d_bgr_left);
+    r.weight = static_cast<const uint8_t*>(d_weight);
+    if (enqueue_tsdf_fuse(h, r) != hipSuccess) return fail_call(h, who);
+    h->fly.tsdff_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_fuse(adc_handle* h, const float* map, const uint8_t* bgr_left, const uint8_t* weight, const adc_tsdf_frame* frame,
+                  const adc_tsdf_fuse_params* params, adc_tsdf_fuse_report* report)
+{
+    const char* who = "adc_tsdf_fuse";
+    adc_tsdf_fuse_params p;
+    if (tsdf_fuse_check(h, map, bgr_left, frame, params, false, &p, who) != 0) return 1;
+    hipSetDevice(h->device);
+    const size_t P = (size_t)h->p.W * h->p.H;
+    hipError_t e = MEM_ONCE(h->tsdfs_map, P * 4);
+    if (e == hipSuccess && bgr_left) e = MEM_ONCE(h->tsdfs_img, P * 3);
+    if (e == hipSuccess && weight) e = MEM_ONCE(h->tsdfs_wgt, P);
+    if (e != hipSuccess) return scratch_failed(who);
+    if ((e = ADC_HIP(hipMemcpy(h->tsdfs_map, map, P * 4, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_fuse: upload", e); (void)hipGetLastError(); return 2; }
+    if (bgr_left && (e = ADC_HIP(hipMemcpy(h->tsdfs_img, bgr_left, P * 3, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_fuse: image upload", e); (void)hipGetLastError(); return 2; }
+    if (weight && (e = ADC_HIP(hipMemcpy(h->tsdfs_wgt, weight, P, hipMemcpyHostToDevice))) != hipSuccess) { set_error("adc_tsdf_fuse: weight upload", e); (void)hipGetLastError(); return 2; }
+    int rc = adc_tsdf_fuse_device(h, h->tsdfs_map, bgr_left ? h->tsdfs_img : nullptr, weight ? h->tsdfs_wgt : nullptr, frame, &p);
+    if (rc == 0) rc = adc_wait(h);
+    if (rc != 0) return rc;
+    if (report) *report = h->tsdf_freport;
+    return 0;
+}
+
+int adc_get_tsdf_fuse_report(adc_handle* h, adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report)
+{
+    if (!h || (!fuse_report && !weight_report)) { g_last_error = "adc_get_tsdf_fuse_report: null argument"; return 1; }
+    if (fuse_report && !h->tsdf_freport_valid) { g_last_error = "adc_get_tsdf_fuse_report: no fuse call has completed on this handle"; return 1; }
+    if (weight_report && !h->tsdf_wreport_valid) { g_last_error = "adc_get_tsdf_fuse_report: no weights call has completed on this handle"; return 1; }
+    if (fuse_report) *fuse_report = h->tsdf_freport;
+    if (weight_report) *weight_report = h->tsdf_wreport;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------ triangle mesh of the TSDF volume (k_tsdf.hip)

@@ -311,6 +311,20 @@ bool ADCensusStereo::TsdfTrack(const float32* map, const adc_tsdf_frame* frame, 
     return impl_ && adc_tsdf_track(impl_, map, frame, params, result) == 0;
 }
 bool ADCensusStereo::GetTrackResult(TrackResult* result) { return impl_ && adc_get_track_result(impl_, result) == 0; }
+bool ADCensusStereo::TsdfWeights(const float32* map, const uint8* provenance, const float32* confidence, const adc_tsdf_frame* frame, const adc_tsdf_weight_params* params,
+                                 uint8* weight, adc_tsdf_weight_report* report)
+{
+    return impl_ && adc_tsdf_weights(impl_, map, provenance, confidence, frame, params, weight, report) == 0;
+}
+bool ADCensusStereo::TsdfFuse(const float32* map, const uint8* bgr_left, const uint8* weight, const adc_tsdf_frame* frame, const adc_tsdf_fuse_params* params,
+                              adc_tsdf_fuse_report* report)
+{
+    return impl_ && adc_tsdf_fuse(impl_, map, bgr_left, weight, frame, params, report) == 0;
+}
+bool ADCensusStereo::GetTsdfFuseReport(adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report)
+{
+    return impl_ && adc_get_tsdf_fuse_report(impl_, fuse_report, weight_report) == 0;
+}
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

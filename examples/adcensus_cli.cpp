@@ -50,6 +50,12 @@
 // device): MAP.pfm is a disparity map of the pair's size and calibration, GUESS.txt a file like that of --pose, default: the pose of
 // --pose.  The parameters are the API's defaults with z_far = the distance from the guess camera to the volume's farthest corner.  One
 // report line is printed and the recovered pose goes to <out>-track.txt, 12 numbers in the format --pose reads.
+// --tsdf-fuse CW0,CW1,CW2,CW3,MINCONF,POWER,ZREF[,GAP] (only with --tsdf; refused otherwise while the arguments are parsed) fuses the map
+// with ADCensusStereo::TsdfWeights / TsdfFuse instead of TsdfIntegrate: the provenance and confidence maps of the SAME Match become a
+// weight per pixel (class weights CW0..CW3 of the four fill classes, pixels measured with a confidence below MINCONF get 0, the weight
+// falls with (ZREF / Z)^POWER, POWER 0, 2 or 4) and, with GAP, the map is read by the bilinear interpolation gated by GAP disparities.
+// --tsdf-mesh, --tsdf-raycast and --tsdf-track then see that volume; one more report line is printed; the run's other files are what
+// they were.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -549,6 +555,37 @@ int main(int argc, char** argv)
             argc -= i + 1 < argc ? 2 : 1;
             break;
         }
+    bool with_tsdf_fuse = false; // (--tsdf-fuse and its value likewise)
+    adc_tsdf_weight_params fuse_weights;
+    adc_tsdf_fuse_params fuse_params;
+    memset(&fuse_weights, 0, sizeof(fuse_weights));
+    memset(&fuse_params, 0, sizeof(fuse_params));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf-fuse")) {
+            if (!with_tsdf) { printf("--tsdf-fuse refused: it needs --tsdf\n"); return -1; }
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int cw[4] = {-1, -1, -1, -1}, power = -1;
+            float minconf = -1.0f, zref = 0.0f, gap = -1.0f;
+            char tail = 0;
+            int n = sscanf(v, "%d,%d,%d,%d,%f,%d,%f,%f%c", &cw[0], &cw[1], &cw[2], &cw[3], &minconf, &power, &zref, &gap, &tail);
+            if (n == 7 && sscanf(v, "%d,%d,%d,%d,%f,%d,%f%c", &cw[0], &cw[1], &cw[2], &cw[3], &minconf, &power, &zref, &tail) != 7) n = 0;
+            bool fine = (n == 7 || n == 8) && minconf >= 0.0f && minconf <= 1.0f && (power == 0 || power == 2 || power == 4) && std::isfinite(zref) && zref > 0.0f &&
+                        (n == 7 || (std::isfinite(gap) && gap >= 0.0f));
+            for (int k = 0; k < 4; k++) fine = fine && cw[k] >= 0 && cw[k] <= 255;
+            if (!fine) {
+                printf("--tsdf-fuse refused: it needs CW0,CW1,CW2,CW3,MINCONF,POWER,ZREF[,GAP] (CW in 0..255, MINCONF in 0..1, POWER 0, 2 or 4, ZREF > 0, GAP >= 0)\n");
+                return -1;
+            }
+            for (int k = 0; k < 4; k++) fuse_weights.class_weight[k] = (uint8)cw[k];
+            fuse_weights.min_confidence = minconf;
+            fuse_weights.depth_power = (uint32)power;
+            fuse_weights.z_ref = zref;
+            if (n == 8) { fuse_params.flags = ADC_TSDF_FUSE_BILINEAR; fuse_params.interp_gap = gap; }
+            with_tsdf_fuse = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
     if (with_tsdf_raycast && !with_tsdf) { printf("--tsdf-raycast refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf_mesh && !with_tsdf) { printf("--tsdf-mesh refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf && !with_calib) { printf("--tsdf refused: it needs --calib\n"); return -1; }
@@ -776,18 +813,19 @@ int main(int argc, char** argv)
     }
     printf("AD-Census Matching...\n");
     std::vector<float32> disparity((size_t)w * h, 0.0f);
-    std::vector<uint8> provenance(extras ? (size_t)w * h : 0);
-    std::vector<float32> confidence(extras ? (size_t)w * h : 0);
+    const bool with_maps = extras || with_tsdf_fuse; // (--tsdf-fuse weighs the map by the provenance and confidence of the same Match)
+    std::vector<uint8> provenance(with_maps ? (size_t)w * h : 0);
+    std::vector<float32> confidence(with_maps ? (size_t)w * h : 0);
     std::vector<float32> depth(with_calib ? (size_t)w * h : 0);
     std::vector<adc_point> cloud(with_calib ? (size_t)w * h : 0);
     adc_outputs outputs = {&calib, depth.data(), cloud.data(), cloud.size(), nullptr, nullptr};
     // --disp16: ONE Match through MatchProducts delivers the 16-bit map together with whatever the other options ask for
     std::vector<uint16_t> disp16(with_disp16 ? (size_t)w * h : 0);
-    adc_products products = {extras ? provenance.data() : nullptr, extras ? confidence.data() : nullptr, {nullptr, nullptr, nullptr, 0, nullptr, nullptr},
-                             disp16.data(), disp16_scale, 0};
+    adc_products products = {with_maps ? provenance.data() : nullptr, with_maps ? confidence.data() : nullptr, {nullptr, nullptr, nullptr, 0, nullptr, nullptr},
+                             with_disp16 ? disp16.data() : nullptr, disp16_scale, 0};
     if (with_calib) products.out = outputs;
     t0 = std::chrono::steady_clock::now();
-    const bool ok = with_disp16 ? ad_census.MatchProducts(left.data(), right.data(), disparity.data(), &products) : with_calib ? ad_census.MatchOut(left.data(), right.data(), disparity.data(), &outputs) : extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
+    const bool ok = (with_disp16 || with_tsdf_fuse) ? ad_census.MatchProducts(left.data(), right.data(), disparity.data(), &products) : with_calib ? ad_census.MatchOut(left.data(), right.data(), disparity.data(), &outputs) : extras ? ad_census.MatchEx(left.data(), right.data(), disparity.data(), provenance.data(), confidence.data())
                            : ad_census.Match(left.data(), right.data(), disparity.data());
     if (!ok) { printf("AD-Census matching failed: %s\n", ad_census.LastError()); return -2; }
     t1 = std::chrono::steady_clock::now();
@@ -982,8 +1020,17 @@ int main(int argc, char** argv)
         adc_tsdf_extract_report xrep;
         const uint8* colours = (with_rectify || with_raw) ? rect_left.data() : left.data();
         std::vector<adc_point> points;
-        bool ok = ad_census.TsdfCreate(&tsdf_params) && ad_census.TsdfIntegrate(disparity.data(), colours, &tsdf_frame, &irep) &&
-                  ad_census.TsdfExtract(&tsdf_extract, nullptr, 0, &xrep); // (counts only: the file is sized by the report)
+        adc_tsdf_weight_report wrep;
+        adc_tsdf_fuse_report frep;
+        std::vector<uint8> weight(with_tsdf_fuse ? (size_t)w * h : 0);
+        bool ok = ad_census.TsdfCreate(&tsdf_params);
+        if (ok && with_tsdf_fuse) { // the weights of this Match's own provenance and confidence, then the weighted frame
+            ok = ad_census.TsdfWeights(disparity.data(), provenance.data(), confidence.data(), &tsdf_frame, &fuse_weights, weight.data(), &wrep) &&
+                 ad_census.TsdfFuse(disparity.data(), colours, weight.data(), &tsdf_frame, &fuse_params, &frep);
+            memset(&irep, 0, sizeof(irep));
+            irep.in_frustum = frep.in_frustum; irep.no_depth = frep.no_depth; irep.occluded = frep.occluded; irep.updated = frep.updated;
+        } else if (ok) ok = ad_census.TsdfIntegrate(disparity.data(), colours, &tsdf_frame, &irep);
+        ok = ok && ad_census.TsdfExtract(&tsdf_extract, nullptr, 0, &xrep); // (counts only: the file is sized by the report)
         if (ok && xrep.points) {
             points.resize(xrep.points);
             ok = ad_census.TsdfExtract(&tsdf_extract, points.data(), points.size(), &xrep) && xrep.points == points.size();
@@ -994,6 +1041,9 @@ int main(int argc, char** argv)
         }
         printf("\nTSDF: %u voxels in the frustum, %u without depth, %u occluded, %u updated; %u voxels seen, %u surface points\n", irep.in_frustum, irep.no_depth,
                irep.occluded, irep.updated, xrep.voxels_seen, xrep.points);
+        if (with_tsdf_fuse)
+            printf("TSDF fuse: %u pixels with depth, %u weighted, %u below the confidence, %u saturated; %u voxels unweighted, %u interpolated\n", wrep.valid, wrep.nonzero,
+                   wrep.below_confidence, wrep.saturated, frep.unweighted, frep.interpolated);
         FILE* ply = fopen((out + "-tsdf.ply").c_str(), "wb");
         if (ply) {
             fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"

@@ -21,6 +21,7 @@
  * TsdfMesh / GetTsdfMeshReport (the volume's surface as a triangle mesh),
  * TsdfRaycast / GetTsdfRaycastReport (the volume seen from a camera pose: depth, normal, colour and status maps),
  * Track / TsdfTrack / GetTrackResult (frame-to-model camera tracking against the ray cast's maps: the pose the next TsdfIntegrate needs),
+ * TsdfWeights / TsdfFuse / GetTsdfFuseReport (stereo-aware fusion: per-pixel observation weights, gated bilinear reading of the map),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -48,6 +49,10 @@ struct adc_tsdf_params;
 struct adc_tsdf_frame;
 struct adc_tsdf_report;
 struct adc_tsdf_extract_params;
+struct adc_tsdf_weight_params;
+struct adc_tsdf_weight_report;
+struct adc_tsdf_fuse_params;
+struct adc_tsdf_fuse_report;
 struct adc_tsdf_extract_report;
 struct adc_tsdf_mesh_report;
 struct adc_tsdf_raycast_params;
@@ -212,6 +217,16 @@ public:
                const void* d_model_normals, const TrackParams* params, void* d_result);
     bool TsdfTrack(const float32* map, const adc_tsdf_frame* frame, const TrackParams* params, TrackResult* result);
     bool GetTrackResult(TrackResult* result);
+    /** Stereo-aware fusion (adc_tsdf_weights / adc_tsdf_fuse): HOST pointers, synchronous.  TsdfWeights turns a map (with optional
+     *  provenance and confidence maps of the same Match) into a uint8 [H][W] observation weight per pixel; params may be null (the
+     *  defaults), report may be null; it needs no volume.  TsdfFuse is TsdfIntegrate with that weight map (null: 1 everywhere) and an
+     *  optional gated bilinear reading of the map (params, may be null).  GetTsdfFuseReport: the reports of the last completed calls,
+     *  either may be null. */
+    bool TsdfWeights(const float32* map, const uint8* provenance, const float32* confidence, const adc_tsdf_frame* frame, const adc_tsdf_weight_params* params,
+                     uint8* weight, adc_tsdf_weight_report* report);
+    bool TsdfFuse(const float32* map, const uint8* bgr_left, const uint8* weight, const adc_tsdf_frame* frame, const adc_tsdf_fuse_params* params,
+                  adc_tsdf_fuse_report* report);
+    bool GetTsdfFuseReport(adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

@@ -36,6 +36,8 @@
  *   adc_tsdf_mesh         vertex numbers in cell order
  *   adc_tsdf_raycast_device / the volume's surface as seen from a camera pose: depth, normal, colour and status maps of a view, one
  *   adc_tsdf_raycast      ray per pixel marched through the volume
+ *   adc_tsdf_weights_device / per-pixel observation weights of a stereo map (fill class, confidence, depth) and the integrate that
+ *   adc_tsdf_fuse_device    applies them and may read the map by a gated bilinear interpolation
  *   adc_get_stage_ms      HIP-event stage timers (the reference printf()s stage times,
  *                         ADCensusStereo.cpp:81-129)
  *   adc_debug_*           per-stage entry points used ONLY by the parity tests
@@ -1196,6 +1198,97 @@ int adc_track_device(adc_handle* h, const void* d_map, const void* d_frame_norma
                      const adc_track_params* params, void* d_result);
 int adc_tsdf_track(adc_handle* h, const float* map, const adc_tsdf_frame* frame, const adc_track_params* params, adc_track_result* result);
 int adc_get_track_result(adc_handle* h, adc_track_result* out);
+
+/* -------------------------------------------------------------------------------------------
+ * Stereo-aware TSDF fusion: a per-pixel observation weight, and an integrate that applies it and may read the map by a gated bilinear
+ * interpolation (k_tsdf_fuse.hip; the rule is adcensus_amd/csrc/tsdf_fuse.h, tests/tsdf_fuse_ref.py holds the same definition in numpy
+ * and the kernels match it bit for bit).  adc_tsdf_integrate* gives every observation the weight 1 and reads the nearest pixel, which
+ * suits a time-of-flight map; a stereo map's depth error grows with Z^2, its filled pixels are guesses, and its disparity steps make
+ * the nearest pixel a staircase.  Optional: nothing here changes what adc_tsdf_integrate* or any other entry point does.
+ * All float arithmetic is IEEE binary32, one rounding per operation, nothing fused, parenthesised as written.
+ *
+ * Observation weights.  Output: uint8 [H][W] of the handle's geometry, a pure function of one pixel (a caller may as well supply a
+ * weight map of their own to adc_tsdf_fuse*).  Inputs: the float32 [H][W] map with an adc_tsdf_frame, of which kind and calib are read
+ * as adc_tsdf_integrate reads them (R, t must be finite and are not used); optional provenance (uint8 [H][W]) and confidence (float32
+ * [H][W]) maps as adc_match_device_ex delivers them; adc_tsdf_weight_params (64 bytes): uint8 class_weight[4] indexed by ADC_FILL_*;
+ * float min_confidence in [0, 1]; uint32 flags: ADC_TSDF_W_SCALE_CONFIDENCE; uint32 depth_power, 0, 2 or 4; float z_ref, finite and
+ * > 0, in the unit of Z; uint32 reserved_[11] = 0.  NULL: class_weight {16, 4, 1, 0}, min_confidence 0, flags 0, depth_power 4, z_ref 1
+ * (defaults of the interface, not measured optima).  For a pixel with map value v, code and conf:
+ *   1. D = the Z of v by the frame's kind; a pixel without depth gets 0 (it is not `valid`).
+ *   2. fill = (code >> ADC_PROV_FILL_SHIFT) & 3; without a provenance map fill = ADC_FILL_WTA.
+ *   3. wc = class_weight[fill]; with a provenance map and (code & ADC_PROV_SPECKLE): wc = 0.
+ *   4. with a confidence map and fill == ADC_FILL_WTA: if !(conf >= min_confidence) (a NaN fails): wc = 0, count below_confidence;
+ *      otherwise, with ADC_TSDF_W_SCALE_CONFIDENCE: cq = (int)floorf(fminf(fmaxf(conf, 0.0f), 1.0f) * 256.0f + 0.5f);
+ *      wc = (wc * cq + 128) >> 8.
+ *   5. wc == 0 or D == +inf (an overflowing fb / s): 0.  Otherwise g = z_ref / D; s = (float)wc for depth_power 0, s = (float)wc *
+ *      (g * g) for 2, s = (float)wc * ((g * g) * (g * g)) for 4; w = (int)floorf(fminf(s, 255.0f) + 0.5f).
+ * Report (adc_tsdf_weight_report, uint32 each): valid (pixels with depth), nonzero (w > 0), below_confidence, saturated (w == 255),
+ * four reserved words.
+ *
+ * Fuse.  adc_tsdf_fuse_params (32 bytes): uint32 flags: ADC_TSDF_FUSE_BILINEAR; float interp_gap, in the map's own unit (disparity or
+ * depth as stored), finite and >= 0; uint32 reserved_[6] = 0.  NULL: no flag, interp_gap 0.  Steps 1 to 5 and 8 are those of
+ * adc_tsdf_integrate; with x, y, u, v of its steps 4 and 5:
+ *   6.  D = the Z of map[y][x] by the frame's kind; a pixel without depth: skip, count no_depth.
+ *   6a. wo = weight[y][x], or 1 without a weight map; wo == 0: skip, count unweighted (nothing further is loaded).
+ *   6b. only with ADC_TSDF_FUSE_BILINEAR: x0 = (int)floorf(u), y0 = (int)floorf(v).  The interpolation is used iff 0 <= x0 && x0 + 1 <
+ *       W && 0 <= y0 && y0 + 1 < H (in integers, before any load); the raw values a = map[y0][x0], b = map[y0][x0+1], c = map[y0+1][x0],
+ *       d = map[y0+1][x0+1] all have depth by the kind's rule; fmaxf(fmaxf(a, b), fmaxf(c, d)) - fminf(fminf(a, b), fminf(c, d)) <=
+ *       interp_gap; and val has depth by the kind's rule, where fx = u - (float)x0, fy = v - (float)y0, top = a + fx * (b - a), bot = c +
+ *       fx * (d - c), val = top + fy * (bot - top).  Then D = the Z of val and the voxel counts as interpolated (whatever step 7 then
+ *       decides); otherwise D stays the nearest pixel's.  The raw values are interpolated: a disparity is affine in the pixel on a
+ *       plane, so a plane comes back exactly up to rounding.
+ *   7.  as adc_tsdf_integrate, on that D.
+ *   9'. m = w + wo; t' = ((t + 32767) * w + (q + 32767) * wo + m / 2) / m - 32767 in non-negative 64-bit integers (the numerator can
+ *       reach 65534 * 65535 + 65534 * 255 + 32895 > 2^32); w' = min(m, max_weight); count updated.  With wo == 1 this is step 9 bit for bit.
+ *   10. colour as adc_tsdf_integrate: the nearest pixel (x, y), cm = cw + 1 whatever wo.
+ * Report (adc_tsdf_fuse_report, uint32 each): in_frustum, no_depth, unweighted, occluded, updated, interpolated, two reserved words;
+ * in_frustum = no_depth + unweighted + occluded + updated.  Without a weight map and without the flag the volume and the four common
+ * counts equal those of adc_tsdf_integrate_device.
+ *
+ * adc_tsdf_weights_device   d_map 4-byte aligned; d_provenance, d_confidence (4-byte aligned) may be NULL; d_weight uint8 [H][W], any
+ *                           alignment.  Needs no volume.  Asynchronous on the handle's stream, completed by adc_wait.
+ * adc_tsdf_weights          the same with HOST pointers, synchronous; its device scratch is allocated on the first call.
+ * adc_tsdf_fuse_device      as adc_tsdf_integrate_device with d_weight (uint8 [H][W], any alignment, or NULL: 1 everywhere) and params
+ *                           (or NULL).  Asynchronous; calls may be enqueued back to back, behind adc_tsdf_weights_device and in
+ *                           front of adc_tsdf_raycast_device / adc_track_device with one adc_wait.
+ * adc_tsdf_fuse             the same with HOST pointers, synchronous.
+ * adc_get_tsdf_fuse_report  the reports of the last completed fuse / weights call; either pointer may be NULL (not both); a report
+ *                           that is asked for and does not exist yet is refused.
+ * Return codes and refusals as for adc_tsdf_integrate_device (every refusal stands before the first HIP call), and: a bad field, flag
+ * or reserved word of either params.
+ * ------------------------------------------------------------------------------------------- */
+#define ADC_TSDF_W_SCALE_CONFIDENCE 1u
+#define ADC_TSDF_FUSE_BILINEAR 1u
+typedef struct adc_tsdf_weight_params {
+    uint8_t class_weight[4]; /* ADC_FILL_WTA, _VOTING, _INTERPOLATION, _NONE */
+    float min_confidence;    /* [0, 1] */
+    uint32_t flags;          /* ADC_TSDF_W_SCALE_CONFIDENCE */
+    uint32_t depth_power;    /* 0, 2, 4 */
+    float z_ref;             /* finite, > 0 */
+    uint32_t reserved_[11];
+} adc_tsdf_weight_params; /* 64 bytes */
+typedef struct adc_tsdf_weight_report {
+    uint32_t valid, nonzero, below_confidence, saturated;
+    uint32_t reserved_[4];
+} adc_tsdf_weight_report;
+typedef struct adc_tsdf_fuse_params {
+    uint32_t flags;          /* ADC_TSDF_FUSE_BILINEAR */
+    float interp_gap;        /* finite, >= 0 */
+    uint32_t reserved_[6];
+} adc_tsdf_fuse_params; /* 32 bytes */
+typedef struct adc_tsdf_fuse_report {
+    uint32_t in_frustum, no_depth, unweighted, occluded, updated, interpolated;
+    uint32_t reserved_[2];
+} adc_tsdf_fuse_report;
+int adc_tsdf_weights_device(adc_handle* h, const void* d_map, const void* d_provenance, const void* d_confidence, const adc_tsdf_frame* frame,
+                            const adc_tsdf_weight_params* params, void* d_weight);
+int adc_tsdf_weights(adc_handle* h, const float* map, const uint8_t* provenance, const float* confidence, const adc_tsdf_frame* frame,
+                     const adc_tsdf_weight_params* params, uint8_t* weight, adc_tsdf_weight_report* report);
+int adc_tsdf_fuse_device(adc_handle* h, const void* d_map, const void* d_bgr_left, const void* d_weight, const adc_tsdf_frame* frame,
+                         const adc_tsdf_fuse_params* params);
+int adc_tsdf_fuse(adc_handle* h, const float* map, const uint8_t* bgr_left, const uint8_t* weight, const adc_tsdf_frame* frame,
+                  const adc_tsdf_fuse_params* params, adc_tsdf_fuse_report* report);
+int adc_get_tsdf_fuse_report(adc_handle* h, adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report);
 
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
