@@ -365,6 +365,51 @@ class TsdfFuseReport(C.Structure):
                 ("interpolated", C.c_uint32), ("reserved_", C.c_uint32 * 2)]
 
 
+TSDF_SHIFT_ENTRY_POINTS = ("adc_tsdf_shift_device", "adc_tsdf_shift", "adc_get_tsdf_shift_report", "adc_tsdf_get_offset", "adc_tsdf_follow_plan")
+TSDF_SHIFT_MAX_OFFSET = 1 << 24  # the largest |total offset| of a volume, in voxels
+
+
+class TsdfShiftParams(C.Structure):
+    """adc_tsdf_shift_params: the shift in voxels (the window moves by +shift in the world), min_weight in [1, 65535] of the leaving
+    surface points; flags and the reserved words 0."""
+    _fields_ = [("shift", C.c_int32 * 3), ("min_weight", C.c_uint32), ("flags", C.c_uint32), ("reserved_", C.c_uint32 * 3)]
+
+    def __init__(self, shift=(0, 0, 0), min_weight=1, flags=0):
+        super().__init__()
+        self.shift = (C.c_int32 * 3)(*[int(v) for v in shift])
+        self.min_weight, self.flags = int(min_weight), int(flags)
+
+
+class TsdfShiftReport(C.Structure):
+    """adc_tsdf_shift_report: voxels that stayed with a voxel word other than 0; leaving voxels with one; leaving voxels with
+    w >= min_weight; leaving surface points whatever the capacity."""
+    _fields_ = [("moved_nonempty", C.c_uint32), ("left_nonempty", C.c_uint32), ("left_seen", C.c_uint32), ("points", C.c_uint32), ("reserved_", C.c_uint32 * 4)]
+
+
+class TsdfFollowParams(C.Structure):
+    """adc_tsdf_follow_params: the camera-frame point that should stay near the volume's centre, the distance in voxels it may stray
+    (margin >= 0) and the step of a shift (quantum >= 1); the reserved words 0."""
+    _fields_ = [("anchor", C.c_float * 3), ("margin", C.c_int32), ("quantum", C.c_int32), ("reserved_", C.c_uint32 * 3)]
+
+    def __init__(self, anchor=(0.0, 0.0, 2.5), margin=8, quantum=4):
+        super().__init__()
+        self.anchor = (C.c_float * 3)(*[float(v) for v in anchor])
+        self.margin, self.quantum = int(margin), int(quantum)
+
+
+def tsdf_follow_plan(params, R, t, follow=None):
+    """How far to shift so that the anchor of a pose stays near the volume's centre (adc_tsdf_follow_plan; pure: no handle, no device).
+    params a TsdfParams with the CURRENT origin; R (9, row-major) and t (3) take a world point into the camera frame; follow a
+    TsdfFollowParams or None for the defaults.  Returns (sx, sy, sz).  Raises when refused."""
+    f = TsdfFollowParams() if follow is None else follow
+    Rc = (C.c_float * 9)(*[float(v) for v in R])
+    tc = (C.c_float * 3)(*[float(v) for v in t])
+    out = (C.c_int32 * 3)()
+    if lib().adc_tsdf_follow_plan(C.byref(params), Rc, tc, C.byref(f), out) != 0:
+        raise ValueError("adc_tsdf_follow_plan refused: " + last_error())
+    return tuple(out)
+
+
 TSDF_MESH_ENTRY_POINTS = ("adc_tsdf_mesh_device", "adc_tsdf_mesh", "adc_get_tsdf_mesh_report")
 
 
@@ -625,6 +670,14 @@ def lib():
         L.adc_tsdf_fuse.argtypes = [vp, vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfFuseParams), C.POINTER(TsdfFuseReport)]
         L.adc_get_tsdf_fuse_report.argtypes = [vp, C.POINTER(TsdfFuseReport), C.POINTER(TsdfWeightReport)]
         for name in TSDF_FUSE_ENTRY_POINTS:
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "adc_tsdf_shift_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
+        L.adc_tsdf_shift_device.argtypes = [vp, C.POINTER(TsdfShiftParams), vp, C.c_uint64, vp]
+        L.adc_tsdf_shift.argtypes = [vp, C.POINTER(TsdfShiftParams), vp, C.c_uint64, C.POINTER(TsdfShiftReport)]
+        L.adc_get_tsdf_shift_report.argtypes = [vp, C.POINTER(TsdfShiftReport)]
+        L.adc_tsdf_get_offset.argtypes = [vp, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_float * 3)]
+        L.adc_tsdf_follow_plan.argtypes = [C.POINTER(TsdfParams), C.POINTER(C.c_float * 9), C.POINTER(C.c_float * 3), C.POINTER(TsdfFollowParams), C.POINTER(C.c_int32 * 3)]
+        for name in TSDF_SHIFT_ENTRY_POINTS:
             getattr(L, name).restype = C.c_int
     if hasattr(L, "adc_track_device"):  # (absent from A/B builds of older revisions, ADC_HIP_LIB)
         L.adc_track_device.argtypes = [vp, vp, vp, C.POINTER(TsdfFrame), C.POINTER(TsdfRaycastParams), vp, vp, C.POINTER(TrackParams), vp]
@@ -1583,6 +1636,48 @@ class ADCensusStereo:
         """The TrackResult of the last track wait() has completed (adc_get_track_result), or None."""
         res = TrackResult()
         return res if lib().adc_get_track_result(self._h, C.byref(res)) == 0 else None
+
+    # -- moving volume (adc_tsdf_shift*): the window shifts by whole voxels, the surface that leaves is handed out once --------------
+    def tsdf_shift_device(self, shift, d_points=None, capacity=0, min_weight=1, d_count=None):
+        """Shifts the volume's window by `shift` = (sx, sy, sz) voxels (adc_tsdf_shift_device; a TsdfShiftParams is taken as it is)
+        and writes the surface points whose voxels leave (d_points adc_point records, 16-byte aligned, or None with capacity 0;
+        d_count one uint32 device word or None); asynchronous, call wait(), then tsdf_shift_report().  tsdf_volume_device() returns
+        other addresses after every non-zero shift.  False when refused or on a HIP failure (the volume is then as it was)."""
+        sp = shift if isinstance(shift, TsdfShiftParams) else TsdfShiftParams(shift, min_weight)
+        return lib().adc_tsdf_shift_device(self._h, C.byref(sp), d_points, int(capacity), d_count) == 0
+
+    def tsdf_shift(self, shift, min_weight=1, capacity=None):
+        """Host convenience (adc_tsdf_shift): returns (leaving points POINT_DTYPE [min(points, capacity)], TsdfShiftReport); capacity
+        None: all of them.  Raises on failure."""
+        sp = shift if isinstance(shift, TsdfShiftParams) else TsdfShiftParams(shift, min_weight)
+        rep = TsdfShiftReport()
+        if capacity is None:  # (the leaving points are a sub-list of the whole volume's: its count bounds them)
+            xrep = TsdfExtractReport()
+            xp = TsdfExtractParams(sp.min_weight)
+            if lib().adc_tsdf_extract(self._h, C.byref(xp), None, 0, C.byref(xrep)) != 0:
+                raise RuntimeError("adc_tsdf_shift failed: " + last_error())
+            capacity = xrep.points
+        pts = np.zeros(max(int(capacity), 1), POINT_DTYPE)
+        if lib().adc_tsdf_shift(self._h, C.byref(sp), pts.ctypes.data, int(capacity), C.byref(rep)) != 0:
+            raise RuntimeError("adc_tsdf_shift failed: " + last_error())
+        return pts[:min(rep.points, int(capacity))].copy(), rep
+
+    def tsdf_shift_report(self):
+        """The TsdfShiftReport of the last shift wait() has completed (adc_get_tsdf_shift_report), or None."""
+        rep = TsdfShiftReport()
+        return rep if lib().adc_get_tsdf_shift_report(self._h, C.byref(rep)) == 0 else None
+
+    def tsdf_offset(self):
+        """((ox, oy, oz) the sum of all shifts in voxels, (x, y, z) the origin given to tsdf_create) (adc_tsdf_get_offset)."""
+        off, org = (C.c_int32 * 3)(), (C.c_float * 3)()
+        if lib().adc_tsdf_get_offset(self._h, off, org) != 0:
+            raise RuntimeError("adc_tsdf_get_offset failed: " + last_error())
+        return tuple(off), tuple(org)
+
+    def tsdf_follow_plan(self, R, t, follow=None):
+        """tsdf_follow_plan for this handle's volume with its current origin: the shift to hand to tsdf_shift[_device]."""
+        _, _, p = self.tsdf_volume_device()
+        return tsdf_follow_plan(p, R, t, follow)
 
     def tsdf_volume_device(self):
         """(device address of the voxel words, of the colour words or None, TsdfParams) for a GPU consumer (adc_tsdf_get_volume_device)."""

@@ -139,6 +139,7 @@ struct AdcInFlight {
     int track_pending;    // adc_track_device: a track was enqueued -> adc_wait moves the pinned record track_pin into track_result
     int tsdff_pending;    // adc_tsdf_fuse_device: a frame was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_FUSE..] into tsdf_freport
     int tsdfw_pending;    // adc_tsdf_weights_device: a weight map was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_WEIGHT..] into tsdf_wreport
+    int tsdfh_pending;    // adc_tsdf_shift_device: a shift was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_SHIFT..] into tsdf_sreport
     int tsdfm_pending;    // adc_tsdf_mesh_device: a mesh of the volume was enqueued -> adc_wait moves pin_flags[ADC_PIN_TSDF_MESH..] into tsdf_mreport
     AdcMatchReq req;      // the request resolver / the entry points: what the Match in flight was asked for -> adc_wait (match_req_clear)
 };
@@ -174,7 +175,8 @@ struct AdcRectSide {
 #define ADC_PIN_TSDF_RAY (ADC_PIN_TSDF + 16)          // rays, the five status counts, the 64-bit sample count of the last ray cast
 #define ADC_PIN_TSDF_FUSE (ADC_PIN_TSDF + 24)         // in_frustum, no_depth, unweighted, occluded, updated, interpolated of the last fuse call (k_tsdf_fuse.hip)
 #define ADC_PIN_TSDF_WEIGHT (ADC_PIN_TSDF + 32)       // valid, nonzero, below_confidence, saturated of the last weights call
-#define ADC_PIN_WORDS (ADC_PIN_TSDF + 40)             // int32 words of pin_flags
+#define ADC_PIN_TSDF_SHIFT (ADC_PIN_TSDF + 40)        // moved_nonempty, left_nonempty, left_seen, points of the last shift call (k_tsdf_shift.hip)
+#define ADC_PIN_WORDS (ADC_PIN_TSDF + 48)             // int32 words of pin_flags
 #define ADC_PIN_NORMALS 24 // usable, fitted, few_points, degenerate of the last normals call (k_normals.hip): adc_get_normals_report
 struct adc_handle {
     AdcParams p;
@@ -390,6 +392,15 @@ struct adc_handle {
     uint8_t* tsdfs_wgt;       // device scratch of adc_tsdf_weights / adc_tsdf_fuse (host callers): the weight map, its provenance and
     uint8_t* tsdfs_prov;      // confidence inputs, each allocated on the first call that needs it (the map and the image use tsdfs_map, tsdfs_img)
     float* tsdfs_conf;
+    // moving volume (adc_tsdf_shift*; k_tsdf_shift.hip).  origin0 and offset are set by adc_tsdf_create; no memory exists before the
+    // first shift call (the report words) and the first non-zero shift (the second planes, which swap roles with tsdf_vol / tsdf_col)
+    float tsdf_origin0[3];    // the origin given to adc_tsdf_create: tsdf_params.origin = origin0 + (float)offset * voxel
+    int32_t tsdf_offset[3];   // the sum of all shifts, |.| <= 2^24
+    uint32_t* tsdf_vol2;      // the planes the next shift writes
+    uint32_t* tsdf_col2;
+    uint32_t* tsdf_shift_rep; // 8 words in the layout of adc_tsdf_shift_report: the kernels add to [0..2], the scan writes [3]
+    adc_tsdf_shift_report tsdf_sreport;   // adc_get_tsdf_shift_report
+    int tsdf_sreport_valid;
     // frame-to-model tracking (adc_track_device / adc_tsdf_track; nothing of it exists before the first call)
     struct AdcTrackState* track_state; // device: the sums, the counts, the `done` word and the record the kernels work on (k_tsdf_track.hip)
     adc_track_result* track_pin;       // pinned: the record of the last enqueued track; no Match writes here
@@ -527,6 +538,20 @@ hipError_t adc_launch_tsdf_integrate(adc_handle* h, const float* map, const uint
 hipError_t adc_launch_tsdf_measure(adc_handle* h, const AdcTsdfExtReq& r);
 hipError_t adc_launch_tsdf_scan(adc_handle* h, const AdcTsdfExtReq& r);
 hipError_t adc_launch_tsdf_emit(adc_handle* h, const AdcTsdfExtReq& r);
+hipError_t adc_launch_tsdf_scan_on(adc_handle* h, uint32_t* tbase, int ntiles, uint32_t* rep, uint32_t* count); // k_tsdf_scan on any tile array: rep[1] and *count = the total
+// k_tsdf_shift.hip: the leaving list of a shift on tsdf_tiles (measure and emit; the scan between them is adc_launch_tsdf_scan_on with
+// rep = tsdf_shift_rep + 2), and the old planes into the second pair (counts added to tsdf_shift_rep[0..2])
+#define ADC_TSDF_SHIFT_WORDS 4 // the counts of adc_tsdf_shift_report in front of its reserved words
+struct AdcTsdfShiftReq {
+    int32_t shift[3];
+    uint32_t min_weight;
+    void* points;              // may be NULL: counts only
+    uint32_t capacity;
+    uint32_t* count;           // the caller's device word, may be NULL
+};
+hipError_t adc_launch_tsdf_leave_measure(adc_handle* h, const AdcTsdfShiftReq& r);
+hipError_t adc_launch_tsdf_leave_emit(adc_handle* h, const AdcTsdfShiftReq& r);
+hipError_t adc_launch_tsdf_shift(adc_handle* h, const AdcTsdfShiftReq& r, bool move);
 // the triangle mesh of the volume: one fused measure (crossings and triangles per tile into the two halves of tsdf_tiles; voxels_seen,
 // cells_seen, cells_surface added to tsdf_rep[ADC_TSDF_REP_MESH..]), the scan once per list (which: 0 vertices, 1 triangles), the vertex
 // pass (records; with_first also tsdf_first), the triangle pass

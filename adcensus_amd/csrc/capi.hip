@@ -9,6 +9,7 @@
 #include "tsdf_ray.h"   // tsdf_raycast_refusal
 #include "tsdf_track.h" // track_params_refusal, track_model_refusal, track_size_refusal
 #include "tsdf_fuse.h"  // tsdf_weight_params_refusal, tsdf_fuse_params_refusal, the defaults
+#include "tsdf_shift.h" // the refusals of a shift, the origin from the total offset, the follow rule
 
 #include <math.h>
 #include <stdio.h>
@@ -924,6 +925,12 @@ static void wait_take_reports(adc_handle* h)
         memcpy(&h->tsdf_xreport, h->pin_flags + ADC_PIN_TSDF_EXTRACT, 2 * sizeof(uint32_t));
         h->tsdf_xreport_valid = 1;
         h->fly.tsdfx_pending = 0;
+    }
+    if (h->fly.tsdfh_pending) {
+        memset(&h->tsdf_sreport, 0, sizeof(h->tsdf_sreport));
+        memcpy(&h->tsdf_sreport, h->pin_flags + ADC_PIN_TSDF_SHIFT, ADC_TSDF_SHIFT_WORDS * sizeof(uint32_t));
+        h->tsdf_sreport_valid = 1;
+        h->fly.tsdfh_pending = 0;
     }
     if (h->fly.tsdfm_pending) {
         memset(&h->tsdf_mreport, 0, sizeof(h->tsdf_mreport));
@@ -2030,6 +2037,8 @@ static void tsdf_release(adc_handle* h)
 {
     dev_mem_release<HipMem>(&h->mem, &h->tsdf_vol);
     dev_mem_release<HipMem>(&h->mem, &h->tsdf_col);
+    dev_mem_release<HipMem>(&h->mem, &h->tsdf_vol2); // (the second planes of a volume that was shifted: no call for one that was not)
+    dev_mem_release<HipMem>(&h->mem, &h->tsdf_col2);
     h->tsdf_set = 0;
 }
 
@@ -2073,6 +2082,7 @@ int adc_tsdf_create(adc_handle* h, const adc_tsdf_params* params)
         return rc;
     }
     h->tsdf_params = *params;
+    for (int a = 0; a < 3; a++) { h->tsdf_origin0[a] = params->origin[a]; h->tsdf_offset[a] = 0; }
     h->tsdf_set = 1;
     return 0;
 }
@@ -2402,6 +2412,172 @@ int adc_get_tsdf_fuse_report(adc_handle* h, adc_tsdf_fuse_report* fuse_report, a
     if (weight_report && !h->tsdf_wreport_valid) { g_last_error = "adc_get_tsdf_fuse_report: no weights call has completed on this handle"; return 1; }
     if (fuse_report) *fuse_report = h->tsdf_freport;
     if (weight_report) *weight_report = h->tsdf_wreport;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ moving volume (k_tsdf_shift.hip)
+// In the style of the extraction: the device form enqueues on the object stream and is completed by adc_wait, which moves the four
+// report words from pin_flags[ADC_PIN_TSDF_SHIFT..] into tsdf_sreport.  The shift works out of place into tsdf_vol2 / tsdf_col2; the
+// HOST swaps the plane pointers, the offset and the origin only after every call of the sequence has been enqueued, so a HIP failure
+// (fail_call drains the stream) leaves the volume, its origin and its offset as they were.  Every refusal stands in front of the
+// first HIP call.
+static int tsdf_shift_check(adc_handle* h, const adc_tsdf_shift_params* params, const void* points, uint64_t capacity, const void* count, bool device,
+                            int32_t offset[3], const char* who)
+{
+    const char* why = nullptr;
+    if (!h) why = "null handle";
+    else if (!params) why = "null params";
+    else if ((why = tsdf_shift_params_refusal(*params)) != nullptr) {}
+    else if (!points && capacity != 0) why = "null points with a capacity";
+    else if (device && ((uintptr_t)points & 15u)) why = "d_points must be 16-byte aligned";
+    else if (device && ((uintptr_t)count & 3u)) why = "d_count must be 4-byte aligned";
+    else if (!h->tsdf_set) why = "no volume (adc_tsdf_create first)";
+    else if ((why = tsdf_shift_offset_refusal(h->tsdf_offset, params->shift, offset)) != nullptr) {}
+    else if (match_in_flight(h)) why = "a Match is pending (adc_wait first)";
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    return 0;
+}
+
+// apply == false: the leaving list and its count only (the counting pass of the host form); the volume stays
+static hipError_t enqueue_tsdf_shift(adc_handle* h, const AdcTsdfShiftReq& r, bool apply)
+{
+    const adc_tsdf_params& p = h->tsdf_params;
+    const bool zero = tsdf_shift_is_zero(r.shift), all = tsdf_shift_all_leave(tsdf_shift_rule(p, r.shift));
+    HIP_TRY(MEM_ONCE(h->tsdf_shift_rep, 8 * sizeof(uint32_t)));
+    HIP_OK(hipMemsetAsync(h->tsdf_shift_rep, 0, 8 * sizeof(uint32_t), h->stream));
+    if (zero) {
+        if (r.count) HIP_OK(hipMemsetAsync(r.count, 0, sizeof(uint32_t), h->stream));
+    } else {
+        if (apply) {
+            HIP_TRY(MEM_ONCE(h->tsdf_vol2, tsdf_voxels(p) * sizeof(uint32_t)));
+            if (h->tsdf_col) HIP_TRY(MEM_ONCE(h->tsdf_col2, tsdf_voxels(p) * sizeof(uint32_t)));
+        }
+        HIP_TRY(MEM_GROW(h->tsdf_tiles, h->tsdf_tiles_cap, adc_tsdf_tile_count(&p), sizeof(uint32_t)));
+        HIP_OK(adc_launch_tsdf_leave_measure(h, r));
+        HIP_OK(adc_launch_tsdf_scan_on(h, h->tsdf_tiles, (int)adc_tsdf_tile_count(&p), h->tsdf_shift_rep + 2, r.count));
+        if (r.points && r.capacity) HIP_OK(adc_launch_tsdf_leave_emit(h, r));
+        if (apply && all) { // everything leaves: the new planes are empty, the kernel only counts
+            HIP_OK(hipMemsetAsync(h->tsdf_vol2, 0, tsdf_voxels(p) * sizeof(uint32_t), h->stream));
+            if (h->tsdf_col) HIP_OK(hipMemsetAsync(h->tsdf_col2, 0, tsdf_voxels(p) * sizeof(uint32_t), h->stream));
+        }
+        if (apply) HIP_OK(adc_launch_tsdf_shift(h, r, !all));
+    }
+    HIP_OK(hipMemcpyAsync(h->pin_flags + ADC_PIN_TSDF_SHIFT, h->tsdf_shift_rep, ADC_TSDF_SHIFT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    return hipSuccess;
+}
+
+static int tsdf_shift_call(adc_handle* h, const adc_tsdf_shift_params* params, void* d_points, uint64_t capacity, void* d_count, const int32_t offset[3], bool apply,
+                           const char* who)
+{
+    AdcTsdfShiftReq r;
+    for (int a = 0; a < 3; a++) r.shift[a] = params->shift[a];
+    r.min_weight = params->min_weight;
+    r.points = d_points;
+    r.capacity = msh_cap32(capacity);
+    r.count = static_cast<uint32_t*>(d_count);
+    if (enqueue_tsdf_shift(h, r, apply) != hipSuccess) return fail_call(h, who);
+    if (apply && !tsdf_shift_is_zero(r.shift)) {
+        // everything is enqueued: the planes swap roles, the origin follows the total offset
+        std::swap(h->tsdf_vol, h->tsdf_vol2);
+        if (h->tsdf_col) std::swap(h->tsdf_col, h->tsdf_col2);
+        for (int a = 0; a < 3; a++) {
+            h->tsdf_offset[a] = offset[a];
+            h->tsdf_params.origin[a] = tsdf_shift_origin(h->tsdf_origin0[a], offset[a], h->tsdf_params.voxel);
+        }
+    }
+    h->fly.tsdfh_pending = 1;
+    return 0;
+}
+
+int adc_tsdf_shift_device(adc_handle* h, const adc_tsdf_shift_params* params, void* d_points, uint64_t capacity, void* d_count)
+{
+    const char* who = "adc_tsdf_shift_device";
+    int32_t offset[3];
+    if (tsdf_shift_check(h, params, d_points, capacity, d_count, true, offset, who) != 0) return 1;
+    hipSetDevice(h->device);
+    return tsdf_shift_call(h, params, d_points, capacity, d_count, offset, true, who);
+}
+
+int adc_tsdf_shift(adc_handle* h, const adc_tsdf_shift_params* params, adc_point* points, uint64_t capacity, adc_tsdf_shift_report* report)
+{
+    const char* who = "adc_tsdf_shift";
+    int32_t offset[3];
+    if (tsdf_shift_check(h, params, points, capacity, nullptr, false, offset, who) != 0) return 1;
+    hipSetDevice(h->device);
+    // as adc_tsdf_extract: no more records than the volume can give, and a scratch that would have to grow is sized by a counting pass.
+    // The list is made and copied out BEFORE the volume moves (a list-only pass): whatever fails, the caller either has the shifted
+    // volume and its leaving points, or the volume as it was.
+    const size_t most = 3 * tsdf_voxels(h->tsdf_params);
+    size_t cap = capacity < most ? (size_t)capacity : most;
+    hipError_t e = hipSuccess;
+    int rc = 0;
+    if (points && cap > h->tsdfs_pts_cap) {
+        rc = tsdf_shift_call(h, params, nullptr, 0, nullptr, offset, false, who);
+        if (rc == 0) rc = adc_wait(h);
+        if (rc != 0) return rc;
+        if (h->tsdf_sreport.points < cap) cap = h->tsdf_sreport.points;
+    }
+    if (points && cap) {
+        if ((e = MEM_GROW(h->tsdfs_pts, h->tsdfs_pts_cap, cap, sizeof(adc_point))) != hipSuccess) return scratch_failed(who);
+        rc = tsdf_shift_call(h, params, h->tsdfs_pts, cap, nullptr, offset, false, who);
+        if (rc == 0) rc = adc_wait(h);
+        if (rc != 0) return rc;
+        const size_t n = h->tsdf_sreport.points < cap ? h->tsdf_sreport.points : cap;
+        if (n && (e = ADC_HIP(hipMemcpy(points, h->tsdfs_pts, n * sizeof(adc_point), hipMemcpyDeviceToHost))) != hipSuccess) { set_error("adc_tsdf_shift: copy-out", e); (void)hipGetLastError(); return 2; }
+    }
+    const adc_tsdf_params before = h->tsdf_params;
+    const int32_t offset_before[3] = {h->tsdf_offset[0], h->tsdf_offset[1], h->tsdf_offset[2]};
+    rc = tsdf_shift_call(h, params, nullptr, 0, nullptr, offset, true, who);
+    if (rc != 0) return rc;
+    if ((rc = adc_wait(h)) != 0) {
+        // the wait failed behind a shift that was enqueued (the failure epilogue has drained the stream): the old planes were only
+        // read, so the planes swap back and the volume, its origin and its offset are what they were
+        if (!tsdf_shift_is_zero(params->shift)) {
+            std::swap(h->tsdf_vol, h->tsdf_vol2);
+            if (h->tsdf_col) std::swap(h->tsdf_col, h->tsdf_col2);
+            h->tsdf_params = before;
+            for (int a = 0; a < 3; a++) h->tsdf_offset[a] = offset_before[a];
+        }
+        return rc;
+    }
+    if (report) *report = h->tsdf_sreport;
+    return 0;
+}
+
+int adc_get_tsdf_shift_report(adc_handle* h, adc_tsdf_shift_report* out)
+{
+    if (!h || !out) { g_last_error = "adc_get_tsdf_shift_report: null argument"; return 1; }
+    if (!h->tsdf_sreport_valid) { g_last_error = "adc_get_tsdf_shift_report: no shift call has completed on this handle"; return 1; }
+    *out = h->tsdf_sreport;
+    return 0;
+}
+
+int adc_tsdf_get_offset(adc_handle* h, int32_t offset[3], float origin0[3])
+{
+    const char* why = !h || (!offset && !origin0) ? "null argument" : !h->tsdf_set ? "no volume (adc_tsdf_create first)" : nullptr;
+    if (why) { g_last_error = std::string("adc_tsdf_get_offset: ") + why; return 1; }
+    for (int a = 0; a < 3; a++) {
+        if (offset) offset[a] = h->tsdf_offset[a];
+        if (origin0) origin0[a] = h->tsdf_origin0[a];
+    }
+    return 0;
+}
+
+int adc_tsdf_follow_plan(const adc_tsdf_params* params, const float R[9], const float t[3], const adc_tsdf_follow_params* follow_params, int32_t shift_out[3])
+{
+    const char* who = "adc_tsdf_follow_plan";
+    const char* why = nullptr;
+    if (!params || !R || !t || !follow_params || !shift_out) why = "null argument";
+    else if ((why = tsdf_params_refusal(*params)) != nullptr) {}
+    else if ((why = tsdf_follow_params_refusal(*follow_params)) != nullptr) {}
+    else {
+        for (int i = 0; i < 9 && !why; i++)
+            if (!__builtin_isfinite(R[i])) why = "R has a non-finite entry";
+        for (int i = 0; i < 3 && !why; i++)
+            if (!__builtin_isfinite(t[i])) why = "t has a non-finite entry";
+    }
+    if (why) { g_last_error = std::string(who) + ": " + why; return 1; }
+    tsdf_follow_plan(*params, R, t, *follow_params, shift_out);
     return 0;
 }
 

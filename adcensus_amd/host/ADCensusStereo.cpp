@@ -325,6 +325,16 @@ bool ADCensusStereo::GetTsdfFuseReport(adc_tsdf_fuse_report* fuse_report, adc_ts
 {
     return impl_ && adc_get_tsdf_fuse_report(impl_, fuse_report, weight_report) == 0;
 }
+bool ADCensusStereo::TsdfShift(const adc_tsdf_shift_params* params, adc_point* points, uint64 capacity, adc_tsdf_shift_report* report)
+{
+    return impl_ && adc_tsdf_shift(impl_, params, points, capacity, report) == 0;
+}
+bool ADCensusStereo::GetTsdfShiftReport(adc_tsdf_shift_report* report) { return impl_ && adc_get_tsdf_shift_report(impl_, report) == 0; }
+bool ADCensusStereo::TsdfGetOffset(sint32 offset[3], float32 origin0[3]) { return impl_ && adc_tsdf_get_offset(impl_, offset, origin0) == 0; }
+bool ADCensusStereo::TsdfFollowPlan(const adc_tsdf_params* params, const float32 R[9], const float32 t[3], const adc_tsdf_follow_params* follow_params, sint32 shift_out[3])
+{
+    return adc_tsdf_follow_plan(params, R, t, follow_params, shift_out) == 0;
+}
 bool ADCensusStereo::SetCloudVoxelGrid(const adc_voxel_grid* grid) { return impl_ && grid && adc_set_cloud_voxel_grid(impl_, grid) == 0; }
 bool ADCensusStereo::ClearCloudVoxelGrid() { return impl_ && adc_clear_cloud_voxel_grid(impl_) == 0; }
 bool ADCensusStereo::GetVoxelReport(adc_voxel_report* report) const { return impl_ && report && adc_get_voxel_report(impl_, report) == 0; }

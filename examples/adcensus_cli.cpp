@@ -56,6 +56,10 @@
 // falls with (ZREF / Z)^POWER, POWER 0, 2 or 4) and, with GAP, the map is read by the bilinear interpolation gated by GAP disparities.
 // --tsdf-mesh, --tsdf-raycast and --tsdf-track then see that volume; one more report line is printed; the run's other files are what
 // they were.
+// --tsdf-shift SX,SY,SZ[,MINW] (only with --tsdf; refused otherwise while the arguments are parsed) moves the volume's window by SX, SY, SZ
+// voxels after the pair's map is fused (ADCensusStereo::TsdfShift) and writes the surface points whose voxels leave (weight >= MINW,
+// default that of --tsdf) to <out>-tsdf-left.ply, a file like <out>-tsdf.ply; one more report line is printed.  <out>-tsdf.ply,
+// --tsdf-mesh, --tsdf-raycast and --tsdf-track then see the shifted volume; the run's other files are what they are without the flag.
 // --speckle SIZE,DIFF (anywhere after the program name) switches the device-side speckle filter on (ADCensusStereo::SetSpeckleFilter:
 // components of at most SIZE pixels whose neighbours differ by at most DIFF become invalid): EVERY file of the run comes from
 // the filtered map; without the flag the files are what they were.
@@ -586,6 +590,30 @@ int main(int argc, char** argv)
             argc -= i + 1 < argc ? 2 : 1;
             break;
         }
+    bool with_tsdf_shift = false; // (--tsdf-shift and its value likewise)
+    adc_tsdf_shift_params tsdf_shift;
+    memset(&tsdf_shift, 0, sizeof(tsdf_shift));
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--tsdf-shift")) {
+            if (!with_tsdf) { printf("--tsdf-shift refused: it needs --tsdf\n"); return -1; }
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            int s[3] = {0, 0, 0}, minw = (int)tsdf_extract.min_weight;
+            char tail = 0;
+            int n = sscanf(v, "%d,%d,%d,%d%c", &s[0], &s[1], &s[2], &minw, &tail);
+            if (n == 3 && sscanf(v, "%d,%d,%d%c", &s[0], &s[1], &s[2], &tail) != 3) n = 0;
+            bool fine = (n == 3 || n == 4) && minw >= 1 && minw <= 65535;
+            for (int k = 0; k < 3; k++) fine = fine && s[k] >= -(1 << 24) && s[k] <= (1 << 24);
+            if (!fine) {
+                printf("--tsdf-shift refused: it needs SX,SY,SZ[,MINW] (whole voxels, each at most 2^24 in size, MINW in 1..65535)\n");
+                return -1;
+            }
+            for (int k = 0; k < 3; k++) tsdf_shift.shift[k] = s[k];
+            tsdf_shift.min_weight = (uint32)minw;
+            with_tsdf_shift = true;
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= i + 1 < argc ? 2 : 1;
+            break;
+        }
     if (with_tsdf_raycast && !with_tsdf) { printf("--tsdf-raycast refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf_mesh && !with_tsdf) { printf("--tsdf-mesh refused: it needs --tsdf\n"); return -1; }
     if (with_tsdf && !with_calib) { printf("--tsdf refused: it needs --calib\n"); return -1; }
@@ -1030,6 +1058,26 @@ int main(int argc, char** argv)
             memset(&irep, 0, sizeof(irep));
             irep.in_frustum = frep.in_frustum; irep.no_depth = frep.no_depth; irep.occluded = frep.occluded; irep.updated = frep.updated;
         } else if (ok) ok = ad_census.TsdfIntegrate(disparity.data(), colours, &tsdf_frame, &irep);
+        std::vector<adc_point> left_points;
+        adc_tsdf_shift_report srep;
+        memset(&srep, 0, sizeof(srep));
+        if (ok && with_tsdf_shift) { // the window moves; what leaves it is a sub-list of the whole volume's points, which sizes the buffer
+            adc_tsdf_extract_params all = tsdf_extract;
+            all.min_weight = tsdf_shift.min_weight;
+            ok = ad_census.TsdfExtract(&all, nullptr, 0, &xrep);
+            left_points.resize(ok ? xrep.points : 0);
+            ok = ok && ad_census.TsdfShift(&tsdf_shift, left_points.empty() ? nullptr : left_points.data(), left_points.size(), &srep) && srep.points <= left_points.size();
+            sint32 offset[3] = {0, 0, 0};
+            float32 origin0[3] = {0.0f, 0.0f, 0.0f};
+            ok = ok && ad_census.TsdfGetOffset(offset, origin0);
+            if (ok) {
+                left_points.resize(srep.points);
+                for (int a = 0; a < 3; a++) { // (the volume's origin now, by its definition: what the ray cast's and the track's defaults read)
+                    const float32 step = (float32)offset[a] * tsdf_params.voxel;
+                    tsdf_params.origin[a] = origin0[a] + step;
+                }
+            }
+        }
         ok = ok && ad_census.TsdfExtract(&tsdf_extract, nullptr, 0, &xrep); // (counts only: the file is sized by the report)
         if (ok && xrep.points) {
             points.resize(xrep.points);
@@ -1044,6 +1092,20 @@ int main(int argc, char** argv)
         if (with_tsdf_fuse)
             printf("TSDF fuse: %u pixels with depth, %u weighted, %u below the confidence, %u saturated; %u voxels unweighted, %u interpolated\n", wrep.valid, wrep.nonzero,
                    wrep.below_confidence, wrep.saturated, frep.unweighted, frep.interpolated);
+        if (with_tsdf_shift) {
+            printf("TSDF shift %d,%d,%d: %u voxels moved, %u left, %u of them seen; %u leaving surface points\n", tsdf_shift.shift[0], tsdf_shift.shift[1], tsdf_shift.shift[2],
+                   srep.moved_nonempty, srep.left_nonempty, srep.left_seen, srep.points);
+            FILE* lply = fopen((out + "-tsdf-left.ply").c_str(), "wb");
+            if (lply) {
+                fprintf(lply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", left_points.size());
+                for (size_t i = 0; i < left_points.size(); i++) {
+                    fwrite(&left_points[i].x, 4, 3, lply);
+                    fwrite(&left_points[i].r, 1, 3, lply);
+                }
+                fclose(lply);
+            } else printf("cannot write %s-tsdf-left.ply\n", out.c_str());
+        }
         FILE* ply = fopen((out + "-tsdf.ply").c_str(), "wb");
         if (ply) {
             fprintf(ply, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"

@@ -22,6 +22,7 @@
  * TsdfRaycast / GetTsdfRaycastReport (the volume seen from a camera pose: depth, normal, colour and status maps),
  * Track / TsdfTrack / GetTrackResult (frame-to-model camera tracking against the ray cast's maps: the pose the next TsdfIntegrate needs),
  * TsdfWeights / TsdfFuse / GetTsdfFuseReport (stereo-aware fusion: per-pixel observation weights, gated bilinear reading of the map),
+ * TsdfShift / GetTsdfShiftReport / TsdfGetOffset / TsdfFollowPlan (moving volume: the window shifts by whole voxels, the surface that leaves is handed out once),
  * MatchProducts / MatchAsyncProducts (every optional product of one Match through one request, synchronous or completed by Wait).
  */
 #pragma once
@@ -53,6 +54,9 @@ struct adc_tsdf_weight_params;
 struct adc_tsdf_weight_report;
 struct adc_tsdf_fuse_params;
 struct adc_tsdf_fuse_report;
+struct adc_tsdf_shift_params;
+struct adc_tsdf_shift_report;
+struct adc_tsdf_follow_params;
 struct adc_tsdf_extract_report;
 struct adc_tsdf_mesh_report;
 struct adc_tsdf_raycast_params;
@@ -227,6 +231,16 @@ public:
     bool TsdfFuse(const float32* map, const uint8* bgr_left, const uint8* weight, const adc_tsdf_frame* frame, const adc_tsdf_fuse_params* params,
                   adc_tsdf_fuse_report* report);
     bool GetTsdfFuseReport(adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report);
+    /** Moving volume (adc_tsdf_shift: HOST pointers, synchronous).  TsdfShift moves the volume's window by params->shift voxels on the
+     *  device -- the origin moves along, so every other call goes on as before -- and writes the first min(points, capacity) surface
+     *  points whose voxels leave (the records of TsdfExtract, each handed out at most once over a session); points may be null with
+     *  capacity 0, report may be null.  GetTsdfShiftReport: the report of the last completed call.  TsdfGetOffset: the sum of all
+     *  shifts in voxels and the origin given to TsdfCreate; either may be null.  TsdfFollowPlan (no object needed): the shift that keeps
+     *  a point of the camera frame near the volume's centre for the pose R, t (WORLD -> camera); params holds the CURRENT origin. */
+    bool TsdfShift(const adc_tsdf_shift_params* params, adc_point* points, uint64 capacity, adc_tsdf_shift_report* report);
+    bool GetTsdfShiftReport(adc_tsdf_shift_report* report);
+    bool TsdfGetOffset(sint32 offset[3], float32 origin0[3]);
+    static bool TsdfFollowPlan(const adc_tsdf_params* params, const float32 R[9], const float32 t[3], const adc_tsdf_follow_params* follow_params, sint32 shift_out[3]);
     /** Optional voxel-grid filter of the cloud on the device (adc_set_cloud_voxel_grid, include/adcensus_c_api.h holds the definition):
      *  every later cloud of MatchOut / MatchProducts / MatchAsyncProducts holds one point per occupied voxel of edge `leaf` (mean
      *  position and colour, pad = min(points, 255)), in the order of the voxels' first pixels; CloudCount counts voxels.  A cloud then

@@ -1290,6 +1290,82 @@ int adc_tsdf_fuse(adc_handle* h, const float* map, const uint8_t* bgr_left, cons
                   const adc_tsdf_fuse_params* params, adc_tsdf_fuse_report* report);
 int adc_get_tsdf_fuse_report(adc_handle* h, adc_tsdf_fuse_report* fuse_report, adc_tsdf_weight_report* weight_report);
 
+/* -------------------------------------------------------------------------------------------
+ * Moving TSDF volume: the window shifts by whole voxels on the device, the origin moves along, and the surface points whose voxels
+ * leave are handed out exactly once (k_tsdf_shift.hip; the rule is adcensus_amd/csrc/tsdf_shift.h, tests/tsdf_shift_ref.py holds the
+ * same definition in numpy and the kernels match it byte for byte).  Optional: nothing of it exists before the first shift call, and
+ * no other entry point changes -- every consumer reads the volume's origin, which is all a whole-voxel shift changes for them.
+ *
+ * Shift.  s = (sx, sy, sz) in voxels, any int32; the window moves by +s in the world.  New voxel (i, j, k) takes the voxel word (with
+ * a colour volume also the colour word) of old voxel (i + sx, j + sy, k + sz) if that lies inside [0, nx) x [0, ny) x [0, nz);
+ * otherwise both words become 0, the empty voxel.  An old voxel LEAVES iff (i - sx, j - sy, k - sz) lies outside the box.  Space that
+ * re-enters the window is empty: what is fused there later is a new observation.
+ *
+ * Origin.  The handle keeps origin0, the origin given to adc_tsdf_create, and int32 offset[3], the sum of all shifts since
+ * (adc_tsdf_create clears it, adc_tsdf_reset keeps it).  After a shift the volume's origin[a] = origin0[a] + (float)offset[a] * voxel:
+ * binary32, one multiply and one add, nothing fused, from the TOTAL offset and never accumulated, so the rounding does not drift.
+ * |offset[a]| stays <= 2^24 (the conversion is exact): a shift that would pass it is refused.  adc_tsdf_upload, adc_tsdf_download,
+ * integrate, fuse, extract, mesh, ray cast and track behave as before, on the new origin.
+ *
+ * Leaving surface.  The crossings of adc_tsdf_extract's definition on the OLD volume (the min_weight gate, the pair a, b = a + 1 on
+ * an axis, the record, computed with the OLD origin) for which a or b leaves, in the extraction's order (ascending n of a, then x, y,
+ * z), cut by the capacity as extract cuts them; d_count (optional) receives the count.  Over a session each crossing is handed out at
+ * most once: an edge with a leaving endpoint is emitted now, and the endpoint that stays then sits on the window's face without a
+ * neighbour on that side; every other edge is still in the window, for a later shift or the final adc_tsdf_extract.
+ *
+ * A zero shift is valid: bits, device addresses and offset unchanged, a report of zeros, d_count = 0.  With |s_a| >= n_a on any axis
+ * everything leaves: the list is the whole list of adc_tsdf_extract and the new volume is empty.
+ *
+ * Parameters (adc_tsdf_shift_params, 32 bytes): int32 shift[3]; uint32 min_weight in [1, 65535]; uint32 flags = 0; uint32
+ * reserved_[3] = 0.  Report (adc_tsdf_shift_report, uint32 each): moved_nonempty (voxels that stayed and whose voxel word is not 0),
+ * left_nonempty (leaving voxels whose voxel word is not 0), left_seen (leaving voxels with w >= min_weight), points (the leaving
+ * list's length whatever the capacity), four reserved words.
+ *
+ * adc_tsdf_shift_device   d_points adc_point records, 16-byte aligned, or NULL with capacity 0 (counts only); d_count one uint32
+ *                         device word, 4-byte aligned, or NULL.  Asynchronous on the handle's stream, completed by adc_wait; calls
+ *                         may follow one another (and integrate / extract calls) without a wait.  The shift works out of place: the
+ *                         first non-zero shift allocates a second plane of voxel words (and of colour words), which adc_tsdf_destroy,
+ *                         adc_destroy and a replacing adc_tsdf_create free.  THE DEVICE ADDRESSES adc_tsdf_get_volume_device RETURNS
+ *                         CHANGE WITH EVERY NON-ZERO SHIFT: ask again after each.
+ * adc_tsdf_shift          the same with HOST pointers, synchronous; copies out min(points, capacity) records; points may be NULL
+ *                         with capacity 0.  Its device scratch is that of adc_tsdf_extract and grows the same way.
+ * adc_get_tsdf_shift_report  the report of the last completed shift call.
+ * adc_tsdf_get_offset     the total offset and origin0; either out pointer may be NULL (not both).
+ * adc_tsdf_follow_plan    PURE (no handle, no HIP): how far to shift so that a point of the camera frame stays near the volume's
+ *                         centre.  params: the volume with its CURRENT origin; R, t: world -> camera as in adc_tsdf_frame;
+ *                         adc_tsdf_follow_params (32 bytes): float anchor[3] in the camera frame (e.g. 0, 0, 2.5), int32 margin >= 0
+ *                         and int32 quantum >= 1 in voxels, uint32 reserved_[3] = 0.  binary64, in this order: d = anchor - t;
+ *                         A[a] = (R[0][a]*d[0] + R[1][a]*d[1]) + R[2][a]*d[2]; p = (A[a] - origin[a]) / voxel - n_a / 2;
+ *                         shift[a] = quantum * trunc(p / quantum) if |p| > margin, else 0 (clipped to +-2^30).  With quantum <=
+ *                         margin the plan that follows an applied shift is 0 on every axis (while |shift| * voxel is exact in
+ *                         binary32), and the sign of a shift follows the anchor.
+ * Return codes: 0; 1 before the first HIP call (a NULL argument, no volume, a bad field, flag or reserved word, a non-finite R, t or
+ * anchor, an offset that would pass 2^24, a misaligned d_points or d_count, points NULL with a capacity, a Match pending); 2 on a HIP
+ * failure: the volume, its origin and its offset are as before the call.  Not a product of adc_products or the farm.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct adc_tsdf_shift_params {
+    int32_t shift[3];
+    uint32_t min_weight; /* [1, 65535] */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved_[3];
+} adc_tsdf_shift_params; /* 32 bytes */
+typedef struct adc_tsdf_shift_report {
+    uint32_t moved_nonempty, left_nonempty, left_seen, points;
+    uint32_t reserved_[4];
+} adc_tsdf_shift_report;
+typedef struct adc_tsdf_follow_params {
+    float anchor[3];     /* camera frame */
+    int32_t margin;      /* >= 0, voxels */
+    int32_t quantum;     /* >= 1, voxels */
+    uint32_t reserved_[3];
+} adc_tsdf_follow_params; /* 32 bytes */
+int adc_tsdf_shift_device(adc_handle* h, const adc_tsdf_shift_params* params, void* d_points, uint64_t capacity, void* d_count);
+int adc_tsdf_shift(adc_handle* h, const adc_tsdf_shift_params* params, adc_point* points, uint64_t capacity, adc_tsdf_shift_report* report);
+int adc_get_tsdf_shift_report(adc_handle* h, adc_tsdf_shift_report* out);
+int adc_tsdf_get_offset(adc_handle* h, int32_t offset[3], float origin0[3]);
+int adc_tsdf_follow_plan(const adc_tsdf_params* params, const float R[9], const float t[3], const adc_tsdf_follow_params* follow_params,
+                         int32_t shift_out[3]);
+
 /* Stage timers (ms, HIP events on the handle's stream) of the most recent completed match.
  * Enable with adc_set_profiling(h,1).  Order: see adc_stage_name().
  * Level 2 records only the marks around the aggregation launches (adc_aggregate_info: the live duration of the roofline kernel) and
